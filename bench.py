@@ -15,10 +15,12 @@ scaling; for N>1 one packed RCCL all-gather of the embeddings + one flat gradien
 `--workload c2` = configs[1] (ViT-L/14 image-tower forward, batch 256), c4 / c5 = the audio / point-cloud recipes.
 A "step" = one pass of that path over one batch.  Inputs are resident in HBM when timing starts.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the bf16 MFMA GEMM; achieved =
-algorithmic FLOPs / HIP-event time of those launches, measured live in the timed region) and
-`cpu_baseline` (the oracle = CPU restatement of the reference, timed on this node's host cores on a
-bounded sample; a reported baseline, not the target).
+Prints ONE JSON line (rank 0) as the last line of stdout: `value` (modality-pairs/sec), `ms_per_step` (one timed step).
+A plain run does only what that line needs: set-up, --warmup steps, --steps timed steps, the outputs of the last timed step
+when --dump-outputs DIR is given, the line.  With --full the line also carries `roofline` (dominant kernel = the bf16 MFMA
+GEMM; achieved = algorithmic FLOPs / HIP-event time of those launches, measured live in the timed region or in a serial
+pass after it) and `cpu_baseline` (the oracle = CPU restatement of the reference, timed on this node's host cores on a
+bounded sample; a reported baseline, not the target); without it both are null.
 """
 import argparse
 import json
@@ -83,11 +85,22 @@ def parse():
                     help="--gpus 1 only: initialise a ONE-rank RCCL communicator and run the step's multi-rank code path on it "
                          "(packed all-gather, bucketed async all-reduce; prints collective_ms_per_step) - the API / stream "
                          "contract of the exchange exercised on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-launch GEMM `roofline` (HIP events on every "
+                         "GEMM, plus the serial pass when the frozen towers overlap), the committed PMC / traffic figures and the "
+                         "`cpu_baseline`.  Off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the loss "
+                         "of a training step and its updated trainable parameters (`param.<name>`; above 65 536 elements a fixed, "
+                         "seeded sample of them), or the features of the c2 forward.  At most 64 MB in all; rank 0 only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="CPU-baseline sample: images (c2, default 48) / triplets per step (c3, default 8)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="default: one thread per physical core of the host")
-    ap.add_argument("--detail", default="", help="optional path for a per-GEMM-shape breakdown (json)")
-    return ap.parse_args()
+    ap.add_argument("--cpu-threads", type=int, default=0, help="default: one thread per physical core this process may use")
+    ap.add_argument("--detail", default="", help="optional path for a per-GEMM-shape breakdown (json); needs --full")
+    a = ap.parse_args()
+    if a.detail and not a.full:
+        ap.error("--detail is a per-launch measurement: it needs --full")
+    return a
 
 
 def seeded_vitl_weights(seed=1234):
@@ -290,7 +303,8 @@ def cpu_baseline(sample, sd, threads):
 
 
 def host_threads(req=0):
-    """One thread per physical core (SMT siblings only add contention to fp32 GEMMs); `cores` in the JSON = what was used."""
+    """One thread per physical core (SMT siblings only add contention to fp32 GEMMs), no more than this process may run on
+    (its CPU affinity, OMP_NUM_THREADS when set); `cores` in the JSON = what was used."""
     if req > 0:
         return req
     n = os.cpu_count() or 1
@@ -299,7 +313,48 @@ def host_threads(req=0):
         n = psutil.cpu_count(logical=False) or n
     except Exception:
         n = max(1, n // 2)
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
     return n
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 16           # elements kept of a larger tensor (a fixed, seeded sample)
+
+
+def _dump_sample(name, t, n):
+    """`t` flattened, or n of its elements at sorted indices drawn from a generator seeded by `name` when it has more."""
+    import zlib
+    t = t.detach().float().reshape(-1)
+    if t.numel() > n:
+        g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+        idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, outputs, params=None):
+    """Write `outputs` {name: tensor} and `params` {name: tensor} (as path/param.<name>.npy), all in float32, DUMP_BYTES at
+    most in all.  The outputs are written whole when they fit in half of that, else each as a seeded sample of its share; a
+    parameter above DUMP_SAMPLE elements (or above its share of what is left) is a seeded sample.  Samples are drawn from a
+    generator seeded by the tensor's name, so that two runs - or two builds - sample the same elements."""
+    import numpy as np
+    params = params or {}
+    budget = DUMP_BYTES // 4                                   # float32 elements
+    if sum(t.numel() for t in outputs.values()) <= budget // 2:
+        arrays = {n: t.detach().float().cpu().numpy() for n, t in outputs.items()}
+    else:
+        arrays = {n: _dump_sample(n, t, budget // 2 // len(outputs)) for n, t in outputs.items()}
+    per = min(DUMP_SAMPLE, (budget - sum(a.size for a in arrays.values())) // max(1, len(params)))
+    arrays.update({"param." + n: _dump_sample(n, t, per) for n, t in params.items()})
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float32))
 
 
 def cpu_baseline_c3(n_trip, sd, threads, steps=3):
@@ -509,6 +564,8 @@ def selftest_main(a, rank, world):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"output": f.reshape(1)}, {"w": w})
     per_rank_ms, coll = None, None
     if world > 1:
         comm.on = False
@@ -565,7 +622,9 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     from vitlens_hip import engine, ops
-    timer = GemmTimer(ops); timer.install(engine)
+    timer = None
+    if a.full:           # per-launch HIP events on every GEMM: the roofline figures, not the headline
+        timer = GemmTimer(ops); timer.install(engine)
     comm = None
     if use_dist:
         from vitlens_hip import step as _vstep
@@ -661,7 +720,8 @@ def main():
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.on = not overlapped          # two towers sharing the chip: per-launch events are taken in the serial pass below
+    if timer is not None:
+        timer.on = not overlapped      # two towers sharing the chip: per-launch events are taken in the serial pass below
     if comm is not None:
         comm.on = True
     t0 = time.perf_counter()
@@ -672,11 +732,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    timer.on = False
+    if timer is not None:
+        timer.on = False
     if comm is not None:
         comm.on = False
+    if a.dump_outputs and rank == 0:       # before anything else runs a step: the state the last timed step left
+        if a.workload == "c2":
+            dump_outputs(a.dump_outputs, {"features": f})
+        elif trainer_obj is not None:
+            dump_outputs(a.dump_outputs, {"loss": f.reshape(1)}, trainer_obj.masters)
+        else:
+            dump_outputs(a.dump_outputs, {"loss": f.reshape(1)}, {n: p for n, p in model.named_parameters() if p.requires_grad})
     serial_ms = None
-    if overlapped:
+    if overlapped and a.full:
         # per-launch roofline figures: the SAME step with the frozen towers in the launch stream, outside the timed region
         # (`value` / `ms_per_step` above are the default, overlapped path); every rank runs it - the step has collectives
         trainer_obj.overlap_frozen = False              # (one stream for everything: `_overlap_active` is False)
@@ -704,7 +772,7 @@ def main():
         ms = dt / a.steps * 1e3
         value = world * a.batch * a.steps / dt
         gf_unit = {"c2": GF_PER_IMAGE, "c3": 531.3, "c4": 543.6, "c5": 733.1}[a.workload]      # SURVEY.md 8(d) / BASELINE.md section 3
-        shapes = timer.summary()
+        shapes = timer.summary() if timer is not None else []
         dom = max(shapes, key=lambda s: s["avg_ms"] * s["launches"]) if shapes else None
         tot_fl = sum(s["flops_per_launch"] * s["launches"] for s in shapes)
         tot_ms = sum(s["avg_ms"] * s["launches"] for s in shapes)
@@ -766,11 +834,12 @@ def main():
             out["per_rank_ms_per_step"] = per_rank_ms
             out["collective_ms_per_step"] = coll
             out["collective_share"] = round(sum(coll.values()) / ms, 4) if coll else 0.0
-        if not a.no_cpu_baseline and world == 1 and a.workload == "c2":
+        baseline = a.full and not a.no_cpu_baseline and world == 1
+        if baseline and a.workload == "c2":
             out["cpu_baseline"] = cpu_baseline(a.cpu_sample or 48, sd, host_threads(a.cpu_threads))
-        elif not a.no_cpu_baseline and world == 1 and a.workload == "c3" and sd is not None:
+        elif baseline and a.workload == "c3" and sd is not None:
             out["cpu_baseline"] = cpu_baseline_c3(a.cpu_sample or 8, sd, host_threads(a.cpu_threads))
-        elif not a.no_cpu_baseline and world == 1 and a.workload in ("c4", "c5"):
+        elif baseline and a.workload in ("c4", "c5"):
             out["cpu_baseline"] = cpu_baseline_lens(a.workload, a.cpu_sample or 4, sd, host_threads(a.cpu_threads))
         else:
             out["cpu_baseline"] = None

@@ -11,7 +11,6 @@ for p in (ROOT, os.path.join(ROOT, "vit-lens_amd"), os.path.join(ROOT, "oracle")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "needs_reference: needs /root/reference (build container only)")
 
 
 def _has_gpu():
@@ -24,9 +23,6 @@ def _has_gpu():
 
 def pytest_collection_modifyitems(config, items):
     gpu = _has_gpu()
-    have_ref = os.path.isdir("/root/reference/vitlens/src/open_clip")
     for it in items:
         if "gpu" in it.keywords and not gpu:
             it.add_marker(pytest.mark.skip(reason="no GPU in this container"))
-        if "needs_reference" in it.keywords and not have_ref:
-            it.add_marker(pytest.mark.skip(reason="/root/reference not present"))

@@ -49,3 +49,79 @@ def specs_from_meta(meta):
         disable_adapter_pos=bool(a.get("disable_visual_adapter_pos", False)),
         weight_tie_layers=bool(a.get("perceiver_weight_tie_layers", False)))
     return tower, text, lens
+
+
+REFERENCE = os.path.join(GOLDEN, "reference")
+
+
+def _inputs_digest(script, args, outputs=()):
+    """What a stored reference output was computed from: the script, and each argument - a file the script writes
+    (`outputs`) or a directory (the oracle / tests folders, a scratch folder) by its kind only, an input file by its
+    content, anything else as given."""
+    import hashlib
+    h = hashlib.sha256(script.encode())
+    for a in args:
+        if a in outputs:
+            h.update(b"out")
+        elif os.path.isfile(a):
+            with open(a, "rb") as f:
+                h.update(b"file:" + hashlib.sha256(f.read()).digest())
+        elif os.path.isdir(a):
+            h.update(b"dir")
+        else:
+            h.update(b"arg:" + str(a).encode())
+    return h.hexdigest()
+
+
+def reference_run(key, script, args=(), files=(), timeout=600):
+    """The reference's side of a comparison test, from tests/golden/reference/<key>/: what `python -c script *args` printed
+    after "JSON" when it ran against the imported reference (stdout.json.xz), and the files it wrote (`files`, paths among
+    `args`), which are put back where the script would have written them.  The suite needs no reference tree.  inputs.sha256
+    records what the output was computed from (the script, and the input files by content); a test whose script or inputs
+    changed since fails here instead of comparing against a stale output.
+
+    To record (re)generate the outputs in a tree where the reference is importable (oracle/ref_loader.py finds it through
+    VITLENS_REFERENCE), run the comparison tests with VITLENS_RECORD_REFERENCE=1: the script runs and its outputs are stored."""
+    import lzma
+    import subprocess
+    import sys
+    d = os.path.join(REFERENCE, key)
+    digest = _inputs_digest(script, args, files)
+    if os.environ.get("VITLENS_RECORD_REFERENCE") == "1":
+        r = subprocess.run([sys.executable, "-c", script, *args], capture_output=True, text=True, timeout=timeout)
+        assert r.returncode == 0, r.stderr[-3000:]
+        os.makedirs(d, exist_ok=True)
+        with lzma.open(os.path.join(d, "stdout.json.xz"), "wt", encoding="utf-8") as f:
+            f.write(r.stdout[r.stdout.index("JSON") + 4:].strip() if "JSON" in r.stdout else "null")
+        for p in files:
+            with open(p, "rb") as src, lzma.open(os.path.join(d, os.path.basename(p) + ".xz"), "wb") as dst:
+                dst.write(src.read())
+        with open(os.path.join(d, "inputs.sha256"), "w") as f:
+            f.write(digest + "\n")
+    else:
+        with open(os.path.join(d, "inputs.sha256")) as f:
+            stored = f.read().strip()
+        assert stored == digest, (f"tests/golden/reference/{key} was recorded from another script or other inputs than this test "
+                                  "now uses: record it again with VITLENS_RECORD_REFERENCE=1 where the reference is importable")
+        for p in files:
+            with lzma.open(os.path.join(d, os.path.basename(p) + ".xz"), "rb") as src, open(p, "wb") as dst:
+                dst.write(src.read())
+    with lzma.open(os.path.join(d, "stdout.json.xz"), "rt", encoding="utf-8") as f:
+        return json.loads(f.read())
+
+
+def seeded_like(stats, seed):
+    """A state_dict from `stats` {name: [shape, mean, std, dtype]}: per tensor, in name order, normal values of that mean and
+    standard deviation from one seeded generator (an integer buffer holds its mean).  The full-size reference comparisons
+    load it into the reference model when they are recorded, and hand it to the oracle when they replay: a 1.7 GB state_dict
+    is reproduced from a few kB."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k in sorted(stats):
+        shape, mean, std, dtype = stats[k]
+        dt = getattr(torch, dtype.split(".")[-1])
+        if dt.is_floating_point:
+            sd[k] = (torch.randn(shape, generator=g) * std + mean).to(dt)
+        else:
+            sd[k] = torch.full(shape, round(mean), dtype=dt)
+    return sd

@@ -8,6 +8,7 @@ import tempfile
 
 import pytest
 import torch
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,12 +38,8 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_state_dict_and_lock_recipes_match_reference():
-    r = subprocess.run([sys.executable, "-c", _REF_KEYS, os.path.join(ROOT, "oracle")], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_state_dict_and_lock_recipes_match_reference", _REF_KEYS, [os.path.join(ROOT, "oracle")])
     import importlib
     for k in [k for k in sys.modules if k == "open_clip" or k.startswith("open_clip.")]:
         del sys.modules[k]
@@ -245,14 +242,11 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_resize_pos_embed_equals_the_reference():
     """open_clip/model.py:1079-1150 (imported, build container only) against the product's factory.resize_pos_embed: grid
     -> latent counts that are / are not perfect squares (bicubic, then the nearest resample), equal lengths, plain grids."""
     from types import SimpleNamespace
-    r = subprocess.run([sys.executable, "-c", _REF_RESIZE, os.path.join(ROOT, "oracle")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_resize_pos_embed_equals_the_reference", _REF_RESIZE, [os.path.join(ROOT, "oracle")])
     import importlib
     for k in [k for k in sys.modules if k == "open_clip" or k.startswith("open_clip.")]:
         del sys.modules[k]
@@ -295,17 +289,14 @@ print("JSON" + json.dumps({"missing": sorted(inc.missing_keys), "unexpected": so
 '''
 
 
-@pytest.mark.needs_reference
 def test_load_checkpoint_equals_the_reference(tmp_path):
     """factory.load_checkpoint (factory.py:119-160, imported, build container only) on an open_clip-style checkpoint
     (`visual.*` = the image encoder, `module.` prefix, {"state_dict": ...}): the same tensors end up in every parameter
     of the tri-modal model (`visual.* -> image.*` duplication AND the modality tower initialised from the ViT), the same
     keys are reported missing / unexpected."""
     from types import SimpleNamespace
-    r = subprocess.run([sys.executable, "-c", _REF_LOAD, os.path.join(ROOT, "oracle"), str(tmp_path)], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_load_checkpoint_equals_the_reference", _REF_LOAD, [os.path.join(ROOT, "oracle"), str(tmp_path)],
+                        files=[str(tmp_path / f) for f in ("tiny-lens.json", "clip.pt", "loaded.pt")])
     want = torch.load(tmp_path / "loaded.pt")
     import importlib
     for k in [k for k in sys.modules if k == "open_clip" or k.startswith("open_clip.")]:
@@ -349,13 +340,10 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_model_cfg_values_equal_the_reference():
     """mm_vit_lens/model_cfg.py (imported, build container only): for every modality the configuration has exactly the
     reference's keys and values, plus the four attributes TriCLIP.forward / lock read and the reference's defaults omit."""
-    r = subprocess.run([sys.executable, "-c", _REF_CFG, os.path.join(ROOT, "oracle")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_model_cfg_values_equal_the_reference", _REF_CFG, [os.path.join(ROOT, "oracle")])
     from mm_vit_lens.model_cfg import fetch_model_cfg
     for m, want in ref.items():
         assert "__error__" not in want, (m, want)
@@ -398,16 +386,12 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_public_signatures_equal_the_reference():
     """SURVEY 8(b) "callables to keep": parameter names, order and defaults of the drop-in surface against the imported
     reference (build container only).  The product may only APPEND optional parameters (e.g. `device`, `chunk_rows`)."""
     import importlib
     import inspect
-    r = subprocess.run([sys.executable, "-c", _REF_SIG, os.path.join(ROOT, "oracle"), json.dumps(_SIG_TARGETS)], capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_public_signatures_equal_the_reference", _REF_SIG, [os.path.join(ROOT, "oracle"), json.dumps(_SIG_TARGETS)])
     for k in [k for k in sys.modules if k.split(".")[0] in ("open_clip", "mm_vit_lens", "training")]:
         del sys.modules[k]
     bad = []
@@ -449,11 +433,8 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_constants_and_dtype_helpers_equal_the_reference():
-    r = subprocess.run([sys.executable, "-c", _REF_CONST, os.path.join(ROOT, "oracle")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_api_contract.test_constants_and_dtype_helpers_equal_the_reference", _REF_CONST, [os.path.join(ROOT, "oracle")])
     import importlib
     for k in [k for k in sys.modules if k == "open_clip" or k.startswith("open_clip.")]:
         del sys.modules[k]

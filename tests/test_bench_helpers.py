@@ -96,3 +96,34 @@ def test_committed_counter_summary_is_found_under_the_round5_kernel_names():
     bench.LN_FOLDED = True
     assert bench.pmc_mfma_busy({"N": 5, "K": 7, "epi": 0, "act": 0}) is None
     assert not hasattr(bench, "leftover_launch_ms")
+
+
+def test_dump_outputs_samples_large_tensors_the_same_way_every_time(tmp_path, monkeypatch):
+    """bench.dump_outputs: a parameter above DUMP_SAMPLE elements is a seeded sample - the same elements on every call, taken
+    at sorted indices from the tensor itself; small tensors and the outputs are written whole, float32; and outputs larger
+    than half of the byte cap are sampled too, so that the cap holds instead of the run aborting after its timed steps."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(3 * bench.DUMP_SAMPLE + 5, generator=g, dtype=torch.float64)
+    small = torch.randn(7, 3, generator=g)
+    loss = torch.tensor([1.25])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": loss}, {"big.w": big, "small": small})
+    for n in ("loss", "param.big.w", "param.small"):
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    s = np.load(tmp_path / "a" / "param.big.w.npy")
+    assert s.shape == (bench.DUMP_SAMPLE,)
+    assert np.isin(s, big.float().numpy()).all()                                   # elements of the tensor, not a summary
+    pos = np.searchsorted(np.sort(big.float().numpy()), s)                          # (the values are distinct)
+    assert len(set(pos.tolist())) > bench.DUMP_SAMPLE * 0.7                         # spread over the tensor, not one block
+    assert np.array_equal(np.load(tmp_path / "a" / "param.small.npy"), small.reshape(-1).numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), loss.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    feats = torch.randn(1024, 768, generator=g)                                     # 3 MB > the (patched) 1 MB cap
+    bench.dump_outputs(str(tmp_path / "c"), {"features": feats}, {"big.w": big})
+    total = sum(os.path.getsize(tmp_path / "c" / n) for n in os.listdir(tmp_path / "c"))
+    assert total <= (1 << 20) + 2 * 128                                             # (+ the .npy headers)
+    f = np.load(tmp_path / "c" / "features.npy")
+    assert 0 < f.size <= (1 << 20) // 8 and np.isin(f, feats.numpy()).all()

@@ -87,3 +87,24 @@ def test_result_line_is_the_last_line_of_stdout_even_behind_native_prints(gpus):
     assert lines and lines[-1].startswith("{"), lines[-3:]
     assert json.loads(lines[-1])["n_gpus"] == int(gpus)
     assert "native banner line" in p.stdout          # (it was printed - in front of the result, not behind it)
+
+
+def test_dump_outputs_are_float32_and_identical_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy in float32; the same arguments give the same
+    inputs, so two runs write the same arrays."""
+    import numpy as np
+    for d in ("a", "b"):
+        p = _run(["--steps", "3", "--warmup", "1", "--workload", "selftest", "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        (j,) = _json_lines(p.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names and names == sorted(os.listdir(tmp_path / "b")) and all(n.endswith(".npy") for n in names)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+
+
+def test_per_launch_detail_needs_full():
+    p = _run(["--workload", "selftest", "--detail", "detail.json"], timeout=120)
+    assert p.returncode != 0 and "--full" in p.stderr

@@ -4,6 +4,7 @@ plumbing, loud failures where a front end is not available.  The GPU side is in 
 import numpy as np
 import pytest
 import torch
+from golden_util import reference_run
 
 
 def test_pre_caption_matches_the_reference_rules():
@@ -88,17 +89,13 @@ def test_text_processor_against_the_reference(tmp_path):
     import os
     import subprocess
     import sys
-    if not os.path.isdir("/root/reference/vitlens/src/mm_vit_lens"):
-        pytest.skip("/root/reference not present")
     from test_tokenizer import _fuzz_texts
     from mm_vit_lens.data_processors import TextProcessor
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     texts = _fuzz_texts(600, seed=1)
     p = tmp_path / "texts.json"
     json.dump(texts, open(p, "w"))
-    r = subprocess.run([sys.executable, "-c", _REF_PRE, os.path.join(root, "oracle"), str(p)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_data_processors.test_text_processor_against_the_reference", _REF_PRE, [os.path.join(root, "oracle"), str(p)])
     tp, tp5 = TextProcessor(), TextProcessor(max_words=5)
     assert [tp.pre_caption(t) for t in texts] == ref["pre"]
     assert [tp5.pre_caption(t) for t in texts] == ref["pre5"]

@@ -9,6 +9,7 @@ import sys
 import pytest
 import torch
 import torch.multiprocessing as mp
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -82,12 +83,8 @@ def _norm(o):
     return json.loads(json.dumps(o))                                             # int keys -> str, tuples -> lists, as the reference's dump
 
 
-@pytest.mark.needs_reference
 def test_metrics_equal_the_reference():
-    r = subprocess.run([sys.executable, "-c", _REF, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")], capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_metrics_host.test_metrics_equal_the_reference", _REF, [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")])
     mine = _norm(_mine(_data()))
     assert mine["acc"] == ref["acc"] and mine["acc_multi"] == ref["acc_multi"]
     assert mine["map"]["map_cnt"] == ref["map"]["map_cnt"] and abs(mine["map"]["map"] - ref["map"]["map"]) < 1e-9

@@ -1,4 +1,4 @@
-"""CPU, build container only: the oracle's restatement of the `pnsa` point tokenizer (PointNet set abstraction,
+"""CPU: the oracle's restatement of the `pnsa` point tokenizer (PointNet set abstraction,
 open_clip/modal_3d/models/pointnet/pointnet_util.py:345-368) against the imported reference class.
 
 The reference module imports `dgl.geometry` and `torch_redstone` at module level; neither is installed.  For THIS test
@@ -14,47 +14,67 @@ import pytest
 import torch
 
 import vitlens_oracle as O
+from golden_util import reference_run
 
-REF = "/root/reference/vitlens/src/open_clip/modal_3d/models/pointnet/pointnet_util.py"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_REF = r'''
+import json, sys
+from types import SimpleNamespace
+import torch
+sys.path.insert(0, sys.argv[1])
+import ref_loader
+ref = ref_loader.load_pointnet_util()
+training = sys.argv[2] == "train"
+cfg = SimpleNamespace(num_group=24, radius=0.35, group_size=8, in_dim=3, encoder_dims=32, trans_dim=48)
+torch.manual_seed(0)
+tok = ref.PointNSATokenizer(cfg)
+with torch.no_grad():
+    for bn in tok.sa.mlp_bns:                                                 # non-trivial running statistics for eval mode
+        bn.running_mean.normal_(0, 0.2); bn.running_var.uniform_(0.5, 1.5)
+        bn.weight.normal_(1, 0.1); bn.bias.normal_(0, 0.1)
+tok.train(training)
+g = torch.Generator().manual_seed(1)
+B, N = 3, 400
+xyz = torch.rand(B, N, 3, generator=g) * 2 - 1
+feats = torch.rand(B, N, 3, generator=g)
+sd = {k: [str(v.dtype), list(v.shape), v.detach().reshape(-1).tolist()] for k, v in tok.state_dict().items()}
+torch.manual_seed(7)
+start = torch.randint(0, N, (B,), dtype=torch.long)                           # what the fallback FPS draws first
+torch.manual_seed(7)
+with torch.no_grad():
+    want = tok(feats, xyz=xyz)["x"]
+torch.manual_seed(7)
+cidx = ref.farthest_point_sample(xyz, cfg.num_group)
+new_xyz = ref.index_points(xyz, cidx)
+print("JSON" + json.dumps({"sd": sd, "start": start.tolist(), "tokens": want.tolist(), "fps": cidx.tolist(),
+                           "ball": ref.query_ball_point(cfg.radius, cfg.group_size, xyz, new_xyz).tolist(),
+                           "ball_tight": ref.query_ball_point(0.05, 8, xyz, new_xyz).tolist()}))
+'''
 
 
-def _reference_module():
-    import ref_loader
-    return ref_loader.load_pointnet_util()
-
-
-@pytest.mark.needs_reference
 @pytest.mark.parametrize("training", [False, True])
 def test_pnsa_tokens_equal_the_reference(training):
-    if not os.path.exists(REF):
-        pytest.skip("reference tree not present")
-    ref = _reference_module()
+    """The reference's PointNSATokenizer (imported when recorded) on seeded weights and points: its state_dict, tokens, FPS
+    picks and ball-query indices, against the oracle on the same state_dict and points."""
+    ref = reference_run(f"test_oracle_pnsa.test_pnsa_tokens_equal_the_reference.{'train' if training else 'eval'}", _REF,
+                        [os.path.join(ROOT, "oracle"), "train" if training else "eval"])
     cfg = SimpleNamespace(num_group=24, radius=0.35, group_size=8, in_dim=3, encoder_dims=32, trans_dim=48)
-    torch.manual_seed(0)
-    tok = ref.PointNSATokenizer(cfg)
-    with torch.no_grad():
-        for bn in tok.sa.mlp_bns:                                                 # non-trivial running statistics for eval mode
-            bn.running_mean.normal_(0, 0.2); bn.running_var.uniform_(0.5, 1.5)
-            bn.weight.normal_(1, 0.1); bn.bias.normal_(0, 0.1)
-    tok.train(training)
+    sd = {"a." + k: torch.tensor(v, dtype=getattr(torch, dt.split(".")[-1])).reshape(sh) for k, (dt, sh, v) in ref["sd"].items()}
     g = torch.Generator().manual_seed(1)
     B, N = 3, 400
     xyz = torch.rand(B, N, 3, generator=g) * 2 - 1
     feats = torch.rand(B, N, 3, generator=g)
-    sd = {"a." + k: v.detach().clone() for k, v in tok.state_dict().items()}
-    torch.manual_seed(7)
-    start = torch.randint(0, N, (B,), dtype=torch.long)                           # what the fallback FPS draws first
-    torch.manual_seed(7)
-    want = tok(feats, xyz=xyz)["x"]
+    start = torch.tensor(ref["start"])
+    want = torch.tensor(ref["tokens"])
     got, cidx, bidx = O.pnsa_tokens(sd, "a.", feats, xyz, cfg.num_group, cfg.radius, cfg.group_size, start, training=training)
     assert got.shape == want.shape == (B, cfg.num_group, cfg.trans_dim)
     assert float((got - want).abs().max()) < 2e-5, float((got - want).abs().max())
     # the pieces, individually: FPS picks, ball query (incl. short groups filled with the first index)
-    torch.manual_seed(7)
-    assert torch.equal(cidx, ref.farthest_point_sample(xyz, cfg.num_group))
-    new_xyz = ref.index_points(xyz, cidx)
-    assert torch.equal(bidx, ref.query_ball_point(cfg.radius, cfg.group_size, xyz, new_xyz))
-    tight = ref.query_ball_point(0.05, 8, xyz, new_xyz)
+    assert torch.equal(cidx, torch.tensor(ref["fps"]))
+    assert torch.equal(bidx, torch.tensor(ref["ball"]))
+    new_xyz = torch.stack([xyz[b, cidx[b]] for b in range(B)])
+    tight = torch.tensor(ref["ball_tight"])
     assert torch.equal(O.ball_query_indices(0.05, 8, xyz, new_xyz), tight)
     assert bool((tight == tight[..., :1]).all(-1).any())                          # some groups hold only their centre
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import vitlens_oracle as O
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,38 +21,56 @@ def _cloud(n, c, seed):
     return pts
 
 
-@pytest.mark.needs_reference
+_REF = r'''
+import glob, importlib.util, json, os, sys, types
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
+import ref_loader
+from test_pc_processor import _cloud
+sys.modules.setdefault("omegaconf", types.SimpleNamespace(OmegaConf=None))      # only used by the config plumbing
+spec = importlib.util.spec_from_file_location("ref_pc_processor", os.path.join(ref_loader.REF_SRC, "open_clip", "modal_3d", "processors",
+                                                                               "pc_processor.py"))
+ref = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref)
+pts = _cloud(700, 6, 1)
+np.random.seed(5)
+fps = ref.farthest_point_sample(pts, 128)
+out = {"fps": fps.tolist(), "norm": ref.pc_norm(fps).tolist()}
+np.random.seed(9)
+out["random_sample"] = ref.random_sample(pts, 100).tolist()
+out["examples"] = []
+for f in sorted(glob.glob(os.path.join(ref_loader.REF_ROOT, "assets", "example", "pc_*.npy")))[:2]:
+    pc = np.load(f)
+    np.random.seed(3)
+    out["examples"].append({"name": os.path.basename(f), "pc": pc.tolist(), "dtype": str(pc.dtype),
+                            "eval": ref.PCProcessorEval(8192, True)(pc).numpy().tolist()})
+print("JSON" + json.dumps(out))
+'''
+
+
 def test_oracle_pc_processing_equals_reference_functions():
-    ref_root = "/root/reference/vitlens/src/open_clip/modal_3d/processors"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present")
-    import importlib.util, types
-    sys.modules.setdefault("omegaconf", types.SimpleNamespace(OmegaConf=None))      # only used by the config plumbing
-    spec = importlib.util.spec_from_file_location("ref_pc_processor", os.path.join(ref_root, "pc_processor.py"))
-    ref = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref)
+    """pc_processor.py's farthest_point_sample / pc_norm / random_sample / PCProcessorEval (imported when recorded; the
+    reference's example clouds with them) against the oracle."""
+    ref = reference_run("test_pc_processor.test_oracle_pc_processing_equals_reference_functions", _REF,
+                        [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")])
     pts = _cloud(700, 6, 1)
-    np.random.seed(5)
-    want = ref.farthest_point_sample(pts, 128)
     np.random.seed(5)
     start = np.random.randint(0, 700)
     got, idx = O.pc_farthest_point_sample(pts, 128, start)
+    want = np.array(ref["fps"], dtype=got.dtype)
     assert np.array_equal(got, want)
-    assert np.allclose(O.pc_norm(got), ref.pc_norm(want), rtol=0, atol=0)
+    assert np.allclose(O.pc_norm(got), np.array(ref["norm"], dtype=got.dtype), rtol=0, atol=0)
     # the random-subset branch (pc_processor.py:41-45,81-84): the product draws np.random.permutation(N)[:n], the reference
     # shuffles arange(N) in place - the same draws of the legacy global RNG
     np.random.seed(9)
-    want = ref.random_sample(pts, 100)
-    np.random.seed(9)
-    assert np.array_equal(pts[np.random.permutation(700)[:100]], want)
+    assert np.array_equal(pts[np.random.permutation(700)[:100]], np.array(ref["random_sample"], dtype=pts.dtype))
     # and the example clouds of the reference (8192 points = npoint: the processor takes the random-subset branch)
-    files = sorted(__import__("glob").glob("/root/reference/assets/example/pc_*.npy"))
-    for f in files[:2]:
-        pc = np.load(f)
-        np.random.seed(3)
-        want = ref.PCProcessorEval(8192, True)(pc).numpy()
+    assert len(ref["examples"]) == 2
+    for e in ref["examples"]:
+        pc = np.array(e["pc"], dtype=e["dtype"])
         np.random.seed(3)
         sub = np.random.permutation(pc.shape[0])[:8192]
-        assert np.array_equal(O.pc_norm(pc[sub]), want), f
+        got = O.pc_norm(pc[sub])
+        assert np.array_equal(got, np.array(e["eval"], dtype=got.dtype)), e["name"]
 
 
 @pytest.mark.gpu

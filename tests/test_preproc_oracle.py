@@ -86,20 +86,18 @@ def test_depth_eval_transform_matches_the_torch_pipeline():
     assert got.shape == (1, 224, 224) and np.abs(got[0] - want.numpy()).max() < 1e-4
 
 
-@pytest.mark.needs_reference
 def test_oracle_on_the_reference_example_photographs():
-    """BASELINE config C1's inputs: the four JPEGs of /root/reference/assets/example (build container only) through
+    """BASELINE config C1's inputs: the four example JPEGs of the reference (stored in tests/golden/c1_examples.npz) through
     Pillow + torch (what `image_transform(224, is_train=False)` of the reference computes) against the restatement -
     real photographs with smooth gradients and saturated regions instead of noise; and the product's tables on the
     same geometries."""
-    import glob
+    import io
+    from golden_util import load_npz
     from open_clip.constants import OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
     from vitlens_hip import preproc
-    files = sorted(glob.glob("/root/reference/assets/example/image_*.jpg"))
-    if len(files) < 4:
-        pytest.skip("reference example images not present")
-    for f in files:
-        im = Image.open(f).convert("RGB")
+    z = load_npz("c1_examples.npz")
+    for f in ("bird", "fire", "dog", "beach"):
+        im = Image.open(io.BytesIO(z[f"jpeg/{f}"].tobytes())).convert("RGB")
         w, h = im.size
         nh, nw = po.resized_output_size(h, w, 224)
         top, left = po.center_crop_origin(nh, nw, 224)

@@ -7,6 +7,7 @@ import sys
 
 import pytest
 import torch
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [("cosine_lr", dict(base_lr=5e-4, warmup_length=10, steps=100)), ("const_lr", dict(base_lr=2e-4, warmup_length=5, steps=50)),
@@ -29,13 +30,9 @@ print("JSON" + json.dumps(out))
 '''
 
 
-@pytest.mark.needs_reference
 def test_schedules_equal_the_reference():
     from training import scheduler as S
-    r = subprocess.run([sys.executable, "-c", _REF, os.path.join(ROOT, "oracle"), json.dumps(CASES)], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_scheduler_host.test_schedules_equal_the_reference", _REF, [os.path.join(ROOT, "oracle"), json.dumps(CASES)])
 
     class Opt:
         def __init__(self):

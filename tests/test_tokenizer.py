@@ -4,7 +4,7 @@ import os
 
 import torch
 
-from golden_util import GOLDEN
+from golden_util import GOLDEN, reference_run
 
 
 def test_tokenizer_kat_bit_exact():
@@ -73,16 +73,12 @@ def test_tokenizer_fuzz_against_the_reference(tmp_path):
     import subprocess
     import sys
     import pytest
-    if not os.path.isdir("/root/reference/vitlens/src/open_clip"):
-        pytest.skip("/root/reference not present")
     from open_clip.tokenizer import tokenize
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     texts = _fuzz_texts()
     p = tmp_path / "texts.json"
     json.dump(texts, open(p, "w"))
-    r = subprocess.run([sys.executable, "-c", _REF_TOK, os.path.join(root, "oracle"), str(p)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_tokenizer.test_tokenizer_fuzz_against_the_reference", _REF_TOK, [os.path.join(root, "oracle"), str(p)])
     got77, got20 = tokenize(texts), tokenize(texts, context_length=20)
     bad = [i for i in range(len(texts)) if got77[i].tolist() != ref["ids77"][i] or got20[i].tolist() != ref["ids20"][i]]
     assert not bad, (len(bad), [texts[i] for i in bad[:3]])
@@ -96,8 +92,6 @@ def test_tokenizer_unicode_fuzz_against_the_reference(tmp_path):
     import subprocess
     import sys
     import pytest
-    if not os.path.isdir("/root/reference/vitlens/src/open_clip"):
-        pytest.skip("/root/reference not present")
     from open_clip.tokenizer import tokenize
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rng = random.Random(5)
@@ -107,9 +101,7 @@ def test_tokenizer_unicode_fuzz_against_the_reference(tmp_path):
     texts = ["".join(rng.choice(words) + rng.choice(seps) for _ in range(rng.choice([1, 2, 4, 9, 40]))) for _ in range(500)]
     p = tmp_path / "texts.json"
     json.dump(texts, open(p, "w"))
-    r = subprocess.run([sys.executable, "-c", _REF_TOK, os.path.join(root, "oracle"), str(p)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_tokenizer.test_tokenizer_unicode_fuzz_against_the_reference", _REF_TOK, [os.path.join(root, "oracle"), str(p)])
     got77, got20 = tokenize(texts), tokenize(texts, context_length=20)
     bad = [i for i in range(len(texts)) if got77[i].tolist() != ref["ids77"][i] or got20[i].tolist() != ref["ids20"][i]]
     assert not bad, (len(bad), [texts[i] for i in bad[:3]])

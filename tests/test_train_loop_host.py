@@ -9,6 +9,7 @@ import sys
 
 import pytest
 import torch
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -79,11 +80,9 @@ torch.save(out, sys.argv[2])
 '''
 
 
-@pytest.mark.needs_reference
 def test_epoch_drivers_equal_the_reference(tmp_path):
-    r = subprocess.run([sys.executable, "-c", _REF, os.path.join(ROOT, "oracle"), str(tmp_path / "ref.pt")], capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
+    reference_run("test_train_loop_host.test_epoch_drivers_equal_the_reference", _REF, [os.path.join(ROOT, "oracle"), str(tmp_path / "ref.pt")],
+                  files=[str(tmp_path / "ref.pt")])
     ref = torch.load(tmp_path / "ref.pt")
     ns = {}
     exec(_COMMON, ns)

@@ -6,6 +6,7 @@ import sys
 
 import pytest
 import torch
+from golden_util import reference_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -73,12 +74,10 @@ print("JSON" + json.dumps([w.tolist(), w2.tolist()]))
 '''
 
 
-@pytest.mark.needs_reference
 def test_classifier_equals_reference_builder():
     import json
-    r = subprocess.run([sys.executable, "-c", _REF, os.path.join(ROOT, "oracle")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref, ref_legacy = (torch.tensor(t) for t in json.loads(r.stdout[r.stdout.index("JSON") + 4:]))
+    ref, ref_legacy = (torch.tensor(t) for t in reference_run("test_zero_shot_host.test_classifier_equals_reference_builder", _REF,
+                                                               [os.path.join(ROOT, "oracle")]))
     oc = _oc()
     w = oc.build_zero_shot_classifier(_StubModel(), oc.tokenize, CLASSES, TEMPLATES[:2], num_classes_per_batch=3, device="cpu")
     assert torch.allclose(w, ref, atol=1e-6)
@@ -105,13 +104,10 @@ print("JSON" + json.dumps(res))
 '''
 
 
-@pytest.mark.needs_reference
 def test_accuracy_helpers_equal_reference():
     """accuracy / acc / cond_acc of training/zero_shot.py:36-81 (imported, build container only)."""
     import json
-    r = subprocess.run([sys.executable, "-c", _REF_ACC, os.path.join(ROOT, "oracle")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("JSON") + 4:])
+    ref = reference_run("test_zero_shot_host.test_accuracy_helpers_equal_reference", _REF_ACC, [os.path.join(ROOT, "oracle")])
     oc = _oc()
     g = torch.Generator().manual_seed(3)
     out = torch.randn(64, 12, generator=g)

@@ -38,7 +38,7 @@ def patch(name):
 
 def run(bench_args):
     import bench
-    sys.argv = ["bench.py"] + bench_args
+    sys.argv = ["bench.py"] + bench_args + ([] if "--full" in bench_args else ["--full"])      # the roofline figures below
     buf = io.StringIO()
     with redirect_stdout(buf):
         bench.main()
