@@ -5,7 +5,13 @@ position so the tile hand-over (DMA prefetch across the tile boundary, epilogue 
 import pytest
 import torch
 
+from errloc import assert_blocks
+
 pytestmark = pytest.mark.gpu
+
+# per 256x256 output tile (tests/errloc.py), worst block measured on the MI355X in the comment
+TILE_TOL_BF16 = 5e-3           # measured 2.4e-3 (dgelu, M = 256 x 40, N = 1024)
+TILE_TOL_F32 = 7e-7            # measured 3.4e-7 (fp32 residual, M = 256 x 5, K = 3072)
 
 
 @pytest.fixture(params=[8, 10])
@@ -49,15 +55,18 @@ def test_p4_bf16_epilogues(M, N, K, pcfg):
     acc = a.float() @ w.float().t() + bias
     # plain, GELU, ReLU, no bias
     assert relerr(ops.gemm(a, w, bias, epi=ops.EPI_BF16, cfg=pcfg), acc) < 4e-3
+    assert_blocks(ops.gemm(a, w, bias, epi=ops.EPI_BF16, cfg=pcfg), acc, TILE_TOL_BF16, 256, 256, what="bias")
     assert relerr(ops.gemm(a, w, None, epi=ops.EPI_BF16, cfg=pcfg, alpha=0.5), 0.5 * (acc - bias)) < 4e-3
     out = ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=pcfg)
     ref = torch.nn.functional.gelu(acc)
     assert relerr(out, ref) < 4e-3 and bool(((out.float() - ref).abs() <= ref.abs() * 2.0 ** -7 + 2e-3).all())
+    assert_blocks(out, ref, TILE_TOL_BF16, 256, 256, what="gelu")
     assert relerr(ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_RELU, cfg=pcfg), torch.relu(acc)) < 4e-3
     # GELU with the saved pre-activation (training forward)
     u = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
     out = ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=pcfg, out2=u)
     assert relerr(u, acc) < 4e-3 and relerr(out, torch.nn.functional.gelu(u.float())) < 4e-3
+    assert_blocks(u, acc, TILE_TOL_BF16, 256, 256, what="saved pre-activation")
     # same results as the 8-wave kernel up to the bf16 rounding point of the GELU (fp32 vs bf16-rounded pre-activation)
     old = ops.gemm(a, w, bias, epi=ops.EPI_BF16, cfg=5)
     assert torch.equal(old, ops.gemm(a, w, bias, epi=ops.EPI_BF16, cfg=pcfg))
@@ -73,6 +82,7 @@ def test_p4_residual_and_dgelu(M, N, K, pcfg):
     res = rnd(M, N, seed=7).bfloat16().cuda()
     o1 = ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_BF16, cfg=pcfg)
     assert relerr(o1, res.float() + acc + bias) < 4e-3
+    assert_blocks(o1, res.float() + acc + bias, TILE_TOL_BF16, 256, 256, what="residual")
     assert torch.equal(o1, ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_BF16, cfg=5))
     x = res.clone()
     ops.gemm(a, w, bias, out=x, res=x, epi=ops.EPI_RES_BF16, cfg=pcfg)
@@ -83,6 +93,7 @@ def test_p4_residual_and_dgelu(M, N, K, pcfg):
     uf = u.float().requires_grad_(True)
     torch.nn.functional.gelu(uf).sum().backward()
     assert relerr(out, acc * uf.grad) < 4e-3
+    assert_blocks(out, acc * uf.grad, TILE_TOL_BF16, 256, 256, what="dgelu")
     assert torch.equal(out, ops.gemm(a, w, None, res=u, epi=ops.EPI_DGELU, cfg=5, out=torch.empty_like(out)))
 
 
@@ -227,6 +238,7 @@ def test_fp32_residual_epilogue_on_the_persistent_kernel(M, N, K):
     acc = a.float() @ w.float().t()
     out8 = ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_F32, cfg=8)
     assert relerr(out8, acc + bias + res) < 1e-5
+    assert_blocks(out8, acc + bias + res, TILE_TOL_F32, 256, 256, what="cfg 8")
     out5 = ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_F32, cfg=5)
     assert float((out8 - out5).abs().max()) <= 2e-6 * float(out5.abs().max())
     x = res.clone()
@@ -239,6 +251,8 @@ def test_fp32_residual_epilogue_on_the_persistent_kernel(M, N, K):
     # what the auto dispatch does with it (whole rounds persistent + leftover rows)
     auto = ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_F32)
     assert relerr(auto, acc + bias + res) < 1e-5
+    mm = ops._lib.vl_gemm_main_rows(M, N)
+    assert_blocks(auto, acc + bias + res, TILE_TOL_F32, 256, 256, extra=[("rows", mm, M)] if 0 < mm < M else (), what="auto")
 
 
 def test_many_tiles_every_epilogue_variant():

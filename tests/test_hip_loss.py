@@ -100,6 +100,15 @@ def test_row_blocked_pair_loss_vs_oracle_and_whole_matrix(R, Cn, off, w_col, chu
     assert abs(float(loss_b) - float(loss_w)) < 2e-5 * max(1.0, abs(ref_loss))
     assert rel(dx_b, ref_dx) < 4e-2 and rel(dy_b, ref_dy) < 4e-2, (rel(dx_b, ref_dx), rel(dy_b, ref_dy))
     assert rel(dx_b, dx_w) < 1e-2 and rel(dy_b, dy_w) < 1e-2, (rel(dx_b, dx_w), rel(dy_b, dy_w))
+    # per row chunk, the two rows either side of every chunk boundary a block of their own (tests/errloc.py); worst block
+    # measured on the MI355X:
+    from errloc import assert_blocks
+    cr = ctx_b[9]
+    seams = [("rows", c - 1, c + 1) for c in range(cr, R, cr)]
+    assert_blocks(dx_b, ref_dx.cuda(), 8e-3, cr, 768, extra=seams, what="dx")                # 3.8e-3 (a seam row)
+    assert_blocks(dx_b, dx_w, 3e-4, cr, 768, extra=seams, what="dx vs whole matrix")          # 1.4e-4
+    assert_blocks(dy_b, ref_dy.cuda(), 5e-3, cr, 768, what="dy")                              # 2.6e-3
+    assert_blocks(dy_b, dy_w, 3e-4, cr, 768, what="dy vs whole matrix")                       # 1.4e-4
     assert abs(float(ds_b) - ref_ds) < 2e-2 * max(1e-3, abs(ref_ds)) + 2e-5, (float(ds_b), ref_ds)
     assert abs(float(ds_b) - float(ds_w)) < 1e-2 * max(1e-3, abs(ref_ds)) + 2e-5
 
