@@ -3,17 +3,19 @@
 // (channels = columns, batch = rows), forward (train-mode batch statistics or eval-mode running statistics) and
 // backward, plus the backward of the per-group max and the per-group sum.  All HBM-bound: each kernel streams
 // the matrix once with 16-byte (bf16x8) accesses; column reductions are two-stage and deterministic (row-chunk
-// partials in a caller-provided workspace, then one finalize launch - no atomics).
+// partials in a caller-provided workspace, then one finalize launch - no atomics; the statistics' partials are per-chunk
+// Welford (mean, M2), merged with Chan's formula).
 //   vl_bn_stats        mean/var per column (biased var, as F.batch_norm normalises) + running-stat update
 //   vl_bn_apply        y = gamma*(x-mean)*rstd + beta, optional ReLU, bf16 out
 //   vl_bn_bwd          dgamma += sum dy'*xhat, dbeta += sum dy'; dx = gamma*rstd*(dy' - [train](mean(dy') + xhat*mean(dy'*xhat)))
-//                      with dy' = dy * (y > 0) when the ReLU is fused
+//                      with dy' = dy * (y > 0) when the ReLU is fused; the gate evaluates y with vl_bn_apply's own expression
 //   vl_bn_stats_local / vl_bn_stats_merge / vl_bn_bwd_reduce / vl_bn_bwd_apply
 //                      the same two passes split at the point where SyncBatchNorm exchanges data between ranks
 //                      (torch.nn.SyncBatchNorm, enabled by --use-bn-sync: training/point_cloud/pc_tri_main.py:372-373):
 //                      forward = all-gather of per-rank (mean, M2, count) then a Chan merge in rank order; backward =
 //                      all-reduce of (sum dy', sum dy'*xhat) then the elementwise pass with the global count
-//   vl_group_max_bwd   df = base + one_hot(argmax over the M rows of a group) * dg      (torch.max(dim) backward)
+//   vl_group_max_bwd   df = base + one_hot(argmax over the M rows of a group) * dg      (torch.max(dim) backward: the
+//                      first maximum, or the first NaN, of the group)
 //   vl_group_sum       out[g,:] = sum over the M rows of group g                          (backward of the expand)
 #include "vl_common.h"
 #include "vitlens_hip.h"
@@ -24,63 +26,89 @@ extern "C" int vl_set_error(const char* msg);
 namespace {
 
 // ------------------------------------------------------------------------------------------------ statistics
+// Chan et al.: merge a part of nk rows with mean muk and M2 = sum (x - muk)^2 into the running (n, mu, m2)
+__device__ inline void chan_add(double& n, double& mu, double& m2, double nk, double muk, double m2k) {
+  const double d = muk - mu, nn = n + nk;
+  mu += d * (nk / nn);
+  m2 += m2k + d * d * (n * nk / nn);
+  n = nn;
+}
+
 // block = 4 waves; a wave owns rows r0+w, r0+w+4, ...; lane owns 2 adjacent columns (one 4-byte load).
-// Sums are taken about the first row (shift) so that E[d^2]-E[d]^2 does not cancel for columns with |mean| >> std.
+// Each thread keeps Welford's running mean and M2 of its rows, so that neither columns with |mean| >> std nor an outlier row
+// make a sum of squares cancel (sums about row 0 of the batch lost 5e-6 of the variance at 2 M rows, 5e-3 with row 0 100 std
+// from its column's mean); the 4 waves merge in wave order in double and the chunk stores (mean, M2) - its row count follows
+// from R.
 __global__ void __launch_bounds__(256) bn_partial_kernel(const bf16_t* __restrict__ x, long ldx, int R, int C, int rows_per_chunk,
                                                          float* __restrict__ ws) {
   __shared__ float red[4][2][128];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 128 + lane * 2;
   const int r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-  float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
+  float ma = 0.f, mb = 0.f, qa = 0.f, qb = 0.f;
   if (c < C) {
-    const unsigned int x0 = *(const unsigned int*)(x + c);
-    const float sa = bf2f((bf16_t)(x0 & 0xffff)), sb = bf2f((bf16_t)(x0 >> 16));
+    int n = 0;
     for (int r = r0 + w; r < r1; r += 4) {
       const unsigned int v = *(const unsigned int*)(x + (long)r * ldx + c);
-      const float a = bf2f((bf16_t)(v & 0xffff)) - sa, b = bf2f((bf16_t)(v >> 16)) - sb;
-      s1a += a; s1b += b; s2a = fmaf(a, a, s2a); s2b = fmaf(b, b, s2b);
+      const float a = bf2f((bf16_t)(v & 0xffff)), b = bf2f((bf16_t)(v >> 16));
+      const float inv = __builtin_amdgcn_rcpf((float)++n);
+      const float da = a - ma, db = b - mb;
+      ma = fmaf(da, inv, ma); mb = fmaf(db, inv, mb);
+      qa = fmaf(da, a - ma, qa); qb = fmaf(db, b - mb, qb);
     }
   }
-  red[w][0][lane * 2] = s1a; red[w][0][lane * 2 + 1] = s1b;
-  red[w][1][lane * 2] = s2a; red[w][1][lane * 2 + 1] = s2b;
+  red[w][0][lane * 2] = ma; red[w][0][lane * 2 + 1] = mb;
+  red[w][1][lane * 2] = qa; red[w][1][lane * 2 + 1] = qb;
   __syncthreads();
   if (threadIdx.x < 128) {
     const int cc = blockIdx.x * 128 + threadIdx.x;
     if (cc < C) {
       const int t = threadIdx.x;
-      ws[((long)blockIdx.y * 2 + 0) * C + cc] = red[0][0][t] + red[1][0][t] + red[2][0][t] + red[3][0][t];
-      ws[((long)blockIdx.y * 2 + 1) * C + cc] = red[0][1][t] + red[1][1][t] + red[2][1][t] + red[3][1][t];
+      double n = 0.0, mu = 0.0, m2 = 0.0;
+      for (int k = 0; k < 4; ++k) {
+        const int nk = r1 - r0 - k > 0 ? (r1 - r0 - k + 3) / 4 : 0;          // rows wave k walked
+        if (nk > 0) chan_add(n, mu, m2, nk, red[k][0][t], red[k][1][t]);
+      }
+      ws[((long)blockIdx.y * 2 + 0) * C + cc] = (float)mu;
+      ws[((long)blockIdx.y * 2 + 1) * C + cc] = (float)m2;
     }
   }
 }
 
-__global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const bf16_t* __restrict__ x, const float* __restrict__ ws, int nchunk,
-                                                                int R, int C, float* mean, float* var, float* rmean, float* rvar,
+// the chunks' (mean, M2) merged in chunk order; chunks past R hold no rows
+__device__ inline void merge_chunks(const float* __restrict__ ws, int nchunk, int rows_per_chunk, int R, int C, int c, double& n,
+                                    double& mu, double& m2) {
+  n = 0.0; mu = 0.0; m2 = 0.0;
+  for (int k = 0; k < nchunk; ++k) {
+    const int nk = min(R - k * rows_per_chunk, rows_per_chunk);
+    if (nk > 0) chan_add(n, mu, m2, nk, ws[((long)k * 2) * C + c], ws[((long)k * 2 + 1) * C + c]);
+  }
+}
+
+__global__ void __launch_bounds__(256) bn_stats_finalize_kernel(const float* __restrict__ ws, int nchunk, int rows_per_chunk, int R,
+                                                                int C, float* mean, float* var, float* rmean, float* rvar,
                                                                 float momentum) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < nchunk; ++k) { s1 += ws[((long)k * 2) * C + c]; s2 += ws[((long)k * 2 + 1) * C + c]; }
-  const double m = s1 / R;
-  const double v = fmax(s2 / R - m * m, 0.0);
-  const float mu = (float)(m + (double)bf2f(x[c]));
+  double n, m, m2;
+  merge_chunks(ws, nchunk, rows_per_chunk, R, C, c, n, m, m2);
+  const double v = fmax(m2 / R, 0.0);
+  const float mu = (float)m;
   mean[c] = mu; var[c] = (float)v;
   if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mu;
   if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)(R > 1 ? v * R / (R - 1) : v);   // unbiased, as nn.BatchNorm1d
 }
 
 // per-rank statistics for SyncBN: local[c] = mean, local[C+c] = M2 = sum (x - mean)^2, local[2C] = row count (int bits)
-__global__ void __launch_bounds__(256) bn_local_finalize_kernel(const bf16_t* __restrict__ x, const float* __restrict__ ws, int nchunk,
-                                                                int R, int C, float* __restrict__ local) {
+__global__ void __launch_bounds__(256) bn_local_finalize_kernel(const float* __restrict__ ws, int nchunk, int rows_per_chunk, int R,
+                                                                int C, float* __restrict__ local) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c == 0) local[2 * C] = __builtin_bit_cast(float, R);
   if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < nchunk; ++k) { s1 += ws[((long)k * 2) * C + c]; s2 += ws[((long)k * 2 + 1) * C + c]; }
-  const double m = s1 / R;
-  local[c] = (float)(m + (double)bf2f(x[c]));
-  local[C + c] = (float)fmax(s2 - s1 * m, 0.0);
+  double n, m, m2;
+  merge_chunks(ws, nchunk, rows_per_chunk, R, C, c, n, m, m2);
+  local[c] = (float)m;
+  local[C + c] = (float)fmax(m2, 0.0);
 }
 
 // Chan et al. pairwise merge of the ranks' (count, mean, M2) in rank order: every rank computes the same bits
@@ -186,17 +214,17 @@ __global__ void __launch_bounds__(256) bn_bwd_partial_kernel(const BnBwdP p) {
   const int r0 = blockIdx.y * p.rows_per_chunk, r1 = min(p.R, r0 + p.rows_per_chunk);
   float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
   if (c < p.C) {
-    float mu[2], rs[2], g[2], b[2];
+    float mu[2], rs[2], s[2], b[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) { mu[h] = p.mean[c + h]; rs[h] = __builtin_amdgcn_rsqf(p.var[c + h] + p.eps); g[h] = p.gamma[c + h]; b[h] = p.beta[c + h]; }
+    for (int h = 0; h < 2; ++h) { mu[h] = p.mean[c + h]; rs[h] = __builtin_amdgcn_rsqf(p.var[c + h] + p.eps); s[h] = p.gamma[c + h] * rs[h]; b[h] = p.beta[c + h]; }
     for (int r = r0 + w; r < r1; r += 4) {
       const unsigned int xv = *(const unsigned int*)(p.x + (long)r * p.ldx + c);
       const unsigned int dv = *(const unsigned int*)(p.dy + (long)r * p.lddy + c);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const float xh = (bf2f((bf16_t)(h ? (xv >> 16) : (xv & 0xffff))) - mu[h]) * rs[h];
+        const float xm = bf2f((bf16_t)(h ? (xv >> 16) : (xv & 0xffff))) - mu[h], xh = xm * rs[h];
         float d = bf2f((bf16_t)(h ? (dv >> 16) : (dv & 0xffff)));
-        if (p.relu && fmaf(xh, g[h], b[h]) <= 0.f) d = 0.f;
+        if (p.relu && fmaf(xm, s[h], b[h]) <= 0.f) d = 0.f;         // the forward's own expression: gate = (its output > 0)
         s1[h] += d; s2[h] = fmaf(d, xh, s2[h]);
       }
     }
@@ -244,11 +272,11 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const BnBwdP p) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int cc = c + 2 * k + h;
-      const float rs = __builtin_amdgcn_rsqf(p.var[cc] + p.eps), g = p.gamma[cc];
-      const float xh = (bf2f((bf16_t)(h ? (xv[k] >> 16) : (xv[k] & 0xffff))) - p.mean[cc]) * rs;
+      const float rs = __builtin_amdgcn_rsqf(p.var[cc] + p.eps), s = p.gamma[cc] * rs;
+      const float xm = bf2f((bf16_t)(h ? (xv[k] >> 16) : (xv[k] & 0xffff))) - p.mean[cc], xh = xm * rs;
       float d = bf2f((bf16_t)(h ? (dv[k] >> 16) : (dv[k] & 0xffff)));
-      if (p.relu && fmaf(xh, g, p.beta[cc]) <= 0.f) d = 0.f;
-      y[h] = g * rs * (d - fin[cc] * inv_n - xh * (fin[p.C + cc] * inv_n));
+      if (p.relu && fmaf(xm, s, p.beta[cc]) <= 0.f) d = 0.f;
+      y[h] = s * (d - fin[cc] * inv_n - xh * (fin[p.C + cc] * inv_n));
     }
     o[k] = pack2bf(y[0], y[1]);
   }
@@ -260,10 +288,10 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_rows_kernel(const BnBwdP p) 
   const int tpr = p.C >> 3, rpb = 256 / tpr;
   const int c = (threadIdx.x % tpr) * 8;
   const float inv_n = p.total ? 1.0f / (float)*p.total : 1.0f;
-  float rs[8], mu[8], g[8], b[8], f1[8], f2[8];
+  float rs[8], mu[8], s[8], b[8], f1[8], f2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    rs[e] = __builtin_amdgcn_rsqf(p.var[c + e] + p.eps); mu[e] = p.mean[c + e]; g[e] = p.gamma[c + e]; b[e] = p.beta[c + e];
+    rs[e] = __builtin_amdgcn_rsqf(p.var[c + e] + p.eps); mu[e] = p.mean[c + e]; s[e] = p.gamma[c + e] * rs[e]; b[e] = p.beta[c + e];
     f1[e] = p.fin[c + e] * inv_n; f2[e] = p.fin[p.C + c + e] * inv_n;
   }
   for (long r = (long)blockIdx.x * rpb + threadIdx.x / tpr; r < p.R; r += (long)gridDim.x * rpb) {
@@ -276,10 +304,10 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_rows_kernel(const BnBwdP p) 
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int e = 2 * k + h;
-        const float xh = (bf2f((bf16_t)(h ? (xv[k] >> 16) : (xv[k] & 0xffff))) - mu[e]) * rs[e];
+        const float xm = bf2f((bf16_t)(h ? (xv[k] >> 16) : (xv[k] & 0xffff))) - mu[e], xh = xm * rs[e];
         float d = bf2f((bf16_t)(h ? (dv[k] >> 16) : (dv[k] & 0xffff)));
-        if (p.relu && fmaf(xh, g[e], b[e]) <= 0.f) d = 0.f;
-        y[h] = g[e] * rs[e] * (d - f1[e] - xh * f2[e]);
+        if (p.relu && fmaf(xm, s[e], b[e]) <= 0.f) d = 0.f;
+        y[h] = s[e] * (d - f1[e] - xh * f2[e]);
       }
       o[k] = pack2bf(y[0], y[1]);
     }
@@ -301,8 +329,8 @@ __global__ void __launch_bounds__(256) group_max_bwd_kernel(const bf16_t* __rest
   for (int m = 0; m < M; ++m) {
     const unsigned int v = *(const unsigned int*)(fp + (long)m * ldf);
     const float a = bf2f((bf16_t)(v & 0xffff)), b = bf2f((bf16_t)(v >> 16));
-    if (a > best[0]) { best[0] = a; arg[0] = m; }
-    if (b > best[1]) { best[1] = b; arg[1] = m; }
+    if (a > best[0] || (a != a && best[0] == best[0])) { best[0] = a; arg[0] = m; }   // as torch.max(dim): the first
+    if (b > best[1] || (b != b && best[1] == best[1])) { best[1] = b; arg[1] = m; }   // maximum, or the first NaN
   }
   const unsigned int dv = *(const unsigned int*)(dg + g * lddg + c);
   const float d0 = bf2f((bf16_t)(dv & 0xffff)), d1 = bf2f((bf16_t)(dv >> 16));
@@ -353,7 +381,7 @@ extern "C" int vl_bn_stats(const void* x, long ldx, int R, int C, float* ws, int
   if (!ws_shape_ok(R, nchunk) || C <= 0 || (C & 1) || (ldx & 1)) return vl_set_error("vl_bn_stats: need R>=1, even C and ldx, 1<=nchunk<=65535");
   const int rpc = (R + nchunk - 1) / nchunk;
   hipLaunchKernelGGL(bn_partial_kernel, dim3((C + 127) / 128, nchunk), dim3(256), 0, stream, (const bf16_t*)x, ldx, R, C, rpc, ws);
-  hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, (const bf16_t*)x, ws, nchunk, R, C, mean, var,
+  hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, ws, nchunk, rpc, R, C, mean, var,
                      running_mean, running_var, momentum);
   VL_HIP_OK(hipGetLastError());
   return 0;
@@ -390,7 +418,7 @@ extern "C" int vl_bn_stats_local(const void* x, long ldx, int R, int C, float* w
   if (!ws_shape_ok(R, nchunk) || C <= 0 || (C & 1) || (ldx & 1)) return vl_set_error("vl_bn_stats_local: need R>=1, even C and ldx, 1<=nchunk<=65535");
   const int rpc = (R + nchunk - 1) / nchunk;
   hipLaunchKernelGGL(bn_partial_kernel, dim3((C + 127) / 128, nchunk), dim3(256), 0, stream, (const bf16_t*)x, ldx, R, C, rpc, ws);
-  hipLaunchKernelGGL(bn_local_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, (const bf16_t*)x, ws, nchunk, R, C, local);
+  hipLaunchKernelGGL(bn_local_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, ws, nchunk, rpc, R, C, local);
   VL_HIP_OK(hipGetLastError());
   return 0;
 }

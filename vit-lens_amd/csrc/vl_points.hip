@@ -380,14 +380,17 @@ __global__ void __launch_bounds__(256) ball_group_kernel(const float* xyz, const
   }
 }
 
-// out[g, c] = max_{m < M} x[g*M + m, c]
+// out[g, c] = max_{m < M} x[g*M + m, c]; a NaN in the group makes it NaN, as torch.max (fmaxf would drop it)
 template <typename TOUT>
 __global__ void __launch_bounds__(256) group_max_kernel(const bf16_t* x, long ldx, TOUT* out, long ldo, long groups, int M, int C) {
   const long n = groups * C;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const long g = i / C; const int c = (int)(i - g * C);
     float m = -INFINITY;
-    for (int r = 0; r < M; ++r) m = fmaxf(m, bf2f(x[(g * M + r) * ldx + c]));
+    for (int r = 0; r < M; ++r) {
+      const float v = bf2f(x[(g * M + r) * ldx + c]);
+      if (v > m || v != v) m = v;              // once m is NaN, no comparison replaces it
+    }
     if constexpr (sizeof(TOUT) == 4) out[g * ldo + c] = m; else out[g * ldo + c] = f2bf(m);
   }
 }
