@@ -60,7 +60,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 601
+#define VL_ABI_VERSION 602
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -143,6 +143,24 @@ int vl_attn_fwd_f32(const float* q, const float* k, const float* v, const long* 
                     int B, int H, int Lq, int Lk, int dh, float scale, int causal, hipStream_t stream);
 int vl_im2col_f32(const float* x, float* patches, int N, int C, int H, int W, int kh, int kw, int sh, int sw,
                   int Kp, int transpose_hw, hipStream_t stream);
+/* The fp32 Lenses (audio, EEG, point cloud, depth with a Perceiver; vitlens_hip/f32.py):
+ *   vl_gemm_f32_ex   vl_gemm_f32 with two more epilogues; with geglu = res_pre = 0 and res_div = 1 it IS vl_gemm_f32 (same
+ *                    kernel, bit-identical outputs).
+ *                    res_pre = 1: out = act(alpha A W^T + bias + res[m / res_div]) - the residual (row stride ldo) joins BEFORE
+ *                    the activation, one row per res_div output rows (PointBERT's second conv, relu(f W3l^T + (max(f) W3g^T +
+ *                    b3)[group]), dvae.py:207-210).  res_div > 1 needs res_pre.
+ *                    geglu = 1: W rows interleaved (a_j, gate_j), N even, out f32 [M, N/2] = (acc + b)[2j] * gelu((acc + b)[2j+1])
+ *                    (erff, as the GELU epilogue; the Perceiver FeedForward, perceiver.py:85-102); no residual, act = none
+ *   vl_knn_group_f32 vl_knn_group (same selection code: the same neighbour sets) writing fp32 patches x_j - centre, zero padded
+ *                    to Kp (a multiple of 4)
+ *   vl_group_max_f32 vl_group_max on f32 input and output (NaN propagates, as torch.max)
+ *   vl_pad3_f32      centres [R,3] f32 -> f32 [R,Kp] zero padded (Kp a multiple of 4) */
+int vl_gemm_f32_ex(const float* A, const float* W, const float* bias, float* out, const float* res, int M, int N, int K,
+                   int lda, int ldw, int ldo, float alpha, int act, int res_div, int res_pre, int geglu, hipStream_t stream);
+int vl_knn_group_f32(const float* xyz, const int64_t* center_idx, int* nidx, float* patches, int B, int N, int G,
+                     int k, int Kp, hipStream_t stream);
+int vl_group_max_f32(const float* x, long ldx, float* out, long ldo, long groups, int M, int C, hipStream_t stream);
+int vl_pad3_f32(const float* c, float* out, long R, int Kp, hipStream_t stream);
 
 int vl_device_info(int device, char* arch, int arch_len, int* cus, int* clock_khz, long* hbm_bytes);
 

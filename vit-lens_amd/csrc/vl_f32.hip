@@ -5,7 +5,9 @@
 // who asks for fp32 evaluation gets fp32 features (1e-5 of the CPU path), not so that anything trains on it:
 //   gemm_f32_kernel   C = act(alpha A W^T + bias) (+ res): 128x128 tile per workgroup, 4 waves of 64x64 (2x2 blocks of
 //                     `v_mfma_f32_32x32x2_f32`), 16-deep k-slabs through LDS (rows padded to 17 floats: the fragment read -
-//                     32 consecutive rows at one k - touches 32 banks), next slab in registers under the MFMAs of the current
+//                     32 consecutive rows at one k - touches 32 banks), next slab in registers under the MFMAs of the current;
+//                     vl_gemm_f32_ex runs the same main loop with the Lenses' epilogues: the Perceiver FeedForward's GEGLU
+//                     and PointBERT's per-group residual added before the ReLU
 //   attn_f32_kernel   softmax(q k^T + causal mask) v with one THREAD per query row (q and the output row in registers), keys
 //                     and values staged in LDS 64 at a time and read as broadcasts, online softmax per 16 keys
 // Replaces nn.Linear / F.multi_head_attention_forward of VisionTransformer / TextTransformer (open_clip/transformer.py:
@@ -21,11 +23,19 @@ struct GemmF32P {
   const float* A; const float* W; const float* bias; const float* res; float* out;
   int M, N, K, lda, ldw, ldo;
   float alpha;
+  int res_div;            // F32_RES_PRE: residual row = m / res_div
 };
 
 constexpr int FT = 128, FK = 16, FP = FK + 1;
 
-template <int ACT>
+// epilogue forms of gemm_f32_kernel (the main loop is the same code for all of them)
+constexpr int F32_PLAIN = 0;     // act(alpha acc + bias) (+ res[m])                    vl_gemm_f32
+constexpr int F32_RES_PRE = 1;   // act(alpha acc + bias + res[m / res_div])            vl_gemm_f32_ex, res_pre
+constexpr int F32_GEGLU = 2;     // out[m, n/2] = (alpha acc + bias)[n] * gelu((alpha acc + bias)[n+1]), n even
+
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
+template <int ACT, int MODE = F32_PLAIN>
 __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmF32P p) {
   __shared__ float As[FT * FP], Ws[FT * FP];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -83,6 +93,26 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmF32P p) {
     }
   }
   // D[i][j]: lane owns column j = lane & 31 and the rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the 32 x 32 block
+  if constexpr (MODE == F32_GEGLU) {
+    // columns (2j, 2j + 1) = (a_j, gate_j) sit in lanes (2l, 2l + 1): the odd lane's value comes over by DPP (quad_perm
+    // [1,0,3,2]), no LDS.  Every lane runs the swap (no early exit before it); the even lane stores column n / 2
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn * 64 + j * 32 + fr;
+        const bool nok = n < p.N;
+        const float b = (p.bias && nok) ? p.bias[n] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+          const float v = fmaf(acc[i][j][r], p.alpha, b);
+          const float g = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
+          if (!(fr & 1) && nok && m < p.M) p.out[(size_t)m * p.ldo + (n >> 1)] = v * gelu_erf(g);
+        }
+      }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -95,9 +125,16 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmF32P p) {
         const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
         if (m >= p.M) continue;
         float v = fmaf(acc[i][j][r], p.alpha, b);
-        if constexpr (ACT == VL_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-        else if constexpr (ACT == VL_ACT_RELU) v = fmaxf(v, 0.f);
-        if (p.res) v += p.res[(size_t)m * p.ldo + n];
+        if constexpr (MODE == F32_RES_PRE) {
+          // the residual joins BEFORE the activation, one row per res_div output rows (a group's broadcast term)
+          if (p.res) v += p.res[(size_t)(m / p.res_div) * p.ldo + n];
+          if constexpr (ACT == VL_ACT_GELU) v = gelu_erf(v);
+          else if constexpr (ACT == VL_ACT_RELU) v = fmaxf(v, 0.f);
+        } else {
+          if constexpr (ACT == VL_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+          else if constexpr (ACT == VL_ACT_RELU) v = fmaxf(v, 0.f);
+          if (p.res) v += p.res[(size_t)m * p.ldo + n];
+        }
         p.out[(size_t)m * p.ldo + n] = v;
       }
     }
@@ -195,12 +232,41 @@ extern "C" int vl_gemm_f32(const float* A, const float* W, const float* bias, fl
   if (M <= 0 || N <= 0 || K <= 0) return vl_set_error("vl_gemm_f32: empty problem");
   if ((K & 3) || (lda & 3) || (ldw & 3)) return vl_set_error("vl_gemm_f32: K, lda, ldw must be multiples of 4 (16-byte rows)");
   if ((((uintptr_t)A) | ((uintptr_t)W)) & 15) return vl_set_error("vl_gemm_f32: operands must be 16-byte aligned");
-  const GemmF32P p{A, W, bias, res, out, M, N, K, lda, ldw, ldo, alpha};
+  const GemmF32P p{A, W, bias, res, out, M, N, K, lda, ldw, ldo, alpha, 1};
   const dim3 grid(((M + FT - 1) / FT) * ((N + FT - 1) / FT));
   if (act == VL_ACT_NONE) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_NONE>, grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_GELU) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_GELU>, grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_RELU) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_RELU>, grid, dim3(256), 0, stream, p);
   else return vl_set_error("vl_gemm_f32: act must be none, GELU or ReLU");
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
+}
+
+extern "C" int vl_gemm_f32_ex(const float* A, const float* W, const float* bias, float* out, const float* res, int M, int N,
+                              int K, int lda, int ldw, int ldo, float alpha, int act, int res_div, int res_pre, int geglu,
+                              hipStream_t stream) {
+  if (!geglu && !res_pre && res_div == 1)            // the defaults: vl_gemm_f32 itself (same kernel, same bits)
+    return vl_gemm_f32(A, W, bias, out, res, M, N, K, lda, ldw, ldo, alpha, act, stream);
+  if (!A || !W || !out) return vl_set_error("vl_gemm_f32_ex: null operand");
+  if (M <= 0 || N <= 0 || K <= 0) return vl_set_error("vl_gemm_f32_ex: empty problem");
+  if ((K & 3) || (lda & 3) || (ldw & 3)) return vl_set_error("vl_gemm_f32_ex: K, lda, ldw must be multiples of 4 (16-byte rows)");
+  if ((((uintptr_t)A) | ((uintptr_t)W)) & 15) return vl_set_error("vl_gemm_f32_ex: operands must be 16-byte aligned");
+  if (res_div < 1) return vl_set_error("vl_gemm_f32_ex: res_div must be >= 1");
+  if (geglu) {
+    if (res) return vl_set_error("vl_gemm_f32_ex: GEGLU takes no residual");
+    if (N & 1) return vl_set_error("vl_gemm_f32_ex: GEGLU needs an even N (interleaved (a, gate) rows)");
+    if (act != VL_ACT_NONE) return vl_set_error("vl_gemm_f32_ex: GEGLU is the activation (pass act = none)");
+    if (res_pre || res_div != 1) return vl_set_error("vl_gemm_f32_ex: GEGLU takes no residual options");
+  } else if (!res_pre) {
+    return vl_set_error("vl_gemm_f32_ex: res_div > 1 needs res_pre (the broadcast residual joins before the activation)");
+  }
+  const GemmF32P p{A, W, bias, res, out, M, N, K, lda, ldw, ldo, alpha, res_div};
+  const dim3 grid(((M + FT - 1) / FT) * ((N + FT - 1) / FT));
+  if (geglu) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_NONE, F32_GEGLU>), grid, dim3(256), 0, stream, p);
+  else if (act == VL_ACT_NONE) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_NONE, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
+  else if (act == VL_ACT_GELU) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_GELU, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
+  else if (act == VL_ACT_RELU) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_RELU, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
+  else return vl_set_error("vl_gemm_f32_ex: act must be none, GELU or ReLU");
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
 }

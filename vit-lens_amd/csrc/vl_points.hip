@@ -92,9 +92,16 @@ __device__ __forceinline__ unsigned int sort_key(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// centre-subtracted coordinate as a patch element: the bf16 GEMM operand of the 16-bit tokenizer, or the fp32 value itself
+// (precision="fp32" inference).  The selection is the same code for both: the neighbour sets are identical
+template <typename TP> __device__ __forceinline__ TP patch_val(float v);
+template <> __device__ __forceinline__ bf16_t patch_val<bf16_t>(float v) { return f2bf(v); }
+template <> __device__ __forceinline__ float patch_val<float>(float v) { return v; }
+
 // one wave per centre; the N sortable distance keys of the wave live in LDS (conflict-free lane-strided access)
+template <typename TP>
 __global__ void __launch_bounds__(256) knn_group_kernel(const float* xyz, const int64_t* cidx, int N, int G, int k,
-                                                        int* nidx, bf16_t* patches, int Kp) {
+                                                        int* nidx, TP* patches, int Kp) {
   extern __shared__ unsigned int s_keys[];
   const int lane = threadIdx.x & 63;
   unsigned int* key = s_keys + (size_t)(threadIdx.x >> 6) * N;
@@ -144,8 +151,9 @@ __global__ void __launch_bounds__(256) knn_group_kernel(const float* xyz, const 
       const int slot = base + __popcll(bt & lt_mask);
       if (nidx) nidx[w * k + slot] = i;
       if (patches) {
-        bf16_t* o = patches + ((size_t)w * k + slot) * Kp;
-        o[0] = f2bf(__fsub_rn(P[i * 3], cx)); o[1] = f2bf(__fsub_rn(P[i * 3 + 1], cy)); o[2] = f2bf(__fsub_rn(P[i * 3 + 2], cz));
+        TP* o = patches + ((size_t)w * k + slot) * Kp;
+        o[0] = patch_val<TP>(__fsub_rn(P[i * 3], cx)); o[1] = patch_val<TP>(__fsub_rn(P[i * 3 + 1], cy));
+        o[2] = patch_val<TP>(__fsub_rn(P[i * 3 + 2], cz));
         for (int e = 3; e < Kp; ++e) o[e] = 0;
       }
     }
@@ -170,9 +178,9 @@ __device__ __forceinline__ int wave_sum_int(int v) {
 // its 96 KB twice through L1 / L2 (12.6 GB of cache traffic per 128 x 512 centres of 8192 points); the squared norms are the
 // same expression evaluated once per cloud instead of twice per centre.  Same arithmetic, same bits, same selection order.
 constexpr int KNN_CAP = 256;      // candidate list entries per wave (LDS-staged form)
-template <int NPL, int WPB, bool LDSC>
+template <int NPL, int WPB, bool LDSC, typename TP>
 __global__ void __launch_bounds__(WPB * 64) knn_group_reg_kernel(const float* xyz, const int64_t* cidx, int G, int k, int* nidx,
-                                                                bf16_t* patches, int Kp) {
+                                                                TP* patches, int Kp) {
   constexpr int N = NPL * 64;
   extern __shared__ __attribute__((aligned(16))) float s_cloud[];    // LDSC: [N * 3] points, [N] squared norms, [WPB][2][KNN_CAP] candidates
   const int lane = threadIdx.x & 63;
@@ -217,8 +225,9 @@ __global__ void __launch_bounds__(WPB * 64) knn_group_reg_kernel(const float* xy
   auto emit = [&](int i, int slot) {
     if (nidx) nidx[w * k + slot] = i;
     if (patches) {
-      bf16_t* o = patches + ((size_t)w * k + slot) * Kp;
-      o[0] = f2bf(__fsub_rn(coord(i, 0), cx)); o[1] = f2bf(__fsub_rn(coord(i, 1), cy)); o[2] = f2bf(__fsub_rn(coord(i, 2), cz));
+      TP* o = patches + ((size_t)w * k + slot) * Kp;
+      o[0] = patch_val<TP>(__fsub_rn(coord(i, 0), cx)); o[1] = patch_val<TP>(__fsub_rn(coord(i, 1), cy));
+      o[2] = patch_val<TP>(__fsub_rn(coord(i, 2), cz));
       for (int e = 3; e < Kp; ++e) o[e] = 0;
     }
   };
@@ -381,25 +390,27 @@ __global__ void __launch_bounds__(256) ball_group_kernel(const float* xyz, const
 }
 
 // out[g, c] = max_{m < M} x[g*M + m, c]; a NaN in the group makes it NaN, as torch.max (fmaxf would drop it)
-template <typename TOUT>
-__global__ void __launch_bounds__(256) group_max_kernel(const bf16_t* x, long ldx, TOUT* out, long ldo, long groups, int M, int C) {
+template <typename TOUT, typename TIN = bf16_t>
+__global__ void __launch_bounds__(256) group_max_kernel(const TIN* x, long ldx, TOUT* out, long ldo, long groups, int M, int C) {
   const long n = groups * C;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const long g = i / C; const int c = (int)(i - g * C);
     float m = -INFINITY;
     for (int r = 0; r < M; ++r) {
-      const float v = bf2f(x[(g * M + r) * ldx + c]);
+      float v;
+      if constexpr (sizeof(TIN) == 4) v = x[(g * M + r) * ldx + c]; else v = bf2f(x[(g * M + r) * ldx + c]);
       if (v > m || v != v) m = v;              // once m is NaN, no comparison replaces it
     }
     if constexpr (sizeof(TOUT) == 4) out[g * ldo + c] = m; else out[g * ldo + c] = f2bf(m);
   }
 }
 
-// centres [R,3] f32 -> bf16 [R,Kp] zero padded (operand of the pos_embed MLP's first Linear)
-__global__ void __launch_bounds__(256) pad3_kernel(const float* c, bf16_t* out, long R, int Kp) {
+// centres [R,3] f32 -> bf16 (or f32) [R,Kp] zero padded (operand of the pos_embed MLP's first Linear)
+template <typename TP>
+__global__ void __launch_bounds__(256) pad3_kernel(const float* c, TP* out, long R, int Kp) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < R * Kp; i += (long)gridDim.x * 256) {
     const long r = i / Kp; const int e = (int)(i - r * Kp);
-    out[i] = e < 3 ? f2bf(c[r * 3 + e]) : (bf16_t)0;
+    out[i] = e < 3 ? patch_val<TP>(c[r * 3 + e]) : (TP)0;
   }
 }
 
@@ -468,11 +479,11 @@ extern "C" int vl_fps(const float* xyz, const int64_t* start, int64_t* idx, floa
   return 0;
 }
 
-extern "C" int vl_knn_group(const float* xyz, const int64_t* center_idx, int* nidx, void* patches, int B, int N, int G,
-                            int k, int Kp, hipStream_t stream) {
-  if (B <= 0 || G <= 0 || k <= 0 || k > N) return vl_set_error("vl_knn_group: bad shape");
-  if ((N & 63) || ((long)B * G) % 4) return vl_set_error("vl_knn_group: N must be a multiple of 64 and B*G of 4");
-  if (patches && Kp < 3) return vl_set_error("vl_knn_group: Kp < 3");
+// the launch of both kNN entries: TP = bf16_t (the 16-bit tokenizer's GEMM operand) or float (precision="fp32" inference);
+// shapes are checked by the entries
+template <typename TP>
+static int knn_launch(const float* xyz, const int64_t* center_idx, int* nidx, TP* patches, int B, int N, int G, int k, int Kp,
+                      hipStream_t stream) {
   const dim3 grid((unsigned)(((long)B * G) / 4)), block(256);
   // keys in registers for the cloud sizes of the configs (8192: the Lens, 1024 / 2048: ablations, 256: the tests); with 8
   // centres of one cloud per workgroup the cloud itself is staged in LDS (16 bytes per point)
@@ -481,14 +492,14 @@ extern "C" int vl_knn_group(const float* xyz, const int64_t* center_idx, int* ni
 #define VL_KNN_REG(NPLV)                                                                                                       \
   case NPLV * 64:                                                                                                              \
     if (lds_ok) {                                                                                                              \
-      static const hipError_t attr = hipFuncSetAttribute((const void*)knn_group_reg_kernel<NPLV, 8, true>,                     \
+      static const hipError_t attr = hipFuncSetAttribute((const void*)knn_group_reg_kernel<NPLV, 8, true, TP>,                 \
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, NPLV * 64 * 16 + 8 * KNN_CAP * 8);          \
       VL_HIP_OK(attr);                                                                                                         \
-      hipLaunchKernelGGL((knn_group_reg_kernel<NPLV, 8, true>), dim3((unsigned)(((long)B * G) / 8)), dim3(512),                \
-                         (size_t)NPLV * 64 * 16 + 8 * KNN_CAP * 8, stream, xyz, center_idx, G, k, nidx, (bf16_t*)patches, Kp);                   \
+      hipLaunchKernelGGL((knn_group_reg_kernel<NPLV, 8, true, TP>), dim3((unsigned)(((long)B * G) / 8)), dim3(512),            \
+                         (size_t)NPLV * 64 * 16 + 8 * KNN_CAP * 8, stream, xyz, center_idx, G, k, nidx, patches, Kp);          \
     } else {                                                                                                                   \
-      hipLaunchKernelGGL((knn_group_reg_kernel<NPLV, 4, false>), grid, block, 0, stream, xyz, center_idx, G, k, nidx,          \
-                         (bf16_t*)patches, Kp);                                                                                \
+      hipLaunchKernelGGL((knn_group_reg_kernel<NPLV, 4, false, TP>), grid, block, 0, stream, xyz, center_idx, G, k, nidx,      \
+                         patches, Kp);                                                                                         \
     }                                                                                                                          \
     VL_HIP_OK(hipGetLastError());                                                                                              \
     return 0;
@@ -498,11 +509,27 @@ extern "C" int vl_knn_group(const float* xyz, const int64_t* center_idx, int* ni
   }
   const size_t smem = (size_t)4 * N * sizeof(unsigned int);
   if (smem > 160 * 1024) return vl_set_error("vl_knn_group: at most 10240 points per cloud");
-  static bool attr = false;
-  if (!attr) { VL_HIP_OK(hipFuncSetAttribute((const void*)knn_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
-  hipLaunchKernelGGL(knn_group_kernel, grid, block, smem, stream, xyz, center_idx, N, G, k, nidx, (bf16_t*)patches, Kp);
+  static const hipError_t attr = hipFuncSetAttribute((const void*)knn_group_kernel<TP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  VL_HIP_OK(attr);
+  hipLaunchKernelGGL(knn_group_kernel<TP>, grid, block, smem, stream, xyz, center_idx, N, G, k, nidx, patches, Kp);
   VL_HIP_OK(hipGetLastError());
   return 0;
+}
+
+extern "C" int vl_knn_group(const float* xyz, const int64_t* center_idx, int* nidx, void* patches, int B, int N, int G,
+                            int k, int Kp, hipStream_t stream) {
+  if (B <= 0 || G <= 0 || k <= 0 || k > N) return vl_set_error("vl_knn_group: bad shape");
+  if ((N & 63) || ((long)B * G) % 4) return vl_set_error("vl_knn_group: N must be a multiple of 64 and B*G of 4");
+  if (patches && Kp < 3) return vl_set_error("vl_knn_group: Kp < 3");
+  return knn_launch<bf16_t>(xyz, center_idx, nidx, (bf16_t*)patches, B, N, G, k, Kp, stream);
+}
+
+extern "C" int vl_knn_group_f32(const float* xyz, const int64_t* center_idx, int* nidx, float* patches, int B, int N, int G,
+                                int k, int Kp, hipStream_t stream) {
+  if (B <= 0 || G <= 0 || k <= 0 || k > N) return vl_set_error("vl_knn_group_f32: bad shape");
+  if ((N & 63) || ((long)B * G) % 4) return vl_set_error("vl_knn_group_f32: N must be a multiple of 64 and B*G of 4");
+  if (patches && (Kp < 4 || (Kp & 3))) return vl_set_error("vl_knn_group_f32: Kp must be a multiple of 4 (the fp32 GEMM's K)");
+  return knn_launch<float>(xyz, center_idx, nidx, patches, B, N, G, k, Kp, stream);
 }
 
 extern "C" int vl_ball_group(const float* xyz, const float* feats, const int64_t* center_idx, int* idx, void* patches, int B,
@@ -527,9 +554,25 @@ extern "C" int vl_group_max(const void* x, long ldx, void* out, int out_dtype, l
   return 0;
 }
 
+extern "C" int vl_group_max_f32(const float* x, long ldx, float* out, long ldo, long groups, int M, int C, hipStream_t stream) {
+  if (groups <= 0 || M <= 0 || C <= 0) return vl_set_error("vl_group_max_f32: bad shape");
+  if (!x || !out) return vl_set_error("vl_group_max_f32: null operand");
+  hipLaunchKernelGGL((group_max_kernel<float, float>), dim3(grid_for(groups * C)), dim3(256), 0, stream, x, ldx, out, ldo, groups, M, C);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int vl_pad3_bf16(const float* c, void* out, long R, int Kp, hipStream_t stream) {
   if (R <= 0 || Kp < 3) return vl_set_error("vl_pad3_bf16: bad shape");
-  hipLaunchKernelGGL(pad3_kernel, dim3(grid_for(R * Kp)), dim3(256), 0, stream, c, (bf16_t*)out, R, Kp);
+  hipLaunchKernelGGL(pad3_kernel<bf16_t>, dim3(grid_for(R * Kp)), dim3(256), 0, stream, c, (bf16_t*)out, R, Kp);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int vl_pad3_f32(const float* c, float* out, long R, int Kp, hipStream_t stream) {
+  if (R <= 0 || Kp < 4 || (Kp & 3)) return vl_set_error("vl_pad3_f32: bad shape (Kp a multiple of 4)");
+  if (!c || !out) return vl_set_error("vl_pad3_f32: null operand");
+  hipLaunchKernelGGL(pad3_kernel<float>, dim3(grid_for(R * Kp)), dim3(256), 0, stream, c, out, R, Kp);
   VL_HIP_OK(hipGetLastError());
   return 0;
 }

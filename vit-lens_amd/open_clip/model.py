@@ -471,27 +471,40 @@ class VisionTransformer(nn.Module):
             return feat.clone()
         f32 = self._engine_f32() if (self.arith_f32 and not self.training) else None
         if f32 is not None:
-            return f32.encode(x)
+            return f32.encode(x, **kwargs)
         eng = self.engine()
         if self.modality in ("image", "tactile"):
             return eng.encode_image(x)
         return eng.encode(x, **kwargs)
 
     def _engine_f32(self):
-        """The fp32-arithmetic executor of this tower (precision="fp32", inference), or None where it does not exist: the
-        Perceiver / point-cloud / audio / EEG Lenses and head dims other than 32 / 64 stay on the 16-bit engines."""
+        """The fp32-arithmetic executor of this tower (precision="fp32", inference), or None where it does not exist: the pnsa
+        point tokenizer and head dims other than 32 / 64 (tower, Perceiver cross or latent attention) stay on the 16-bit engines.
+        image / tactile / depth with an identity Perceiver: VitEngineF32; audio / EEG / point cloud (pointbert) / depth with a
+        Perceiver: LensEngineF32 (vitlens_hip/f32.py)."""
         from vitlens_hip import f32 as F
-        simple = self.modality in ("image", "tactile") or (self.modality == "depth" and self.perceiver_identity)
-        if not simple or not F.f32_supported(self.cfg.width, self.heads) or self.class_embedding.device.type != "cuda":
+        if self.class_embedding.device.type != "cuda":
             return None
-        # (the device is part of the key: after `.to(other_gpu)` the cached engine's operands live on the old device)
-        vers = (str(self.class_embedding.device), {n: p._version for n, p in self.named_parameters()})
+        simple = self.modality in ("image", "tactile") or (self.modality == "depth" and self.perceiver_identity)
+        tower, lens = self._cfgs()
+        if simple:
+            if not F.f32_supported(self.cfg.width, self.heads):
+                return None
+        elif not F.f32_lens_supported(tower, lens):
+            return None
+        # (the device is part of the key: after `.to(other_gpu)` the cached engine's operands live on the old device; the
+        # buffers too: the point tokenizer folds the BatchNorm running statistics into its operands)
+        vers = (str(self.class_embedding.device), {n: p._version for n, p in self.named_parameters()},
+                {n: b._version for n, b in self.named_buffers()})
         if self._f32_engine is None or vers != self._f32_vers:
             sd = {("t." + k): v for k, v in self.state_dict().items()}
-            tower, lens = self._cfgs()
-            self._f32_engine = F.VitEngineF32(sd, "t.", tower, self.class_embedding.device, depth=self.modality == "depth",
-                                              use_orig_pos=True if lens is None else lens.use_orig_pos,
-                                              disable_adapter_pos=False if lens is None else lens.disable_adapter_pos)
+            dev = self.class_embedding.device
+            if simple:
+                self._f32_engine = F.VitEngineF32(sd, "t.", tower, dev, depth=self.modality == "depth",
+                                                  use_orig_pos=True if lens is None else lens.use_orig_pos,
+                                                  disable_adapter_pos=False if lens is None else lens.disable_adapter_pos)
+            else:
+                self._f32_engine = F.LensEngineF32(sd, "t.", tower, lens, dev)
             self._f32_vers = vers
         return self._f32_engine
 
@@ -663,9 +676,11 @@ class TriCLIP(nn.Module):
             self.precision_effective = ("eval mode, no autograd graph: true fp32 arithmetic (fp32-input MFMA, vitlens_hip/f32.py; 1/16 of "
                                         "the bf16 matrix rate: ViT-L/14 584 img/s against 5 425 with bf16 operands - pass "
                                         "precision='amp_bf16' for throughput) for the "
-                                        "image / tactile / depth(identity Perceiver) towers and the text tower with head dim 32 or 64; "
-                                        "otherwise (train mode, towers with trainable parameters, Perceiver / audio / point-cloud / EEG "
-                                        "Lenses): " + self.precision_effective)
+                                        "image / tactile towers, the text tower and the Lenses - depth (identity Perceiver or not), "
+                                        "audio, EEG and point cloud (pointbert tokenizer: FPS, kNN patches, BatchNorm folded in fp32, "
+                                        "group maxima in fp32) with their Perceivers - wherever every attention head dim is 32 or 64; "
+                                        "otherwise (train mode, grad-enabled calls of towers with trainable parameters, the pnsa point "
+                                        "tokenizer, other head dims): " + self.precision_effective)
             warnings.warn("precision='fp32': fp32 arithmetic runs for eval-mode inference (model.eval(), no trainable tower in the "
                           "call); training keeps bf16 matrix operands with fp32 accumulation on fp32 residual / gradient streams - "
                           "the MI355X path has no fp32 backward.  See model.precision_effective.", UserWarning, stacklevel=3)

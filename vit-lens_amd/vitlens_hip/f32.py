@@ -5,16 +5,18 @@ chains, 157 TFLOP/s peak = 1/16 of the bf16 rate), attention in fp32 on the VALU
 assembly / embedding on the existing f32 kernels.  Forward only - a tower whose parameters require grad under an enabled
 autograd keeps the bf16-operand trainers with fp32 residual and gradient streams (open_clip/model.py says so in
 `precision_effective`).  Covered: the image / tactile towers (conv stem + ViT), the depth Lens with an identity Perceiver
-(DepthTokenizer -> ViT) and the text tower, with head dim 32 or 64; anything else stays on the 16-bit engines.
+(DepthTokenizer -> ViT), the text tower, and the Lenses with a Perceiver - audio, EEG, point cloud (pointbert) and depth
+(LensEngineF32) - with every attention head dim 32 or 64 (f32_lens_supported); anything else stays on the 16-bit engines.
 
 Reference ops: VisionTransformer.forward (open_clip/transformer.py:723-792), ResidualAttentionBlock (:254-272),
-TriCLIP.encode_text (open_clip/model.py:528-540)."""
+TriCLIP.encode_text (open_clip/model.py:528-540), Perceiver.forward (open_clip/perceiver.py:289-328), PointTokenizer.forward
+(modal_3d/models/pointbert/point_encoder.py:350-362)."""
 from typing import Dict, Optional
 
 import torch
 
 from . import ops
-from .engine import TextCfg, TowerCfg, _dev, _pad64
+from .engine import LensCfg, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64
 
 
 def f32_supported(width: int, heads: int) -> bool:
@@ -50,17 +52,66 @@ def run_blocks_f32(blocks, ws: _Ws, B, L, D, H, causal=False):
         ops.gemm_f32(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x)
 
 
-def _conv_as_gemm_f32(w: torch.Tensor, device) -> torch.Tensor:
-    """Conv2d weight [O,C,kh,kw] -> f32 [O, Kp] (K zero-padded to a multiple of 64, as the 16-bit stem lays it out)."""
+def conv_as_gemm_f32(w: torch.Tensor, device="cpu") -> torch.Tensor:
+    """Conv weight [O, C, *kernel] -> f32 [O, Kp] (K = C * prod(kernel) zero-padded to a multiple of 64, as the 16-bit stem
+    lays it out; column order (c, i, j) = im2col's)."""
     O, K = w.shape[0], w[0].numel()
     out = torch.zeros(O, _pad64(K), dtype=torch.float32, device=device)
     out[:, :K] = w.detach().reshape(O, K).float().to(device)
     return out
 
 
+_conv_as_gemm_f32 = conv_as_gemm_f32
+
+
+def fold_bn_f32(w, b, gamma, beta, running_mean, running_var, eps=1e-5):
+    """Eval-mode BatchNorm after a 1x1 conv, folded into it IN FP32: bn(x W^T + b) = x (s W)^T + (b - mean) s + beta with
+    s = gamma / sqrt(var + eps) (dvae.py:183-194 in eval mode).  -> (W' [O, K], b' [O]) f32."""
+    f = lambda t: t.detach().float()
+    s = f(gamma) / torch.sqrt(f(running_var) + eps)
+    return f(w) * s[:, None], (f(b) - f(running_mean)) * s + f(beta)
+
+
+def pad_k4(w: torch.Tensor) -> torch.Tensor:
+    """[O, K] -> f32 [O, K rounded up to a multiple of 4], zero columns (the fp32 GEMM reads 16-byte rows)."""
+    K = w.shape[1]
+    out = torch.zeros(w.shape[0], (K + 3) // 4 * 4, dtype=torch.float32, device=w.device)
+    out[:, :K] = w.float()
+    return out
+
+
+def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
+    """Linear(D, 8D) rows [a ; gate] -> interleaved (a_j, gate_j) (the GEGLU epilogue's layout; engine._interleave_geglu)."""
+    return _interleave_geglu(w, b)
+
+
+def deinterleave_geglu(wi: torch.Tensor, bi: torch.Tensor):
+    """Inverse of interleave_geglu: rows (a_j, gate_j) -> [a ; gate]."""
+    return torch.cat([wi[0::2], wi[1::2]], 0), torch.cat([bi[0::2], bi[1::2]], 0)
+
+
+def f32_lens_supported(tower: TowerCfg, lens: Optional[LensCfg]) -> bool:
+    """Does LensEngineF32 take this `visual` tower?  Audio / EEG / pointbert point cloud / depth, every attention head dim 32 or
+    64 (tower, Perceiver cross and latent attention: the fp32 attention keeps a query row in registers), widths that the fp32
+    GEMM's 16-byte rows take.  pnsa, other head dims, other modalities: no (they keep the 16-bit engines)."""
+    if lens is None or lens.modality not in ("audio", "eeg", "pc", "depth"):
+        return False
+    if not f32_supported(tower.width, tower.heads):
+        return False
+    if lens.modality == "pc" and (lens.pc_tokenizer != "pointbert" or lens.perceiver_identity):
+        return False
+    if not lens.perceiver_identity:
+        if lens.cross_dim_head not in (32, 64) or lens.latent_dim_head not in (32, 64):
+            return False
+        if lens.latent_dim % 4 or lens.input_chan % 4:
+            return False
+    return True
+
+
 class VitEngineF32:
     """One ViT tower in fp32: `image.` / `visual.` of TriCLIP for the image and tactile modalities, and - with `depth=True` - the
-    depth Lens with an identity Perceiver (visual_adapter.conv1 + pos_emb in front of the same trunk)."""
+    depth Lens with an identity Perceiver (visual_adapter.conv1 + pos_emb in front of the same trunk).  A `visual.` tower of the
+    other Lenses has no stem of its own: LensEngineF32 feeds `trunk` the Perceiver's latents."""
 
     def __init__(self, sd, prefix: str, cfg: TowerCfg, device, depth: bool = False, use_orig_pos: bool = True,
                  disable_adapter_pos: bool = False):
@@ -74,31 +125,40 @@ class VitEngineF32:
         self.projT = _dev(sd[prefix + "proj"].t(), device) if prefix + "proj" in sd else None       # [E, D]
         self.blocks = [_block(sd, f"{prefix}transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
         self.pos2 = None
+        self.conv_w = None
         if depth:
             a = prefix + "visual_adapter."
             self.conv_w = _conv_as_gemm_f32(sd[a + "conv1.weight"], device)
             self.pos2 = _dev(sd[a + "pos_emb"].detach().float() * (0.0 if disable_adapter_pos else 1.0), device)
-        else:
+        elif prefix + "conv1.weight" in sd:
             self.conv_w = _conv_as_gemm_f32(sd[prefix + "conv1.weight"], device)
         self._ws = {}
 
-    def encode(self, x: torch.Tensor, normalize: bool = False, **kw) -> torch.Tensor:
+    def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos: bool = True) -> torch.Tensor:
+        """tokens f32 [B*T, D] -> un-normalised features f32 [B, E]: [cls; tokens] + pos (+ pos2) -> ln_pre -> blocks ->
+        ln_post(cls) @ proj (VitEngine.trunk in fp32; transformer.py:756-787)."""
         cfg = self.cfg
-        B, D, p = x.shape[0], cfg.width, cfg.patch
-        cols, gh, gw = ops.im2col_f32(x.to(self.device).contiguous().float(), p, p, p, p, self.conv_w.shape[1])
-        tok = ops.gemm_f32(cols, self.conv_w)
-        T = gh * gw
+        D = cfg.width
+        T = tokens.shape[0] // B
         L = T + 1
         key = (B, L)
         if key not in self._ws:
             self._ws[key] = _Ws(B, L, D, cfg.heads, int(D * cfg.mlp_ratio), self.device)
         ws = self._ws[key]
-        pos = self.pos if (self.use_orig_pos or not self.depth) else torch.zeros_like(self.pos)
-        ops.assemble_ln_pre(tok, self.cls, pos, self.pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
+        pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
+        ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
         run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
         ops.layernorm(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
-        f = pooled if self.projT is None else ops.gemm_f32(pooled, self.projT)
+        return pooled if self.projT is None else ops.gemm_f32(pooled, self.projT)
+
+    def encode(self, x: torch.Tensor, normalize: bool = False, **kw) -> torch.Tensor:
+        if self.conv_w is None:
+            raise RuntimeError("VitEngineF32.encode: this tower has no conv stem (a Lens tower: use LensEngineF32)")
+        p = self.cfg.patch
+        cols, gh, gw = ops.im2col_f32(x.to(self.device).contiguous().float(), p, p, p, p, self.conv_w.shape[1])
+        tok = ops.gemm_f32(cols, self.conv_w)
+        f = self.trunk(tok, x.shape[0], pos2=self.pos2, use_orig_pos=self.use_orig_pos or not self.depth)
         return ops.l2_normalize(f) if normalize else f
 
     encode_image = encode
@@ -134,4 +194,199 @@ class TextEngineF32:
         pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
         ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         f = ops.gemm_f32(pooled, self.projT)
+        return ops.l2_normalize(f) if normalize else f
+
+
+# ------------------------------------------------------------------------------------------------
+# The Lenses with a Perceiver (audio, EEG, point cloud, depth): tokenizer -> (+pos) -> Perceiver -> trunk, all in fp32
+# ------------------------------------------------------------------------------------------------
+def _attn_f32(sd, p, device, packed_self: bool):
+    d = {"to_out_w": _dev(sd[p + "to_out.weight"], device), "to_out_b": _dev(sd[p + "to_out.bias"], device)}
+    if packed_self:
+        d["qkv_w"] = _dev(torch.cat([sd[p + "to_q.weight"].detach().float(), sd[p + "to_kv.weight"].detach().float()], 0), device)
+    else:
+        d["q_w"], d["kv_w"] = _dev(sd[p + "to_q.weight"], device), _dev(sd[p + "to_kv.weight"], device)
+    return d
+
+
+def _ff_f32(sd, p, device):
+    w0, b0 = interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
+    return {"w0": _dev(w0, device), "b0": _dev(b0, device),
+            "w2": _dev(sd[p + "net.2.weight"], device), "b2": _dev(sd[p + "net.2.bias"], device)}
+
+
+class PerceiverEngineF32:
+    """Perceiver.forward(return_embeddings=True) (open_clip/perceiver.py:289-328) in fp32: LayerNorm of latents and context,
+    bias-free to_q / to_kv, cross attention (Lq = num_latents, Lk = context length) and latent self-attention on
+    vl_attn_fwd_f32, to_out + residual, the GEGLU FeedForward as ONE GEMM with the GEGLU epilogue (vl_gemm_f32_ex) + the
+    down projection with the residual.  weight_tie_layers: layers 1 .. depth-1 are one set of operands (perceiver.py:249-254)."""
+
+    def __init__(self, sd, prefix: str, cfg: LensCfg, device):
+        for dh in (cfg.cross_dim_head, cfg.latent_dim_head):
+            if dh not in (32, 64):
+                raise NotImplementedError("fp32 inference: Perceiver head dims must be 32 or 64")
+        self.cfg, self.device = cfg, torch.device(device)
+        self.latents = _dev(sd[prefix + "latents"], device)
+        ln = lambda q: (_dev(sd[q + ".weight"], device), _dev(sd[q + ".bias"], device))
+        self.layers = []
+        for i in range(cfg.depth):
+            if cfg.weight_tie_layers and i >= 2:
+                self.layers.append(self.layers[1])
+                continue
+            q = f"{prefix}layers.{i}."
+            lay = {"x_norm": ln(q + "0.norm"), "x_norm_ctx": ln(q + "0.norm_context"), "x_attn": _attn_f32(sd, q + "0.fn.", device, False),
+                   "x_ff_norm": ln(q + "1.norm"), "x_ff": _ff_f32(sd, q + "1.fn.", device), "selfs": []}
+            for j in range(cfg.self_per_cross):
+                r = f"{q}2.{j}."
+                lay["selfs"].append({"norm": ln(r + "0.norm"), "attn": _attn_f32(sd, r + "0.fn.", device, True),
+                                     "ff_norm": ln(r + "1.norm"), "ff": _ff_f32(sd, r + "1.fn.", device)})
+            self.layers.append(lay)
+        self._ws = {}
+
+    def _workspace(self, B, Tc):
+        key = (B, Tc)
+        if key in self._ws:
+            return self._ws[key]
+        c, dev = self.cfg, self.device
+        n, D = c.num_latents, c.latent_dim
+        xi, si = c.cross_heads * c.cross_dim_head, c.latent_heads * c.latent_dim_head
+        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        ws = {"x": f(B * n, D), "h": f(B * n, D), "ctx": f(B * Tc, c.input_chan), "xq2": f(B * n, xi), "xkv2": f(B * Tc, 2 * xi),
+              "xa": f(B * n, xi), "sqkv2": f(B * n, 3 * si), "sa": f(B * n, si), "hid": f(B * n, 4 * D)}
+        ws["xq"] = ops.heads_view(ws["xq2"], B, n, c.cross_heads, c.cross_dim_head)
+        ws["xk"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head)
+        ws["xv"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head, xi)
+        for i, nm in enumerate(("sq", "sk", "sv")):
+            ws[nm] = ops.heads_view(ws["sqkv2"], B, n, c.latent_heads, c.latent_dim_head, i * si)
+        self._ws[key] = ws
+        return ws
+
+    def _ff(self, ws, norm, ff, rows, D):
+        ops.layernorm(ws["x"], norm[0], norm[1], ws["h"], rows, D)
+        ops.gemm_f32_ex(ws["h"], ff["w0"], ff["b0"], out=ws["hid"], geglu=True)
+        ops.gemm_f32(ws["hid"], ff["w2"], ff["b2"], out=ws["x"], res=ws["x"])
+
+    def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
+        """data f32 [B*Tc, C] -> latents f32 [B*n, D] (a view of an internal workspace)."""
+        c = self.cfg
+        Tc, n, D = data.shape[0] // B, c.num_latents, c.latent_dim
+        ws = self._workspace(B, Tc)
+        ws["x"].view(B, n, D).copy_(self.latents)          # repeat(latents, 'n d -> b n d')
+        rows = B * n
+        for lay in self.layers:
+            a = lay["x_attn"]
+            ops.layernorm(ws["x"], lay["x_norm"][0], lay["x_norm"][1], ws["h"], rows, D)
+            ops.layernorm(data, lay["x_norm_ctx"][0], lay["x_norm_ctx"][1], ws["ctx"], B * Tc, c.input_chan)
+            ops.gemm_f32(ws["h"], a["q_w"], out=ws["xq2"])
+            ops.gemm_f32(ws["ctx"], a["kv_w"], out=ws["xkv2"])
+            ops.attn_fwd_f32(ws["xq"], ws["xk"], ws["xv"], ws["xa"], scale=c.cross_dim_head ** -0.5)
+            ops.gemm_f32(ws["xa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"])
+            self._ff(ws, lay["x_ff_norm"], lay["x_ff"], rows, D)
+            for sl in lay["selfs"]:
+                a = sl["attn"]
+                ops.layernorm(ws["x"], sl["norm"][0], sl["norm"][1], ws["h"], rows, D)
+                ops.gemm_f32(ws["h"], a["qkv_w"], out=ws["sqkv2"])
+                ops.attn_fwd_f32(ws["sq"], ws["sk"], ws["sv"], ws["sa"], scale=c.latent_dim_head ** -0.5)
+                ops.gemm_f32(ws["sa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"])
+                self._ff(ws, sl["ff_norm"], sl["ff"], rows, D)
+        return ws["x"]
+
+
+def point_tokenizer_operands_f32(sd, a: str, eps: float = 1e-5):
+    """fp32 operands of PointTokenizerEngineF32 from the reference's parameters (prefix `a` = "...visual_adapter."), on the
+    device the parameters live on: the two eval-mode BatchNorms folded in fp32 into the convs before them, the 3-channel
+    inputs zero-padded to K = 4, second_conv.0 split into its global (first half of the input channels: the broadcast group
+    maximum, dvae.py:207-209) and local halves."""
+    f = lambda k: sd[a + k].detach().float()
+    bn = lambda k: [f(k + n) for n in (".weight", ".bias", ".running_mean", ".running_var")]
+    w1, b1 = fold_bn_f32(f("encoder.first_conv.0.weight")[:, :, 0], f("encoder.first_conv.0.bias"), *bn("encoder.first_conv.1"), eps=eps)
+    w3, b3 = fold_bn_f32(f("encoder.second_conv.0.weight")[:, :, 0], f("encoder.second_conv.0.bias"), *bn("encoder.second_conv.1"), eps=eps)
+    half = w3.shape[1] // 2
+    return {"w1": pad_k4(w1), "b1": b1, "w2": f("encoder.first_conv.3.weight")[:, :, 0], "b2": f("encoder.first_conv.3.bias"),
+            "w3g": w3[:, :half], "w3l": w3[:, half:], "b3": b3,
+            "w4": f("encoder.second_conv.3.weight")[:, :, 0], "b4": f("encoder.second_conv.3.bias"),
+            "wr": f("reduce_dim.weight"), "br": f("reduce_dim.bias"),
+            "wp0": pad_k4(f("pos_embed.0.weight")), "bp0": f("pos_embed.0.bias"), "wp2": f("pos_embed.2.weight"), "bp2": f("pos_embed.2.bias")}
+
+
+class PointTokenizerEngineF32:
+    """PointTokenizer.forward (point_encoder.py:350-362) in fp32, BatchNorm in eval mode: FPS (vl_fps, bit-exact fp32), kNN
+    grouping into fp32 centred patches (vl_knn_group_f32: the 16-bit engine's neighbour sets), the mini-PointNet (dvae.py:
+    196-212) with the BatchNorms folded in fp32, the two group maxima in fp32, reduce_dim, and the centre MLP with exact GELU.
+    forward -> tokens + pos, f32 [B*G, trans_dim]."""
+
+    def __init__(self, sd, a: str, lens: LensCfg, device):
+        self.lens, self.device = lens, torch.device(device)
+        self.op = {k: _dev(v, device) for k, v in point_tokenizer_operands_f32(sd, a).items()}
+
+    def group(self, pts: torch.Tensor, fps_start=None, want_idx=False):
+        L = self.lens
+        pts = pts.to(self.device).contiguous().float()
+        if fps_start is None:   # misc.py:60 draws the first centre at random
+            fps_start = torch.randint(0, pts.shape[1], (pts.shape[0],), device=self.device, dtype=torch.long)
+        cidx, centers = ops.fps(pts, fps_start.to(self.device), L.pc_num_group)
+        patches, nidx = ops.knn_group_f32(pts, cidx, L.pc_group_size, Kp=self.op["w1"].shape[1], want_idx=want_idx)
+        return cidx, centers, patches, nidx
+
+    def forward(self, pts: torch.Tensor, fps_start=None) -> torch.Tensor:
+        M, o = self.lens.pc_group_size, self.op
+        _, centers, patches, _ = self.group(pts, fps_start)
+        h1 = ops.gemm_f32(patches, o["w1"], o["b1"], act=ops.ACT_RELU)                       # conv 3->128 + BN + ReLU
+        f = ops.gemm_f32(h1, o["w2"], o["b2"])                                               # conv 128->256
+        t = ops.gemm_f32(ops.group_max_f32(f, M), o["w3g"], o["b3"])                         # global half of conv 512->512 (+ BN)
+        h2 = ops.gemm_f32_ex(f, o["w3l"], None, res=t, res_div=M, res_pre=True, act=ops.ACT_RELU)   # + local half, ReLU
+        tok = ops.gemm_f32(ops.group_max_f32(ops.gemm_f32(h2, o["w4"], o["b4"]), M), o["wr"], o["br"])
+        p1 = ops.gemm_f32(ops.pad3_f32(centers, o["wp0"].shape[1]), o["wp0"], o["bp0"], act=ops.ACT_GELU)
+        return ops.gemm_f32(p1, o["wp2"], o["bp2"], res=tok)                                 # tokens + pos
+
+
+class LensEngineF32:
+    """The `visual.` tower of a Lens under precision="fp32", eval mode (VisionTransformer.forward, transformer.py:723-792):
+    audio (AST conv over [N,1,F,T] with f / t strides), EEG (PatchEmbed1D: Conv1d with bias), point cloud (pointbert) or depth
+    tokens -> + adapter pos -> PerceiverEngineF32 -> VitEngineF32.trunk.  Every matrix product on the fp32-input MFMA."""
+
+    def __init__(self, sd, prefix: str, tower: TowerCfg, lens: LensCfg, device):
+        if not f32_lens_supported(tower, lens):
+            raise NotImplementedError("fp32 inference: this Lens is not covered (f32_lens_supported)")
+        self.tower, self.lens, self.device = tower, lens, torch.device(device)
+        self.vit = VitEngineF32(sd, prefix, tower, device)
+        a = prefix + "visual_adapter."
+        scale = 0.0 if lens.disable_adapter_pos else 1.0
+        self.adapter_pos = self.points = None
+        if lens.modality in ("depth", "audio"):
+            self.conv_w, self.conv_b = conv_as_gemm_f32(sd[a + "conv1.weight"], device), None
+        elif lens.modality == "eeg":
+            self.conv_w = conv_as_gemm_f32(sd[a + "proj.weight"].unsqueeze(2), device)
+            self.conv_b = _dev(sd[a + "proj.bias"], device)
+        else:
+            self.points = PointTokenizerEngineF32(sd, a, lens, device)
+        if self.points is None:
+            self.adapter_pos = _dev(sd[a + "pos_emb"].detach().float() * scale, device)
+        self.perceiver = None if lens.perceiver_identity else PerceiverEngineF32(sd, prefix + "perceiver.", lens, device)
+
+    def tokens(self, x: torch.Tensor) -> torch.Tensor:
+        """-> tokens f32 [B*T, width] of the depth / audio / EEG tokenizer (without the adapter pos)."""
+        L, p = self.lens, self.tower.patch
+        x = x.to(self.device).contiguous().float()
+        if L.modality == "depth":       # DepthTokenizer.py:35-60
+            cols, _, _ = ops.im2col_f32(x, p, p, p, p, self.conv_w.shape[1])
+        elif L.modality == "audio":     # AST_tokenizer.py:44-57: [N,T,F] -> conv over [N,1,F,T]
+            cols, _, _ = ops.im2col_f32(x.unsqueeze(1), p, p, L.audio_fstride, L.audio_tstride, self.conv_w.shape[1], transpose_hw=True)
+        else:                           # EEG_tokenizer.py:35-42: windows of the time axis, column order (chan, tap)
+            cols, _, _ = ops.im2col_f32(x.unsqueeze(2), 1, L.eeg_window_size, 1, L.eeg_stride, self.conv_w.shape[1])
+        return ops.gemm_f32(cols, self.conv_w, self.conv_b)
+
+    def encode(self, x: torch.Tensor, normalize: bool = False, fps_start=None, **kw) -> torch.Tensor:
+        B = x.shape[0]
+        if self.points is not None:
+            tok = self.points.forward(x, fps_start)                   # tokens + pos, f32 [B*G, trans_dim]
+        else:
+            t = self.tokens(x)
+            if self.perceiver is None:
+                f = self.vit.trunk(t, B, pos2=self.adapter_pos, use_orig_pos=self.lens.use_orig_pos)
+                return ops.l2_normalize(f) if normalize else f
+            tok = torch.empty_like(t)
+            ops.add_rows(t, self.adapter_pos, tok, t.shape[0], t.shape[0] // B, t.shape[1])
+        lat = self.perceiver.forward(tok, B)
+        f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos)
         return ops.l2_normalize(f) if normalize else f

@@ -141,6 +141,31 @@ def attn_fwd_f32(q, k, v, out, lse=None, causal=False, scale=1.0):
     return out
 
 
+def gemm_f32_ex(a, w, bias=None, out=None, res=None, act=ACT_NONE, alpha=1.0, res_div=1, res_pre=False, geglu=False):
+    """vl_gemm_f32_ex: gemm_f32 with the epilogues of the fp32 Lenses.  res_pre: out = act(alpha a @ w.T + bias + res[m // res_div])
+    (res [ceil(M / res_div), N] with out's row stride).  geglu: w rows interleaved (a_j, gate_j) -> out f32 [M, N/2] =
+    a * gelu(gate); no residual.  With the defaults this is gemm_f32 (the library routes it to the same kernel)."""
+    _chk2d(a, "a", torch.float32); _chk2d(w, "w", torch.float32)
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"gemm_f32_ex: K mismatch {a.shape} vs {w.shape}")
+    if out is None:
+        out = torch.empty(M, N // 2 if geglu else N, device=a.device, dtype=torch.float32)
+    _chk2d(out, "out", torch.float32)
+    if res is not None:
+        _chk2d(res, "res", torch.float32)
+        if res.stride(0) != out.stride(0):
+            raise ValueError("gemm_f32_ex: residual must share out's row stride")
+        if res.shape[0] * res_div < M:
+            raise ValueError("gemm_f32_ex: residual has too few rows")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
+        raise ValueError("gemm_f32_ex: bias must be f32 [N]")
+    check(_lib.vl_gemm_f32_ex(_p(a), _p(w), _p(bias), _p(out), _p(res), M, N, K, a.stride(0), w.stride(0), out.stride(0),
+                              float(alpha), act, int(res_div), 1 if res_pre else 0, 1 if geglu else 0, _stream()))
+    return out
+
+
 def im2col_f32(x, kh, kw, sh, sw, Kp, transpose_hw=False):
     """im2col with f32 patches (the conv stem under precision="fp32")."""
     if x.dtype != torch.float32 or not x.is_contiguous():
@@ -699,6 +724,38 @@ def pad3(c, Kp=64):
     c = c.reshape(-1, 3).contiguous()
     out = torch.empty(c.shape[0], Kp, device=c.device, dtype=torch.bfloat16)
     check(_lib.vl_pad3_bf16(_p(c), _p(out), c.shape[0], Kp, _stream()))
+    return out
+
+
+# ---- fp32 point-tokenizer pieces (precision="fp32" inference, vitlens_hip/f32.py) ----
+def knn_group_f32(xyz, center_idx, k, Kp=4, want_idx=False, out=None):
+    """knn_group with fp32 patches [B*G*k, Kp] = x_j - centre, zero padded (Kp a multiple of 4); same neighbour sets."""
+    B, N, _ = xyz.shape
+    G = center_idx.shape[1]
+    nidx = torch.empty(B, G, k, device=xyz.device, dtype=torch.int32) if want_idx else None
+    patches = torch.empty(B * G * k, Kp, device=xyz.device, dtype=torch.float32) if out is None else out
+    if patches.dtype != torch.float32 or not patches.is_contiguous() or tuple(patches.shape) != (B * G * k, Kp):
+        raise ValueError(f"knn_group_f32: out must be contiguous f32 [{B * G * k}, {Kp}]")
+    check(_lib.vl_knn_group_f32(_p(xyz.contiguous()), _p(center_idx.contiguous()), _p(nidx), _p(patches), B, N, G, k, Kp,
+                                _stream()))
+    return patches, nidx
+
+
+def group_max_f32(x, M, out=None):
+    """out f32 [rows / M, C] = max over the M rows of each group of x f32 [rows, C] (NaN propagates, as torch.max)."""
+    _chk2d(x, "x", torch.float32)
+    groups = x.shape[0] // M
+    if out is None:
+        out = torch.empty(groups, x.shape[1], device=x.device, dtype=torch.float32)
+    _chk2d(out, "out", torch.float32)
+    check(_lib.vl_group_max_f32(_p(x), x.stride(0), _p(out), out.stride(0), groups, M, x.shape[1], _stream()))
+    return out
+
+
+def pad3_f32(c, Kp=4):
+    c = c.reshape(-1, 3).contiguous()
+    out = torch.empty(c.shape[0], Kp, device=c.device, dtype=torch.float32)
+    check(_lib.vl_pad3_f32(_p(c), _p(out), c.shape[0], Kp, _stream()))
     return out
 
 
