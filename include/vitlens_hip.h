@@ -133,7 +133,8 @@ int vl_attn_fwd_f16(const void* q, const void* k, const void* v, const long* str
  *   vl_gemm_f32      out f32 [M,N] = act(alpha * A[M,K] W[N,K]^T + bias) (+ res f32 [M,N], in place allowed); any M, N;
  *                    K, lda, ldw multiples of 4; act none / GELU (erff) / ReLU        (csrc/vl_f32.hip, v_mfma_f32_32x32x2_f32)
  *   vl_attn_fwd_f32  softmax(scale * q k^T [+ causal mask]) v on strided f32 [B,H,L,dh] views (strides as vl_attn_fwd_bf16,
- *                    multiples of 4), dh = 32 or 64; out f32 [B,Lq,H*dh]; lse optional (natural log)
+ *                    multiples of 4), dh = 32, 64 or a multiple of 8 in (64, 128]; out f32 [B,Lq,H*dh]; lse optional
+ *                    (natural log)
  *   vl_im2col_f32    vl_im2col_bf16 with f32 patches
  * LayerNorm, the token assembly and the text embedding already take f32 in and out.  Forward only: training under
  * precision="fp32" keeps bf16 operands with fp32 residual / gradient streams (vitlens_hip/f32.py says what runs). */

@@ -9,7 +9,14 @@
 //                     vl_gemm_f32_ex runs the same main loop with the Lenses' epilogues: the Perceiver FeedForward's GEGLU
 //                     and PointBERT's per-group residual added before the ReLU
 //   attn_f32_kernel   softmax(q k^T + causal mask) v with one THREAD per query row (q and the output row in registers), keys
-//                     and values staged in LDS 64 at a time and read as broadcasts, online softmax per 16 keys
+//                     and values staged in LDS 64 at a time and read as broadcasts, online softmax per 16 keys; head dims 32, 64
+//   attn_f32_wide_kernel  the same algorithm for head dims 72 .. 128 (multiples of 8: ViT-H-14 80, ViT-bigG-14 104): a row
+//                     per thread would hold q[128] + o[128] = 256 VGPRs and leave one wave per SIMD, so each query row is split
+//                     over a quad of 4 lanes (DP/4 columns of q and of o per lane: 2 x 32 VGPRs at DP = 128), the partial dot
+//                     products summed across the quad by two DPP quad_perm adds in a fixed order; zero-padded to a multiple
+//                     of 16 in registers and LDS only.  98 / 126 / 160 / 180 VGPRs at DP = 80 / 96 / 112 / 128 (the compiler
+//                     keeps a 16-key block's LDS reads in flight on top of q and o), no scratch: 4 / 4 / 3 / 2 waves per SIMD,
+//                     against 234 VGPRs and one wave for the dh 64 kernel (tests/test_f32_wide_heads_host.py prints them)
 // Replaces nn.Linear / F.multi_head_attention_forward of VisionTransformer / TextTransformer (open_clip/transformer.py:
 // 226-272, 241-252) under precision="fp32".
 #include "vl_common.h"
@@ -224,6 +231,105 @@ __global__ void __launch_bounds__(256) attn_f32_kernel(const AttnF32P p) {
   if (p.lse) p.lse[((size_t)b * p.H + h) * p.Lq + qi] = m + __logf(l);
 }
 
+// Head dims 72 .. 128 (multiples of 8), zero-padded to DP = 80 / 96 / 112 / 128 in registers and LDS, never in memory: one
+// query row per QUAD of lanes (a DPP quad).  Lane `sub` of the quad holds the float4 chunks c = 0 .. DP/16 - 1 of the row at
+// columns 16c + 4 sub .. 16c + 4 sub + 3, of q and of the output (DP/2 floats: 64 VGPRs at DP = 128 where one thread per row
+// would need 256).  Each key's partial dot products are summed over the quad in a fixed butterfly (xor 1, then xor 2: every
+// lane ends with the same bits, (p0 + p1) + (p2 + p3)), so the softmax bookkeeping runs identically in the four lanes.  64 rows
+// per workgroup; keys and values staged in LDS 32 at a time (2 x 16 KiB at DP = 128), a wave's 16 quads reading one 64-byte
+// row segment per ds_read_b128 (a broadcast, no bank conflict).  Only the real dh columns are read and written.
+constexpr int AWK = 32;   // keys per LDS chunk
+constexpr int AWR = 64;   // query rows per workgroup
+
+__device__ __forceinline__ float quad_sum(float x) {
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));  // [1,0,3,2]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));  // [2,3,0,1]
+  return x;
+}
+
+template <int DP>
+__global__ void __launch_bounds__(256) attn_f32_wide_kernel(const AttnF32P p, const int dh) {
+  constexpr int NC = DP / 16;
+  __shared__ float Ks[AWK * DP], Vs[AWK * DP];
+  const int b = blockIdx.z, h = blockIdx.y, tid = threadIdx.x, sub = tid & 3;
+  const int qi = blockIdx.x * AWR + (tid >> 2);
+  const bool live = qi < p.Lq;                                       // the same for the four lanes of a quad
+  const float* Kg = p.k + b * p.s[3] + h * p.s[4];
+  const float* Vg = p.v + b * p.s[6] + h * p.s[7];
+  f32x4 q[NC], o[NC];
+  {
+    const float* Qg = p.q + b * p.s[0] + h * p.s[1] + (long)(live ? qi : p.Lq - 1) * p.s[2];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int col = 16 * c + 4 * sub;
+      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      if (col < dh) t = *(const f32x4*)(Qg + col);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { q[c][e] = t[e] * p.scale; o[c][e] = 0.f; }
+    }
+  }
+  float m = -INFINITY, l = 0.f;
+  const int k_hi = p.causal ? min(p.Lk, (int)(blockIdx.x * AWR + AWR)) : p.Lk;
+  for (int kc = 0; kc < k_hi; kc += AWK) {
+    __syncthreads();
+    for (int i = tid; i < AWK * DP / 4; i += 256) {
+      const int row = i / (DP / 4), col = (i % (DP / 4)) * 4;
+      f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+      if (kc + row < k_hi && col < dh) { kv = *(const f32x4*)(Kg + (long)(kc + row) * p.s[5] + col); vv = *(const f32x4*)(Vg + (long)(kc + row) * p.s[8] + col); }
+      *(f32x4*)(Ks + row * DP + col) = kv; *(f32x4*)(Vs + row * DP + col) = vv;
+    }
+    __syncthreads();
+    if (!live) continue;
+    for (int j0 = 0; j0 < AWK && kc + j0 < k_hi; j0 += 16) {
+      float s[16];
+      float bm = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int key = kc + j0 + j;
+        float acc = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const f32x4 kv = *(const f32x4*)(Ks + (j0 + j) * DP + 16 * c + 4 * sub);
+          acc = fmaf(q[c][0], kv[0], acc); acc = fmaf(q[c][1], kv[1], acc); acc = fmaf(q[c][2], kv[2], acc); acc = fmaf(q[c][3], kv[3], acc);
+        }
+        acc = quad_sum(acc);
+        s[j] = (key < k_hi && (!p.causal || key <= qi)) ? acc : -INFINITY;
+        bm = fmaxf(bm, s[j]);
+      }
+      if (bm == -INFINITY) continue;                                 // every key of the block masked for this row
+      if (bm > m) {
+        const float f = __expf(m - bm);                              // (m = -inf on the first block: f = 0)
+        l *= f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[c][e] *= f;
+        m = bm;
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float pj = __expf(s[j] - m);                           // masked keys: exp(-inf) = 0
+        l += pj;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const f32x4 vv = *(const f32x4*)(Vs + (j0 + j) * DP + 16 * c + 4 * sub);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[c][e] = fmaf(pj, vv[e], o[c][e]);
+        }
+      }
+    }
+  }
+  if (!live) return;
+  const float inv = 1.0f / l;
+  float* dst = p.out + ((size_t)b * p.Lq + qi) * (p.H * dh) + h * dh;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int col = 16 * c + 4 * sub;
+    if (col < dh) *(f32x4*)(dst + col) = f32x4{o[c][0] * inv, o[c][1] * inv, o[c][2] * inv, o[c][3] * inv};
+  }
+  if (p.lse && sub == 0) p.lse[((size_t)b * p.H + h) * p.Lq + qi] = m + __logf(l);
+}
+
 }  // namespace
 
 extern "C" int vl_gemm_f32(const float* A, const float* W, const float* bias, float* out, const float* res, int M, int N, int K,
@@ -274,13 +380,24 @@ extern "C" int vl_gemm_f32_ex(const float* A, const float* W, const float* bias,
 extern "C" int vl_attn_fwd_f32(const float* q, const float* k, const float* v, const long* strides, float* out, float* lse,
                                int B, int H, int Lq, int Lk, int dh, float scale, int causal, hipStream_t stream) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return vl_set_error("vl_attn_fwd_f32: empty problem");
-  if (dh != 32 && dh != 64) return vl_set_error("vl_attn_fwd_f32: head dim must be 32 or 64 (the query and its output row live in registers)");
+  const bool wide = dh > 64 && dh <= 128 && dh % 8 == 0;
+  if (dh != 32 && dh != 64 && !wide)
+    return vl_set_error("vl_attn_fwd_f32: head dim must be 32, 64 or a multiple of 8 in (64, 128]");
   if (!strides || !q || !k || !v || !out) return vl_set_error("vl_attn_fwd_f32: null operand");
   for (int i = 0; i < 9; ++i)
     if (strides[i] & 3) return vl_set_error("vl_attn_fwd_f32: operand strides must be multiples of 4 elements (16-byte rows)");
   if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)out)) & 15) return vl_set_error("vl_attn_fwd_f32: operands must be 16-byte aligned");
   AttnF32P p{q, k, v, {0}, out, lse, B, H, Lq, Lk, causal, scale};
   for (int i = 0; i < 9; ++i) p.s[i] = strides[i];
+  if (wide) {
+    const dim3 wgrid((Lq + AWR - 1) / AWR, H, B);
+    if (dh <= 80) hipLaunchKernelGGL(attn_f32_wide_kernel<80>, wgrid, dim3(256), 0, stream, p, dh);
+    else if (dh <= 96) hipLaunchKernelGGL(attn_f32_wide_kernel<96>, wgrid, dim3(256), 0, stream, p, dh);
+    else if (dh <= 112) hipLaunchKernelGGL(attn_f32_wide_kernel<112>, wgrid, dim3(256), 0, stream, p, dh);
+    else hipLaunchKernelGGL(attn_f32_wide_kernel<128>, wgrid, dim3(256), 0, stream, p, dh);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
+  }
   const dim3 grid((Lq + 255) / 256, H, B);
   if (dh == 64) hipLaunchKernelGGL(attn_f32_kernel<64>, grid, dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(attn_f32_kernel<32>, grid, dim3(256), 0, stream, p);

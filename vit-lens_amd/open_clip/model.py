@@ -479,7 +479,8 @@ class VisionTransformer(nn.Module):
 
     def _engine_f32(self):
         """The fp32-arithmetic executor of this tower (precision="fp32", inference), or None where it does not exist: the pnsa
-        point tokenizer and head dims other than 32 / 64 (tower, Perceiver cross or latent attention) stay on the 16-bit engines.
+        point tokenizer, tower head dims other than 32, 64 and the multiples of 8 in (64, 128] (ViT-H-14: 80, ViT-bigG-14: 104)
+        and Perceiver cross or latent head dims other than 32 / 64 stay on the 16-bit engines.
         image / tactile / depth with an identity Perceiver: VitEngineF32; audio / EEG / point cloud (pointbert) / depth with a
         Perceiver: LensEngineF32 (vitlens_hip/f32.py)."""
         from vitlens_hip import f32 as F
@@ -678,9 +679,10 @@ class TriCLIP(nn.Module):
                                         "precision='amp_bf16' for throughput) for the "
                                         "image / tactile towers, the text tower and the Lenses - depth (identity Perceiver or not), "
                                         "audio, EEG and point cloud (pointbert tokenizer: FPS, kNN patches, BatchNorm folded in fp32, "
-                                        "group maxima in fp32) with their Perceivers - wherever every attention head dim is 32 or 64; "
-                                        "otherwise (train mode, grad-enabled calls of towers with trainable parameters, the pnsa point "
-                                        "tokenizer, other head dims): " + self.precision_effective)
+                                        "group maxima in fp32) with their Perceivers - wherever the tower / text head dim is 32, 64 or a "
+                                        "multiple of 8 in (64, 128] (ViT-H-14, ViT-bigG-14 included) and the Perceiver head dims are "
+                                        "32 or 64; otherwise (train mode, grad-enabled calls of towers with trainable parameters, the "
+                                        "pnsa point tokenizer, other head dims): " + self.precision_effective)
             warnings.warn("precision='fp32': fp32 arithmetic runs for eval-mode inference (model.eval(), no trainable tower in the "
                           "call); training keeps bf16 matrix operands with fp32 accumulation on fp32 residual / gradient streams - "
                           "the MI355X path has no fp32 backward.  See model.precision_effective.", UserWarning, stacklevel=3)

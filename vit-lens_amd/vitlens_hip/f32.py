@@ -1,12 +1,14 @@
 """True fp32 INFERENCE executors: what `precision="fp32"` of the reference's factory means (open_clip/factory.py:260-295,
 training/precision.py:5-12 - no autocast, fp32 parameters, fp32 nn.Linear / attention).  Rounds 1-4 ran bf16 operands under
 that precision and warned; these classes run every matrix product on gfx950's fp32-input MFMA (`vl_gemm_f32`, exact fmaf
-chains, 157 TFLOP/s peak = 1/16 of the bf16 rate), attention in fp32 on the VALU (`vl_attn_fwd_f32`), LayerNorm / token
+chains, 157 TFLOP/s peak = 1/16 of the bf16 rate), attention in fp32 on the VALU (`vl_attn_fwd_f32`: head dims 32, 64 and the
+multiples of 8 in (64, 128] - ViT-H-14's 80, ViT-bigG-14's 104), LayerNorm / token
 assembly / embedding on the existing f32 kernels.  Forward only - a tower whose parameters require grad under an enabled
 autograd keeps the bf16-operand trainers with fp32 residual and gradient streams (open_clip/model.py says so in
 `precision_effective`).  Covered: the image / tactile towers (conv stem + ViT), the depth Lens with an identity Perceiver
-(DepthTokenizer -> ViT), the text tower, and the Lenses with a Perceiver - audio, EEG, point cloud (pointbert) and depth
-(LensEngineF32) - with every attention head dim 32 or 64 (f32_lens_supported); anything else stays on the 16-bit engines.
+(DepthTokenizer -> ViT) and the text tower wherever the head dim is one of those (f32_supported), and the Lenses with a
+Perceiver - audio, EEG, point cloud (pointbert) and depth (LensEngineF32) - over such a trunk when the Perceiver's cross and
+latent head dims are 32 or 64 (f32_lens_supported); anything else stays on the 16-bit engines.
 
 Reference ops: VisionTransformer.forward (open_clip/transformer.py:723-792), ResidualAttentionBlock (:254-272),
 TriCLIP.encode_text (open_clip/model.py:528-540), Perceiver.forward (open_clip/perceiver.py:289-328), PointTokenizer.forward
@@ -19,8 +21,13 @@ from . import ops
 from .engine import LensCfg, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64
 
 
+def f32_head_dim_ok(dh: int) -> bool:
+    """The head dims vl_attn_fwd_f32 takes: 32, 64, or a multiple of 8 in (64, 128] (ViT-H-14: 80, ViT-bigG-14: 104)."""
+    return dh in (32, 64) or (64 < dh <= 128 and dh % 8 == 0)
+
+
 def f32_supported(width: int, heads: int) -> bool:
-    return width % heads == 0 and width // heads in (32, 64) and width % 4 == 0
+    return width % heads == 0 and f32_head_dim_ok(width // heads) and width % 4 == 0
 
 
 def _block(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
@@ -91,8 +98,8 @@ def deinterleave_geglu(wi: torch.Tensor, bi: torch.Tensor):
 
 
 def f32_lens_supported(tower: TowerCfg, lens: Optional[LensCfg]) -> bool:
-    """Does LensEngineF32 take this `visual` tower?  Audio / EEG / pointbert point cloud / depth, every attention head dim 32 or
-    64 (tower, Perceiver cross and latent attention: the fp32 attention keeps a query row in registers), widths that the fp32
+    """Does LensEngineF32 take this `visual` tower?  Audio / EEG / pointbert point cloud / depth, a trunk that f32_supported
+    takes (head dim 32, 64 or a multiple of 8 in (64, 128]), Perceiver cross and latent head dims 32 or 64, widths that the fp32
     GEMM's 16-byte rows take.  pnsa, other head dims, other modalities: no (they keep the 16-bit engines)."""
     if lens is None or lens.modality not in ("audio", "eeg", "pc", "depth"):
         return False
@@ -116,7 +123,7 @@ class VitEngineF32:
     def __init__(self, sd, prefix: str, cfg: TowerCfg, device, depth: bool = False, use_orig_pos: bool = True,
                  disable_adapter_pos: bool = False):
         if not f32_supported(cfg.width, cfg.heads):
-            raise NotImplementedError("fp32 inference: head dim must be 32 or 64")
+            raise NotImplementedError("fp32 inference: head dim must be 32, 64 or a multiple of 8 in (64, 128]")
         self.cfg, self.device, self.depth, self.use_orig_pos = cfg, torch.device(device), depth, use_orig_pos
         self.cls = _dev(sd[prefix + "class_embedding"], device)
         self.pos = _dev(sd[prefix + "positional_embedding"], device)
@@ -169,7 +176,7 @@ class TextEngineF32:
 
     def __init__(self, sd, cfg: TextCfg, device):
         if not f32_supported(cfg.width, cfg.heads):
-            raise NotImplementedError("fp32 inference: head dim must be 32 or 64")
+            raise NotImplementedError("fp32 inference: head dim must be 32, 64 or a multiple of 8 in (64, 128]")
         self.cfg, self.device = cfg, torch.device(device)
         self.tok = _dev(sd["token_embedding.weight"], device)
         self.pos = _dev(sd["positional_embedding"], device)

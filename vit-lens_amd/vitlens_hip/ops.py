@@ -125,7 +125,8 @@ def gemm_f32(a, w, bias=None, out=None, res=None, act=ACT_NONE, alpha=1.0):
 
 
 def attn_fwd_f32(q, k, v, out, lse=None, causal=False, scale=1.0):
-    """softmax(scale * q k^T [+ causal mask]) v on strided f32 [B,H,L,dh] views -> out f32 [B*Lq, H*dh] (dh = 32 or 64)."""
+    """softmax(scale * q k^T [+ causal mask]) v on strided f32 [B,H,L,dh] views -> out f32 [B*Lq, H*dh] (dh = 32, 64 or a
+    multiple of 8 in (64, 128]; strides multiples of 4; the library refuses anything else)."""
     import ctypes
     B, H, Lq, dh = q.shape
     Lk = k.shape[2]
