@@ -60,7 +60,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 602
+#define VL_ABI_VERSION 603
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -405,6 +405,34 @@ int vl_group_sum(const void* x, long ldx, void* out, long ldo, long groups, int 
 /* torch.optim.AdamW step on one tensor (grad is multiplied by grad_scale first); step counts from 1. */
 int vl_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int step, float grad_scale, hipStream_t stream);
+/* Squared 2-norm of a contiguous fp32 buffer, written to ONE device float: out[0] = sum_i x[i]^2.  Any n >= 0 (n = 0 writes
+ * 0), any 4-byte-aligned x.  Two stages on a grid that depends on n alone, combined in a fixed order: two calls on the same
+ * input agree bit for bit (no floating-point atomics).  The squares are accumulated in fp64 and rounded to fp32 once, so the
+ * result is the correctly rounded sum up to the fp64 accumulation error; NaN and +-inf propagate as in
+ * torch.linalg.vector_norm (a sum beyond FLT_MAX is +inf).  ws: vl_sumsq_ws_floats() floats from the caller, 8-byte aligned.
+ * With vl_adamw_multi_step this is torch.nn.utils.clip_grad_norm_(norm_type=2) without a host read of the norm. */
+long vl_sumsq_ws_floats(void);
+int vl_sumsq_f32(const float* x, long n, float* out, float* ws, hipStream_t stream);
+/* One slot of vl_adamw_multi_step's device table: one tensor of the optimizer (48 bytes, no padding besides `reserved`). */
+typedef struct vl_adamw_slot {
+  float* p; const float* g; float* m; float* v;  /* parameter, gradient, first and second moment: n contiguous floats each */
+  long n;
+  float weight_decay;                           /* per tensor: the no-decay group passes 0 */
+  int reserved;                                 /* 0 */
+} vl_adamw_slot;
+#define VL_ADAMW_MAX_SLOTS 1024
+/* vl_adamw_step on EVERY tensor of a table in ONE launch, with torch.nn.utils.clip_grad_norm_ folded in:
+ *   coef = min(1, max_norm / (grad_scale * sqrt(sumsq[0]) + 1e-6))       derived on the device by every thread
+ *   update of vl_adamw_step applied to g * grad_scale * coef             (the same __device__ function: with coef == 1 the
+ *                                                                         two entries produce the same bits)
+ * sumsq: device float, the squared norm of ALL gradients of the table as vl_sumsq_f32 leaves it (so grad_scale * sqrt(sumsq)
+ * is the norm of the gradient the optimizer sees - DDP's mean with grad_scale = 1 / world).  A NaN norm gives a NaN
+ * coefficient (clip_grad_norm_ with error_if_nonfinite=False).  The host never reads the norm or the coefficient.
+ * slots: DEVICE array of nslots <= VL_ADAMW_MAX_SLOTS entries; the work is split by element over the whole table (tiles of
+ * 2048 elements dealt to the workgroups), not by tensor.  norm_out: optional device float, receives the UNCLIPPED norm
+ * grad_scale * sqrt(sumsq).  max_norm > 0. */
+int vl_adamw_multi_step(const vl_adamw_slot* slots, int nslots, float lr, float beta1, float beta2, float eps, int step,
+                        float grad_scale, float max_norm, const float* sumsq, float* norm_out, hipStream_t stream);
 int vl_clamp_scalar(float* p, float lo, float hi, hipStream_t stream);
 int vl_axpy_f32(float* y, const float* x, float alpha, long n, hipStream_t stream);
 /* out[i] = x[i] * exp(log_scale[0]) * mul (in place allowed): `logit_scale.exp()` (open_clip/model.py:619, loss.py:125-127)

@@ -4,6 +4,9 @@
 //   vl_colsum             out[j] += sum_r a[r,j]                            (bias gradients)
 //   vl_gelu_bf16          y = gelu(u)                                       (recompute of the MLP hidden)
 //   vl_adamw_step         torch.optim.AdamW update (decoupled weight decay), one launch per tensor
+//   vl_sumsq_f32          squared 2-norm of the flat gradient buffer: two stages, fp64 partials, bit-reproducible
+//   vl_adamw_multi_step   the same update on a device table of tensors in ONE launch, with clip_grad_norm_'s coefficient
+//                         derived on the device from that squared norm (training/train.py: --grad-clip-norm)
 //   vl_clamp_scalar       logit_scale.clamp_(0, ln 100)   (training/train.py:248-249)
 // Autograd counterparts of open_clip/transformer.py:17-34 (LayerNorm), :226-234 (MLP) and of
 // `optim.AdamW` as configured in training/depth/depth_tri_main.py:394-419.
@@ -333,16 +336,159 @@ __global__ void __launch_bounds__(256) geglu_kernel(const bf16_t* h, bf16_t* y, 
 
 // AdamW (PyTorch semantics): p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
 //                            p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+// The update of ONE element, shared by the per-tensor and the multi-tensor kernel.  Which products the compiler fuses into
+// an fma depends on the code around the expression, so the roundings are spelled out - the ones adamw_kernel has always had
+// (1 - lr*wd and the first moment fused, everything else rounded per operation) - and contraction is off in here: both
+// kernels produce the same bits from the same inputs.
+struct AdamwC { float lr, b1, b2, eps, bc1, bc2_sqrt; };
+__device__ __forceinline__ void adamw_update(float& pi, const float gi, float& mi, float& vi, const AdamwC c, const float wd) {
+#pragma clang fp contract(off)
+  const float decay = fmaf(-c.lr, wd, 1.0f);
+  mi = fmaf(1.0f - c.b1, gi, c.b1 * mi);
+  vi = c.b2 * vi + ((1.0f - c.b2) * gi) * gi;
+  pi = pi * decay - ((c.lr / c.bc1) * mi) / (sqrtf(vi) / c.bc2_sqrt + c.eps);
+}
+
 __global__ void __launch_bounds__(256) adamw_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float b1,
                                                     float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+  const AdamwC c{lr, b1, b2, eps, bc1, bc2_sqrt};
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_update(pi, g[i] * gscale, mi, vi, c, wd);
     m[i] = mi; v[i] = vi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
     p[i] = pi;
+  }
+}
+
+// ---- global gradient norm: sum of squares in two stages, fixed grid, fixed combination order (no atomics) ----
+constexpr int kSumsqMaxBlocks = 2048;          // partials = workspace doubles
+constexpr int kSumsqPerBlock = 256 * 16;       // elements a workgroup takes per sweep of the grid (4 x 16 bytes per thread)
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over the 256 threads of a workgroup, the same order every time; valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v) {
+  __shared__ double sh[4];
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// x[0:head) scalar (up to the first 16-byte boundary), the aligned body in 16-byte loads, the last n4 % 4 elements scalar.
+// Squares are exact in fp64 and a thread's accumulators are fp64: the result is the fp64 sum, rounded to fp32 once.
+__global__ void __launch_bounds__(256) sumsq_partial_kernel(const float* x, long n, double* part) {
+  const long head = min(n, (long)((4 - (((uintptr_t)x >> 2) & 3)) & 3));
+  const f32x4* x4 = (const f32x4*)(x + head);
+  const long n4 = (n - head) >> 2;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  const long stride = (long)gridDim.x * 1024;
+  for (long base = (long)blockIdx.x * 1024; base < n4; base += stride) {
+    const long i = base + threadIdx.x;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    f32x4 t0, t1, t2, t3;
+    if (base + 1024 <= n4) {          // (workgroup-uniform)
+      t0 = x4[i]; t1 = x4[i + 256]; t2 = x4[i + 512]; t3 = x4[i + 768];
+    } else {                          // the one ragged span at the end of the body
+      t0 = i < n4 ? x4[i] : z; t1 = i + 256 < n4 ? x4[i + 256] : z;
+      t2 = i + 512 < n4 ? x4[i + 512] : z; t3 = i + 768 < n4 ? x4[i + 768] : z;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a0 = fma((double)t0[e], (double)t0[e], a0); a1 = fma((double)t1[e], (double)t1[e], a1);
+      a2 = fma((double)t2[e], (double)t2[e], a2); a3 = fma((double)t3[e], (double)t3[e], a3);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 8) {          // head and tail: fewer than 4 elements each
+    const long t = threadIdx.x < 4 ? threadIdx.x : head + n4 * 4 + (threadIdx.x - 4);
+    const bool live = threadIdx.x < 4 ? t < head : t < n;
+    if (live) a1 = fma((double)x[t], (double)x[t], a1);
+  }
+  const double s = block_sum_f64((a0 + a1) + (a2 + a3));
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(256) sumsq_final_kernel(const double* part, int nparts, float* out) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
+  const double s = block_sum_f64(a);
+  if (threadIdx.x == 0) out[0] = (float)s;
+}
+
+// ---- AdamW on a table of tensors in one launch, clip_grad_norm_'s coefficient derived from the device-side squared norm ----
+constexpr int kAdamTile = 2048;          // elements per tile: 256 threads x 2 x 16 bytes
+
+// clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1); a NaN norm stays NaN (fminf would drop it)
+__device__ __forceinline__ float clip_coef(const float norm, const float max_norm) {
+  const float c = max_norm / (norm + 1e-6f);
+  return c > 1.0f ? 1.0f : c;
+}
+
+__global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* slots, int nslots, AdamwC c, float gscale,
+                                                          float max_norm, const float* sumsq, float* norm_out) {
+  // first[s] = index of slot s's first tile; wave 0 scans the tile counts (16 consecutive slots per lane)
+  __shared__ int first[VL_ADAMW_MAX_SLOTS + 1];
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    int cnt[16], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int s = lane * 16 + k;
+      cnt[k] = s < nslots ? (int)((slots[s].n + kAdamTile - 1) / kAdamTile) : 0;
+      sum += cnt[k];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += t;
+    }
+    int run = incl - sum;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int s = lane * 16 + k;
+      if (s < nslots) first[s] = run;
+      run += cnt[k];
+    }
+    if (lane == 63) first[nslots] = incl;
+  }
+  __syncthreads();
+  const int ntiles = first[nslots];
+  const float norm = gscale * sqrtf(sumsq[0]);
+  const float gmul = clip_coef(norm, max_norm);
+  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int lo = 0, hi = nslots - 1;          // the last slot whose first tile is <= tile (empty slots own no tile)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (first[mid] <= tile) lo = mid; else hi = mid - 1;
+    }
+    const vl_adamw_slot S = slots[lo];
+    const long base = (long)(tile - first[lo]) * kAdamTile;
+    const int cntE = (int)min((long)kAdamTile, S.n - base);
+    float* p = S.p + base; const float* g = S.g + base; float* m = S.m + base; float* v = S.v + base;
+    const float wd = S.weight_decay;
+    const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+    const int nvec = vec ? (cntE >> 2) : 0;
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+      f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+      const f32x4 gg = ((const f32x4*)g)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adamw_update(pe, gg[e] * gscale * gmul, me, ve, c, wd);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)p)[i] = pp;
+    }
+    for (int i = nvec * 4 + threadIdx.x; i < cntE; i += 256) {
+      float pe = p[i], me = m[i], ve = v[i];
+      adamw_update(pe, g[i] * gscale * gmul, me, ve, c, wd);
+      m[i] = me; v[i] = ve; p[i] = pe;
+    }
   }
 }
 
@@ -485,6 +631,36 @@ extern "C" int vl_adamw_step(float* p, const float* g, float* m, float* v, long 
   const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
                      bc1, bc2s, grad_scale);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" long vl_sumsq_ws_floats(void) { return 2L * kSumsqMaxBlocks; }
+
+extern "C" int vl_sumsq_f32(const float* x, long n, float* out, float* ws, hipStream_t stream) {
+  if (n < 0) return vl_set_error("vl_sumsq_f32: negative n");
+  if (!out || !ws || (n > 0 && !x)) return vl_set_error("vl_sumsq_f32: null argument");
+  if (((uintptr_t)x & 3) || ((uintptr_t)out & 3)) return vl_set_error("vl_sumsq_f32: x and out must be 4-byte aligned");
+  if ((uintptr_t)ws & 7) return vl_set_error("vl_sumsq_f32: workspace of vl_sumsq_ws_floats() floats, 8-byte aligned, required");
+  // one workgroup per 4096 elements up to the cap: the grid, and with it the order of the sum, depends on n alone
+  const long want = (n / 4 + 1023) / 1024;
+  const int nb = (int)(want > kSumsqMaxBlocks ? kSumsqMaxBlocks : (want < 1 ? 1 : want));
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, stream, x, n, (double*)ws);
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, nb, out);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int vl_adamw_multi_step(const vl_adamw_slot* slots, int nslots, float lr, float beta1, float beta2, float eps, int step,
+                                   float grad_scale, float max_norm, const float* sumsq, float* norm_out, hipStream_t stream) {
+  if (nslots < 0 || nslots > VL_ADAMW_MAX_SLOTS) return vl_set_error("vl_adamw_multi_step: 0 <= nslots <= VL_ADAMW_MAX_SLOTS");
+  if (step < 1) return vl_set_error("vl_adamw_multi_step: step counts from 1");
+  if (!(max_norm > 0.0f)) return vl_set_error("vl_adamw_multi_step: max_norm must be positive");
+  if (!sumsq || (nslots > 0 && !slots)) return vl_set_error("vl_adamw_multi_step: null argument");
+  if (nslots == 0) return 0;
+  const AdamwC c{lr, beta1, beta2, eps, 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step))};
+  // the table lives on the device: the grid cannot follow the element count, the tiles are dealt round-robin to 2048 workgroups
+  hipLaunchKernelGGL(adamw_multi_kernel, dim3(2048), dim3(256), 0, stream, slots, nslots, c, grad_scale, max_norm, sumsq, norm_out);
   VL_HIP_OK(hipGetLastError());
   return 0;
 }

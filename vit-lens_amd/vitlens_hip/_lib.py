@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 602
+ABI_VERSION = 603
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -88,6 +88,9 @@ SIGNATURES = {
     "vl_attn_bwd_fused_supported": [I, I, I, I],
     "vl_attn_bwd_fused_bf16": [P, P, P, P, P, P, P, P, P, P, L, L, I, I, I, I, F, F, P],
     "vl_adamw_step": [P, P, P, P, L, F, F, F, F, F, I, F, P],
+    "vl_sumsq_ws_floats": [],
+    "vl_sumsq_f32": [P, L, P, P, P],
+    "vl_adamw_multi_step": [P, I, F, F, F, F, I, F, F, P, P, P],
     "vl_clamp_scalar": [P, F, F, P],
     "vl_axpy_f32": [P, P, F, L, P],
     "vl_scale_exp_f32": [P, P, L, P, F, P],
@@ -103,7 +106,7 @@ SIGNATURES = {
 
 
 # functions that do not return a status code
-_RET = {"vl_colreduce_ws_floats": L, "vl_ce_grad_ws_floats": L}
+_RET = {"vl_colreduce_ws_floats": L, "vl_ce_grad_ws_floats": L, "vl_sumsq_ws_floats": L}
 
 
 def load_library():

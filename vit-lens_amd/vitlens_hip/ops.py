@@ -649,6 +649,54 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
                              float(weight_decay), int(step), float(grad_scale), _stream()))
 
 
+ADAMW_MAX_SLOTS = 1024          # VL_ADAMW_MAX_SLOTS
+# (device, stream handle) -> workspace of vl_sumsq_f32 (16 KiB).  Calls on one stream run in order, so they share one; two
+# streams must not, hence the key.  Never pruned: one entry per stream a caller clips on, and a recycled handle is again one
+# stream.  As everywhere in this module the tensor is taken to live on the current device, whose current stream _stream() gives.
+_sumsq_ws = {}
+
+
+def grad_sumsq(flat, out=None):
+    """out[0] = sum(flat ** 2), the squared 2-norm of a contiguous f32 tensor (any shape, any element count, 0 included), as a
+    1-element f32 tensor on the device: fp64 accumulation, fixed reduction order (bit-reproducible), no host read."""
+    if flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("grad_sumsq: contiguous f32 tensor required")
+    if not flat.is_cuda:
+        raise RuntimeError("vitlens_hip ops need GPU tensors (no CPU fallback)")
+    if out is None:
+        out = torch.empty(1, device=flat.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.numel() != 1 or out.device != flat.device:
+        raise ValueError("grad_sumsq: out must be one f32 element on the input's device")
+    key = (flat.device, torch.cuda.current_stream(flat.device).cuda_stream)
+    ws = _sumsq_ws.get(key)
+    if ws is None:
+        ws = _sumsq_ws[key] = torch.empty(int(_lib.vl_sumsq_ws_floats()) // 2, device=flat.device, dtype=torch.float64)
+    check(_lib.vl_sumsq_f32(_p(flat) if flat.numel() else None, flat.numel(), _p(out), _p(ws), _stream()))
+    return out
+
+
+def adamw_multi(slots, nslots, lr, beta1, beta2, eps, step, grad_scale, max_norm, sumsq, norm_out=None):
+    """AdamW on every tensor of a device slot table in ONE launch, the gradients multiplied by grad_scale and by
+    clip_grad_norm_'s coefficient min(1, max_norm / (grad_scale * sqrt(sumsq) + 1e-6)), which is derived on the device.
+    slots: int64 [nslots, 6] on the device, rows (p, g, m, v addresses, n, weight_decay's f32 bits) = struct vl_adamw_slot
+    (`train.pack_adamw_slots`); sumsq: 1-element f32 device tensor (`grad_sumsq` of all gradients of the table);
+    norm_out: optional 1-element f32 device tensor that receives the unclipped norm."""
+    if slots.dtype != torch.int64 or slots.dim() != 2 or slots.shape[1] != 6 or not slots.is_contiguous():
+        raise ValueError("adamw_multi: slots must be a contiguous int64 [nslots, 6] table")
+    if not 0 <= int(nslots) <= min(slots.shape[0], ADAMW_MAX_SLOTS):
+        raise ValueError(f"adamw_multi: nslots {nslots} outside the table of {slots.shape[0]} rows (at most {ADAMW_MAX_SLOTS} per launch)")
+    if sumsq.dtype != torch.float32 or sumsq.numel() != 1:
+        raise ValueError("adamw_multi: sumsq must be one f32 element")
+    if norm_out is not None and (norm_out.dtype != torch.float32 or norm_out.numel() != 1):
+        raise ValueError("adamw_multi: norm_out must be one f32 element")
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"adamw_multi: max_norm must be positive, got {max_norm}")
+    if int(step) < 1:
+        raise ValueError("adamw_multi: step counts from 1")
+    check(_lib.vl_adamw_multi_step(_p(slots), int(nslots), float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                   float(grad_scale), float(max_norm), _p(sumsq), _p(norm_out), _stream()))
+
+
 def clamp_scalar(p, lo, hi):
     check(_lib.vl_clamp_scalar(_p(p), float(lo), float(hi), _stream()))
 

@@ -186,7 +186,7 @@ class _StepState:
     and `optimizer.state_dict()`)."""
 
     def _init_host(self, sd, device, micro_batch, rank, world_size, comm=None, local_loss=False, gather_with_grad=False,
-                   force_comm=False, overlap_frozen=False, overlap_backward=True):
+                   force_comm=False, overlap_frozen=False, overlap_backward=True, grad_clip_norm=None):
         """Everything of a step that is HOST state - flags, the communicator, the (still empty apart from logit_scale) master
         table, the gradient-bucket bookkeeping - and nothing that touches an engine or a kernel.  Every step's `__init__`
         runs this first and then its `_build()` (engines, masters of the trainable set); tests/test_step_gloo.py drives the
@@ -213,6 +213,26 @@ class _StepState:
         self.trainers = []       # one activation store per micro-batch (created lazily)
         self.flat_grad, self.grads = None, {}
         self._pending, self._reduced_upto, self._reduce_done = [], None, False
+        # --grad-clip-norm / training.grad_clip_norm: clip the global norm of the (mean) gradient before AdamW; None = off
+        if grad_clip_norm is not None and not float(grad_clip_norm) > 0.0:
+            raise ValueError(f"grad_clip_norm must be positive (or None), got {grad_clip_norm}")
+        self.grad_clip_norm = None if grad_clip_norm is None else float(grad_clip_norm)
+        self._sumsq = None
+
+    @property
+    def last_grad_norm(self):
+        """The unclipped global gradient norm of the last clipped optimizer step (of DDP's mean gradient), a 0-d tensor on the
+        device; None before the first one or without `grad_clip_norm`."""
+        return self.opt.last_grad_norm
+
+    def _clipped_optimizer_step(self):
+        """finish_reduce -> squared norm of the flat gradient buffer (its alignment padding is zero) -> every master in one
+        launch with torch.nn.utils.clip_grad_norm_'s coefficient derived on the device: no host read of norm or coefficient."""
+        self.finish_reduce()
+        if self._sumsq is None:
+            self._sumsq = torch.zeros(1, device=self.dev, dtype=torch.float32)
+        ops.grad_sumsq(self.flat_grad, out=self._sumsq)
+        self.opt.step(self.grads, grad_scale=1.0 / self.world, max_norm=self.grad_clip_norm, sumsq=self._sumsq)
 
     @property
     def dist(self) -> bool:
@@ -436,11 +456,12 @@ class TriModalDepthStep(_StepState):
                  rank: int = 0, world_size: int = 1, gemm_cfg: int = -1, comm=None, frozen_res_dtype=torch.float32,
                  local_loss: bool = False, gather_with_grad: bool = False, train_res_dtype=torch.float32,
                  grad_checkpointing: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
-                 overlap_frozen: bool = True, overlap_backward: bool = True):
+                 overlap_frozen: bool = True, overlap_backward: bool = True,
+                 grad_clip_norm: Optional[float] = None):
         """overlap_frozen (default ON since round 6): the image / text towers' forwards run on a second HIP stream beside
         the trainable tower's forward (`_side_by_side`); results are bit-identical to the serial order."""
         self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward)
+                        overlap_backward, grad_clip_norm)
         self.grad_checkpointing = bool(grad_checkpointing)      # block recompute in the trainable tower (transformer.py:366-368)
         self.unlock_first_n = unlock_first_n
         self._build(sd, tower, text, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
@@ -551,7 +572,9 @@ class TriModalDepthStep(_StepState):
         return self.grads
 
     def optimizer_step(self):
-        if self.dist:
+        if self.grad_clip_norm is not None:
+            self._clipped_optimizer_step()
+        elif self.dist:
             # DDP semantics: mean of per-rank gradients.  Block buckets were started during the last micro-batch's backward
             # (reverse layer order); what is left - logit_scale and the adapter, produced last - goes in one more call.
             self.finish_reduce()
@@ -819,7 +842,9 @@ class _PerceiverLensStep(_StepState):
         return self.grads
 
     def optimizer_step(self):
-        if self.dist:
+        if self.grad_clip_norm is not None:
+            self._clipped_optimizer_step()
+        elif self.dist:
             self.finish_reduce()
             self.opt.step(self.grads, grad_scale=1.0 / self.world)
         else:
@@ -838,9 +863,10 @@ class DualAudioStep(_PerceiverLensStep):
                  betas=(0.9, 0.98), eps: float = 1e-6, weight_decay: float = 0.2, rank: int = 0, world_size: int = 1,
                  gemm_cfg: int = -1, comm=None, frozen_res_dtype=torch.float32, local_loss: bool = False,
                  gather_with_grad: bool = False, train_res_dtype=torch.float32, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
-                 overlap_frozen: bool = True, overlap_backward: bool = True):
+                 overlap_frozen: bool = True, overlap_backward: bool = True,
+                 grad_clip_norm: Optional[float] = None):
         self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward)
+                        overlap_backward, grad_clip_norm)
         self._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                     text_wsplit=text_wsplit, text_arith=text_arith)
         self.opt = AdamW(self.masters, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -912,9 +938,10 @@ class TriModalPCStep(_PerceiverLensStep):
                  gemm_cfg: int = -1, bn_training: bool = True, unlock_cls: bool = False, comm=None,
                  frozen_res_dtype=torch.float32, local_loss: bool = False, gather_with_grad: bool = False,
                  train_res_dtype=torch.float32, bn_sync: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
-                 overlap_frozen: bool = True, overlap_backward: bool = True):
+                 overlap_frozen: bool = True, overlap_backward: bool = True,
+                 grad_clip_norm: Optional[float] = None):
         self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward)
+                        overlap_backward, grad_clip_norm)
         self._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                     text_wsplit=text_wsplit, text_arith=text_arith, bn_training=bn_training, bn_sync=bn_sync, unlock_cls=unlock_cls)
         self.opt = AdamW(self.masters, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)

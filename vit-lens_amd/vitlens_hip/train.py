@@ -442,11 +442,56 @@ class TextTowerTrainer(TowerTrainer):
         self.grad_buffer("token_embedding.weight", e.tok).index_add_(0, text.reshape(-1), S.dx)
 
 
+def clip_coef(sumsq: torch.Tensor, max_norm: float, grad_scale: float = 1.0) -> torch.Tensor:
+    """What vl_adamw_multi_step derives on the device, restated on tensors (f32 arithmetic, the same operations):
+    min(1, max_norm / (grad_scale * sqrt(sumsq) + 1e-6)) = torch.nn.utils.clip_grad_norm_'s coefficient for the gradient
+    grad_scale * g; a NaN norm gives NaN (error_if_nonfinite=False), an infinite one 0."""
+    norm = torch.sqrt(sumsq.float()) * float(grad_scale)          # (a Python scalar: no host-to-device copy)
+    return torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+
+
+def clip_grad_norm_(flat_or_tensors, max_norm: float) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) for callers that hold the gradients themselves
+    (a fused step's `flat_grad` / `reduced_grads()`) and run their own optimizer: the squared norm comes from the
+    sum-of-squares kernel (`ops.grad_sumsq`, one launch pair per tensor - pass the flat buffer where there is one), the
+    coefficient is derived and applied on the device (an in-place multiplication by a device scalar).  Takes one f32 tensor,
+    a list of them or a dict (its values); scales them in place; returns the unclipped norm as a 0-d device tensor."""
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be positive, got {max_norm}")
+    if torch.is_tensor(flat_or_tensors):
+        ts = [flat_or_tensors]
+    else:
+        ts = [t for t in (flat_or_tensors.values() if isinstance(flat_or_tensors, dict) else flat_or_tensors) if t is not None]
+    if not ts:
+        raise ValueError("clip_grad_norm_: no tensors")
+    parts = [ops.grad_sumsq(t) for t in ts]          # (argument checks: contiguous f32 on a GPU)
+    sumsq = parts[0] if len(parts) == 1 else torch.cat(parts).sum(dtype=torch.float64).float().reshape(1)
+    coef = clip_coef(sumsq, float(max_norm)).reshape(())
+    for t in ts:
+        t.mul_(coef)
+    return torch.sqrt(sumsq).reshape(())
+
+
+def pack_adamw_slots(rows) -> torch.Tensor:
+    """rows of (p, g, m, v addresses, n, weight_decay) -> the int64 [len, 6] image of `struct vl_adamw_slot[]` (host tensor):
+    four pointers, the element count, and the f32 bits of the weight decay in the low half of the last word."""
+    import struct
+    t = torch.empty(len(rows), 6, dtype=torch.int64)
+    for i, (p, g, m, v, n, wd) in enumerate(rows):
+        t[i] = torch.tensor([p, g, m, v, n, struct.unpack("<I", struct.pack("<f", wd))[0]], dtype=torch.int64)
+    return t
+
+
 class AdamW:
     """torch.optim.AdamW semantics on f32 master tensors, one fused kernel launch per tensor
-    (reference: depth_tri_main.py:394-419 -- two groups: no weight decay for ndim<2 / bn / ln / bias / logit_scale)."""
+    (reference: depth_tri_main.py:394-419 -- two groups: no weight decay for ndim<2 / bn / ln / bias / logit_scale).
+    `step(..., max_norm=c)` clips the global gradient norm first (torch.nn.utils.clip_grad_norm_(params, c), the reference's
+    --grad-clip-norm / training.grad_clip_norm) and updates every tensor in ONE launch; the norm and the coefficient stay
+    on the device, `last_grad_norm` holds the unclipped norm."""
 
     def __init__(self, params: Dict[str, torch.Tensor], lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2):
+        self._slots, self._slot_key = None, None      # the device table of the clipped step, kept while no tensor moves
+        self.last_grad_norm = None                    # 0-d f32 device tensor after a clipped step
         # `param_groups[i]["lr"]` is what the reference's schedulers assign (training/scheduler.py:4-6); one group here,
         # weight decay is decided per tensor by `decays`
         self.param_groups = [{"lr": lr}]
@@ -467,7 +512,50 @@ class AdamW:
     def decays(name: str, p: torch.Tensor) -> bool:
         return not (p.ndim < 2 or "bn" in name or "ln" in name or "bias" in name or "logit_scale" in name)
 
-    def step(self, grads: Dict[str, torch.Tensor], grad_scale: float = 1.0):
+    def slot_rows(self, grads: Dict[str, torch.Tensor]):
+        """One (p, g, m, v addresses, n, weight_decay) row per parameter that has a gradient, in `params` order."""
+        rows = []
+        for k, p in self.params.items():
+            g = grads.get(k)
+            if g is None:
+                continue
+            for t in (p, g, self.m[k], self.v[k]):
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"AdamW: contiguous f32 tensors required ({k})")
+            if g.numel() != p.numel():
+                raise ValueError(f"AdamW: gradient of {k} has {g.numel()} elements, the parameter {p.numel()}")
+            rows.append((p.data_ptr(), g.data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), p.numel(),
+                         self.wd if self.decays(k, p) else 0.0))
+        return rows
+
+    def _clipped_step(self, grads, grad_scale, max_norm, sumsq):
+        if not float(max_norm) > 0.0:
+            raise ValueError(f"AdamW.step: max_norm must be positive, got {max_norm}")
+        rows = self.slot_rows(grads)
+        if not rows:
+            return
+        dev = next(iter(self.params.values())).device
+        key = tuple(rows)
+        if key != self._slot_key:          # first step, or a tensor was re-allocated: one small host-to-device copy
+            self._slots, self._slot_key = pack_adamw_slots(rows).to(dev), key
+        if sumsq is None:                  # gradients in separate allocations: one reduction each, added on the device
+            parts = [ops.grad_sumsq(g) for k, g in grads.items() if k in self.params and g is not None]
+            sumsq = torch.cat(parts).sum(dtype=torch.float64).float().reshape(1)
+        if self.last_grad_norm is None:
+            self.last_grad_norm = torch.zeros((), device=dev, dtype=torch.float32)
+        self.t += 1
+        for a in range(0, len(rows), ops.ADAMW_MAX_SLOTS):
+            n = min(ops.ADAMW_MAX_SLOTS, len(rows) - a)
+            ops.adamw_multi(self._slots[a:a + n], n, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale,
+                            max_norm, sumsq, self.last_grad_norm)
+
+    def step(self, grads: Dict[str, torch.Tensor], grad_scale: float = 1.0, max_norm: Optional[float] = None,
+             sumsq: Optional[torch.Tensor] = None):
+        """max_norm=None: the per-tensor loop.  With a max_norm: the gradients' global 2-norm (of grad_scale * g) is clipped to
+        it; `sumsq` is the squared norm of ALL gradients as `ops.grad_sumsq` leaves it on the device (the fused steps pass the
+        one of their flat buffer; None = computed here, one reduction per tensor)."""
+        if max_norm is not None:
+            return self._clipped_step(grads, grad_scale, max_norm, sumsq)
         self.t += 1
         for k, p in self.params.items():
             g = grads.get(k)
