@@ -38,13 +38,19 @@ typedef struct ihipStream_t* hipStream_t;
 #define VL_EPI_RES_BF16 3 /* out bf16[M,N]   = res bf16 + alpha*acc + bias               */
 #define VL_EPI_GEGLU 5    /* out bf16[M,N/2] = a*gelu(gate), W rows interleaved (a,gate) */
 #define VL_EPI_DGELU 6    /* out bf16[M,N]   = alpha*acc * gelu'(res bf16[M,N])  (dX through GELU); with act =
-                           * VL_ACT_GELU_DSAVE res IS gelu' (left by the forward): the epilogue is one multiplication */
+                           * VL_ACT_GELU_DSAVE or VL_ACT_QGELU_DSAVE res IS the derivative (left by the forward): the epilogue is
+                           * one multiplication, the same kernel for both.  The recompute form (act = VL_ACT_NONE, res = the
+                           * pre-activation) is exact-erf only: VL_ACT_QGELU is refused */
 #define VL_EPI_DGEGLU 7   /* acc = dy[M,N]; res = h bf16[M,2N] interleaved (a,g); out bf16[M,2N] = d h  (dX through GEGLU) */
 #define VL_ACT_NONE 0
 #define VL_ACT_GELU 1     /* exact-erf GELU (nn.GELU default)                            */
 #define VL_ACT_RELU 2
 #define VL_ACT_GELU_DSAVE 4 /* forward of a TRAINED MLP: out = gelu(pre), out2 (required) = gelu'(pre), both of the bf16-rounded
                              * pre-activation; pair it with VL_EPI_DGELU + the same act in the backward               */
+#define VL_ACT_QGELU 5    /* QuickGELU, u * sigmoid(1.702 u): the OpenAI-pretrained CLIP towers (transformer.py:37).
+                           * VL_EPI_BF16 only, without out2 (the store-the-pre-activation form is exact-erf only)          */
+#define VL_ACT_QGELU_DSAVE 6 /* VL_ACT_GELU_DSAVE for QuickGELU: out = qgelu(pre), out2 (required) = qgelu'(pre) = s + 1.702 pre s (1 - s),
+                             * s = sigmoid(1.702 pre), both of the bf16-rounded pre-activation                              */
 
 /* dtype tags for mixed-dtype entry points */
 #define VL_F32 0
@@ -60,10 +66,13 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 603
+#define VL_ABI_VERSION 604
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
+ * act: VL_ACT_NONE / GELU / RELU / GELU_DSAVE / QGELU / QGELU_DSAVE with VL_EPI_BF16 (RELU also with VL_EPI_RES_BF16, the _DSAVE
+ * codes also with VL_EPI_DGELU).  Checked and refused: a _DSAVE code without out2, and the QuickGELU codes with any other
+ * epilogue, with the recompute form of VL_EPI_DGELU or (VL_ACT_QGELU) with out2; an epilogue otherwise ignores an act it does not take.
  * cfg selects the kernel family - the ONE selector of this library: nothing else (no environment variable, no global
  * setter) changes which code runs.  VL_GEMM_AUTO (-1) is what every product path passes; the explicit values exist for the
  * parity tests (every family against fp32 and against each other) and the probes under tools/:
@@ -115,7 +124,7 @@ int vl_gemm_bf16_ex(const void* A, const void* W, const float* bias, void* out, 
  * CLIP to fp16 (`convert_weights_to_fp16`, open_clip/model.py:393-419; precision "fp16", factory.py:260-295).  The residual
  * stream stays fp32, 16-bit stores saturate at +-65504.
  *   vl_gemm_f16      C = A . W^T with A [M,K], W [N,K] fp16; epi = VL_EPI_BF16 (here: out fp16 [M,N] = act(alpha*acc + bias),
- *                    act none / GELU) or VL_EPI_RES_F32 (out f32 = res f32 + alpha*acc + bias, in place allowed).  The
+ *                    act none / GELU / QGELU) or VL_EPI_RES_F32 (out f32 = res f32 + alpha*acc + bias, in place allowed).  The
  *                    persistent 256x256 kernel only: M % 256 == N % 256 == 0, K % 64 == 0, K >= 512, 16-byte aligned
  *                    operands - the caller pads its rows to whole tiles (replaces in_proj / out_proj / c_fc / c_proj of
  *                    the text tower's ResidualAttentionBlocks, transformer.py:226-234,254-272)
@@ -131,7 +140,8 @@ int vl_attn_fwd_f16(const void* q, const void* k, const void* v, const long* str
  * training/precision.py:5-12) means fp32 nn.Linear / attention products; rounds 1-4 ran bf16 operands there and said so in a
  * warning.  gfx950 has fp32-input MFMA at the fp32 vector rate (157 TFLOP/s, 1/16 of bf16), exact fmaf chains:
  *   vl_gemm_f32      out f32 [M,N] = act(alpha * A[M,K] W[N,K]^T + bias) (+ res f32 [M,N], in place allowed); any M, N;
- *                    K, lda, ldw multiples of 4; act none / GELU (erff) / ReLU        (csrc/vl_f32.hip, v_mfma_f32_32x32x2_f32)
+ *                    K, lda, ldw multiples of 4; act none / GELU (erff) / ReLU / QGELU (expf and a true division)
+ *                    (csrc/vl_f32.hip, v_mfma_f32_32x32x2_f32)
  *   vl_attn_fwd_f32  softmax(scale * q k^T [+ causal mask]) v on strided f32 [B,H,L,dh] views (strides as vl_attn_fwd_bf16,
  *                    multiples of 4), dh = 32, 64 or a multiple of 8 in (64, 128]; out f32 [B,Lq,H*dh]; lse optional
  *                    (natural log)
@@ -187,8 +197,8 @@ int vl_attn_fwd_bf16(const void* q, const void* k, const void* v, const long* st
  *                              256x256-tile kernel; the entries below take exactly such row ranges (0: none)
  *   vl_gemm_lnfold_bf16        out bf16[M,N] = act(rstd_m * (A Wg^T - mean_m * ln_c) + bias_f); A = raw rows bf16 [M,K],
  *                              Wg = bf16(W * gamma) [N,K], bias_f = b + W beta f32 [N], ln_c f32 [N] (sums of the ROUNDED
- *                              Wg rows), ln_mean / ln_rstd f32 [M]; act = VL_ACT_NONE / VL_ACT_GELU / VL_ACT_GELU_DSAVE
- *                              (out2 = gelu', as vl_gemm_bf16_ex)
+ *                              Wg rows), ln_mean / ln_rstd f32 [M]; act = VL_ACT_NONE / VL_ACT_GELU / VL_ACT_GELU_DSAVE /
+ *                              VL_ACT_QGELU / VL_ACT_QGELU_DSAVE (out2 = the derivative, as vl_gemm_bf16_ex)
  *   vl_gemm_res_rowstats_bf16  out bf16 = res + A W^T + bias (VL_EPI_RES_BF16, in place allowed) and row_part f32
  *                              [M][N/64][2] = (sum, sum of squares) of the STORED bf16 values per row and 64-column slice
  *   vl_ln_row_stats            mean / rstd [rows]: rows < m_main from row_part (P = N/64 slices, summed in slice order),

@@ -124,6 +124,52 @@ __device__ __forceinline__ void gelu_and_grad_pk(unsigned int w, unsigned int& y
   y = pack2bf(gelu_from_parts2(x, g));
   d = pack2bf(gelu_grad_from_parts2(x, g));
 }
+// QuickGELU, the activation of the OpenAI-pretrained CLIP towers (open_clip/transformer.py:37): x * sigmoid(1.702 x), and its
+// derivative s + 1.702 x s (1 - s), from ONE shared evaluation: one v_exp_f32 and one v_rcp_f32 per value (the erf form above:
+// two transcendentals and a degree-4 polynomial).  Evaluated on |x| so that the exponential never overflows:
+//   e = 2^(-1.702 log2(e) |x|) in (0, 1],  r = 1 / (1 + e):   s = r (x >= 0) or e r (x < 0),   s (1 - s) = e r^2 either way
+// (no cancellation in 1 - s).  Finite for every finite x: e underflows to 0 at large |x| (the hardware exponential flushes a
+// denormal result, so from |x| ~ 51 on; the true values there are below 1e-36) and the results are x / 1 (x > 0), -0 / 0 (x < 0);
+// x multiplies last, so no 0 * inf is ever formed.
+struct QGeluParts { float s, t; };                                            // s = sigmoid(1.702 x), t = s (1 - s)
+__device__ __forceinline__ QGeluParts qgelu_parts(float x) {
+  const float e = __builtin_amdgcn_exp2f(fabsf(x) * -2.4554669596f);           // 1.702 * log2(e)
+  const float r = __builtin_amdgcn_rcpf(1.0f + e);
+  const float er = e * r;
+  QGeluParts p;
+  p.s = (x >= 0.0f) ? r : er;
+  p.t = er * r;
+  return p;
+}
+__device__ __forceinline__ float qgelu_from_parts(float x, const QGeluParts p) { return x * p.s; }
+__device__ __forceinline__ float qgelu_grad_from_parts(float x, const QGeluParts p) { return fmaf(x, 1.702f * p.t, p.s); }
+__device__ __forceinline__ float qgelu(float x) { return qgelu_from_parts(x, qgelu_parts(x)); }
+__device__ __forceinline__ float qgelu_grad(float x) { return qgelu_grad_from_parts(x, qgelu_parts(x)); }
+// The same on pairs (packed-fp32 multiplies and FMAs, the same roundings as the scalar forms: tests/test_qgelu_pairs_host.py)
+struct QGeluParts2 { vl_f32x2 s, t; };
+__device__ __forceinline__ QGeluParts2 qgelu_parts2(vl_f32x2 x) {
+  const vl_f32x2 z = __builtin_elementwise_abs(x) * -2.4554669596f;
+  const vl_f32x2 e = {__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])};
+  const vl_f32x2 d = e + 1.0f;
+  const vl_f32x2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+  const vl_f32x2 er = e * r;
+  QGeluParts2 p;
+  p.s = vl_f32x2{(x[0] >= 0.0f) ? r[0] : er[0], (x[1] >= 0.0f) ? r[1] : er[1]};
+  p.t = er * r;
+  return p;
+}
+__device__ __forceinline__ vl_f32x2 qgelu_from_parts2(vl_f32x2 x, const QGeluParts2 p) { return x * p.s; }
+__device__ __forceinline__ vl_f32x2 qgelu_grad_from_parts2(vl_f32x2 x, const QGeluParts2 p) {
+  return __builtin_elementwise_fma(x, p.t * 1.702f, p.s);
+}
+__device__ __forceinline__ vl_f32x2 qgelu2(vl_f32x2 x) { return qgelu_from_parts2(x, qgelu_parts2(x)); }
+// One packed pair of bf16 pre-activations -> packed bf16 (qgelu, qgelu'): VL_ACT_QGELU_DSAVE, the twin of gelu_and_grad_pk
+__device__ __forceinline__ void qgelu_and_grad_pk(unsigned int w, unsigned int& y, unsigned int& d) {
+  const vl_f32x2 x = unpack2bf(w);
+  const QGeluParts2 p = qgelu_parts2(x);
+  y = pack2bf(qgelu_from_parts2(x, p));
+  d = pack2bf(qgelu_grad_from_parts2(x, p));
+}
 __device__ __forceinline__ unsigned int mul_pk_bf16(unsigned int a, unsigned int b) {
   return pack2bf(bf2f((bf16_t)(a & 0xffff)) * bf2f((bf16_t)(b & 0xffff)), bf2f((bf16_t)(a >> 16)) * bf2f((bf16_t)(b >> 16)));
 }

@@ -41,6 +41,12 @@ constexpr int F32_RES_PRE = 1;   // act(alpha acc + bias + res[m / res_div])    
 constexpr int F32_GEGLU = 2;     // out[m, n/2] = (alpha acc + bias)[n] * gelu((alpha acc + bias)[n+1]), n even
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+// QuickGELU v * sigmoid(1.702 v) (open_clip/transformer.py:37) with expf and a true division.  On |v| the exponential stays in
+// (0, 1]: sigmoid = 1 / (1 + e) for v >= 0 and e / (1 + e) for v < 0 - finite for every finite v (-0 at large negative v)
+__device__ __forceinline__ float qgelu_f32(float v) {
+  const float e = expf(-1.702f * fabsf(v));
+  return v * ((v >= 0.0f ? 1.0f : e) / (1.0f + e));
+}
 
 template <int ACT, int MODE = F32_PLAIN>
 __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmF32P p) {
@@ -137,9 +143,11 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(const GemmF32P p) {
           if (p.res) v += p.res[(size_t)(m / p.res_div) * p.ldo + n];
           if constexpr (ACT == VL_ACT_GELU) v = gelu_erf(v);
           else if constexpr (ACT == VL_ACT_RELU) v = fmaxf(v, 0.f);
+          else if constexpr (ACT == VL_ACT_QGELU) v = qgelu_f32(v);
         } else {
           if constexpr (ACT == VL_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
           else if constexpr (ACT == VL_ACT_RELU) v = fmaxf(v, 0.f);
+          else if constexpr (ACT == VL_ACT_QGELU) v = qgelu_f32(v);
           if (p.res) v += p.res[(size_t)m * p.ldo + n];
         }
         p.out[(size_t)m * p.ldo + n] = v;
@@ -343,7 +351,8 @@ extern "C" int vl_gemm_f32(const float* A, const float* W, const float* bias, fl
   if (act == VL_ACT_NONE) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_NONE>, grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_GELU) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_GELU>, grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_RELU) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_RELU>, grid, dim3(256), 0, stream, p);
-  else return vl_set_error("vl_gemm_f32: act must be none, GELU or ReLU");
+  else if (act == VL_ACT_QGELU) hipLaunchKernelGGL(gemm_f32_kernel<VL_ACT_QGELU>, grid, dim3(256), 0, stream, p);
+  else return vl_set_error("vl_gemm_f32: act must be none, GELU, ReLU or QGELU");
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
 }
@@ -372,7 +381,8 @@ extern "C" int vl_gemm_f32_ex(const float* A, const float* W, const float* bias,
   else if (act == VL_ACT_NONE) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_NONE, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_GELU) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_GELU, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
   else if (act == VL_ACT_RELU) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_RELU, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
-  else return vl_set_error("vl_gemm_f32_ex: act must be none, GELU or ReLU");
+  else if (act == VL_ACT_QGELU) hipLaunchKernelGGL((gemm_f32_kernel<VL_ACT_QGELU, F32_RES_PRE>), grid, dim3(256), 0, stream, p);
+  else return vl_set_error("vl_gemm_f32_ex: act must be none, GELU, ReLU or QGELU");
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
 }

@@ -17,8 +17,10 @@
 namespace {
 
 // ---- epilogue: lane owns row m = mrow0 + 32*i + fr, columns n = ncol0 + 32*j + 8*q + 4*fg + {0..3} ----
-template <int EPI, int MT, int NTL>
+template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL], int mrow0, int ncol0, int fr, int fg) {
+  constexpr int EPI = epi_base(EPI_);            // EPI_BF16_QG: EPI_BF16 + the QuickGELU codes (vl_gemm_common.h)
+  constexpr bool QG = (EPI_ == EPI_BF16_QG);
   // rows OUTER: a lane writes the 8 column groups of one row back to back, so the 128-byte lines of that row
   // are completed while still in the write-combining window (columns-outer order cost the fc GEMM 40 %).
 #pragma unroll
@@ -49,6 +51,15 @@ __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL
             *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
             continue;
           }
+          if (QG && p.act == VL_ACT_QGELU_DSAVE) {   // the QuickGELU twin: out2 = qgelu' of the bf16-rounded pre-activation
+            unsigned int y0, g0, y1, g1;
+            qgelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
+            qgelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
+            const u32x2 o = {y0, y1}, d = {g0, g1};
+            *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
+            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
+            continue;
+          }
           if (p.act == 1) {
             if (p.out2) {
               u32x2 o2; o2[0] = pack2bf(v[0], v[1]); o2[1] = pack2bf(v[2], v[3]);
@@ -59,6 +70,9 @@ __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL
           } else if (p.act == 2) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          } else if (QG && p.act == VL_ACT_QGELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
           }
           u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
           *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
@@ -121,9 +135,11 @@ __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL
 // dGELU, GELU when the pre-activation is also kept) runs after the read-back on the bf16-rounded values, with
 // coalesced 16-byte loads - the same rounding points as the reference's autocast (bf16 linear output, then the add /
 // activation); bias, alpha, the q scale and GELU-without-save are applied in fp32 before packing.
-template <int EPI, int MT, int NTL>
+template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[MT][NTL], int j0, int mrow0, int ncol0, int fr, int fg,
                                                  int lane, unsigned char* wl) {
+  constexpr int EPI = epi_base(EPI_);            // EPI_BF16_QG: EPI_BF16 + the QuickGELU codes (vl_gemm_common.h)
+  constexpr bool QG = (EPI_ == EPI_BF16_QG);
   // handles the 64 columns of column blocks j0, j0+1 (ncol0 = first column of block j0)
   const int rsub = lane >> 3, c = lane & 7;
   unsigned char* const wr = wl + fr * 128 + fg * 8;
@@ -148,6 +164,9 @@ __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[M
           } else if (p.act == 2) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          } else if (QG && p.act == VL_ACT_QGELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
           }
         }
         u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
@@ -172,6 +191,11 @@ __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[M
           u32x4 d;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
+          *(u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8) = d;
+        } else if (QG && p.act == VL_ACT_QGELU_DSAVE) {
+          u32x4 d;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
           *(u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8) = d;
         }
         *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + n8) = w;
@@ -214,11 +238,13 @@ __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[M
 // 64/128-byte segments, and the bias is loaded once per column block instead of once per row.
 // The transposed attention layouts (q^T, k^T, v^T: token index contiguous) are row-per-lane friendly and keep the
 // direct path.  GEGLU epilogues (Perceiver feed-forward only) fall back to store_tile.
-template <int EPI, int MT, int NTL>
+template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT][NTL], int mrow0, int ncol0, int fr, int fg,
                                                int lane, unsigned char* wl) {
+  constexpr int EPI = epi_base(EPI_);            // EPI_BF16_QG: EPI_BF16 + the QuickGELU codes (vl_gemm_common.h)
+  constexpr bool QG = (EPI_ == EPI_BF16_QG);
   if constexpr (EPI == EPI_GEGLU || EPI == EPI_DGEGLU) {
-    store_tile<EPI, MT, NTL>(p, acc, mrow0, ncol0, fr, fg);
+    store_tile<EPI_, MT, NTL>(p, acc, mrow0, ncol0, fr, fg);
     return;
   } else {
     if constexpr ((EPI == EPI_BF16 || EPI == EPI_RES_BF16 || EPI == EPI_DGELU) && (NTL & 1) == 0) {
@@ -226,7 +252,7 @@ __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT]
       if ((p.N & 7) == 0 && (p.ldo & 7) == 0) {
 #pragma unroll
         for (int j0 = 0; j0 < NTL; j0 += 2)
-          store_tile_lds16<EPI, MT, NTL>(p, acc, j0, mrow0, ncol0 + j0 * 32, fr, fg, lane, wl);
+          store_tile_lds16<EPI_, MT, NTL>(p, acc, j0, mrow0, ncol0 + j0 * 32, fr, fg, lane, wl);
         return;
       }
     }
@@ -275,6 +301,15 @@ __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT]
               *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
               continue;
             }
+            if (QG && p.act == VL_ACT_QGELU_DSAVE) {
+              unsigned int y0, g0, y1, g1;
+              qgelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
+              qgelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
+              const u32x2 o = {y0, y1}, d = {g0, g1};
+              *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
+              *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
+              continue;
+            }
             if (p.act == 1) {
               if (p.out2) {
                 u32x2 o2; o2[0] = pack2bf(v[0], v[1]); o2[1] = pack2bf(v[2], v[3]);
@@ -285,6 +320,9 @@ __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT]
             } else if (p.act == 2) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            } else if (QG && p.act == VL_ACT_QGELU) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
             }
             u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
             *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
@@ -739,20 +777,21 @@ hipError_t launch_best_persist(const GemmP& p0, hipStream_t s) {
   const GemmP& p = p0;
   // 256x256 tiles where N allows them (fewer operand bytes per flop: the chip is power-bound on these GEMMs, DESIGN.md
   // section 7); the ping-pong kernel's 256x128 tiles take N % 256 == 128 (ViT-bigG: 1664 = 13 x 128)
-  if (vl_gemm_park_supported(EPI, &p)) return (hipError_t)vl_gemm_park_launch(EPI, &p, num_cus(), s);
-  if (vl_gemm_pp_supported(EPI, &p)) return (hipError_t)vl_gemm_pp_launch(EPI, &p, num_cus(), s);
+  // (the round-2 / round-3 kernels instantiate per act: EPI_BF16_QG is plain EPI_BF16 to them)
+  if (vl_gemm_park_supported(epi_base(EPI), &p)) return (hipError_t)vl_gemm_park_launch(epi_base(EPI), &p, num_cus(), s);
+  if (vl_gemm_pp_supported(epi_base(EPI), &p)) return (hipError_t)vl_gemm_pp_launch(epi_base(EPI), &p, num_cus(), s);
   return launch_persist<EPI>(p, s);
 }
 
 template <int EPI>
 hipError_t dispatch(const GemmP& p, int cfg, hipStream_t s) {
   if (cfg == 8) {
-    if (!vl_gemm_park_supported(EPI, &p)) return hipErrorInvalidValue;
-    return (hipError_t)vl_gemm_park_launch(EPI, &p, num_cus(), s);
+    if (!vl_gemm_park_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
+    return (hipError_t)vl_gemm_park_launch(epi_base(EPI), &p, num_cus(), s);
   }
   if (cfg == 10) {
-    if (!vl_gemm_pp_supported(EPI, &p)) return hipErrorInvalidValue;
-    return (hipError_t)vl_gemm_pp_launch(EPI, &p, num_cus(), s);
+    if (!vl_gemm_pp_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
+    return (hipError_t)vl_gemm_pp_launch(epi_base(EPI), &p, num_cus(), s);
   }
   // cfg bit0: 0 = 256x256 tile (8 waves), 1 = 128x128 tile (4 waves); bit1: 1 = register staging
   if (cfg == 4 || cfg == 5) return launch_persist<EPI>(p, s);       // 4: historical alias
@@ -842,8 +881,10 @@ extern "C" int vl_gemm_lnfold_bf16(const void* A, const void* Wg, const float* b
                                    const float* ln_rstd, void* out, void* out2, int M, int N, int K, int lda, int ldw, int ldo,
                                    int act, hipStream_t stream) {
   VL_CHECK_ARG(A && Wg && bias_f && ln_c && ln_mean && ln_rstd && out, "vl_gemm_lnfold_bf16: null operand");
-  VL_CHECK_ARG(act == VL_ACT_NONE || act == VL_ACT_GELU || act == VL_ACT_GELU_DSAVE, "vl_gemm_lnfold_bf16: act must be none, GELU or GELU_DSAVE");
-  VL_CHECK_ARG((act == VL_ACT_GELU_DSAVE) == (out2 != nullptr), "vl_gemm_lnfold_bf16: out2 goes with VL_ACT_GELU_DSAVE");
+  VL_CHECK_ARG(act == VL_ACT_NONE || act == VL_ACT_GELU || act == VL_ACT_GELU_DSAVE || act == VL_ACT_QGELU || act == VL_ACT_QGELU_DSAVE,
+               "vl_gemm_lnfold_bf16: act must be none, GELU, GELU_DSAVE, QGELU or QGELU_DSAVE");
+  VL_CHECK_ARG((act == VL_ACT_GELU_DSAVE || act == VL_ACT_QGELU_DSAVE) == (out2 != nullptr),
+               "vl_gemm_lnfold_bf16: out2 goes with VL_ACT_GELU_DSAVE / VL_ACT_QGELU_DSAVE");
   VL_CHECK_ARG((((uintptr_t)ln_c | (uintptr_t)bias_f) & 15) == 0, "vl_gemm_lnfold_bf16: column vectors must be 16-byte aligned");
   GemmP p{};
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)Wg; p.bias = bias_f; p.out = out; p.out2 = out2;
@@ -893,16 +934,27 @@ extern "C" int vl_gemm_bf16_ex(const void* A, const void* W, const float* bias, 
   GemmP p{};
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res; p.out2 = out2;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = alpha; p.act = act; p.res_div = res_div;
+  // QuickGELU (VL_ACT_QGELU, VL_ACT_QGELU_DSAVE): the activation of a VL_EPI_BF16 output, or - the _DSAVE code - the saved
+  // derivative of VL_EPI_DGELU.  Every other epilogue, the recompute form of VL_EPI_DGELU and the store-the-pre-activation
+  // form (VL_ACT_GELU + out2) are exact-erf only.
+  const bool qg = act == VL_ACT_QGELU || act == VL_ACT_QGELU_DSAVE;
+  VL_CHECK_ARG(!qg || epi == VL_EPI_BF16 || epi == VL_EPI_DGELU, "vl_gemm_bf16: QuickGELU goes with VL_EPI_BF16 (or, saved, VL_EPI_DGELU) only");
   hipError_t e;
   switch (epi) {
     case VL_EPI_BF16:
       VL_CHECK_ARG(act != VL_ACT_GELU_DSAVE || out2, "vl_gemm_bf16: VL_ACT_GELU_DSAVE needs out2 (the gelu' tensor)");
-      e = run_gemm<EPI_BF16>(p, cfg, stream); break;
+      VL_CHECK_ARG(act != VL_ACT_QGELU_DSAVE || out2, "vl_gemm_bf16: VL_ACT_QGELU_DSAVE needs out2 (the qgelu' tensor)");
+      VL_CHECK_ARG(act != VL_ACT_QGELU || !out2, "vl_gemm_bf16: VL_ACT_QGELU takes no out2 (saving the pre-activation is exact-erf only; use VL_ACT_QGELU_DSAVE)");
+      e = qg ? run_gemm<EPI_BF16_QG>(p, cfg, stream) : run_gemm<EPI_BF16>(p, cfg, stream); break;
     case VL_EPI_F32: e = run_gemm<EPI_F32>(p, cfg, stream); break;
     case VL_EPI_RES_F32: VL_CHECK_ARG(res, "vl_gemm_bf16: residual missing"); e = run_gemm<EPI_RES_F32>(p, cfg, stream); break;
     case VL_EPI_RES_BF16: VL_CHECK_ARG(res, "vl_gemm_bf16: residual missing"); e = run_gemm<EPI_RES_BF16>(p, cfg, stream); break;
     case VL_EPI_GEGLU: e = run_gemm<EPI_GEGLU>(p, cfg, stream); break;
-    case VL_EPI_DGELU: VL_CHECK_ARG(res, "vl_gemm_bf16: pre-activation tensor missing"); e = run_gemm<EPI_DGELU>(p, cfg, stream); break;
+    case VL_EPI_DGELU:
+      VL_CHECK_ARG(res, "vl_gemm_bf16: pre-activation tensor missing");
+      VL_CHECK_ARG(act != VL_ACT_QGELU, "vl_gemm_bf16: VL_EPI_DGELU recomputes the exact-erf gelu' only; QuickGELU needs the saved derivative (VL_ACT_QGELU_DSAVE)");
+      if (act == VL_ACT_QGELU_DSAVE) p.act = VL_ACT_GELU_DSAVE;      // res is the saved derivative either way: one multiplication, the same kernels
+      e = run_gemm<EPI_DGELU>(p, cfg, stream); break;
     case VL_EPI_DGEGLU: VL_CHECK_ARG(res, "vl_gemm_bf16: pre-activation tensor missing"); VL_CHECK_ARG((ldo & 7) == 0, "vl_gemm_bf16: DGEGLU needs ldo % 8 == 0"); e = run_gemm<EPI_DGEGLU>(p, cfg, stream); break;
     default: return vl_set_error("vl_gemm_bf16: unknown epilogue");
   }
@@ -917,7 +969,7 @@ extern "C" int vl_gemm_f16(const void* A, const void* W, const float* bias, void
   VL_CHECK_ARG(A && W && out, "vl_gemm_f16: null operand");
   VL_CHECK_ARG(epi == VL_EPI_BF16 || epi == VL_EPI_RES_F32, "vl_gemm_f16: VL_EPI_BF16 (16-bit output, here fp16) or VL_EPI_RES_F32");
   VL_CHECK_ARG(epi != VL_EPI_RES_F32 || (res && act == VL_ACT_NONE), "vl_gemm_f16: VL_EPI_RES_F32 needs res and takes no activation");
-  VL_CHECK_ARG(act == VL_ACT_NONE || act == VL_ACT_GELU, "vl_gemm_f16: act must be none or GELU");
+  VL_CHECK_ARG(act == VL_ACT_NONE || act == VL_ACT_GELU || act == VL_ACT_QGELU, "vl_gemm_f16: act must be none, GELU or QGELU");
   GemmP p{};
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = alpha; p.act = act; p.res_div = 1; p.f16 = 1;

@@ -15,7 +15,12 @@ enum Epi : int {
   EPI_GEGLU = 5,  // rows interleaved (a_j, gate_j): out bf16[M, N/2] = a * gelu(gate)
   EPI_DGELU = 6,  // out bf16 = acc * gelu'(aux[m,n])   (backward through GELU fused into the dX GEMM)
   EPI_DGEGLU = 7, // acc = dy[M,N]; res = h[M,2N] interleaved (a,g): out[M,2N] = (dy*gelu(g), dy*a*gelu'(g)) interleaved
+  // vl_gemm.hip's kernels with a RUNTIME act (plain tiles, leftover rows, round-1 persistent): EPI_BF16 whose epilogue also carries
+  // the QuickGELU codes.  Instantiations of their own, launched for VL_ACT_QGELU / VL_ACT_QGELU_DSAVE only, so that the kernels every
+  // other act runs keep exactly the code they had
+  EPI_BF16_QG = 8,
 };
+constexpr int epi_base(int e) { return e == EPI_BF16_QG ? (int)EPI_BF16 : e; }
 
 struct GemmP {
   const bf16_t* A;   // [M, K]
@@ -27,7 +32,7 @@ struct GemmP {
   int M, N, K;
   int lda, ldw, ldo; // row strides in elements
   float alpha;
-  int act;           // 0 none, 1 gelu(erf), 2 relu
+  int act;           // VL_ACT_*: 0 none, 1 gelu(erf), 2 relu, 4 gelu + out2 = gelu', 5 QuickGELU, 6 QuickGELU + out2 = qgelu'
   int res_div;       // residual row = m / res_div (>=1): broadcast one row over a group of res_div rows
   int m_off;         // absolute row of local row 0 of a row-split launch (EPI_RES_BF16 indexes its residual with it)
   // split-K (gemm_nt_kernel only): blockIdx.y owns k-slabs [y*ksplit_len, (y+1)*ksplit_len) and writes its

@@ -82,7 +82,9 @@ using IC = std::integral_constant<int, I>;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // ACT (EPI_BF16 only): 0 none, 1 GELU, 2 ReLU, 3 GELU with the pre-activation also written to out2 (saved for backward),
-// 4 GELU with gelu'(pre-activation) written to out2.  EPI_DGELU: ACT 4 = the aux operand is that saved gelu'.
+// 4 GELU with gelu'(pre-activation) written to out2, 5 QuickGELU, 6 QuickGELU with qgelu'(pre-activation) written to out2
+// (VL_ACT_QGELU / VL_ACT_QGELU_DSAVE: the twins of 1 and 4, same stores, other arithmetic).  EPI_DGELU: ACT 4 = the aux operand
+// is the saved derivative (of either activation).
 // The main loop runs on `v_mfma_f32_16x16x32_*` (32 MFMAs of 16 384 flop per 32-deep half k-step from 8 + 4 fragments): against
 // `v_mfma_f32_32x32x16_*` (rounds 2-3a; removed in round 5 with its A/B switch) the same LDS traffic and accumulator registers,
 // a quarter of the accumulator read-modify-write per flop.  The board is power-limited on real data (profiles/
@@ -97,14 +99,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     gemm_nt_pk_kernel(const GemmP p PK_PROF_ARG) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool HAS_AUX = (EPI == EPI_RES_BF16 || EPI == EPI_DGELU);   // second operand of the output's shape
-  // LayerNorm folding (round 4; GemmP::ln_*): ACT 10 / 11 / 14 = ACT 0 / 1 / 4 with the row-statistics epilogue
+  // LayerNorm folding (round 4; GemmP::ln_*): ACT 10 / 11 / 14 / 15 / 16 = ACT 0 / 1 / 4 / 5 / 6 with the row-statistics epilogue
   // rstd_m * (acc - mean_m * c_n) + bias_n on the raw residual rows; EPI_RES_BF16 with ACT 20 also emits the partial row
   // statistics (sum, sum of squares per 64-column slice) of what it stores, for the LayerNorm that follows it
   constexpr bool LNF = (EPI == EPI_BF16 && ACT >= 10 && ACT < 20);
   constexpr int ACTB = LNF ? ACT - 10 : ACT;
   constexpr bool STATS = (EPI == EPI_RES_BF16 && ACT == 20);
-  static_assert(!F16 || ((EPI == EPI_BF16 && (ACT == 0 || ACT == 1)) || (EPI == EPI_RES_F32 && ACT == 0)),
-                "fp16 operands: plain / GELU 16-bit output and the fp32 residual epilogue only");
+  static_assert(!F16 || ((EPI == EPI_BF16 && (ACT == 0 || ACT == 1 || ACT == 5)) || (EPI == EPI_RES_F32 && ACT == 0)),
+                "fp16 operands: plain / GELU / QuickGELU 16-bit output and the fp32 residual epilogue only");
   // GEGLU (Perceiver feed-forward, perceiver.py:85-102): rows of W interleaved (a_j, gate_j) -> out[M, N/2] = a * gelu(gate),
   // optionally the bf16 pre-activation [M, N] to out2 (row stride 2 * ldo).  DGEGLU (its backward): acc = dy[M, N], res =
   // the saved pre-activation h[M, 2N]: out[M, 2N] = (dy * gelu(g), dy * a * gelu'(g)) interleaved (ldo = row stride of h / out).
@@ -271,14 +273,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   // count: NST is a MINIMUM).  An epilogue that issued fewer stores than NST would let this barrier pass before k-step 1 of
   // the tile has landed; -DVL_GEMM_SAFE_WAIT builds wait for everything (debug A/B of exactly that failure).
   constexpr int ST_PER_CHUNK = (EPI == EPI_F32 || EPI == EPI_RES_F32) ? NTL
-                               : (IS_DGEGLU || STATS || (EPI == EPI_BF16 && (ACTB == 3 || ACTB == 4))) ? 2 : 1;
+                               : (IS_DGEGLU || STATS || (EPI == EPI_BF16 && (ACTB == 3 || ACTB == 4 || ACTB == 6))) ? 2 : 1;
 #ifdef VL_GEMM_SAFE_WAIT
   constexpr int NST = 0;
 #else
   constexpr int NST = NCH * ST_PER_CHUNK;
 #endif
   static_assert(NCH == 4 * 4 && NST <= 63, "NST = stores per wave and tile; vmcnt is a 6-bit counter");
-  static_assert(!(EPI == EPI_BF16 && (ACTB == 3 || ACTB == 4)) || ST_PER_CHUNK == 2, "two-output epilogues store twice per chunk");
+  static_assert(!(EPI == EPI_BF16 && (ACTB == 3 || ACTB == 4 || ACTB == 6)) || ST_PER_CHUNK == 2, "two-output epilogues store twice per chunk");
   auto first_wait_and_barrier = [&]() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" PK_BAR ::"n"(NST) : "memory");
   };
@@ -474,6 +476,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             } else if constexpr (EPI == EPI_BF16 && ACTB == 2) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            } else if constexpr (EPI == EPI_BF16 && ACTB == 5) {
+#pragma unroll
+              for (int e = 0; e < 4; e += 2) {
+                const vl_f32x2 y = qgelu2(vl_f32x2{v[e], v[e + 1]});
+                v[e] = y[0]; v[e + 1] = y[1];
+              }
             }
             u32x2 o;
             if constexpr (F16) { o[0] = pack2h(v[0], v[1]); o[1] = pack2h(v[2], v[3]); }
@@ -530,6 +538,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             u32x4 d;                                              // out2 = gelu'(pre) for the dX GEMM of the backward
 #pragma unroll
             for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
+            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
+          } else if constexpr (EPI == EPI_BF16 && ACTB == 6) {
+            u32x4 d;                                              // out2 = qgelu'(pre)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g;
+              if constexpr (LNF) __builtin_amdgcn_sched_barrier(0);      // one pair at a time: with the four interleaved the folded variant spills (256 VGPRs + scratch)
+            }
             __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
           } else if constexpr (EPI == EPI_RES_BF16) {
 #pragma unroll
@@ -627,8 +643,9 @@ bool vl_gemm_park_supported(int epi, const void* params) {
   if ((p.M & 255) || (p.N & 255) || (p.K & 63) || p.K < 512 || p.M <= 0 || p.N <= 0) return false;
   if (p.res_div != 1) return false;
   if (epi == EPI_RES_BF16 && p.act != 0) return false;
-  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4) return false;
-  if (epi == EPI_BF16 && p.act == 4 && !p.out2) return false;
+  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4 && p.act != VL_ACT_QGELU_DSAVE) return false;
+  if (epi == EPI_BF16 && (p.act == 4 || p.act == VL_ACT_QGELU_DSAVE) && !p.out2) return false;
+  if (epi == EPI_DGELU && (p.act == VL_ACT_QGELU || p.act == VL_ACT_QGELU_DSAVE)) return false;   // (the dispatcher passes the saved form as 4)
   if (p.ldo & 7) return false;
   // 16-byte accesses on every operand
   if (((uintptr_t)p.A | (uintptr_t)p.W) & 15) return false;
@@ -642,6 +659,7 @@ int vl_gemm_park_launch(int epi, const void* params, int ncu, hipStream_t s) {
     if (p.ln_mean || p.row_part || p.out2) return (int)hipErrorInvalidValue;
     if (epi == EPI_BF16 && p.act == 0) return (int)launch_pk<EPI_BF16, 0, true>(p, ncu, s);
     if (epi == EPI_BF16 && p.act == 1) return (int)launch_pk<EPI_BF16, 1, true>(p, ncu, s);
+    if (epi == EPI_BF16 && p.act == VL_ACT_QGELU) return (int)launch_pk<EPI_BF16, 5, true>(p, ncu, s);
     if (epi == EPI_RES_F32) return (int)launch_pk<EPI_RES_F32, 0, true>(p, ncu, s);
     return (int)hipErrorInvalidValue;
   }
@@ -650,10 +668,14 @@ int vl_gemm_park_launch(int epi, const void* params, int ncu, hipStream_t s) {
       if (p.ln_mean) {        // LayerNorm folded into the epilogue (vl_gemm_lnfold_bf16 checked the rest)
         if (p.act == 1) return (int)launch_pk<EPI_BF16, 11>(p, ncu, s);
         if (p.act == 4) return (int)launch_pk<EPI_BF16, 14>(p, ncu, s);
+        if (p.act == VL_ACT_QGELU) return (int)launch_pk<EPI_BF16, 15>(p, ncu, s);
+        if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pk<EPI_BF16, 16>(p, ncu, s);
         return p.act == 0 ? (int)launch_pk<EPI_BF16, 10>(p, ncu, s) : (int)hipErrorInvalidValue;
       }
       if (p.act == 1) return p.out2 ? (int)launch_pk<EPI_BF16, 3>(p, ncu, s) : (int)launch_pk<EPI_BF16, 1>(p, ncu, s);
       if (p.act == 4) return (int)launch_pk<EPI_BF16, 4>(p, ncu, s);
+      if (p.act == VL_ACT_QGELU) return (int)launch_pk<EPI_BF16, 5>(p, ncu, s);
+      if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pk<EPI_BF16, 6>(p, ncu, s);
       return p.act == 2 ? (int)launch_pk<EPI_BF16, 2>(p, ncu, s) : (int)launch_pk<EPI_BF16, 0>(p, ncu, s);
     case EPI_RES_BF16:
       if (p.row_part) return (int)launch_pk<EPI_RES_BF16, 20>(p, ncu, s);

@@ -43,7 +43,8 @@ using IC = std::integral_constant<int, I>;
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// ACT (EPI_BF16 only): 0 none, 1 GELU, 2 ReLU, 3 GELU with the pre-activation also written to out2 (saved for backward)
+// ACT (EPI_BF16 only): 0 none, 1 GELU, 2 ReLU, 3 GELU with the pre-activation also written to out2 (saved for backward),
+// 4 GELU with gelu'(pre-activation) written to out2, 5 QuickGELU, 6 QuickGELU with qgelu'(pre-activation) written to out2
 template <int EPI, int ACT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
     gemm_nt_pp_kernel(const GemmP p) {
@@ -270,6 +271,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             } else if constexpr (EPI == EPI_BF16 && ACT == 2) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            } else if constexpr (EPI == EPI_BF16 && ACT == 5) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
             }
             u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
             *(u32x2*)(wr + (((j * 4 + q) ^ wsw) << 4)) = o;
@@ -290,6 +294,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             u32x4 d;                                              // out2 = gelu'(pre) for the dX GEMM of the backward
 #pragma unroll
             for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
+            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
+          } else if constexpr (EPI == EPI_BF16 && ACT == 6) {
+            u32x4 d;                                              // out2 = qgelu'(pre)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
             __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
           } else if constexpr (EPI == EPI_RES_BF16) {
 #pragma unroll
@@ -347,8 +356,9 @@ bool vl_gemm_pp_supported(int epi, const void* params) {
   if (p.K < 128) return false;                  // the DMA prologue issues two steps of tile 0 up front
   if (p.res_div != 1) return false;
   if (epi == EPI_RES_BF16 && p.act != 0) return false;
-  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4) return false;
-  if (epi == EPI_BF16 && p.act == 4 && !p.out2) return false;
+  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4 && p.act != VL_ACT_QGELU_DSAVE) return false;
+  if (epi == EPI_BF16 && (p.act == 4 || p.act == VL_ACT_QGELU_DSAVE) && !p.out2) return false;
+  if (epi == EPI_DGELU && (p.act == VL_ACT_QGELU || p.act == VL_ACT_QGELU_DSAVE)) return false;   // (the dispatcher passes the saved form as 4)
   if (p.ldo & 7) return false;
   if (((uintptr_t)p.A | (uintptr_t)p.W) & 15) return false;
   if (((uintptr_t)p.out | (uintptr_t)p.res | (uintptr_t)p.out2) & 15) return false;
@@ -361,6 +371,8 @@ int vl_gemm_pp_launch(int epi, const void* params, int ncu, hipStream_t s) {
     case EPI_BF16:
       if (p.act == 1) return p.out2 ? (int)launch_pp<EPI_BF16, 3>(p, ncu, s) : (int)launch_pp<EPI_BF16, 1>(p, ncu, s);
       if (p.act == 4) return (int)launch_pp<EPI_BF16, 4>(p, ncu, s);
+      if (p.act == VL_ACT_QGELU) return (int)launch_pp<EPI_BF16, 5>(p, ncu, s);
+      if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pp<EPI_BF16, 6>(p, ncu, s);
       return p.act == 2 ? (int)launch_pp<EPI_BF16, 2>(p, ncu, s) : (int)launch_pp<EPI_BF16, 0>(p, ncu, s);
     case EPI_RES_BF16: return (int)launch_pp<EPI_RES_BF16, 0>(p, ncu, s);
     case EPI_DGELU: return p.act == 4 ? (int)launch_pp<EPI_DGELU, 4>(p, ncu, s) : (int)launch_pp<EPI_DGELU, 0>(p, ncu, s);

@@ -24,7 +24,8 @@ def _create(name, device, args):
     import warnings
     with warnings.catch_warnings():
         warnings.filterwarnings("ignore", message="precision='fp32'")
-        return tri_create_model(name, None, precision="fp32", device=device, args=args)
+        return tri_create_model(name, None, precision="fp32", device=device, args=args,
+                                force_quick_gelu=bool(getattr(args, "force_quick_gelu", False)))
 
 
 class ViTLens(nn.Module):

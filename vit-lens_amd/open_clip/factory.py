@@ -1,6 +1,7 @@
 """Model registry / factory with the reference's signatures (open_clip/factory.py:60-128,164-366,368-466,750-851).
 Download / HF-hub / OpenAI-JIT loading are out of scope (no network): `pretrained` may be a
-local checkpoint path, which is loaded with the reference's `visual.* -> image.*` duplication rule."""
+local checkpoint path, which is loaded with the reference's `visual.* -> image.*` duplication rule.  OpenAI-weight towers
+(QuickGELU) are built with `force_quick_gelu=True` or a `-quickgelu` config around such a checkpoint."""
 import json
 import logging
 import os
@@ -99,8 +100,15 @@ def tri_create_model(model_name: str, pretrained: Optional[str] = None, precisio
     cfg = get_model_config(model_name)
     if cfg is None:
         raise RuntimeError(f"Model config for {model_name} not found; available models {list_models()}.")
-    if jit or force_custom_text or force_quick_gelu or pretrained_image:
-        raise NotImplementedError("jit / custom-text / quick-gelu / timm towers are outside the hot path")
+    if jit or force_custom_text or pretrained_image:
+        raise NotImplementedError("jit / custom-text / timm towers are outside the hot path")
+    if pretrained and str(pretrained).lower() == "openai":
+        # (factory.py:204-215: the OpenAI archive is a TorchScript file fetched from the network and rebuilt by a JIT loader)
+        raise NotImplementedError("pretrained='openai' needs the OpenAI network archive and its JIT loader, which are out of scope; "
+                                  "what works: a checkpoint of those weights in open_clip layout (a state_dict file) as `pretrained`, "
+                                  "with force_quick_gelu=True or a '-quickgelu' model config (e.g. ViT-B-32-quickgelu)")
+    if force_quick_gelu:
+        cfg["quick_gelu"] = True          # override for use of QuickGELU on non-OpenAI transformer models (factory.py:224-226)
     if precision not in ("fp32", "amp", "amp_bf16", "amp_bfloat16", "bf16"):
         raise NotImplementedError(f"precision {precision!r}: the MI355X path computes GEMMs in bf16 with fp32 accumulation")
     if force_image_size is not None:

@@ -137,9 +137,12 @@ def _block_params(prefix, D, hidden, text_init=None):
 class VisionTransformer(nn.Module):
     """Parameter holder + HIP forward for one ViT tower (image tower, or Lens + ViT `visual` tower)."""
 
-    def __init__(self, embed_dim: int, cfg: CLIPVisionCfg):
+    def __init__(self, embed_dim: int, cfg: CLIPVisionCfg, quick_gelu: bool = False):
         super().__init__()
         self.cfg, self.embed_dim = cfg, embed_dim
+        # `act_layer = QuickGELU if quick_gelu else nn.GELU` of the transformer blocks (model.py:130); the Perceiver's GEGLU and the
+        # point tokenizer's MLP are erf-GELU whatever this says, as in the reference
+        self.quick_gelu = bool(quick_gelu)
         a = cfg.exp_args
         D, P = cfg.width, cfg.patch_size
         self.heads = D // cfg.head_width
@@ -337,7 +340,7 @@ class VisionTransformer(nn.Module):
         from vitlens_hip import engine as E
         c, a = self.cfg, self.cfg.exp_args
         tower = E.TowerCfg(width=c.width, layers=c.layers, heads=self.heads, mlp_ratio=c.mlp_ratio, patch=c.patch_size,
-                           image_size=c.image_size, embed_dim=self.embed_dim)
+                           image_size=c.image_size, embed_dim=self.embed_dim, quick_gelu=self.quick_gelu)
         lens = None
         if self.modality not in ("image", "tactile"):
             lens = E.LensCfg(
@@ -615,8 +618,9 @@ class TriCLIP(nn.Module):
     def __init__(self, embed_dim: int, vision_cfg, text_cfg, quick_gelu: bool = False, cast_dtype=None,
                  output_dict: bool = False):
         super().__init__()
-        if quick_gelu:
-            raise NotImplementedError("QuickGELU towers are not part of the named configs")
+        # QuickGELU (x * sigmoid(1.702 x), what the OpenAI-pretrained CLIP weights were trained with) in the transformer blocks of
+        # all three towers, as the reference's _build_vision_tower / _build_text_tower calls do (model.py:422-435)
+        self.quick_gelu = bool(quick_gelu)
         vision_cfg = CLIPVisionCfg(**vision_cfg) if isinstance(vision_cfg, dict) else vision_cfg
         text_cfg = CLIPTextCfg(**text_cfg) if isinstance(text_cfg, dict) else text_cfg
         self.exp_args = vision_cfg.exp_args
@@ -627,8 +631,8 @@ class TriCLIP(nn.Module):
         img_cfg = CLIPVisionCfg(layers=vision_cfg.layers, width=vision_cfg.width, head_width=vision_cfg.head_width,
                                 mlp_ratio=vision_cfg.mlp_ratio, patch_size=vision_cfg.patch_size,
                                 image_size=vision_cfg.image_size, exp_args=vision_cfg.exp_args)
-        self.image = VisionTransformer(embed_dim, img_cfg)            # module_cfg.set_default_image_cfg
-        self.visual = VisionTransformer(embed_dim, vision_cfg)
+        self.image = VisionTransformer(embed_dim, img_cfg, quick_gelu=self.quick_gelu)      # module_cfg.set_default_image_cfg
+        self.visual = VisionTransformer(embed_dim, vision_cfg, quick_gelu=self.quick_gelu)
         # text tower flattened into the root (model.py:435-443)
         self.text_cfg = text_cfg
         self.context_length, self.vocab_size = text_cfg.context_length, text_cfg.vocab_size
@@ -713,6 +717,12 @@ class TriCLIP(nn.Module):
         self.visual.set_grad_checkpointing(enable); self.image.set_grad_checkpointing(enable)
 
     # ---- encoders ---------------------------------------------------------------------------------
+    def _text_cfg(self):
+        from vitlens_hip import engine as E
+        t = self.text_cfg
+        return E.TextCfg(context_length=t.context_length, vocab_size=t.vocab_size, width=t.width, heads=t.heads, layers=t.layers,
+                         embed_dim=self.text_projection.shape[1], quick_gelu=self.quick_gelu)
+
     def _text(self):
         from vitlens_hip import engine as E
         dev = self.positional_embedding.device
@@ -731,9 +741,7 @@ class TriCLIP(nn.Module):
             self._text_engine, self._text_key = {}, {}
         if slot not in self._text_engine or key != self._text_key.get(slot):
             sd = {k: v for k, v in self.state_dict().items() if not k.startswith(("image.", "visual."))}
-            t = self.text_cfg
-            cfg = E.TextCfg(context_length=t.context_length, vocab_size=t.vocab_size, width=t.width, heads=t.heads, layers=t.layers,
-                            embed_dim=self.text_projection.shape[1])
+            cfg = self._text_cfg()
             if f32:
                 self._text_engine[slot] = F32.TextEngineF32(sd, cfg, dev)
             else:
@@ -766,9 +774,7 @@ class TriCLIP(nn.Module):
         key = (str(dev), tuple(prm[n]._version for n in names))
         if getattr(self, "_text_trainer_obj", None) is None or key != self._text_trainer_key:
             sd = {k: v for k, v in self.state_dict().items() if not k.startswith(("image.", "visual."))}
-            t = self.text_cfg
-            cfg = E.TextCfg(context_length=t.context_length, vocab_size=t.vocab_size, width=t.width, heads=t.heads, layers=t.layers,
-                            embed_dim=self.text_projection.shape[1])
+            cfg = self._text_cfg()
             old = getattr(self, "_text_trainer_obj", None)
             eng = E.TextEngine(sd, cfg, dev, res_dtype=torch.float32, arith="bf16")
             tr = TR.TextTowerTrainer(eng)

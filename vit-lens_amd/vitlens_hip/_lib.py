@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 603
+ABI_VERSION = 604
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {

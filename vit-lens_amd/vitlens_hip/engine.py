@@ -28,6 +28,7 @@ class TowerCfg:
     image_size: int = 224
     embed_dim: int = 768
     in_chans: int = 3
+    quick_gelu: bool = False     # the blocks' MLP activation: QuickGELU x * sigmoid(1.702 x) (OpenAI-pretrained CLIP) instead of erf-GELU
 
 
 @dataclass
@@ -38,6 +39,7 @@ class TextCfg:
     heads: int = 12
     layers: int = 12
     embed_dim: int = 768
+    quick_gelu: bool = False     # as TowerCfg.quick_gelu
 
 
 def _pad64(n):
@@ -126,12 +128,14 @@ class _Workspace:
 LN_FOLD = True
 
 
-def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None):
+def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None, quick_gelu=False):
     """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:254-272, 364-371).
+    quick_gelu: the tower's MLP activation (TowerCfg / TextCfg.quick_gelu; `act_layer`, transformer.py:217-231).
     fold (default: engine.LN_FOLD, bf16 stream only): the LayerNorms folded into the GEMMs either side of them - ln_1 / ln_2 are never
     materialised, the in-projection and c_fc read the residual rows and apply (mean, rstd) in their epilogues, the
     out-projection and c_proj leave the partial row sums of what they store (ops.gemm_lnfold / gemm_res_rowstats)."""
     dh = D // H
+    act = ops.mlp_act(quick_gelu)
     res_epi = ops.EPI_RES_F32 if ws.x.dtype == torch.float32 else ops.EPI_RES_BF16
     if fold is None:
         fold = LN_FOLD
@@ -156,14 +160,14 @@ def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=No
             k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=ws.h, h_row0=r_fc) if mm <= r_fc else {}
             ops.ln_row_stats(ws.part, ws.x, mm, ws.mean, ws.rstd, **k_fc)
             ops.gemm_lnfold(ws.x, w["fc_f"], ws.mean, ws.rstd, ws.hid, w["fc_w"], w["fc_b"], w["ln2_w"], w["ln2_b"], ws.h,
-                            act=ops.ACT_GELU, cfg=cfg, h_ready=bool(k_fc))
+                            act=act, cfg=cfg, h_ready=bool(k_fc))
         else:
             ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, B * L, D)
             ops.gemm(ws.h, w["in_w"], w["in_b"], out=ws.qkv, epi=ops.EPI_BF16, cfg=cfg)
             ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
             ops.gemm(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=res_epi, cfg=cfg)
             ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, B * L, D)
-            ops.gemm(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg)
+            ops.gemm(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=act, cfg=cfg)
         if nxt:
             mm = ops.gemm_res_rowstats(ws.hid, w["proj_w"], w["proj_b"], ws.x, ws.x, ws.part, cfg=cfg)
         else:
@@ -192,9 +196,10 @@ def prep_block_wsplit(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, 
     return blk
 
 
-def run_blocks_wsplit(blocks, ws: "_Workspace", B, L, D, H, causal=False, cfg=-1):
+def run_blocks_wsplit(blocks, ws: "_Workspace", B, L, D, H, causal=False, cfg=-1, quick_gelu=False):
     """run_blocks with two-term weights (prep_block_wsplit); the residual stream must be fp32."""
     dh = D // H
+    act = ops.mlp_act(quick_gelu)
     h2 = ws.h2
     for w in blocks:
         ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], h2[:, :D], B * L, D)
@@ -205,7 +210,7 @@ def run_blocks_wsplit(blocks, ws: "_Workspace", B, L, D, H, causal=False, cfg=-1
         ops.gemm(ws.a, w["out_w_lo"], None, out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
         ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], h2[:, :D], B * L, D)
         ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], h2[:, D:], B * L, D)
-        ops.gemm(h2, w["fc_w2"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg)
+        ops.gemm(h2, w["fc_w2"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=act, cfg=cfg)
         ops.gemm(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
         ops.gemm(ws.hid, w["proj_w_lo"], None, out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
 
@@ -272,7 +277,7 @@ class VitEngine:
         ws = self.workspace(B, L)
         pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
         ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
-        run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg)
+        run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
         if self.projT is None:
             pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
@@ -375,13 +380,14 @@ class TextEngine:
         ops.text_embed(text, self.tok, self.pos, ws.x[:rows])
         eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
         qs = (D // H) ** -0.5 * ops.LOG2E
+        act = ops.mlp_act(cfg.quick_gelu)
         for w in self.blocks:
             ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, rows, D)
             ops.gemm_f16(ws.h, w["in_w"], w["in_b"], out=ws.qkv)
             ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=True, qscale=qs)
             ops.gemm_f16(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32)
             ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, rows, D)
-            ops.gemm_f16(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=ops.ACT_GELU)
+            ops.gemm_f16(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=act)
             ops.gemm_f16(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32)
         ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         f = torch.zeros(ws.Bp, self.projT.shape[0], device=self.device, dtype=torch.float32)
@@ -405,12 +411,12 @@ class TextEngine:
         if self.wsplit:
             if not hasattr(ws, "h2"):
                 ws.h2 = torch.empty(B * L, 2 * D, device=self.device, dtype=torch.bfloat16)
-            run_blocks_wsplit(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg)
+            run_blocks_wsplit(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu)
             pooled = torch.empty(B, 2 * D, device=self.device, dtype=torch.bfloat16)
             for half in (pooled[:, :D], pooled[:, D:]):
                 ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], half, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         else:
-            run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg, fold=False)
+            run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg, fold=False, quick_gelu=cfg.quick_gelu)
             pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
             ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         f = ops.gemm(pooled, self.projT, None, epi=ops.EPI_F32, cfg=self.gemm_cfg)

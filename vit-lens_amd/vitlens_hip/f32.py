@@ -46,16 +46,18 @@ class _Ws:
         self.q, self.k, self.v = hv(0), hv(1), hv(2)
 
 
-def run_blocks_f32(blocks, ws: _Ws, B, L, D, H, causal=False):
-    """x <- N pre-LN transformer blocks, fp32 throughout (transformer.py:254-272, 364-371)."""
+def run_blocks_f32(blocks, ws: _Ws, B, L, D, H, causal=False, quick_gelu=False):
+    """x <- N pre-LN transformer blocks, fp32 throughout (transformer.py:254-272, 364-371); quick_gelu: the tower's MLP
+    activation (TowerCfg / TextCfg.quick_gelu)."""
     scale = (D // H) ** -0.5
+    act = ops.mlp_act(quick_gelu)
     for w in blocks:
         ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, B * L, D)
         ops.gemm_f32(ws.h, w["in_w"], w["in_b"], out=ws.qkv)
         ops.attn_fwd_f32(ws.q, ws.k, ws.v, ws.a, causal=causal, scale=scale)
         ops.gemm_f32(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x)
         ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, B * L, D)
-        ops.gemm_f32(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=ops.ACT_GELU)
+        ops.gemm_f32(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=act)
         ops.gemm_f32(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x)
 
 
@@ -154,7 +156,7 @@ class VitEngineF32:
         ws = self._ws[key]
         pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
         ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
-        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads)
+        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads, quick_gelu=cfg.quick_gelu)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
         ops.layernorm(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
         return pooled if self.projT is None else ops.gemm_f32(pooled, self.projT)
@@ -197,7 +199,7 @@ class TextEngineF32:
         text = text.to(self.device).contiguous()
         ops.text_embed(text, self.tok, self.pos, ws.x)
         eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
-        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads, causal=True)
+        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads, causal=True, quick_gelu=cfg.quick_gelu)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
         ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         f = ops.gemm_f32(pooled, self.projT)

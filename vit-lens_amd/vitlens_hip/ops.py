@@ -11,6 +11,15 @@ F32, BF16, F16 = 0, 1, 2
 EPI_BF16, EPI_F32, EPI_RES_F32, EPI_RES_BF16, EPI_GEGLU, EPI_DGELU, EPI_DGEGLU = 0, 1, 2, 3, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 ACT_GELU_DSAVE = 4          # forward: out = gelu(pre), out2 = gelu'(pre);  with EPI_DGELU: res is that gelu' tensor
+ACT_QGELU = 5               # QuickGELU x * sigmoid(1.702 x): the OpenAI-pretrained CLIP towers (TowerCfg / TextCfg.quick_gelu)
+ACT_QGELU_DSAVE = 6         # ACT_GELU_DSAVE for QuickGELU: out2 = qgelu'(pre); EPI_DGELU takes it exactly as ACT_GELU_DSAVE
+
+
+def mlp_act(quick_gelu: bool, dsave: bool = False) -> int:
+    """The activation code of a transformer block's MLP: exact-erf GELU or QuickGELU, plain or with the saved derivative."""
+    if quick_gelu:
+        return ACT_QGELU_DSAVE if dsave else ACT_QGELU
+    return ACT_GELU_DSAVE if dsave else ACT_GELU
 LOG2E = 1.4426950408889634
 
 _lib = load_library()
@@ -47,9 +56,10 @@ def _chk2d(t, name, dtype=None):
 
 def gemm(a, w, bias=None, out=None, res=None, epi=EPI_BF16, act=ACT_NONE, alpha=1.0, cfg=-1, out2=None, res_div=1):
     """out = epilogue(a @ w.T).  a [M,K] bf16, w [N,K] bf16.  out2: optional pre-activation copy (bf16; with
-    act=ACT_GELU_DSAVE: gelu'(pre) instead, the operand of the backward's EPI_DGELU launched with the same act)."""
-    if act == ACT_GELU_DSAVE and epi == EPI_BF16 and out2 is None:
-        raise ValueError("gemm: ACT_GELU_DSAVE needs out2")
+    act=ACT_GELU_DSAVE / ACT_QGELU_DSAVE: the activation's derivative at pre instead, the operand of the backward's EPI_DGELU
+    launched with the same act)."""
+    if act in (ACT_GELU_DSAVE, ACT_QGELU_DSAVE) and epi == EPI_BF16 and out2 is None:
+        raise ValueError("gemm: ACT_GELU_DSAVE / ACT_QGELU_DSAVE need out2")
     _chk2d(a, "a", torch.bfloat16); _chk2d(w, "w", torch.bfloat16)
     M, K = a.shape
     N = w.shape[0]

@@ -91,6 +91,8 @@ class TowerTrainer:
         self.train_ln_pre, self.train_ln_post, self.train_proj = train_ln_pre, train_ln_post, train_proj
         c = eng.cfg
         self.D, self.H, self.hidden, self.layers = c.width, c.heads, int(c.width * c.mlp_ratio), c.layers
+        # the MLP activation of this tower with its derivative saved by the forward: exact-erf GELU, or QuickGELU (cfg.quick_gelu)
+        self.act_dsave = ops.mlp_act(bool(getattr(c, "quick_gelu", False)), dsave=True)
         dev = eng.device
         # transposed bf16 weights for the dX GEMMs (C = dY . W  ==  NT GEMM against W^T)
         self.wT = [{k: w[k].t().contiguous() for k in ("in_w", "out_w", "fc_w", "proj_w")} for w in eng.blocks]
@@ -183,7 +185,7 @@ class TowerTrainer:
             k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=S.h, h_row0=r_fc) if mm <= r_fc else {}
             ops.ln_row_stats(S.part, x1, mm, m2, r2, **k_fc)
             ops.gemm_lnfold(x1, w["fc_f"], m2, r2, hid, w["fc_w"], w["fc_b"], w["ln2_w"], w["ln2_b"], S.h,
-                            act=ops.ACT_GELU_DSAVE, out2=S.u[l], cfg=cfg, h_ready=bool(k_fc))
+                            act=self.act_dsave, out2=S.u[l], cfg=cfg, h_ready=bool(k_fc))
         else:
             ops.layernorm(S.X[2 * l], w["ln1_w"], w["ln1_b"], h1, B * L, D, mean=m1, rstd=r1)
             ops.gemm(h1, w["in_w"], w["in_b"], out=S.qkv[l], epi=ops.EPI_BF16, cfg=cfg)
@@ -191,8 +193,9 @@ class TowerTrainer:
             ops.gemm(S.a[l], w["out_w"], w["out_b"], out=S.X[2 * l + 1], res=S.X[2 * l], epi=res_epi, cfg=cfg)
             ops.layernorm(S.X[2 * l + 1], w["ln2_w"], w["ln2_b"], h2, B * L, D, mean=m2, rstd=r2)
             # S.u[l] = gelu'(fc output): all the backward needs of the pre-activation, evaluated next to gelu() from the same
-            # exp / rational pieces (+3 VALU per element here) - the dX GEMM's epilogue is then one multiplication
-            ops.gemm(h2, w["fc_w"], w["fc_b"], out=hid, epi=ops.EPI_BF16, act=ops.ACT_GELU_DSAVE, cfg=cfg, out2=S.u[l])
+            # exp / rational pieces (+3 VALU per element here) - the dX GEMM's epilogue is then one multiplication, whichever
+            # activation (erf or QuickGELU) left the derivative
+            ops.gemm(h2, w["fc_w"], w["fc_b"], out=hid, epi=ops.EPI_BF16, act=self.act_dsave, cfg=cfg, out2=S.u[l])
         if write_out:
             S.part_of, S.part_rows = None, 0
             if next_folded:
@@ -276,7 +279,7 @@ class TowerTrainer:
             trainable = l in self.train_blocks
             bp = f"{P}transformer.resblocks.{l}."
             # ---- MLP branch: x2 = x1 + proj(gelu(fc(ln2(x1)))) ----
-            ops.gemm(S.dxb, wT["proj_w"], None, out=S.du, res=S.u[l], epi=ops.EPI_DGELU, act=ops.ACT_GELU_DSAVE, cfg=cfg)   # du = (dx W_proj) * gelu'(u)
+            ops.gemm(S.dxb, wT["proj_w"], None, out=S.du, res=S.u[l], epi=ops.EPI_DGELU, act=self.act_dsave, cfg=cfg)   # du = (dx W_proj) * act'(u)
             if trainable:
                 self._dw(bp + "mlp.c_proj.weight", S.dx, S.hidk[l], rows, bp + "mlp.c_proj.bias")
                 self._dw(bp + "mlp.c_fc.weight", S.du, S.h2[l], rows, bp + "mlp.c_fc.bias")
@@ -380,7 +383,7 @@ class _TextAsTower:
     def __init__(self, te):
         from types import SimpleNamespace
         c = te.cfg
-        self.cfg = SimpleNamespace(width=c.width, heads=c.heads, mlp_ratio=4.0, layers=c.layers)
+        self.cfg = SimpleNamespace(width=c.width, heads=c.heads, mlp_ratio=4.0, layers=c.layers, quick_gelu=c.quick_gelu)
         self.device, self.res_dtype, self.gemm_cfg = te.device, torch.float32, te.gemm_cfg
         self.blocks, self.projT, self.ln_post = te.blocks, te.projT, te.ln_final
         self.tok, self.pos = te.tok, te.pos
