@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 604
+#define VL_ABI_VERSION 605
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -281,6 +281,16 @@ int vl_ce_grad(const float* logits, long ld, int R, int C, int label_off, const 
                float w_row, float w_col, void* G, long ldg, void* GT, long ldgt, float logit_scale,
                float* dscale_inout, float* ws, hipStream_t stream);
 long vl_ce_grad_ws_floats(int R, int C, long ldg, long ldgt);
+/* The similarity-masked forms (ClipLossSimMask, loss.py:522-598): the same arguments plus sim f32 [R, ld_sim >= C] (teacher
+ * similarities of the rows against the columns) and thres.  An element (r, c) with c != r + label_off and
+ * sim[r, c] >= thres is read as logit 0.0f (the reference MULTIPLIES the logits by the mask: it stays in the softmax
+ * denominators of its row and its column), its entry of G / GT is 0 and it adds nothing to *dscale.  diag is never masked,
+ * so vl_ce_loss_accum serves both forms.  sim is read only at r < R, c < C; a NaN similarity is kept. */
+int vl_ce_stats_masked(const float* logits, long ld, int R, int C, int label_off, float* row_lse, float* col_lse,
+                       float* diag, float* col_ws, const float* sim, long ld_sim, float thres, hipStream_t stream);
+int vl_ce_grad_masked(const float* logits, long ld, int R, int C, int label_off, const float* row_lse, const float* col_lse,
+                      float w_row, float w_col, void* G, long ldg, void* GT, long ldgt, float logit_scale,
+                      float* dscale_inout, float* ws, const float* sim, long ld_sim, float thres, hipStream_t stream);
 
 /* ---- backward / optimizer (trainable towers; autograd of the ops above) ---------------------- */
 /* dx = dLN(dy) + dres (optional); outputs f32 `dx` and/or a bf16 copy `dx_bf16` (next GEMM operand). */

@@ -6,21 +6,34 @@
 // column statistics and once to emit the gradient matrix G = dL/dlogits (bf16) together with
 // its transpose, so the two feature-gradient GEMMs run as plain NT GEMMs.
 //   labels: row r <-> column (r + label_off)     (label_off = rank*b under --local-loss)
+//
+// MASKED forms (ClipLossSimMask, open_clip/loss.py:522-598): the three kernels that read the logits are templated on a
+// bool.  With MASKED an element (r, c) off the label diagonal whose teacher similarity sim[r, c] >= thres is READ AS
+// LOGIT 0.0f - the reference multiplies the logits by the mask, so such an element still adds exp(0 - lse) to its row's
+// and its column's denominator - and its gradient (no gradient flows through the mask) and its term of d/dscale are 0.
+// A NaN similarity compares false and is kept.  The unmasked instantiation compiles from the same source as before.
 #include "vl_common.h"
 #include "vitlens_hip.h"
 
 namespace {
 
+// is (r, c) masked out?  sim is only indexed inside the logits' own bounds (the callers guarantee r < R, c < C)
+__device__ __forceinline__ bool sim_masked(const float* sim, long ld_sim, float thres, int r, int c, int off) {
+  return c != r + off && sim[(long)r * ld_sim + c] >= thres;
+}
+
 // one wave per row: online (max, sum) -> lse[r]; diag[r] = logits[r, r+off]
+template <bool MASKED>
 __global__ void __launch_bounds__(256) row_lse_kernel(const float* lg, long ld, int R, int C, int off,
-                                                      float* lse, float* diag) {
+                                                      float* lse, float* diag, const float* sim, long ld_sim, float thres) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   const float* row = lg + (long)r * ld;
   float m = -INFINITY, s = 0.f;
   for (int c = lane; c < C; c += 64) {
-    const float v = row[c];
+    float v = row[c];
+    if constexpr (MASKED) { if (sim_masked(sim, ld_sim, thres, r, c, off)) v = 0.f; }
     const float mn = fmaxf(m, v);
     s = s * __expf(m - mn) + __expf(v - mn);
     m = mn;
@@ -40,14 +53,16 @@ __global__ void __launch_bounds__(256) row_lse_kernel(const float* lg, long ld, 
 }
 
 // column partials over a chunk of 64 rows: thread per column (coalesced)
-__global__ void __launch_bounds__(256) col_part_kernel(const float* lg, long ld, int R, int C,
-                                                       float* pm, float* ps) {
+template <bool MASKED>
+__global__ void __launch_bounds__(256) col_part_kernel(const float* lg, long ld, int R, int C, int off,
+                                                       float* pm, float* ps, const float* sim, long ld_sim, float thres) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   const int r0 = blockIdx.y * 64, r1 = min(R, r0 + 64);
   float m = -INFINITY, s = 0.f;
   for (int r = r0; r < r1; ++r) {
-    const float v = lg[(long)r * ld + c];
+    float v = lg[(long)r * ld + c];
+    if constexpr (MASKED) { if (sim_masked(sim, ld_sim, thres, r, c, off)) v = 0.f; }
     const float mn = fmaxf(m, v);
     s = s * __expf(m - mn) + __expf(v - mn);
     m = mn;
@@ -86,10 +101,14 @@ __global__ void __launch_bounds__(256) ce_reduce_kernel(const float* row_lse, co
 }
 
 // G[r,c] = w_row/R * (softmax_row - onehot) + w_col/R * (softmax_col - onehot); also G^T;
+// (a column that is no row's label - R x C logits with C > R - takes no part in the column loss: the caller passes
+// col_lse[c] = +inf there, which makes its column term exactly 0; vitlens_hip.step.pair_forward does)
 // part[block] = sum over the block of G*l (stage 1 of the deterministic d/dscale reduction: no fp32 atomics)
+template <bool MASKED>
 __global__ void __launch_bounds__(256) grad_kernel(const float* lg, long ld, int R, int C, int off,
                                                    const float* row_lse, const float* col_lse, float w_row, float w_col,
-                                                   bf16_t* G, long ldg, bf16_t* GT, long ldgt, float* part) {
+                                                   bf16_t* G, long ldg, bf16_t* GT, long ldgt, float* part,
+                                                   const float* sim, long ld_sim, float thres) {
   __shared__ float tile[32][33];
   __shared__ float red[4];
   const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
@@ -101,11 +120,15 @@ __global__ void __launch_bounds__(256) grad_kernel(const float* lg, long ld, int
     const int r = r0 + ty + k * 8, c = c0 + tx;
     float g = 0.f;
     if (r < R && c < C) {
-      const float l = lg[(long)r * ld + c];
-      const float hot = (c == r + off) ? 1.f : 0.f;
-      if (row_lse) g += w_row * invR * (__expf(l - row_lse[r]) - hot);
-      if (col_lse) g += w_col * invR * (__expf(l - col_lse[c]) - hot);
-      acc = fmaf(g, l, acc);
+      bool keep = true;
+      if constexpr (MASKED) keep = !sim_masked(sim, ld_sim, thres, r, c, off);
+      if (keep) {
+        const float l = lg[(long)r * ld + c];
+        const float hot = (c == r + off) ? 1.f : 0.f;
+        if (row_lse) g += w_row * invR * (__expf(l - row_lse[r]) - hot);
+        if (col_lse) g += w_col * invR * (__expf(l - col_lse[c]) - hot);
+        acc = fmaf(g, l, acc);
+      }
     }
     tile[ty + k * 8][tx] = g;
     if (G && r < R && c < ldg) G[(long)r * ldg + c] = f2bf(g);   // pad columns [C, ldg) get zeros
@@ -277,22 +300,55 @@ __global__ void __launch_bounds__(256) split3_kernel(const float* x, bf16_t* out
 extern "C" int vl_set_error(const char* msg);
 #define VL_HIP_OK(e) do { hipError_t _e = (e); if (_e != hipSuccess) return vl_set_error(hipGetErrorString(_e)); } while (0)
 
-extern "C" int vl_ce_stats(const float* logits, long ld, int R, int C, int label_off, float* row_lse, float* col_lse,
-                           float* diag, float* col_ws, hipStream_t stream) {
+namespace {
+
+template <bool MASKED>
+int ce_stats_launch(const float* logits, long ld, int R, int C, int label_off, float* row_lse, float* col_lse, float* diag,
+                    float* col_ws, const float* sim, long ld_sim, float thres, hipStream_t stream) {
   if (R <= 0 || C <= 0) return vl_set_error("vl_ce_stats: empty problem");
   if (row_lse || diag) {
     if (!row_lse) return vl_set_error("vl_ce_stats: diag requires row_lse");
-    hipLaunchKernelGGL(row_lse_kernel, dim3((R + 3) / 4), dim3(256), 0, stream, logits, ld, R, C, label_off, row_lse, diag);
+    hipLaunchKernelGGL(row_lse_kernel<MASKED>, dim3((R + 3) / 4), dim3(256), 0, stream, logits, ld, R, C, label_off, row_lse, diag,
+                       sim, ld_sim, thres);
   }
   if (col_lse) {
     if (!col_ws) return vl_set_error("vl_ce_stats: col_lse needs a workspace of 2*ceil(R/64)*C floats");
     const int nch = (R + 63) / 64;
     float* pm = col_ws; float* ps = col_ws + (long)nch * C;
-    hipLaunchKernelGGL(col_part_kernel, dim3((C + 255) / 256, nch), dim3(256), 0, stream, logits, ld, R, C, pm, ps);
+    hipLaunchKernelGGL(col_part_kernel<MASKED>, dim3((C + 255) / 256, nch), dim3(256), 0, stream, logits, ld, R, C, label_off, pm, ps,
+                       sim, ld_sim, thres);
     hipLaunchKernelGGL(col_comb_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, pm, ps, nch, C, col_lse);
   }
   VL_HIP_OK(hipGetLastError());
   return 0;
+}
+
+template <bool MASKED>
+int ce_grad_launch(const float* logits, long ld, int R, int C, int label_off, const float* row_lse, const float* col_lse,
+                   float w_row, float w_col, void* G, long ldg, void* GT, long ldgt, float logit_scale, float* dscale_inout,
+                   float* ws, const float* sim, long ld_sim, float thres, hipStream_t stream) {
+  if (R <= 0 || C <= 0) return vl_set_error("vl_ce_grad: empty problem");
+  if (dscale_inout && !ws) return vl_set_error("vl_ce_grad: d/dscale needs a workspace of vl_ce_grad_ws_floats(R, C, ldg, ldgt) floats");
+  const int gc = (int)(((G && ldg > C ? ldg : C) + 31) / 32), gr = (int)(((GT && ldgt > R ? ldgt : R) + 31) / 32);
+  hipLaunchKernelGGL(grad_kernel<MASKED>, dim3(gc, gr), dim3(256), 0, stream, logits, ld, R, C, label_off, row_lse, col_lse, w_row, w_col,
+                     (bf16_t*)G, ldg, (bf16_t*)GT, ldgt, dscale_inout ? ws : nullptr, sim, ld_sim, thres);
+  if (dscale_inout)
+    hipLaunchKernelGGL(part_finalize_kernel, dim3(1), dim3(1024), 0, stream, ws, (long)gc * gr, 1.0f / logit_scale, dscale_inout);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int vl_ce_stats(const float* logits, long ld, int R, int C, int label_off, float* row_lse, float* col_lse,
+                           float* diag, float* col_ws, hipStream_t stream) {
+  return ce_stats_launch<false>(logits, ld, R, C, label_off, row_lse, col_lse, diag, col_ws, nullptr, 0, 0.f, stream);
+}
+
+extern "C" int vl_ce_stats_masked(const float* logits, long ld, int R, int C, int label_off, float* row_lse, float* col_lse,
+                                  float* diag, float* col_ws, const float* sim, long ld_sim, float thres, hipStream_t stream) {
+  if (!sim || ld_sim < C) return vl_set_error("vl_ce_stats_masked: needs sim f32 [R, C] with ld_sim >= C");
+  return ce_stats_launch<true>(logits, ld, R, C, label_off, row_lse, col_lse, diag, col_ws, sim, ld_sim, thres, stream);
 }
 
 extern "C" int vl_ce_loss_accum(const float* row_lse, const float* col_lse, const float* diag, int R, int C, int label_off,
@@ -305,15 +361,17 @@ extern "C" int vl_ce_loss_accum(const float* row_lse, const float* col_lse, cons
 extern "C" int vl_ce_grad(const float* logits, long ld, int R, int C, int label_off, const float* row_lse, const float* col_lse,
                           float w_row, float w_col, void* G, long ldg, void* GT, long ldgt, float logit_scale,
                           float* dscale_inout, float* ws, hipStream_t stream) {
-  if (R <= 0 || C <= 0) return vl_set_error("vl_ce_grad: empty problem");
-  if (dscale_inout && !ws) return vl_set_error("vl_ce_grad: d/dscale needs a workspace of vl_ce_grad_ws_floats(R, C, ldg, ldgt) floats");
-  const int gc = (int)(((G && ldg > C ? ldg : C) + 31) / 32), gr = (int)(((GT && ldgt > R ? ldgt : R) + 31) / 32);
-  hipLaunchKernelGGL(grad_kernel, dim3(gc, gr), dim3(256), 0, stream, logits, ld, R, C, label_off, row_lse, col_lse, w_row, w_col,
-                     (bf16_t*)G, ldg, (bf16_t*)GT, ldgt, dscale_inout ? ws : nullptr);
-  if (dscale_inout)
-    hipLaunchKernelGGL(part_finalize_kernel, dim3(1), dim3(1024), 0, stream, ws, (long)gc * gr, 1.0f / logit_scale, dscale_inout);
-  VL_HIP_OK(hipGetLastError());
-  return 0;
+  return ce_grad_launch<false>(logits, ld, R, C, label_off, row_lse, col_lse, w_row, w_col, G, ldg, GT, ldgt, logit_scale,
+                               dscale_inout, ws, nullptr, 0, 0.f, stream);
+}
+
+extern "C" int vl_ce_grad_masked(const float* logits, long ld, int R, int C, int label_off, const float* row_lse,
+                                 const float* col_lse, float w_row, float w_col, void* G, long ldg, void* GT, long ldgt,
+                                 float logit_scale, float* dscale_inout, float* ws, const float* sim, long ld_sim, float thres,
+                                 hipStream_t stream) {
+  if (!sim || ld_sim < C) return vl_set_error("vl_ce_grad_masked: needs sim f32 [R, C] with ld_sim >= C");
+  return ce_grad_launch<true>(logits, ld, R, C, label_off, row_lse, col_lse, w_row, w_col, G, ldg, GT, ldgt, logit_scale,
+                              dscale_inout, ws, sim, ld_sim, thres, stream);
 }
 
 extern "C" long vl_ce_grad_ws_floats(int R, int C, long ldg, long ldgt) {

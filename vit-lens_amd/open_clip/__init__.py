@@ -3,7 +3,7 @@
 from .constants import OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, ModalityType
 from .factory import (add_model_config, create_loss, get_model_config, get_tokenizer, list_models, load_checkpoint,
                       tri_create_model, tri_create_model_and_transforms, tri_create_model_from_pretrained)
-from .loss import ClipLoss, ClipLossGeneral, TriClipLoss, gather_features
+from .loss import ClipLoss, ClipLossGeneral, ClipLossSimMask, TriClipLoss, gather_features
 from .model import CLIPTextCfg, CLIPVisionCfg, TriCLIP, get_cast_dtype, get_input_dtype
 from .tokenizer import SimpleTokenizer, decode, tokenize
 from .transform import AugmentationCfg, image_transform

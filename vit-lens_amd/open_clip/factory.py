@@ -12,7 +12,7 @@ from typing import Optional, Union
 
 import torch
 
-from .loss import ClipLoss, ClipLossGeneral, TriClipLoss
+from .loss import ClipLoss, ClipLossGeneral, ClipLossSimMask, TriClipLoss
 from .model import TriCLIP, resize_pos_embed
 from .tokenizer import tokenize
 
@@ -183,15 +183,27 @@ def tri_create_model_from_pretrained(model_name: str, pretrained: Optional[str] 
 
 
 def create_loss(args):
-    """factory.py:750-851 restricted to the hot-path losses (general contrastive, tri / dual / plain)."""
+    """factory.py:750-851 restricted to the losses the reference's epoch drivers can run: general contrastive (tri / dual /
+    plain) and the dual `sim_mask` loss.  `label_mask` is dead in the reference (the dual driver passes A_labels / B_labels,
+    which ClipLossLabelMask.forward does not take; the tri factory never sets use_mask) and stays refused."""
     kw = dict(local_loss=args.local_loss, gather_with_grad=args.gather_with_grad, cache_labels=True,
               rank=args.rank, world_size=args.world_size, use_horovod=getattr(args, "horovod", False))
     if getattr(args, "distill", False) or "coca" in getattr(args, "model", "").lower() or getattr(args, "vid_distill_tokens", False):
         raise NotImplementedError("distillation / CoCa / video-token losses are out of scope (SURVEY §2 A5)")
     if getattr(args, "n_tower", 2) == 3:
-        if getattr(args, "contra_loss_type", "general") != "general":
-            raise NotImplementedError("label_mask / sim_mask losses are out of scope (SURVEY §2 A5)")
-        if getattr(args, "use_dual_loss", False):
+        kind = getattr(args, "contra_loss_type", "general")
+        dual = getattr(args, "use_dual_loss", False)
+        if kind == "sim_mask" and dual:
+            logging.info(f"[Loss class]: {ClipLossSimMask.__name__}")
+            return ClipLossSimMask(sim_thres=args.sim_thres, **kw)
+        if kind == "sim_mask":
+            raise NotImplementedError("sim_mask exists for --use_dual_loss only: for the tri-modal loss the reference's factory "
+                                      "falls through to the two-feature ClipLoss, which fails at the three-feature call")
+        if kind != "general":
+            raise NotImplementedError(f"contra_loss_type={kind!r}: label_mask cannot run in the reference either (the dual driver "
+                                      "passes A_labels / B_labels that ClipLossLabelMask.forward does not take, the tri factory "
+                                      "never sets use_mask) and is out of scope (SURVEY §2 A5)")
+        if dual:
             logging.info("[Loss class]: ClipLossGeneral")
             return ClipLossGeneral(**kw)
         logging.info("[Loss class]: TriClipLoss")

@@ -56,8 +56,9 @@ def maybe_move_to_device(inp, device):
 def _refuse(args):
     if getattr(args, "distill", False):
         raise NotImplementedError("distillation is outside the hot path (SURVEY section 2)")
-    if getattr(args, "contra_loss_type", "general") != "general":
-        raise NotImplementedError("label_mask / sim_mask losses are outside the hot path (SURVEY section 2)")
+    if getattr(args, "contra_loss_type", "general") not in ("general", "sim_mask"):
+        raise NotImplementedError("the label_mask loss is outside the hot path (SURVEY section 2): the reference's own drivers "
+                                  "cannot run it")
     if getattr(args, "horovod", False):
         raise NotImplementedError("Horovod is outside the hot path: one process per GPU on torch.distributed (RCCL)")
 

@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 604
+ABI_VERSION = 605
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -55,6 +55,8 @@ SIGNATURES = {
     "vl_ce_loss_accum": [P, P, P, I, I, I, F, F, P, P],
     "vl_ce_grad": [P, L, I, I, I, P, P, F, F, P, L, P, L, F, P, P, P],
     "vl_ce_grad_ws_floats": [I, I, L, L],
+    "vl_ce_stats_masked": [P, L, I, I, I, P, P, P, P, P, L, F, P],
+    "vl_ce_grad_masked": [P, L, I, I, I, P, P, F, F, P, L, P, L, F, P, P, P, L, F, P],
     "vl_gemm_bf16_ex": [P, P, P, P, P, P, I, I, I, I, I, I, F, I, I, I, I, P],
     "vl_kaldi_fbank": [P, L, I, L, P, P, P, I, I, I, I, I, F, F, F, P],
     "vl_fps": [P, P, P, P, I, I, I, P],

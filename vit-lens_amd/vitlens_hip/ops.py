@@ -535,16 +535,35 @@ def split_bf16x3(x, pattern):
     return out
 
 
-def ce_stats(logits, label_off=0, want_cols=True):
+def _chk_sim(logits, sim, thres, who):
+    """The teacher-similarity block of the masked CE entries: f32, the logits' shape and device, unit column stride."""
+    if thres is None:
+        raise ValueError(f"{who}: sim needs thres")
+    if not torch.is_tensor(sim) or sim.dtype != torch.float32 or sim.dim() != 2 or tuple(sim.shape) != tuple(logits.shape):
+        raise ValueError(f"{who}: sim must be an f32 tensor of the logits' shape {tuple(logits.shape)}")
+    if sim.device != logits.device or sim.stride(1) != 1:
+        raise ValueError(f"{who}: sim must live on the logits' device with contiguous rows")
+
+
+def ce_stats(logits, label_off=0, want_cols=True, sim=None, thres=None):
+    """sim / thres (ClipLossSimMask): an element off the label diagonal with sim[r, c] >= thres is read as logit 0.0."""
     _chk2d(logits, "logits", torch.float32)
+    if sim is None and thres is not None:
+        raise ValueError("ce_stats: thres needs sim")
+    if sim is not None:
+        _chk_sim(logits, sim, thres, "ce_stats")
     R, Cc = logits.shape
     dev = logits.device
     row_lse = torch.empty(R, device=dev, dtype=torch.float32)
     diag = torch.empty(R, device=dev, dtype=torch.float32)
     col_lse = torch.empty(Cc, device=dev, dtype=torch.float32) if want_cols else None
     ws = torch.empty(2 * ((R + 63) // 64) * Cc, device=dev, dtype=torch.float32) if want_cols else None
-    check(_lib.vl_ce_stats(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), _p(diag),
-                           _p(ws), _stream()))
+    if sim is None:
+        check(_lib.vl_ce_stats(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), _p(diag),
+                               _p(ws), _stream()))
+    else:
+        check(_lib.vl_ce_stats_masked(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), _p(diag),
+                                      _p(ws), _p(sim), sim.stride(0), float(thres), _stream()))
     return row_lse, col_lse, diag
 
 
@@ -553,7 +572,15 @@ def ce_loss_accum(loss, row_lse, col_lse, diag, R, Cc, label_off, w_row, w_col):
                                 _p(loss), _stream()))
 
 
-def ce_grad(logits, row_lse, col_lse, label_off, w_row, w_col, logit_scale, dscale, need_g=True, need_gt=True):
+def ce_grad(logits, row_lse, col_lse, label_off, w_row, w_col, logit_scale, dscale, need_g=True, need_gt=True, sim=None,
+            thres=None):
+    """sim / thres (ClipLossSimMask): at an element off the label diagonal with sim[r, c] >= thres the logit is read as 0.0
+    and G, GT and the d/dscale term are 0 (no gradient flows through the mask)."""
+    if sim is None and thres is not None:
+        raise ValueError("ce_grad: thres needs sim")
+    if sim is not None:
+        _chk2d(logits, "logits", torch.float32)
+        _chk_sim(logits, sim, thres, "ce_grad")
     R, Cc = logits.shape
     dev = logits.device
     ldg = (Cc + 63) // 64 * 64
@@ -564,8 +591,13 @@ def ce_grad(logits, row_lse, col_lse, label_off, w_row, w_col, logit_scale, dsca
     if dscale is not None:
         ws = torch.empty(int(_lib.vl_ce_grad_ws_floats(R, Cc, ldg if need_g else 0, ldgt if need_gt else 0)), device=dev,
                          dtype=torch.float32)
-    check(_lib.vl_ce_grad(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), float(w_row),
-                          float(w_col), _p(G), ldg, _p(GT), ldgt, float(logit_scale), _p(dscale), _p(ws), _stream()))
+    if sim is None:
+        check(_lib.vl_ce_grad(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), float(w_row),
+                              float(w_col), _p(G), ldg, _p(GT), ldgt, float(logit_scale), _p(dscale), _p(ws), _stream()))
+    else:
+        check(_lib.vl_ce_grad_masked(_p(logits), logits.stride(0), R, Cc, label_off, _p(row_lse), _p(col_lse), float(w_row),
+                                     float(w_col), _p(G), ldg, _p(GT), ldgt, float(logit_scale), _p(dscale), _p(ws), _p(sim),
+                                     sim.stride(0), float(thres), _stream()))
     return G, GT
 
 

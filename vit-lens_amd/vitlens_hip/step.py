@@ -327,8 +327,30 @@ def _is_dev_scale(scale) -> bool:
     return torch.is_tensor(scale)
 
 
+def _mask_operands(mask, R: int, Cn: int):
+    """mask = (teacher features of the rows [R, D], teacher features of the columns [C, D], thres) -> the two bf16x3
+    operands of the similarity GEMM and the threshold.  Always the UN-SCALED features: the similarity that is compared with
+    `thres` is a cosine, whatever the temperature does to the logits' row operand."""
+    trow, tcol, thres = mask
+    if trow.shape[0] != R or tcol.shape[0] != Cn or trow.shape[1] != tcol.shape[1]:
+        raise ValueError(f"pair loss mask: teacher features {tuple(trow.shape)} x {tuple(tcol.shape)} do not describe the "
+                         f"{R} x {Cn} logits")
+    return (ops.split_bf16x3(trow.detach().float().contiguous(), 0), ops.split_bf16x3(tcol.detach().float().contiguous(), 1),
+            float(thres))
+
+
+def _label_columns_only(col_lse, label_off: int, R: int):
+    """The column loss is a mean over the R label columns [label_off, label_off + R).  A column outside them (R x C logits
+    with C > R and w_col != 0) is in no term of it: its log-sum-exp becomes +inf, so that vl_ce_grad's column term
+    exp(l - lse) - 0 is exactly 0 there (vl_ce_loss_accum reads label columns only).  Square logits: nothing to do."""
+    if col_lse is not None and (label_off > 0 or label_off + R < col_lse.shape[0]):
+        col_lse[:max(label_off, 0)] = float("inf")
+        col_lse[label_off + R:] = float("inf")
+    return col_lse
+
+
 def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: float = 0.5,
-                 chunk_rows: Optional[int] = None):
+                 chunk_rows: Optional[int] = None, mask=None):
     """loss contribution w_row*CE(scale*x y^T) + w_col*CE(columns); returns (loss[1] tensor, ctx).
 
     scale: a Python float (the temperature itself), or - round 4 - the LEARNABLE LOG-temperature as a 1-element f32 tensor
@@ -341,38 +363,62 @@ def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: flo
     are never held whole.  Forward = per block of rows: logits GEMM, exact row log-sum-exp, the block's column
     log-sum-exp; the column statistics of the blocks are merged by one logsumexp over [blocks, C].  Backward
     recomputes each block's logits (training/train.py:154-210 reaches batch 2048 by re-running the towers per
-    accumulation step; here only one thin GEMM is re-run)."""
+    accumulation step; here only one thin GEMM is re-run).
+
+    mask (ClipLossSimMask, loss.py:522-598; None = the plain loss, untouched): (teacher features of the rows, teacher
+    features of the columns, thres).  sim = rows @ columns^T comes from the same bf16x3 GEMM as the logits (alpha = 1, on
+    the un-scaled teacher features, ~2^-17 relative), and an element off the label diagonal with sim >= thres enters both
+    softmaxes as logit 0.0 - the reference multiplies the logits by the mask - and carries no gradient.  Row-blocked mode
+    never holds sim whole either: each row block's sim block is computed next to its logits block, and recomputed next to
+    the recomputed logits in the backward."""
     R, Cn = x.shape[0], y.shape[0]
     rb = _chunk_rows(R, Cn, chunk_rows)
     dev_scale = _is_dev_scale(scale)
     alpha = 1.0 if dev_scale else scale
     xb = ops.split_bf16x3(ops.scale_exp(x.contiguous(), scale) if dev_scale else x, 0)
     yb = ops.split_bf16x3(y, 1)
+    tr = tc = thres = None
+    if mask is not None:
+        tr, tc, thres = _mask_operands(mask, R, Cn)
     if rb == 0:
         logits = ops.logits_gemm(xb, yb, alpha)
-        row_lse, col_lse, diag = ops.ce_stats(logits, label_off, want_cols=(w_col != 0.0))
+        if mask is None:
+            sim = None
+            row_lse, col_lse, diag = ops.ce_stats(logits, label_off, want_cols=(w_col != 0.0))
+        else:
+            sim = ops.logits_gemm(tr, tc, 1.0)
+            row_lse, col_lse, diag = ops.ce_stats(logits, label_off, want_cols=(w_col != 0.0), sim=sim, thres=thres)
+        col_lse = _label_columns_only(col_lse, label_off, R)
         loss = torch.zeros(1, device=x.device, dtype=torch.float32)
         ops.ce_loss_accum(loss, row_lse if w_row != 0.0 else None, col_lse, diag, R, Cn, label_off, w_row, w_col)
-        return loss, (x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, 0, None, None)
+        return loss, (x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, 0, None, None, sim, None, thres)
     row_lse = torch.empty(R, device=x.device); diag = torch.empty(R, device=x.device)
     col_parts = []
     for r0 in range(0, R, rb):
         r1 = min(R, r0 + rb)
         lg = ops.logits_gemm(xb[r0:r1], yb, alpha)
-        rl, cl, dg = ops.ce_stats(lg, label_off + r0, want_cols=(w_col != 0.0))
+        if mask is None:
+            rl, cl, dg = ops.ce_stats(lg, label_off + r0, want_cols=(w_col != 0.0))
+        else:
+            sm = ops.logits_gemm(tr[r0:r1], tc, 1.0)
+            rl, cl, dg = ops.ce_stats(lg, label_off + r0, want_cols=(w_col != 0.0), sim=sm, thres=thres)
+            del sm
         row_lse[r0:r1] = rl; diag[r0:r1] = dg
         if cl is not None:
             col_parts.append(cl)
         del lg
-    col_lse = torch.logsumexp(torch.stack(col_parts), dim=0) if col_parts else None
+    col_lse = _label_columns_only(torch.logsumexp(torch.stack(col_parts), dim=0), label_off, R) if col_parts else None
     loss = torch.zeros(1, device=x.device, dtype=torch.float32)
     ops.ce_loss_accum(loss, row_lse if w_row != 0.0 else None, col_lse, diag, R, Cn, label_off, w_row, w_col)
-    return loss, (x, y, None, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb)
+    return loss, (x, y, None, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb, tr, tc, thres)
 
 
 def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True):
-    """-> (dx, dy, dscale).  dscale = dL/d(scale) for a float scale, dL/d(logit_scale) (log domain) for a device scale."""
-    x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb = ctx
+    """-> (dx, dy, dscale).  dscale = dL/d(scale) for a float scale, dL/d(logit_scale) (log domain) for a device scale.
+    With a mask (pair_forward) the masked elements of dL/dlogits are zero, so they reach neither dx, dy nor dscale; the
+    teacher features inside the mask receive nothing (the reference's mask is a comparison: no gradient)."""
+    x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb, sim, tc, thres = ctx
+    mk = (lambda sm: {}) if thres is None else (lambda sm: dict(sim=sm, thres=thres))
     dscale = torch.zeros(1, device=x.device, dtype=torch.float32)
     dev_scale = _is_dev_scale(scale)
     # vl_ce_grad accumulates sum(G * logits) / logit_scale: with 1.0 that IS d/d(log-scale)
@@ -380,7 +426,7 @@ def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True):
     fin = (lambda t: ops.scale_exp(t, scale, out=t)) if dev_scale else (lambda t: t)
     if rb == 0:
         G, GT = ops.ce_grad(logits, row_lse if w_row != 0.0 else None, col_lse, label_off, w_row * g, w_col * g, cscale,
-                            dscale, need_g=need_dx, need_gt=need_dy)
+                            dscale, need_g=need_dx, need_gt=need_dy, **mk(sim))
         dx = dy = None
         if need_dx:
             dx = fin(ops.gemm(G, ops.transpose_to_bf16(y, ldo=G.shape[1]), None, epi=ops.EPI_F32, alpha=alpha))
@@ -391,12 +437,14 @@ def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True):
     dx = torch.empty(R, x.shape[1], device=x.device) if need_dx else None
     dy = torch.zeros(Cn, y.shape[1], device=x.device) if need_dy else None
     yt = None
+    tr = sim                                   # row-blocked: the slot holds the teacher ROW operand, not a sim matrix
     for r0 in range(0, R, rb):
         r1 = min(R, r0 + rb)
         f = (r1 - r0) / R                      # the kernels average over the rows they are given: re-weight to the global mean
         lg = ops.logits_gemm(xb[r0:r1], yb, alpha)
+        sm = None if thres is None else ops.logits_gemm(tr[r0:r1], tc, 1.0)
         G, GT = ops.ce_grad(lg, row_lse[r0:r1] if w_row != 0.0 else None, col_lse, label_off + r0, w_row * g * f, w_col * g * f,
-                            cscale, dscale, need_g=need_dx, need_gt=need_dy)
+                            cscale, dscale, need_g=need_dx, need_gt=need_dy, **mk(sm))
         if need_dx:
             if yt is None:
                 yt = ops.transpose_to_bf16(y, ldo=G.shape[1])
@@ -404,12 +452,13 @@ def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True):
         if need_dy:
             xt = ops.transpose_to_bf16(x[r0:r1].contiguous(), ldo=GT.shape[1])
             ops.gemm(GT, xt, None, out=dy, res=dy, epi=ops.EPI_RES_F32, alpha=alpha)       # dy += scale * G_b^T x_b
-        del lg, G, GT
+        del lg, G, GT, sm
     return (fin(dx) if need_dx else None), (fin(dy) if need_dy else None), dscale
 
 
 def pair_loss_and_grads(comm, rank: int, world: int, xl, yl, ax, ay, scale, local_loss: bool = False,
-                        gather_with_grad: bool = False, need_x: bool = True, need_y: bool = True, dist: Optional[bool] = None):
+                        gather_with_grad: bool = False, need_x: bool = True, need_y: bool = True, dist: Optional[bool] = None,
+                        sim_teacher: Optional[str] = None, sim_thres: Optional[float] = None):
     """One (x, y) pair of ClipLossGeneral / TriClipLoss over the global batch (loss.py:116-138, 293-308) as rank `rank`
     computes it, and the gradients that arrive at THIS rank's features.
 
@@ -422,17 +471,29 @@ def pair_loss_and_grads(comm, rank: int, world: int, xl, yl, ax, ay, scale, loca
     dist: run the multi-rank code path (default: world > 1).  True at world 1 = every collective of the path executes on a
     one-rank communicator (`force_comm` of the steps: the RCCL calls, their streams and their buffer contracts are exercised
     on one GPU; the values are those of the single-rank path).
+    sim_teacher ("x" | "y" | None) with sim_thres: ClipLossSimMask (loss.py:522-598) with the named side as the TEACHER, whose
+      similarities teacher @ teacher^T >= sim_thres mask the off-diagonal logits (to logit 0.0, `pair_forward`).  The caller
+      names the side because the argument order here is the caller's: the reference module has x = teacher, `DualAudioStep`
+      calls with x = visual (student), y = text (teacher).  The full matrix is masked by the symmetric all_t @ all_t^T in
+      either orientation; under local_loss BOTH directions use the one block sim[rank*b + i, j] = t_local @ all_t^T (the
+      reference slices mask and mask^T, which are the same predicate because sim is symmetric): one sim block per rank.
     Returns (loss[1], dxl | None, dyl | None, dscale[1])."""
     b = xl.shape[0]
     dist = world > 1 if dist is None else dist
+    if sim_teacher not in (None, "x", "y"):
+        raise ValueError(f"pair_loss_and_grads: sim_teacher is 'x', 'y' or None, got {sim_teacher!r}")
+    if sim_teacher is not None and sim_thres is None:
+        raise ValueError("pair_loss_and_grads: sim_teacher needs sim_thres")
+    tl, ta = (None, None) if sim_teacher is None else ((xl, ax) if sim_teacher == "x" else (yl, ay))
     if dist and local_loss:
-        l1, c1 = pair_forward(xl, ay, scale, label_off=rank * b, w_row=0.5, w_col=0.0)
-        l2, c2 = pair_forward(yl, ax, scale, label_off=rank * b, w_row=0.5, w_col=0.0)
+        mk = {} if tl is None else dict(mask=(tl, ta, sim_thres))
+        l1, c1 = pair_forward(xl, ay, scale, label_off=rank * b, w_row=0.5, w_col=0.0, **mk)
+        l2, c2 = pair_forward(yl, ax, scale, label_off=rank * b, w_row=0.5, w_col=0.0, **mk)
         dxl, d_ay, ds1 = pair_backward(c1, need_dx=need_x, need_dy=need_y and gather_with_grad)
         dyl, d_ax, ds2 = pair_backward(c2, need_dx=need_y, need_dy=need_x and gather_with_grad)
         loss, ds = l1 + l2, ds1 + ds2
     else:
-        loss, c = pair_forward(ax, ay, scale)
+        loss, c = pair_forward(ax, ay, scale, **({} if ta is None else dict(mask=(ta, ta, sim_thres))))
         d_ax, d_ay, ds = pair_backward(c, need_dx=need_x, need_dy=need_y)
         dxl = dyl = None
 
@@ -857,14 +918,23 @@ class DualAudioStep(_PerceiverLensStep):
     """Audio <-> text dual-tower step (reference `train_dual_one_epoch` + ClipLossGeneral, training/train.py:315-470,
     recipe TRAIN_INFERENCE.md:283-299 with --use_dual_loss --align_to text): text tower frozen, visual tower =
     AST tokenizer + Perceiver (trainable) -> locked ViT with unlocked class_embedding.  Multi-GPU semantics are the
-    tri-modal step's (packed all-gather, flat gradient all-reduce = mean of per-rank gradients of the global loss)."""
+    tri-modal step's (packed all-gather, flat gradient all-reduce = mean of per-rank gradients of the global loss).
+
+    contra_loss_type "general" (default) | "sim_mask" with sim_thres (--contra_loss_type / --sim_thres, params.py:43-54):
+    "sim_mask" is ClipLossSimMask (loss.py:485-598) with the frozen TEXT tower as the teacher - audio clips whose captions
+    are (nearly) the same text, text similarity >= sim_thres, are not each other's negatives; they enter the softmax as
+    logit 0.0, as in the reference (`pair_forward`)."""
 
     def __init__(self, sd, tower: TowerCfg, text: TextCfg, lens: LensCfg, device, micro_batch: int = 256, lr: float = 2e-4,
                  betas=(0.9, 0.98), eps: float = 1e-6, weight_decay: float = 0.2, rank: int = 0, world_size: int = 1,
                  gemm_cfg: int = -1, comm=None, frozen_res_dtype=torch.float32, local_loss: bool = False,
                  gather_with_grad: bool = False, train_res_dtype=torch.float32, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
-                 grad_clip_norm: Optional[float] = None):
+                 grad_clip_norm: Optional[float] = None, contra_loss_type: str = "general", sim_thres: float = 0.8):
+        if contra_loss_type not in ("general", "sim_mask"):
+            raise NotImplementedError(f"DualAudioStep: contra_loss_type is 'general' or 'sim_mask', got {contra_loss_type!r} "
+                                      "(label_mask cannot run in the reference's drivers either)")
+        self.contra_loss_type, self.sim_thres = contra_loss_type, float(sim_thres)
         self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
                         overlap_backward, grad_clip_norm)
         self._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
@@ -911,8 +981,11 @@ class DualAudioStep(_PerceiverLensStep):
             av, at = [t.contiguous() for t in allp.split(E, dim=1)]
         else:
             av, at = fv, ft
+        # sim_mask: the TEACHER is the text side, which sits in the y position of this call
+        mk = dict(sim_teacher="y", sim_thres=self.sim_thres) if self.contra_loss_type == "sim_mask" else {}
         loss, dv, _, ds = pair_loss_and_grads(self.comm, self.rank, self.world, fv, ft, av, at, scale,    # ClipLossGeneral(x=visual, y=text)
-                                              local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_y=False, dist=self.dist)
+                                              local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_y=False, dist=self.dist,
+                                              **mk)
         dvraw = ops.l2_normalize_bwd(fv, dv, vnorm)
         self._backward_all(dvraw, nmb, mb)
         self.grads["logit_scale"] += ds
