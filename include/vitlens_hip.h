@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 605
+#define VL_ABI_VERSION 606
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -342,6 +342,22 @@ int vl_attn_bwd_fused_bf16(const void* q, const void* k, const void* v, const vo
 int vl_kaldi_fbank(const float* wave, long wave_stride, int batch, long n_samples, const float* window, const float* banks,
                    float* out, int target_len, int win, int shift, int nfft, int nmel, float preemph, float mean, float std,
                    hipStream_t stream);
+/* Windowed-sinc polyphase resampler = torchaudio.functional.resample at its defaults (sinc_interp_hann, width 6, rolloff
+ * 0.99; csrc/vl_audio_train.hip; parity unpinned like the filterbank).  o = orig / gcd, n = new / gcd.  in [batch, n_in] f32
+ * (row stride in_stride); offsets int32 [n] and taps f32 [n, K], K = 2W + 1: the compact per-phase table of
+ * vitlens_hip/audio.py sinc_resample_table - output j = i n + p reads the inputs i o - W + offsets[p] + k, k < K, zeros
+ * outside [0, n_in).  out [batch, n_out] f32 (row stride out_stride) receives the output samples out_first ..
+ * out_first + n_out - 1 of the ceil(n n_in / o) a whole-row call gives, bit-identical to them.  Refused: a window outside
+ * that range, an even K, a ratio whose o is so large that one tile's input span does not fit the staging buffer. */
+int vl_resample_sinc(const float* in, long in_stride, int batch, long n_in, const int* offsets, const float* taps, int o, int n,
+                     int K, float* out, long out_stride, long out_first, long n_out, hipStream_t stream);
+/* The training transform after the filterbank (ASTProcessorTrain, at_processor.py:336-362) in one pass, out of place:
+ *   out[b, (t + roll) mod T, f] = ((masked ? 0 : in[b, t, f]) - mean) / std + amp * u(seed_b, t, f)
+ * in / out [batch, T, F] f32; params: per sample 32 bytes {int32 f0, fw, t0, tw; float amp; int32 roll; uint64 seed}: masks
+ * [f0, f0 + fw) over f and [t0, t0 + tw) over t, roll any integer.  u in [0, 1) = (bits >> 8) 2^-24 of Philox4x32-10 keyed
+ * by seed, counter = (t F + f) / 4, word (t F + f) % 4. */
+int vl_fbank_augment(const float* in, float* out, int batch, int T, int F, const void* params, float mean, float std,
+                     hipStream_t stream);
 /* ---- point-cloud tokenizer (PointBERT grouping) ---- */
 /* farthest point sampling: xyz [B,N,3] f32, start [B] (the reference draws it with torch.randint, misc.py:60);
  * idx [B,G] int64 (bit-exact vs misc.fps), centers [B,G,3] optional. */

@@ -4,8 +4,9 @@
 File decoding (JPEG/PNG via Pillow, `.npy`, torch-saved tensors) stays on the host as in the reference; everything after
 the decode runs on the GPU through the on-GPU transforms (open_clip/transform.py, modal_depth / modal_3d /
 modal_tactile processors).  Besides paths every processor accepts already-decoded items (PIL images,
-arrays, tensors).  The audio processor takes spectrogram tensors only: the reference's waveform front end is torchaudio's
-kaldi fbank (modal_audio/processors/at_processor.py:854-903), which is not available here."""
+arrays, tensors).  The audio processor takes spectrogram tensors, waveforms and PCM .wav paths at any sample rate: the
+reference's waveform front end (torchaudio's resampler and kaldi fbank, modal_audio/processors/at_processor.py:854-903)
+is restated in HIP."""
 import re
 from types import SimpleNamespace
 

@@ -1,10 +1,17 @@
-"""Evaluation-time audio preprocessing on the GPU (reference: AudioASTProcessorEval,
-open_clip/modal_audio/processors/at_processor.py:823-903): a waveform -> `n_clip` clips of `clip_duration` seconds ->
-Kaldi log-mel filterbank [512, 128] per clip -> (x - mean) / std.  The spectrogram runs in vl_kaldi_fbank; the clip
-selection is host arithmetic on sample indices.
+"""Audio preprocessing on the GPU.
 
-Inputs: a waveform tensor [channels, n] / [n] at `sampling_rate`, or the path of a PCM .wav file at that rate (read with the
-standard library; torchaudio - the reference's loader and resampler - is not available, other rates are refused).
+Evaluation (reference: AudioASTProcessorEval, open_clip/modal_audio/processors/at_processor.py:823-903): a waveform ->
+`n_clip` clips of `clip_duration` seconds -> Kaldi log-mel filterbank [512, 128] per clip -> (x - mean) / std.  The
+spectrogram runs in vl_kaldi_fbank; the clip selection is host arithmetic on sample indices.
+
+Training (reference: ASTProcessorTrain, :313-436): one random clip -> filterbank -> FrequencyMasking / TimeMasking ->
+Normalize -> uniform noise -> roll along time.  Every random number is drawn on the host from the processor's own
+generator; the transform after the filterbank is one vl_fbank_augment launch for a whole batch.
+
+Inputs: a waveform tensor [channels, n] / [n] (at `sampling_rate` unless `sr=` says otherwise), or the path of a PCM .wav file
+(8 / 16 / 24 / 32-bit, read with the standard library; torchaudio - the reference's loader - is not available).  Audio at
+another rate is resampled by vl_resample_sinc (torchaudio.functional.resample's defaults restated), and only the sample
+ranges the clips need: the clip arithmetic is done in the target rate on the length the whole-file resample would have.
 Clip placement for recordings longer than one clip: `clips_per_video` windows spread uniformly from the start to
 (duration - clip_duration), which is what pytorchvideo's ConstantClipsPerVideoSampler computes for the reference."""
 from fractions import Fraction
@@ -16,7 +23,7 @@ AST_AS_STD = (4.5689974,)
 
 
 def read_wav(path):
-    """-> (waveform [channels, n] float32 in [-1, 1), sample rate): PCM 16 / 32-bit little-endian .wav, channel-major like
+    """-> (waveform [channels, n] float32 in [-1, 1), sample rate): PCM 8 (unsigned) / 16 / 24 / 32-bit little-endian .wav, channel-major like
     torchaudio.load (the reference keeps every channel: `audio_get_clip` subtracts the mean over all of them and
     kaldi.fbank reads channel 0, at_processor.py:193-224,855-866)."""
     import wave
@@ -29,8 +36,14 @@ def read_wav(path):
     with wave.open(str(path), "rb") as f:
         sr, ch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
         raw = f.readframes(n)
-    if width == 2:
+    if width == 1:
+        a = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    elif width == 2:
         a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        a = ((v ^ 0x800000) - 0x800000).astype(np.float32) / 8388608.0               # sign-extend bit 23
     elif width == 4:
         a = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
     else:
@@ -47,6 +60,25 @@ def clip_timepoints(duration: float, clip_duration: float, clips_per_video: int)
     last = Fraction(max(duration - clip_duration, 0.0))
     step = last / max(clips_per_video - 1, 1)
     return [(step * i, step * i + Fraction(clip_duration)) for i in range(clips_per_video)]
+
+
+def random_clip(duration: float, clip_duration: float, rng):
+    """(start, end) seconds of one clip placed uniformly in [0, duration - clip_duration] (0 when the recording is shorter),
+    as Fractions with end = start + clip_duration exactly - pytorchvideo's RandomClipSampler, which the reference's train
+    processor calls (at_processor.py:329-333, 372)."""
+    start = Fraction(rng.uniform(0, max(duration - clip_duration, 0)))
+    return start, start + Fraction(clip_duration)
+
+
+def draw_mask(size: int, param: int, rng):
+    """(start, width) of one masked band along an axis of `size` cells - torchaudio's published mask_along_axis, which
+    FrequencyMasking(param) / TimeMasking(param) apply: v = U param, m = U' (size - v), band [floor(m), floor(m) + floor(v)).
+    0 <= width <= param - 1 and start + width <= size."""
+    if param > size:
+        raise ValueError(f"mask parameter {param} exceeds the axis length {size}")
+    v = rng.random() * param
+    m = rng.random() * (size - v)
+    return int(m), int(v)
 
 
 def audio_get_clip(waveform, sampling_rate, target_duration, start=None, end=None, sub_mean=True, rng=None):
@@ -70,6 +102,41 @@ def audio_get_clip(waveform, sampling_rate, target_duration, start=None, end=Non
     return wf - wf.mean() if sub_mean else wf
 
 
+def _load(item, default_sr, sr=None):
+    """path or waveform -> ([channels, n] float32, its sample rate)."""
+    if isinstance(item, str) or hasattr(item, "__fspath__"):
+        return read_wav(item)
+    wav = torch.as_tensor(item, dtype=torch.float32)
+    return (wav[None] if wav.dim() == 1 else wav), (default_sr if sr is None else int(sr))
+
+
+class _Source:
+    """A recording seen at the processor's rate: `length` samples there, of which `cut(a, b)` materialises [a, b) - a slice,
+    or for another source rate one windowed vl_resample_sinc launch over all channels (bit-identical to the slice of a
+    whole-file resample), so a long recording is never resampled whole for the few clips taken from it."""
+
+    def __init__(self, wav, sr, target_sr, device):
+        from vitlens_hip.audio import resampled_length
+        self.sr, self.target_sr = sr, target_sr
+        self.wav = wav if sr == target_sr else wav.to(device)
+        self.length = wav.shape[1] if sr == target_sr else resampled_length(wav.shape[1], sr, target_sr)
+
+    def cut(self, a=0, b=None):
+        b = self.length if b is None else min(b, self.length)
+        if self.sr == self.target_sr:
+            return self.wav[:, a:b]
+        from vitlens_hip.audio import resample
+        return resample(self.wav, self.sr, self.target_sr, out_first=a, n_out=b - a)
+
+
+def _get_clip(src, sampling_rate, target_duration, start=None, end=None, rng=None):
+    """audio_get_clip on a _Source: the same cut condition, evaluated on the length in the target rate."""
+    dur = float(src.length / sampling_rate)
+    if start is not None and end is not None and start < dur and end <= dur and end - start > 0.5:
+        return audio_get_clip(src.cut(int(start * sampling_rate), int(end * sampling_rate)), sampling_rate, target_duration, rng=rng)
+    return audio_get_clip(src.cut(), sampling_rate, target_duration, rng=rng)
+
+
 class AudioASTProcessorEval:
     def __init__(self, mean=AST_AS_MEAN, std=AST_AS_STD, sampling_rate=16000, clip_duration=5.0, n_clip=3, target_length=512,
                  mel_bins=128, device="cuda"):
@@ -84,20 +151,62 @@ class AudioASTProcessorEval:
         return kaldi_fbank(waveform.to(self.device), target_length=self.target_length, mel_bins=self.mel_bins,
                            sample_freq=float(self.sampling_rate), mean=float(self.mean[0]), std=float(self.std[0]))
 
-    def __call__(self, item, **kwargs):
-        if isinstance(item, str):
-            wav, sr = read_wav(item)
-        else:
-            wav, sr = torch.as_tensor(item, dtype=torch.float32), self.sampling_rate
-            wav = wav[None] if wav.dim() == 1 else wav
-        if sr != self.sampling_rate:
-            raise NotImplementedError(f"resampling {sr} -> {self.sampling_rate} Hz (torchaudio.functional.resample) is not available: "
-                                      "provide audio at the model's sampling rate")
-        dur = wav.shape[1] / self.sampling_rate
+    def __call__(self, item, sr=None, **kwargs):
+        wav, sr = _load(item, self.sampling_rate, sr)
+        src = _Source(wav, sr, self.sampling_rate, self.device)
+        dur = src.length / self.sampling_rate
         if dur <= self.clip_duration:
-            clips = [audio_get_clip(wav, self.sampling_rate, self.clip_duration)] * self.n_clip
+            clips = [_get_clip(src, self.sampling_rate, self.clip_duration)] * self.n_clip
         else:
-            clips = [audio_get_clip(wav, self.sampling_rate, self.clip_duration, start=s, end=e)
+            clips = [_get_clip(src, self.sampling_rate, self.clip_duration, start=s, end=e)
                      for s, e in clip_timepoints(dur, self.clip_duration, self.n_clip)]
         # kaldi.fbank takes channel 0 of each clip (its default `channel=-1` -> 0); the clip mean above was over all channels
         return self.convert2fbank(torch.cat([c[:1] for c in clips], dim=0))            # [n_clip, target_length, mel_bins]
+
+
+class AudioASTProcessorTrain:
+    """ASTProcessorTrain (at_processor.py:313-436) on the GPU.  `seed` starts the processor's own `random.Random`, from which
+    everything random is drawn on the host, per item in this order: the clip (`random_clip`, unless `se` gives start / end
+    seconds), the crop offset of a repeated short recording, the frequency mask, the time mask, the noise amplitude U / 10,
+    the roll in [-10, 10) and the 64-bit key of the noise field - so `batch(items)` equals the single calls of a processor
+    with the same seed."""
+
+    def __init__(self, mean=AST_AS_MEAN, std=AST_AS_STD, sampling_rate=16000, clip_duration=5.0, target_length=512, mel_bins=128,
+                 freqm=48, timem=96, noise_aug=True, device="cuda", seed=None):
+        import random
+        self.mean = mean if mean is not None else AST_AS_MEAN
+        self.std = std if std is not None else AST_AS_STD
+        self.sampling_rate, self.clip_duration = sampling_rate, clip_duration
+        self.target_length, self.mel_bins, self.device = target_length, mel_bins, device
+        self.freqm, self.timem, self.noise_aug = freqm, timem, noise_aug
+        self.rng = random.Random(seed)
+
+    def load_audio_clip(self, item, se=None, sr=None):
+        """-> [channels, sampling_rate * clip_duration]: the clip of at_processor.py:364-386, mean removed."""
+        wav, sr = _load(item, self.sampling_rate, sr)
+        src = _Source(wav, sr, self.sampling_rate, self.device)
+        dur = src.length / self.sampling_rate
+        start, end = random_clip(dur, self.clip_duration, self.rng) if se is None else se
+        return _get_clip(src, self.sampling_rate, self.clip_duration, start=max(0.0, start), end=min(end, dur), rng=self.rng)
+
+    def draw_params(self):
+        """(f0, fw, t0, tw, amp, roll, seed) of one sample; a transform the configuration leaves out draws nothing."""
+        f0, fw = draw_mask(self.mel_bins, self.freqm, self.rng) if self.freqm > 0 else (0, 0)
+        t0, tw = draw_mask(self.target_length, self.timem, self.rng) if self.timem > 0 else (0, 0)
+        if not self.noise_aug:
+            return f0, fw, t0, tw, 0.0, 0, 0
+        return f0, fw, t0, tw, self.rng.random() / 10.0, self.rng.randrange(-10, 10), self.rng.getrandbits(64)
+
+    def batch(self, items, se=None, sr=None):
+        """items: paths / waveforms -> [B, target_length, mel_bins]: one filterbank launch and one augment launch for all."""
+        from vitlens_hip.audio import augment_params, fbank_augment, kaldi_fbank
+        clips, rows = [], []
+        for i, item in enumerate(items):
+            clips.append(self.load_audio_clip(item, None if se is None else se[i], sr)[:1].to(self.device))   # fbank reads channel 0
+            rows.append(self.draw_params())
+        raw = kaldi_fbank(torch.cat(clips, dim=0), target_length=self.target_length, mel_bins=self.mel_bins,
+                          sample_freq=float(self.sampling_rate))                       # raw log-mel, padded rows 0 (ZeroPad2d)
+        return fbank_augment(raw, augment_params(rows, raw.device), float(self.mean[0]), float(self.std[0]))
+
+    def __call__(self, item, se=None, sr=None, **kwargs):
+        return self.batch([item], None if se is None else [se], sr)[0]

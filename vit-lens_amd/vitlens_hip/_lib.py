@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 605
+ABI_VERSION = 606
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -59,6 +59,8 @@ SIGNATURES = {
     "vl_ce_grad_masked": [P, L, I, I, I, P, P, F, F, P, L, P, L, F, P, P, P, L, F, P],
     "vl_gemm_bf16_ex": [P, P, P, P, P, P, I, I, I, I, I, I, F, I, I, I, I, P],
     "vl_kaldi_fbank": [P, L, I, L, P, P, P, I, I, I, I, I, F, F, F, P],
+    "vl_resample_sinc": [P, L, I, L, P, P, I, I, I, P, L, L, L, P],
+    "vl_fbank_augment": [P, P, I, I, I, P, F, F, P],
     "vl_fps": [P, P, P, P, I, I, I, P],
     "vl_pc_gather_normalize": [P, P, P, I, I, I, I, P],
     "vl_resample_h_u8": [P, L, I, I, I, I, P, P, I, I, I, P, P],

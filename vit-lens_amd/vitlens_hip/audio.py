@@ -1,7 +1,11 @@
 """Audio front end on the GPU: Kaldi-compatible log-mel filterbank (vl_kaldi_fbank, csrc/vl_audio.hip) with the window and
 the mel filter matrix built on the host from the published formulas (Kaldi feature-window / mel-computations, the ones
 torchaudio.compliance.kaldi implements), cached per (device, geometry).  Reference call site:
-AudioASTProcessorEval.convert2fbank, open_clip/modal_audio/processors/at_processor.py:854-873."""
+AudioASTProcessorEval.convert2fbank, open_clip/modal_audio/processors/at_processor.py:854-873.
+
+Audio at any sample rate and the training transform (csrc/vl_audio_train.hip): `resample` = torchaudio.functional.resample
+at its defaults as a compact polyphase table (`sinc_resample_table`) applied by vl_resample_sinc, and `fbank_augment` = the
+masks, Normalize, noise and roll of ASTProcessorTrain (:336-362) in one pass over the raw log-mel."""
 import math
 
 import numpy as np
@@ -58,4 +62,107 @@ def kaldi_fbank(wave: torch.Tensor, target_length: int = 512, mel_bins: int = 12
     out = torch.empty(w.shape[0], target_length, mel_bins, device=w.device, dtype=torch.float32)
     check(_lib.vl_kaldi_fbank(_p(w), w.stride(0), w.shape[0], w.shape[1], _p(window), _p(banks), _p(out), target_length, win, shift,
                               nfft, mel_bins, float(preemph), float(mean), float(std), _stream()))
+    return out
+
+
+# ---- resampling: torchaudio.functional.resample(sinc_interp_hann, lowpass_filter_width=6, rolloff=0.99), restated ----
+LOWPASS_FILTER_WIDTH = 6
+ROLLOFF = 0.99
+
+
+def resample_geometry(orig_freq: int, new_freq: int):
+    """-> (o, n, base, W): the rates over their gcd, the cutoff base = min(o, n) * rolloff in units of 1/o of the input rate,
+    and the filter's half width in input samples W = ceil(6 o / base)."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f"sampling rates must be positive, got {orig_freq} -> {new_freq}")
+    g = math.gcd(orig_freq, new_freq)
+    o, n = orig_freq // g, new_freq // g
+    base = min(o, n) * ROLLOFF
+    return o, n, base, int(math.ceil(LOWPASS_FILTER_WIDTH * o / base))
+
+
+def resampled_length(n_in: int, orig_freq: int, new_freq: int) -> int:
+    """ceil(n len / o): the number of samples `resample` gives for n_in."""
+    o, n, _, _ = resample_geometry(orig_freq, new_freq)
+    return -((-n * int(n_in)) // o)
+
+
+def _sinc_table_host(orig_freq, new_freq):
+    o, n, base, W = resample_geometry(orig_freq, new_freq)
+    K = 2 * W + 1
+    # phase p, dense tap k (input i o - W + k for output i n + p): tau = (k - W) / o - p / n in float64
+    tau = np.arange(-W, W + o, dtype=np.float64)[None, :] / o - np.arange(n, dtype=np.float64)[:, None] / n
+    live = np.abs(tau * base) < LOWPASS_FILTER_WIDTH                      # elsewhere the Hann window is zero
+    t = np.clip(tau * base, -LOWPASS_FILTER_WIDTH, LOWPASS_FILTER_WIDTH)
+    window = np.cos(t * math.pi / LOWPASS_FILTER_WIDTH / 2.0) ** 2
+    t = t * math.pi
+    dense = np.where(t == 0.0, 1.0, np.sin(t) / np.where(t == 0.0, 1.0, t)) * window * (base / o)
+    dense = np.where(live, dense, 0.0)
+    # the live taps of a phase are one run of at most 2W entries that starts at most at o + 1; a K-wide slice from
+    # min(first, o - 1) holds all of them and stays inside the dense row
+    offsets = np.minimum(np.argmax(live, axis=1), o - 1).astype(np.int32)
+    taps = np.take_along_axis(dense, offsets[:, None].astype(np.int64) + np.arange(K)[None, :], axis=1)
+    assert (live.sum(axis=1) <= 2 * W).all() and np.count_nonzero(dense) == np.count_nonzero(taps)
+    return offsets, taps.astype(np.float32)
+
+
+def sinc_resample_table(orig_freq: int, new_freq: int, device="cpu"):
+    """The resampling filter as a compact polyphase table, built in float64 and rounded to float32, cached per
+    (device, o, n): (offsets int32 [n], taps float32 [n, K]), K = 2W + 1 (zero padded).  Output sample j = i n + p is
+    sum_k x[i o - W + offsets[p] + k] taps[p, k]."""
+    o, n, _, _ = resample_geometry(orig_freq, new_freq)
+    key = ("sinc", str(torch.device(device)), o, n)
+    if key not in _tables:
+        offsets, taps = _sinc_table_host(o, n)
+        _tables[key] = (torch.from_numpy(offsets).to(device), torch.from_numpy(taps).to(device))
+    return _tables[key]
+
+
+def resample(wave: torch.Tensor, orig_freq: int, new_freq: int, out_first: int = 0, n_out: int = None) -> torch.Tensor:
+    """wave [B, len] (or [len]) f32 on the GPU at orig_freq -> the samples out_first .. out_first + n_out - 1 (default: all
+    ceil(n len / o)) of the recording at new_freq, each bit-identical to the same sample of a whole-row call."""
+    if wave.device.type != "cuda":
+        raise RuntimeError("resample runs on the MI355X kernels only")
+    if int(orig_freq) == int(new_freq):
+        return wave if out_first == 0 and n_out is None else wave[..., out_first:out_first + n_out if n_out is not None else None]
+    w = wave.reshape(1, -1) if wave.dim() == 1 else wave
+    w = w.float()
+    if w.dim() != 2 or w.shape[1] == 0:
+        raise ValueError(f"expected a waveform [B, len] or [len] with len >= 1, got {tuple(wave.shape)}")
+    if w.stride(1) != 1 or (w.shape[0] > 1 and w.stride(0) < w.shape[1]):
+        w = w.contiguous()
+    o, n, _, W = resample_geometry(orig_freq, new_freq)
+    total = -((-n * w.shape[1]) // o)
+    n_out = total - out_first if n_out is None else int(n_out)
+    if out_first < 0 or n_out <= 0 or out_first + n_out > total:
+        raise ValueError(f"output window [{out_first}, {out_first + n_out}) outside the {total} resampled samples")
+    offsets, taps = sinc_resample_table(o, n, w.device)
+    out = torch.empty(w.shape[0], n_out, device=w.device, dtype=torch.float32)
+    check(_lib.vl_resample_sinc(_p(w), w.stride(0) if w.shape[0] > 1 else w.shape[1], w.shape[0], w.shape[1], _p(offsets), _p(taps), o, n,
+                                2 * W + 1, _p(out), n_out, int(out_first), n_out, _stream()))
+    return out[0] if wave.dim() == 1 else out
+
+
+# ---- the training transform after the filterbank ----
+# one record per sample, as csrc/vl_audio_train.hip reads it (32 bytes)
+AUGMENT_DTYPE = np.dtype([("f0", "<i4"), ("fw", "<i4"), ("t0", "<i4"), ("tw", "<i4"), ("amp", "<f4"), ("roll", "<i4"), ("seed", "<u8")])
+
+
+def augment_params(rows, device) -> torch.Tensor:
+    """rows: per sample (f0, fw, t0, tw, amp, roll, seed) -> the device array vl_fbank_augment reads ([B, 8] int32 words)."""
+    a = np.array([tuple(r) for r in rows], dtype=AUGMENT_DTYPE)
+    return torch.from_numpy(a.view(np.int32).reshape(len(a), 8)).to(device)
+
+
+def fbank_augment(fbank: torch.Tensor, params: torch.Tensor, mean: float, std: float) -> torch.Tensor:
+    """fbank [B, T, F] f32 raw log-mel on the GPU (kaldi_fbank(mean=0, std=1): padded rows are 0), params from
+    `augment_params` -> out[b, (t + roll) mod T, f] = ((masked ? 0 : x) - mean) / std + amp * u(seed_b, t, f)."""
+    if fbank.device.type != "cuda":
+        raise RuntimeError("fbank_augment runs on the MI355X kernels only")
+    x = fbank.contiguous().float()
+    if x.dim() != 3 or params.shape != (x.shape[0], 8) or params.dtype != torch.int32 or params.device != x.device:
+        raise ValueError(f"expected fbank [B, T, F] and params int32 [B, 8] on its device, got {tuple(fbank.shape)} / {tuple(params.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.vl_fbank_augment(_p(x), _p(out), x.shape[0], x.shape[1], x.shape[2], _p(params.contiguous()), float(mean), float(std), _stream()))
     return out
