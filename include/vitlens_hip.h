@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 606
+#define VL_ABI_VERSION 607
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -302,6 +302,14 @@ int vl_layernorm_bwd(const void* dy, int dy_dtype, long dy_stride, const void* x
 int vl_layernorm_bwd_g(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
                        const float* mean, const float* rstd, const float* w, const void* dres, void* dx, int g_dtype,
                        void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream);
+/* vl_layernorm_bwd_g with a SPARSE upstream residual gradient: only the rows i * dres_every have one, row i of dres (row
+ * stride dres_stride, dtype g_dtype); every other row adds nothing and reads nothing.  dx is written for all rows, so the
+ * caller keeps no zero-filled residual-gradient buffer (the class-token rows behind a block that ran on those rows only).
+ * dres must not alias dx. */
+int vl_layernorm_bwd_sres(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
+                          const float* mean, const float* rstd, const float* w, const void* dres, int dres_every,
+                          long dres_stride, void* dx, int g_dtype, void* dx_bf16, long dx_stride, int rows, int D,
+                          hipStream_t stream);
 /* Column reductions are deterministic two-stage sums (row slabs -> fixed-order combine, no atomics) and need a caller
  * workspace of vl_colreduce_ws_floats(rows, cols, planes) floats (planes: 2 for the LayerNorm parameters, 1 for vl_colsum). */
 long vl_colreduce_ws_floats(int rows, int cols, int planes);
@@ -333,6 +341,20 @@ int vl_attn_bwd_fused_supported(int Lq, int Lk, int dh, int causal);
 int vl_attn_bwd_fused_bf16(const void* q, const void* k, const void* v, const void* dO, const void* o, const long* strides,
                            const float* lse, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv, int B, int H, int L, int dh,
                            float qscale, float scale, hipStream_t stream);
+/* Single-query attention (csrc/vl_attn_pool.hip): ONE query row per (batch, head) - row `qrow` of the q view - against all L
+ * keys and values; what the last block of a class-token-pooled tower needs.  q, k, v: bf16 [B,H,L,dh] strided views
+ * (strides[9] as vl_attn_fwd_bf16), head dim 64, 1 <= L <= 1024, no mask.  q is multiplied by qscale (softmax scale * log2e)
+ * and rounded to bf16 as in vl_attn_fwd_bf16; fp32 math.  out bf16 [B, H*64] (row stride ld_out), lse f32 [B, H] (optional,
+ * natural-log domain of the scaled scores). */
+int vl_attn_fwd_q1(const void* q, const void* k, const void* v, const long* strides, void* out, long ld_out, float* lse,
+                   int B, int H, int L, int dh, int qrow, float qscale, hipStream_t stream);
+/* Its backward: dO, o bf16 [B, H*64] (row strides ld_do, ld_o), lse [B, H] as the forward left them.  dq / dk / dv are the
+ * token-major [B*L, .] destinations of vl_attn_bwd_bf16 (already offset to their column block, row strides ld_dq / ld_dkv):
+ * dk and dv are written for all L rows, dq for row qrow, and the dq rows of every OTHER token are written as zeros, so the
+ * buffer is fully defined without a fill pass.  scale = softmax scale, qscale = scale * log2e. */
+int vl_attn_bwd_q1(const void* q, const void* k, const void* v, const long* strides, const void* dO, long ld_do,
+                   const void* o, long ld_o, const float* lse, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv,
+                   int B, int H, int L, int dh, int qrow, float qscale, float scale, hipStream_t stream);
 /* ---- audio front end (csrc/vl_audio.hip) ----
  * Kaldi-compatible log-mel filterbank = torchaudio.compliance.kaldi.fbank(htk_compat, 16 kHz, hanning window, 128 bins,
  * no dither, 25 ms / 10 ms frames, snip_edges) + zero-padding / truncation to target_len rows + Normalize(mean, std), i.e.

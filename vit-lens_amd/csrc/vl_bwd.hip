@@ -37,6 +37,9 @@ struct LnBwdP {
   void* dx; bf16_t* dxb;  // outputs: dx in the gradient-stream dtype (may alias dres), optional bf16 copy
   long dys, xs, dxs;      // row strides
   int rows, D;
+  // sparse residual gradient (dres_every > 1): only the rows r = i * dres_every have one, row i of dres (row stride dres_s);
+  // every other row's upstream residual gradient is zero and nothing is read for it.  dres_every <= 1: one per row, stride dxs.
+  int dres_every; long dres_s;
 };
 
 // One wave per row.  NCH > 0: the row (D = NCH*256 elements) is read ONCE into registers with 8/16-byte accesses;
@@ -48,7 +51,11 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdP p) {
   if (row >= p.rows) return;
   const TDY* dy = (const TDY*)p.dy + (long)row * p.dys;
   const TX* x = (const TX*)p.x + (long)row * p.xs;
-  const TG* dres = p.dres ? (const TG*)p.dres + (long)row * p.dxs : nullptr;
+  const TG* dres = nullptr;
+  if (p.dres) {
+    if (p.dres_every <= 1) dres = (const TG*)p.dres + (long)row * p.dxs;
+    else if (row % p.dres_every == 0) dres = (const TG*)p.dres + (long)(row / p.dres_every) * p.dres_s;
+  }
   TG* dx = p.dx ? (TG*)p.dx + (long)row * p.dxs : nullptr;
   bf16_t* dxb = p.dxb ? p.dxb + (long)row * p.dxs : nullptr;
   const float mu = p.mean[row], rs = p.rstd[row];
@@ -534,11 +541,11 @@ static void ln_bwd_launch(const LnBwdP& p, hipStream_t stream) {
   else hipLaunchKernelGGL((ln_bwd_kernel<0, TDY, TX, TG>), g, b, 0, stream, p);
 }
 
-extern "C" int vl_layernorm_bwd_g(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
-                                  const float* mean, const float* rstd, const float* w, const void* dres, void* dx, int g_dtype,
-                                  void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream) {
+static int ln_bwd_run(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
+                      const float* mean, const float* rstd, const float* w, const void* dres, int dres_every, long dres_stride,
+                      void* dx, int g_dtype, void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream) {
   if (rows <= 0 || D <= 0) return vl_set_error("vl_layernorm_bwd: empty problem");
-  LnBwdP p{dy, x, mean, rstd, w, dres, dx, (bf16_t*)dx_bf16, dy_stride, x_stride, dx_stride, rows, D};
+  LnBwdP p{dy, x, mean, rstd, w, dres, dx, (bf16_t*)dx_bf16, dy_stride, x_stride, dx_stride, rows, D, dres_every, dres_stride};
   const int key = (dy_dtype == VL_BF16 ? 4 : 0) | (x_dtype == VL_BF16 ? 2 : 0) | (g_dtype == VL_BF16 ? 1 : 0);
   switch (key) {
     case 0: ln_bwd_launch<float, float, float>(p, stream); break;
@@ -552,6 +559,26 @@ extern "C" int vl_layernorm_bwd_g(const void* dy, int dy_dtype, long dy_stride, 
   }
   VL_HIP_OK(hipGetLastError());
   return 0;
+}
+
+extern "C" int vl_layernorm_bwd_g(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
+                                  const float* mean, const float* rstd, const float* w, const void* dres, void* dx, int g_dtype,
+                                  void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream) {
+  return ln_bwd_run(dy, dy_dtype, dy_stride, x, x_dtype, x_stride, mean, rstd, w, dres, 1, dx_stride, dx, g_dtype, dx_bf16, dx_stride,
+                    rows, D, stream);
+}
+
+// vl_layernorm_bwd_g whose upstream residual gradient exists on every dres_every-th row only (the class-token rows behind a
+// block that ran on those rows alone): row i * dres_every adds row i of dres (row stride dres_stride), every other row adds
+// nothing.  dx is written for ALL rows, so the caller needs no zero-filled residual-gradient buffer; dres must not alias dx.
+extern "C" int vl_layernorm_bwd_sres(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
+                                     const float* mean, const float* rstd, const float* w, const void* dres, int dres_every,
+                                     long dres_stride, void* dx, int g_dtype, void* dx_bf16, long dx_stride, int rows, int D,
+                                     hipStream_t stream) {
+  if (!dres || !dx || dres_every < 1) return vl_set_error("vl_layernorm_bwd_sres: dres, dx and dres_every >= 1 are required");
+  if (dres == dx) return vl_set_error("vl_layernorm_bwd_sres: dres must not alias dx");
+  return ln_bwd_run(dy, dy_dtype, dy_stride, x, x_dtype, x_stride, mean, rstd, w, dres, dres_every, dres_stride, dx, g_dtype, dx_bf16,
+                    dx_stride, rows, D, stream);
 }
 
 extern "C" int vl_layernorm_bwd(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,

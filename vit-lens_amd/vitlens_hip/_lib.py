@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 606
+ABI_VERSION = 607
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -83,6 +83,7 @@ SIGNATURES = {
     "vl_group_sum": [P, L, P, L, L, I, I, P],
     "vl_layernorm_bwd": [P, I, L, P, I, L, P, P, P, P, P, P, L, I, I, P],
     "vl_layernorm_bwd_g": [P, I, L, P, I, L, P, P, P, P, P, I, P, L, I, I, P],
+    "vl_layernorm_bwd_sres": [P, I, L, P, I, L, P, P, P, P, I, L, P, I, P, L, I, I, P],
     "vl_colreduce_ws_floats": [I, I, I],
     "vl_layernorm_bwd_params": [P, I, L, P, I, L, P, P, P, P, I, I, P, P],
     "vl_colsum": [P, I, L, P, I, I, F, P, P],
@@ -91,6 +92,8 @@ SIGNATURES = {
     "vl_attn_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, L, L, I, I, I, I, I, F, I, F, P],
     "vl_attn_bwd_fused_supported": [I, I, I, I],
     "vl_attn_bwd_fused_bf16": [P, P, P, P, P, P, P, P, P, P, L, L, I, I, I, I, F, F, P],
+    "vl_attn_fwd_q1": [P, P, P, P, P, L, P, I, I, I, I, I, F, P],
+    "vl_attn_bwd_q1": [P, P, P, P, P, L, P, L, P, P, P, P, L, L, I, I, I, I, I, F, F, P],
     "vl_adamw_step": [P, P, P, P, L, F, F, F, F, F, I, F, P],
     "vl_sumsq_ws_floats": [],
     "vl_sumsq_f32": [P, L, P, P, P],

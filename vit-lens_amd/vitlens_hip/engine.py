@@ -118,6 +118,10 @@ class _Workspace:
         self.mean = torch.empty(B * L, device=device, dtype=torch.float32)
         self.rstd = torch.empty(B * L, device=device, dtype=torch.float32)
         self.part = torch.empty(B * L * (D // 64) * 2, device=device, dtype=torch.float32) if D % 64 == 0 else None
+        # the pruned last block (PRUNE_LAST_BLOCK): attention output, LayerNorm output and MLP hidden of the class rows only
+        self.a1 = torch.empty(B, D, device=device, dtype=bf)
+        self.h1 = torch.empty(B, D, device=device, dtype=bf)
+        self.hid1 = torch.empty(B, hidden, device=device, dtype=bf)
 
 
 # LayerNorm folding is ON by default since round 5 (the whole GPU suite is green with it: profiles/r05_pytest_gpu_lnfold_on_*.log;
@@ -128,13 +132,49 @@ class _Workspace:
 LN_FOLD = True
 
 
-def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None, quick_gelu=False):
+# A class-token-pooled tower reads ONE row per image of its last block's output (feature = proj(ln_post(x[:, 0]))): behind the
+# dense in-projection (K and V need every token) the last block runs on those B rows only - single-query attention
+# (ops.attn_fwd_q1), then out_proj, ln_2, c_fc and c_proj as B-row problems on the row-strided view of the class rows; the
+# other rows of the block's output are NOT written and nothing reads them.  `engine.PRUNE_LAST_BLOCK = False` runs the last
+# block in full (A/B runs, tests); read when a tower runs.
+PRUNE_LAST_BLOCK = True
+PRUNE_MAX_L = 1024          # the single-query kernels keep one row of scores in LDS
+
+
+def prune_last_ok(D, H, res_dtype, L, pooled_only=True, causal=False):
+    """Whether a tower of width D with H heads on a `res_dtype` residual stream runs its last block on the class rows only:
+    the caller consumes nothing but the pooled class token, bf16 stream, head dim 64, no causal mask, L within the kernels'
+    range.  Everything else runs the block in full."""
+    return bool(PRUNE_LAST_BLOCK and pooled_only and not causal and res_dtype == torch.bfloat16 and H > 0 and D == 64 * H
+                and 1 <= L <= PRUNE_MAX_L)
+
+
+def cls_rows(x2d, B, L):
+    """[B*L, D] token-major matrix -> the [B, D] view of its class-token rows b*L (row stride L*D, no copy)."""
+    D = x2d.shape[1]
+    return x2d.as_strided((B, D), (L * D, 1), x2d.storage_offset())
+
+
+def _pooled_block_tail(w, ws, B, L, D, H, act, cfg):
+    """The last block behind its in-projection, on the class rows of ws.x only (see PRUNE_LAST_BLOCK)."""
+    xc = cls_rows(ws.x, B, L)
+    ops.attn_fwd_q1(ws.q, ws.k, ws.v, ws.a1, qrow=0, qscale=(D // H) ** -0.5 * ops.LOG2E)
+    ops.gemm(ws.a1, w["out_w"], w["out_b"], out=xc, res=xc, epi=ops.EPI_RES_BF16, cfg=cfg)
+    ops.layernorm(xc, w["ln2_w"], w["ln2_b"], ws.h1, B, D, x_row_stride=L * D)
+    ops.gemm(ws.h1, w["fc_w"], w["fc_b"], out=ws.hid1, epi=ops.EPI_BF16, act=act, cfg=cfg)
+    ops.gemm(ws.hid1, w["proj_w"], w["proj_b"], out=xc, res=xc, epi=ops.EPI_RES_BF16, cfg=cfg)
+
+
+def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None, quick_gelu=False, pooled_only=False):
     """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:254-272, 364-371).
     quick_gelu: the tower's MLP activation (TowerCfg / TextCfg.quick_gelu; `act_layer`, transformer.py:217-231).
     fold (default: engine.LN_FOLD, bf16 stream only): the LayerNorms folded into the GEMMs either side of them - ln_1 / ln_2 are never
     materialised, the in-projection and c_fc read the residual rows and apply (mean, rstd) in their epilogues, the
-    out-projection and c_proj leave the partial row sums of what they store (ops.gemm_lnfold / gemm_res_rowstats)."""
+    out-projection and c_proj leave the partial row sums of what they store (ops.gemm_lnfold / gemm_res_rowstats).
+    pooled_only: the caller reads only the class-token rows b*L of the result (VitEngine.trunk) - the last block then runs on
+    those rows alone where prune_last_ok() allows, and the other rows of ws.x are left as the block before it wrote them."""
     dh = D // H
+    prune = prune_last_ok(D, H, ws.x.dtype, L, pooled_only, causal)
     act = ops.mlp_act(quick_gelu)
     res_epi = ops.EPI_RES_F32 if ws.x.dtype == torch.float32 else ops.EPI_RES_BF16
     if fold is None:
@@ -149,12 +189,16 @@ def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=No
         r_in, r_fc = ops.fold_rows(ws.x, ws.qkv, 3 * D), ops.fold_rows(ws.x, ws.hid, ws.hid.shape[1])
     for i, w in enumerate(blocks):
         nxt = i + 1 < len(blocks) and folded[i + 1]   # the consumer of this block's output reads row statistics
+        pruned = prune and i + 1 == len(blocks)
         if folded[i]:
             # (the row-statistics launch also writes the LayerNorm output of the consuming GEMM's leftover rows into ws.h)
             k_in = dict(ln_w=w["ln1_w"], ln_b=w["ln1_b"], h_left=ws.h, h_row0=r_in) if mm <= r_in else {}
             ops.ln_row_stats(ws.part, ws.x, mm, ws.mean, ws.rstd, **k_in)
             ops.gemm_lnfold(ws.x, w["in_f"], ws.mean, ws.rstd, ws.qkv, w["in_w"], w["in_b"], w["ln1_w"], w["ln1_b"], ws.h, cfg=cfg,
                             h_ready=bool(k_in))
+            if pruned:
+                _pooled_block_tail(w, ws, B, L, D, H, act, cfg)
+                break
             ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
             mm = ops.gemm_res_rowstats(ws.a, w["out_w"], w["out_b"], ws.x, ws.x, ws.part, cfg=cfg)
             k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=ws.h, h_row0=r_fc) if mm <= r_fc else {}
@@ -164,6 +208,9 @@ def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=No
         else:
             ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, B * L, D)
             ops.gemm(ws.h, w["in_w"], w["in_b"], out=ws.qkv, epi=ops.EPI_BF16, cfg=cfg)
+            if pruned:
+                _pooled_block_tail(w, ws, B, L, D, H, act, cfg)
+                break
             ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
             ops.gemm(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=res_epi, cfg=cfg)
             ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, B * L, D)
@@ -277,7 +324,8 @@ class VitEngine:
         ws = self.workspace(B, L)
         pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
         ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
-        run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu)
+        # (only the class-token rows are read below: the last block may run on them alone)
+        run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu, pooled_only=True)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
         if self.projT is None:
             pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)

@@ -434,6 +434,25 @@ def attn_fwd(q, k, v, out, lse=None, causal=False, qscale=1.0):
     return out
 
 
+def _q1_rows(t, H, name):
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.bfloat16 or t.shape[1] != H * 64:
+        raise ValueError(f"{name}: need a bf16 [B, H*64] matrix with unit column stride, got {tuple(t.shape)} {t.dtype}")
+
+
+def attn_fwd_q1(q, k, v, out, lse=None, qrow=0, qscale=1.0):
+    """Attention of ONE query row per (batch, head): row `qrow` of q against all keys / values.  q, k, v [B,H,L,64] strided
+    bf16 views (heads_view) -> out bf16 [B, H*64], lse f32 [B, H] (optional).  Conventions of attn_fwd (qscale = scale*log2e)."""
+    B, H, L, dh = q.shape
+    if k.shape != q.shape or v.shape != q.shape or q.dtype != torch.bfloat16:
+        raise ValueError("attn_fwd_q1: q, k, v must be bf16 views of one [B,H,L,dh] shape (self-attention)")
+    _q1_rows(out, H, "attn_fwd_q1: out")
+    if out.shape[0] != B or (lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H)):
+        raise ValueError("attn_fwd_q1: out must have B rows, lse must be a contiguous f32 [B, H]")
+    check(_lib.vl_attn_fwd_q1(_p(q), _p(k), _p(v), _bhld_strides(q, k, v), _p(out), out.stride(0), _p(lse), B, H, L, dh,
+                              int(qrow), float(qscale), _stream()))
+    return out
+
+
 def layernorm(x, w, b, out, rows, D, x_row_stride=None, row_index=None, row_mul=0, mean=None, rstd=None,
               eps=1e-5):
     xs = D if x_row_stride is None else x_row_stride
@@ -622,6 +641,15 @@ def layernorm_bwd(dy, x, mean, rstd, w, rows, D, dres=None, dx=None, dx_bf16=Non
                                   _p(dx), gdt, _p(dx_bf16), D if dx_row_stride is None else dx_row_stride, rows, D, _stream()))
 
 
+def layernorm_bwd_sparse_res(dy, x, mean, rstd, w, rows, D, dres, dres_every, dx):
+    """layernorm_bwd whose upstream residual gradient exists on the rows i * dres_every only (row i of the small matrix
+    `dres`); dx (all `rows` rows, same dtype as dres) = dLN(dy) + that.  No zero-filled gradient buffer is needed."""
+    if dres.dtype != dx.dtype or dres.dim() != 2 or dres.stride(1) != 1 or dres.shape[0] * dres_every < rows - dres_every + 1:
+        raise ValueError("layernorm_bwd_sparse_res: dres must be a row-major matrix of dx's dtype with one row per dres_every rows")
+    check(_lib.vl_layernorm_bwd_sres(_p(dy), _dt(dy), D, _p(x), _dt(x), D, _p(mean), _p(rstd), _p(w), _p(dres), int(dres_every),
+                                     dres.stride(0), _p(dx), _dt(dx), None, D, rows, D, _stream()))
+
+
 _colreduce_ws = {}
 
 
@@ -681,6 +709,24 @@ def attn_bwd(q, k, v, dO, o, lse, delta, dq, dk, dv, ld_dq, ld_dkv, causal=False
         return
     check(_lib.vl_attn_bwd_bf16(_p(q), _p(k), _p(v), _p(dO), _p(o), st, _p(lse), _p(delta), _p(dq), _p(dk), _p(dv),
                                 ld_dq, ld_dkv, B, H, Lq, Lk, dh, float(qs), 1 if causal else 0, float(scale), _stream()))
+
+
+def attn_bwd_q1(q, k, v, dO, o, lse, dq, dk, dv, ld_dq, ld_dkv, qrow=0, softmax_scale=None):
+    """Backward of attn_fwd_q1.  dO, o bf16 [B, H*64]; lse [B, H]; dq / dk / dv: the token-major destinations of attn_bwd.
+    Writes dk, dv for every row, dq for row qrow and ZEROS to every other dq row."""
+    B, H, L, dh = q.shape
+    if k.shape != q.shape or v.shape != q.shape or q.dtype != torch.bfloat16:
+        raise ValueError("attn_bwd_q1: q, k, v must be bf16 views of one [B,H,L,dh] shape (self-attention)")
+    _q1_rows(dO, H, "attn_bwd_q1: dO"); _q1_rows(o, H, "attn_bwd_q1: o")
+    if dO.shape[0] != B or o.shape[0] != B or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H:
+        raise ValueError("attn_bwd_q1: dO and o must have B rows, lse must be a contiguous f32 [B, H]")
+    for t in (dq, dk, dv):
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] < B * L or t.shape[1] < H * 64:
+            raise ValueError("attn_bwd_q1: dq / dk / dv must be bf16 [>= B*L, >= H*64] token-major destinations")
+    scale = dh ** -0.5 if softmax_scale is None else softmax_scale
+    check(_lib.vl_attn_bwd_q1(_p(q), _p(k), _p(v), _bhld_strides(q, k, v), _p(dO), dO.stride(0), _p(o), o.stride(0), _p(lse),
+                              _p(dq), _p(dk), _p(dv), ld_dq, ld_dkv, B, H, L, dh, int(qrow), float(scale * LOG2E), float(scale),
+                              _stream()))
 
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):

@@ -45,7 +45,12 @@ class _Saved:
         for l in range(layers):
             self.X[2 * l] = xres(T, D); self.X[2 * l + 1] = mids[l]
         self.X[2 * layers] = xres(T, D)
-        self.stats = per_layer(lambda: [f32(T) for _ in range(4)])       # mean1, rstd1, mean2, rstd2
+        # mean1, rstd1, mean2, rstd2.  Defined from the start as the identity (mean 0, rstd 1), not uninitialised memory: the
+        # pruned last block (engine.PRUNE_LAST_BLOCK) never runs ln_2 on the rows that are not class tokens and keeps the class
+        # rows' statistics in stats2c, so its (mean2, rstd2) slot is never written
+        ident = lambda: [torch.zeros(T, device=device), torch.ones(T, device=device), torch.zeros(T, device=device),
+                         torch.ones(T, device=device)]
+        self.stats = per_layer(ident)
         # the packed in-projection output of every block; the attention kernels read q / k / v out of it in place
         self.qkv = per_layer(lambda: bf(T, 3 * D))
         hv = lambda m, i=0: ops.heads_view(m, B, L, H, dh, i * D)
@@ -77,6 +82,19 @@ class _Saved:
         self.du = bf(T, hidden); self.dh = bf(T, D)
         self.dOm = bf(T, D); self.dO = hv(self.dOm)          # out-projection input gradient, read by heads in place
         self.delta = f32(B, H, L); self.dqkv = bf(T, 3 * D)
+        # the pruned last block (engine.PRUNE_LAST_BLOCK): everything behind its in-projection exists for the B class rows only,
+        # in buffers of its own - forward: attention output + lse, ln_2 output + statistics, MLP hidden, act'; backward: the
+        # residual gradient of those rows (dxc) and the three small GEMM outputs
+        self.a1 = bf(B, D); self.lse1 = f32(B, H); self.h2c = bf(B, D); self.stats2c = [f32(B), f32(B)]
+        self.hid1 = bf(B, hidden); self.u1 = bf(B, hidden)
+        self.dxc = bf(B, D); self.du1 = bf(B, hidden); self.dhc = bf(B, D); self.dO1 = bf(B, D)
+
+
+def prunes_last_block(layers, train_blocks, checkpoint, causal, res_dtype, D, H, L) -> bool:
+    """Whether a class-token-pooled trainer runs its last block on the class rows only (forward AND backward): the block is
+    frozen and not recomputed, and the tower qualifies (engine.prune_last_ok: switch on, bf16 stream, head dim 64, no mask)."""
+    return bool(layers > 0 and (layers - 1) not in set(train_blocks) and not checkpoint
+                and _engine.prune_last_ok(D, H, res_dtype, L, True, causal))
 
 
 class TowerTrainer:
@@ -101,6 +119,7 @@ class TowerTrainer:
         self._saved = {}
         self.grads: Dict[str, torch.Tensor] = {}
         self.ctx = None
+        self._pruned = False                        # the decision of the last forward(), kept for its backward()
 
     def refresh_derived(self, blocks=(), proj=False):
         """The engine's weights of `blocks` (and proj) were updated in place: redo their transposes."""
@@ -141,8 +160,10 @@ class TowerTrainer:
         res_epi = ops.EPI_RES_F32 if e.res_dtype == torch.float32 else ops.EPI_RES_BF16
         ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
                             xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
+        # only the class rows of the last block's output are read (ln_post below, and its backward)
+        self._pruned = prunes_last_block(self.layers, self.train_blocks, self.checkpoint, self.causal, e.res_dtype, D, H, L)
         for l in range(self.layers):
-            self._block_forward(S, l, B, L)
+            self._block_forward(S, l, B, L, cls_only=self._pruned and l == self.layers - 1)
         xl = S.X[2 * self.layers]
         ops.layernorm(xl, e.ln_post[0], e.ln_post[1], S.pooled, B, D, x_row_stride=L * D,
                       mean=S.post_stats[0], rstd=S.post_stats[1])
@@ -153,10 +174,26 @@ class TowerTrainer:
         self.ctx = (B, L, tokens, pos2 is not None)
         return feat
 
-    def _block_forward(self, S, l, B, L, write_out=True):
+    def _cls_tail_forward(self, S, l, B, L):
+        """The pruned last block behind its in-projection: single-query attention, out_proj + residual, ln_2, c_fc + activation
+        (act' saved) and c_proj + residual on the B class rows b*L of X[2l] / X[2l+1] / X[2l+2] (row-strided views, no copy);
+        the other rows of X[2l+1], X[2l+2] and the big a / hid / u slots of this layer are neither written nor read."""
+        e, D = self.eng, self.D
+        w, cfg = e.blocks[l], e.gemm_cfg
+        x0c, x1c, x2c = (_engine.cls_rows(S.X[i], B, L) for i in (2 * l, 2 * l + 1, 2 * l + 2))
+        ops.attn_fwd_q1(S.q[l], S.k[l], S.v[l], S.a1, lse=S.lse1, qrow=0, qscale=(D // self.H) ** -0.5 * ops.LOG2E)
+        ops.gemm(S.a1, w["out_w"], w["out_b"], out=x1c, res=x0c, epi=ops.EPI_RES_BF16, cfg=cfg)
+        ops.layernorm(x1c, w["ln2_w"], w["ln2_b"], S.h2c, B, D, x_row_stride=L * D, mean=S.stats2c[0], rstd=S.stats2c[1])
+        ops.gemm(S.h2c, w["fc_w"], w["fc_b"], out=S.hid1, epi=ops.EPI_BF16, act=self.act_dsave, cfg=cfg, out2=S.u1)
+        ops.gemm(S.hid1, w["proj_w"], w["proj_b"], out=x2c, res=x1c, epi=ops.EPI_RES_BF16, cfg=cfg)
+        S.part_of, S.part_rows = None, 0
+
+    def _block_forward(self, S, l, B, L, write_out=True, cls_only=False):
         """One ResidualAttentionBlock forward (transformer.py:254-272) into the saved-activation slots of layer l.  With
         write_out=False (the recompute in front of a block's backward) the block output X[2l+2] - already there from the
-        forward pass and not needed by the backward of block l - is not recomputed: the last GEMM is skipped."""
+        forward pass and not needed by the backward of block l - is not recomputed: the last GEMM is skipped.
+        cls_only (the last block of a class-token-pooled tower, prunes_last_block): dense up to the in-projection, then
+        _cls_tail_forward."""
         e, D, H = self.eng, self.D, self.H
         dh = D // H
         cfg = e.gemm_cfg
@@ -180,6 +217,8 @@ class TowerTrainer:
             ops.ln_row_stats(S.part, x0, mm0, m1, r1, **k_in)
             ops.gemm_lnfold(x0, w["in_f"], m1, r1, S.qkv[l], w["in_w"], w["in_b"], w["ln1_w"], w["ln1_b"], S.h, cfg=cfg,
                             h_ready=bool(k_in))
+            if cls_only:
+                return self._cls_tail_forward(S, l, B, L)
             ops.attn_fwd(S.q[l], S.k[l], S.v[l], S.a[l], lse=S.lse[l], causal=self.causal, qscale=dh ** -0.5 * ops.LOG2E)
             mm = ops.gemm_res_rowstats(S.a[l], w["out_w"], w["out_b"], x1, x0, S.part, cfg=cfg)
             k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=S.h, h_row0=r_fc) if mm <= r_fc else {}
@@ -189,6 +228,8 @@ class TowerTrainer:
         else:
             ops.layernorm(S.X[2 * l], w["ln1_w"], w["ln1_b"], h1, B * L, D, mean=m1, rstd=r1)
             ops.gemm(h1, w["in_w"], w["in_b"], out=S.qkv[l], epi=ops.EPI_BF16, cfg=cfg)
+            if cls_only:
+                return self._cls_tail_forward(S, l, B, L)
             ops.attn_fwd(S.q[l], S.k[l], S.v[l], S.a[l], lse=S.lse[l], causal=self.causal, qscale=dh ** -0.5 * ops.LOG2E)
             ops.gemm(S.a[l], w["out_w"], w["out_b"], out=S.X[2 * l + 1], res=S.X[2 * l], epi=res_epi, cfg=cfg)
             ops.layernorm(S.X[2 * l + 1], w["ln2_w"], w["ln2_b"], h2, B * L, D, mean=m2, rstd=r2)
@@ -242,11 +283,17 @@ class TowerTrainer:
             ops.layernorm_bwd_params(dpooled, S.X[2 * self.layers], S.post_stats[0], S.post_stats[1],
                                      self.grad_buffer(P + "ln_post.weight", e.ln_post[0]),
                                      self.grad_buffer(P + "ln_post.bias", e.ln_post[1]), B, D, x_row_stride=L * D)
-        S.dx.zero_()
-        # only the cls rows (row b*L) of the final residual receive gradient: write them in place
-        ops.layernorm_bwd(dpooled, S.X[2 * self.layers], S.post_stats[0], S.post_stats[1], e.ln_post[0], B, D,
-                          dx=S.dx, x_row_stride=L * D, dx_row_stride=L * D)
-        self._blocks_backward(S, B, L, on_block_done)
+        if self._pruned:
+            # only the cls rows (row b*L) of the final residual receive gradient, and the pruned last block carries it in a
+            # [B, D] buffer of its own: no zero fill of the full-size stream (its ln_1 backward writes every row of S.dx)
+            ops.layernorm_bwd(dpooled, S.X[2 * self.layers], S.post_stats[0], S.post_stats[1], e.ln_post[0], B, D,
+                              dx=S.dxc, x_row_stride=L * D)
+        else:
+            S.dx.zero_()
+            # only the cls rows (row b*L) of the final residual receive gradient: write them in place
+            ops.layernorm_bwd(dpooled, S.X[2 * self.layers], S.post_stats[0], S.post_stats[1], e.ln_post[0], B, D,
+                              dx=S.dx, x_row_stride=L * D, dx_row_stride=L * D)
+        self._blocks_backward(S, B, L, on_block_done, cls_only=self._pruned)
         # ---- ln_pre and the [cls; tokens] + pos assembly ----
         dxpre = torch.empty(S.dx.shape, device=S.dx.device, dtype=torch.float32)
         if self.train_ln_pre:
@@ -260,9 +307,28 @@ class TowerTrainer:
         self.dxpre = dxpre
         return dxpre.view(B, L, D)[:, 1:, :].reshape(B * T, D)
 
-    def _blocks_backward(self, S, B, L, on_block_done=None):
+    def _cls_block_backward(self, S, l, B, L):
+        """Backward of the pruned last block (_cls_tail_forward): S.dxc [B, D] = the gradient of the class rows of its output
+        (every other row's is zero) -> S.dx = the gradient of ALL rows of its input.  The MLP branch, ln_2, out_proj and the
+        attention run on B rows; dK / dV, the dX GEMM of the in-projection and the ln_1 backward are dense.  Additions in the
+        order of the full path: dLN_2 + dres on the class rows, then dLN_1 + that on the class rows, dLN_1 alone elsewhere."""
+        e, D = self.eng, self.D
+        w, wT, cfg = e.blocks[l], self.wT[l], e.gemm_cfg
+        m1, r1 = S.stats[l][0], S.stats[l][1]
+        x1c = _engine.cls_rows(S.X[2 * l + 1], B, L)
+        ops.gemm(S.dxc, wT["proj_w"], None, out=S.du1, res=S.u1, epi=ops.EPI_DGELU, act=self.act_dsave, cfg=cfg)
+        ops.gemm(S.du1, wT["fc_w"], None, out=S.dhc, epi=ops.EPI_BF16, cfg=cfg)
+        ops.layernorm_bwd(S.dhc, x1c, S.stats2c[0], S.stats2c[1], w["ln2_w"], B, D, dres=S.dxc, dx=S.dxc, x_row_stride=L * D)
+        ops.gemm(S.dxc, wT["out_w"], None, out=S.dO1, epi=ops.EPI_BF16, cfg=cfg)
+        # (also writes the dQ rows of the other tokens as zeros: S.dqkv is fully defined for the dense GEMM below)
+        ops.attn_bwd_q1(S.q[l], S.k[l], S.v[l], S.dO1, S.a1, S.lse1, S.dqkv, S.dqkv[:, D:], S.dqkv[:, 2 * D:], 3 * D, 3 * D, qrow=0)
+        ops.gemm(S.dqkv, wT["in_w"], None, out=S.dh, epi=ops.EPI_BF16, cfg=cfg)
+        ops.layernorm_bwd_sparse_res(S.dh, S.X[2 * l], m1, r1, w["ln1_w"], B * L, D, dres=S.dxc, dres_every=L, dx=S.dx)
+
+    def _blocks_backward(self, S, B, L, on_block_done=None, cls_only=False):
         """S.dx (the gradient of the last block's output, residual-stream dtype) -> S.dx = the gradient of the first block's
-        input, through every ResidualAttentionBlock in reverse; parameter gradients of the trainable blocks into self.grads."""
+        input, through every ResidualAttentionBlock in reverse; parameter gradients of the trainable blocks into self.grads.
+        cls_only: the last block was pruned by the forward (S.dxc holds the gradient of its class rows instead)."""
         e, D, H = self.eng, self.D, self.H
         rows = B * L
         cfg = e.gemm_cfg
@@ -272,6 +338,9 @@ class TowerTrainer:
         if f32_stream:
             ops.cast_bf16(S.dx, out=S.dxb)
         for l in reversed(range(self.layers)):
+            if cls_only and l == self.layers - 1:
+                self._cls_block_backward(S, l, B, L)
+                continue
             if self.checkpoint:          # refill the shared per-layer buffers with block l's activations
                 self._block_forward(S, l, B, L, write_out=False)
             w, wT = e.blocks[l], self.wT[l]
