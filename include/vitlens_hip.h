@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 607
+#define VL_ABI_VERSION 608
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -135,6 +135,34 @@ int vl_gemm_f16(const void* A, const void* W, const float* bias, void* out, cons
                 int lda, int ldw, int ldo, float alpha, int epi, int act, hipStream_t stream);
 int vl_attn_fwd_f16(const void* q, const void* k, const void* v, const long* strides, void* out, float* lse,
                     int B, int H, int Lq, int Lk, int dh, float qscale, int causal, hipStream_t stream);
+
+/* The text tower on the rows UP TO each caption's pooled position only (ABI 608).  The feature is
+ * ln_final(x[b, argmax(text[b])]) @ text_projection (open_clip/model.py:528-540) and the tower is causal
+ * (transformer.py:870-876): row t depends on rows <= t, so nothing behind the pooled row is ever read.  The captions' needed
+ * rows are packed one behind the other; LayerNorm and the GEMMs are row-wise and simply see fewer rows.
+ *   vl_text_pack_plan       ids int64 [B, L] -> len[b] = argmax(ids[b]) + 1 (first maximum, as torch.argmax; int [B]),
+ *                           start int [B+1] = exclusive sum of len in batch order (start[B] = packed rows), last_row int64 [B]
+ *                           = start[b] + len[b] - 1 (vl_layernorm_fwd's row_index with row_mul = 0: the pooling),
+ *                           total int [2] = {packed rows, longest caption}.  Integer arithmetic only: deterministic.  Any B.
+ *   vl_text_embed_packed    out f32 [>= rows_pad, D]: row start[b] + t = tok_emb[ids[b,t]] + pos[t] for t < len[b]; rows
+ *                           [rows, rows_pad) = 0 (the fp16 GEMMs run whole 256-row tiles); rows beyond are not touched.
+ *                           rows / rows_pad are the host's copy of the plan's total (B <= rows <= B*L checked; a row index at or
+ *                           beyond rows is not written)
+ *   vl_attn_fwd_varlen_f16  causal self-attention per caption on fp16 operands: q, k, v = column blocks of the packed
+ *                           in-projection output [rows, 3*width], strides = (head, row) element strides of q, k, v (6 values,
+ *                           multiples of 8); caption b owns rows start[b] .. start[b] + len[b] - 1 of the operands and of
+ *                           out fp16 [rows, H*64]; lse f32 [rows, H] optional (natural log).  Head dim 64, max_len (>= every
+ *                           len[b]) <= 288 - the limits of vl_attn_fwd_f16; refused with a status otherwise.  Rows at or beyond
+ *                           len[b] are never read: indices are clamped to the caption's own rows.  max_len must be what the
+ *                           plan gave: with a len[b] above it (or above the 32 / 96 / 288-key image chosen from it) only the
+ *                           first rows of that caption are computed, the others are left unwritten and no status tells. */
+int vl_text_pack_plan(const int64_t* ids, int* len, int* start, int64_t* last_row, int* total, int B, int L,
+                      hipStream_t stream);
+int vl_text_embed_packed(const int64_t* ids, const int* start, const int* len, const float* tok_emb, const float* pos,
+                         float* out, int B, int L, int D, int vocab, int rows, int rows_pad, hipStream_t stream);
+int vl_attn_fwd_varlen_f16(const void* q, const void* k, const void* v, const long* strides, const int* start,
+                           const int* len, void* out, float* lse, int B, int H, int max_len, int dh, float qscale,
+                           hipStream_t stream);
 
 /* True fp32 arithmetic for INFERENCE (round 5): `precision="fp32"` of the reference's factory (open_clip/factory.py:260-295,
  * training/precision.py:5-12) means fp32 nn.Linear / attention products; rounds 1-4 ran bf16 operands there and said so in a

@@ -102,14 +102,32 @@ __device__ __forceinline__ void stage_write(const StageSrc& m, int i, u32x4 a, u
   }
 }
 
-template <int DH, int NR, bool ROWS0, bool TRANS0, bool ROWS1, bool TRANS1, int U = 3>
-__device__ __forceinline__ void stage2(const StageSrc& m0, const StageSrc& m1, int row0, int L, int tid, int nthr) {
+// CLAMP (the variable-length forward): only the first `np` work items exist (np = rows/2 * CH for a caller that needs fewer rows
+// than NR), and NO load sits under a lane condition - a row index at or beyond L reads row L-1 and an item index at or beyond np
+// reads item np-1 (a load under a lane condition makes hipcc close the block with s_waitcnt vmcnt(0), vl_attn.hip).  Rows >= L of
+// the images then hold copies of row L-1 instead of zeros: finite wherever the operand is, masked by the caller.
+template <int DH, int NR, bool ROWS0, bool TRANS0, bool ROWS1, bool TRANS1, int U = 3, bool CLAMP = false>
+__device__ __forceinline__ void stage2(const StageSrc& m0, const StageSrc& m1, int row0, int L, int tid, int nthr,
+                                       int np_rt = 0) {
+  static_assert(!CLAMP || DH != 128, "the clamped form has no padded head dims (every chunk of a row is read)");
   constexpr int CH = DH / 8, NP = (NR / 2) * CH;
-  for (int base = 0; base < NP; base += U * nthr) {
+  // (CLAMP: the caller's item count, 1 <= np_rt <= NP, and L >= 1; otherwise the compile-time NP as ever)
+  const int np = CLAMP ? np_rt : NP;
+  for (int base = 0; base < np; base += U * nthr) {
     u32x4 a0[U], b0[U], a1[U], b1[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = base + u * nthr + tid;
+      if constexpr (CLAMP) {
+        const int ic = min(i, np - 1);
+        const int rp = ic / CH, c = ic % CH;
+        const unsigned ra = (unsigned)min(row0 + 2 * rp, L - 1), rb = (unsigned)min(row0 + 2 * rp + 1, L - 1);
+        a0[u] = *(const u32x4*)((const unsigned char*)m0.src + (ra * (unsigned)m0.sr + c * 8) * 2u);
+        a1[u] = *(const u32x4*)((const unsigned char*)m1.src + (ra * (unsigned)m1.sr + c * 8) * 2u);
+        b0[u] = *(const u32x4*)((const unsigned char*)m0.src + (rb * (unsigned)m0.sr + c * 8) * 2u);
+        b1[u] = *(const u32x4*)((const unsigned char*)m1.src + (rb * (unsigned)m1.sr + c * 8) * 2u);
+        continue;
+      }
       const int rp = i / CH, c = i % CH;
       const int row = row0 + 2 * rp;
       const u32x4 z = {0u, 0u, 0u, 0u};
@@ -117,11 +135,11 @@ __device__ __forceinline__ void stage2(const StageSrc& m0, const StageSrc& m1, i
       // 32-bit byte offsets from the uniform base pointers: global_load ... saddr + voffset, one VGPR per address
       const unsigned o0 = ((unsigned)row * (unsigned)m0.sr + c * 8) * 2u, o1 = ((unsigned)row * (unsigned)m1.sr + c * 8) * 2u;
       const bool cok = DH != 128 || c < m0.nch;        // padded head dim: chunks beyond the real row stay zero
-      if (i < NP && row < L && cok) {
+      if (i < np && row < L && cok) {
         a0[u] = *(const u32x4*)((const unsigned char*)m0.src + o0);
         a1[u] = *(const u32x4*)((const unsigned char*)m1.src + o1);
       }
-      if (i < NP && row + 1 < L && cok) {
+      if (i < np && row + 1 < L && cok) {
         b0[u] = *(const u32x4*)((const unsigned char*)m0.src + (o0 + (unsigned)m0.sr * 2u));
         b1[u] = *(const u32x4*)((const unsigned char*)m1.src + (o1 + (unsigned)m1.sr * 2u));
       }
@@ -129,7 +147,7 @@ __device__ __forceinline__ void stage2(const StageSrc& m0, const StageSrc& m1, i
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = base + u * nthr + tid;
-      if (i >= NP) continue;
+      if (i >= np) continue;
       stage_write<DH, NR, ROWS0, TRANS0>(m0, i, a0[u], b0[u]);
       stage_write<DH, NR, ROWS1, TRANS1>(m1, i, a1[u], b1[u]);
     }

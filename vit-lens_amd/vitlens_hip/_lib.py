@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 607
+ABI_VERSION = 608
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -36,6 +36,9 @@ SIGNATURES = {
     "vl_group_max_f32": [P, L, P, L, L, I, I, P],
     "vl_pad3_f32": [P, P, L, I, P],
     "vl_attn_fwd_f16": [P, P, P, P, P, P, I, I, I, I, I, F, I, P],
+    "vl_text_pack_plan": [P, P, P, P, P, I, I, P],
+    "vl_text_embed_packed": [P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "vl_attn_fwd_varlen_f16": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
     "vl_layernorm_fwd": [P, I, L, P, L, P, P, P, I, L, P, P, I, I, F, P],
     "vl_gemm_main_rows": [I, I],
     "vl_gemm_lnfold_bf16": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],

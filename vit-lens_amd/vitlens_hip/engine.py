@@ -340,6 +340,51 @@ class VitEngine:
         return ops.l2_normalize(f) if normalize else f
 
 
+# The text feature is ln_final(x[b, argmax(text[b])]) @ text_projection (model.py:528-540) out of a CAUSAL tower: row t depends on
+# rows <= t only, so the rows behind a caption's pooled position are work nothing reads.  With the switch on, the fp16
+# TextEngine runs only the rows 0 .. argmax(text[b]) of every caption, packed one behind the other (captions are a fraction of
+# the 77-token context: 14 of 77 rows on the benchmark's captions).  LayerNorm and the GEMMs are row-wise and see fewer rows,
+# the attention runs caption by caption (ops.attn_fwd_varlen).  `engine.PACK_TEXT = False` runs every caption at the full
+# context length (A/B runs, and what a captured graph gets: the packed form sizes its launches from the data); read per call.
+PACK_TEXT = True
+
+
+def text_pack_mode(arith: str, text: torch.Tensor, device) -> str:
+    """How a text batch runs: "dense" (every row; PACK_TEXT off, an arithmetic other than "f16", no GPU, or the current stream
+    is being captured into a graph - the packed form needs the row count on the host, and a capture must not read the device),
+    "host" (packed; `text` lives on the CPU: the lengths are taken there, nothing is read back) or "device" (packed; `text`
+    is on the GPU: the plan kernel runs and two integers come back)."""
+    if not PACK_TEXT or arith != "f16" or torch.device(device).type != "cuda":
+        return "dense"
+    if torch.cuda.is_current_stream_capturing():
+        return "dense"
+    return "device" if text.is_cuda else "host"
+
+
+def text_pack_plan_host(text: torch.Tensor):
+    """The packing plan in torch, on whatever device `text` lives: (len, start, last_row, (rows, max_len)) with
+    len[b] = argmax(text[b]) + 1 (first maximum), start = exclusive sum over the batch (B + 1 entries), last_row = start + len - 1.
+    The engine uses it for CPU token tensors; it is also the statement of what vl_text_pack_plan computes."""
+    lens = text.argmax(dim=-1).to(torch.int64) + 1
+    start = torch.zeros(text.shape[0] + 1, dtype=torch.int64, device=text.device)
+    start[1:] = torch.cumsum(lens, 0)
+    last_row = start[:-1] + lens - 1
+    return lens.to(torch.int32), start.to(torch.int32), last_row, (int(start[-1]), int(lens.max()))
+
+
+@dataclass
+class TextPlan:
+    """Which rows a batch of captions needs (TextEngine.plan_text): host integers to size the launches, device arrays for the
+    kernels."""
+    B: int
+    L: int
+    rows: int                 # packed rows = sum of the lengths
+    max_len: int
+    lens: torch.Tensor        # int32 [B]
+    start: torch.Tensor       # int32 [B+1]
+    last_row: torch.Tensor    # int64 [B]: the pooled row of every caption
+
+
 def prep_block_f16(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
     """One ResidualAttentionBlock with IEEE-half GEMM weights (`TextEngine(arith="f16")`): LayerNorm parameters and biases f32."""
     hf = torch.float16
@@ -354,8 +399,13 @@ def prep_block_f16(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, tor
 
 
 class _WorkspaceF16:
-    """Activations of the fp16 text tower.  Rows are padded to whole 256-row tiles (vl_gemm_f16 is the persistent kernel
-    only); the padded rows are zero GEMM inputs, never normalised, never read by the attention or the pooling."""
+    """Activations of the fp16 text tower, sized for the dense run: B*L rows padded to whole 256-row tiles (vl_gemm_f16 is the
+    persistent kernel only).  Rows beyond the ones a call owns - [B*L, Mp) of a dense call, [rows, roundup(rows, 256)) of a packed
+    one - are GEMM padding: never normalised, never read by the attention or the pooling, and their CONTENT is unspecified.
+    They start as zeros, a dense call only ever feeds zeros of h and a into them, but a packed call writes x, qkv and hid there
+    from whatever h and a hold in those rows (stale rows of an earlier, larger call), and with roundup(rows, 256) > B*L that
+    reaches the dense run's padding too.  Nothing depends on it: GEMM rows are independent of each other, and
+    tests/test_hip_text_pack.py runs both paths on NaN-filled workspaces."""
 
     def __init__(self, B, L, D, H, device):
         hf = torch.float16
@@ -369,6 +419,7 @@ class _WorkspaceF16:
         hv = lambda i: ops.heads_view(self.qkv, B, L, H, dh, i * D)
         self.q, self.k, self.v = hv(0), hv(1), hv(2)
         self.pooled = z(self.Bp, D)
+        self.f = None             # [Bp, E] f32, the packed path's feature accumulator (allocated at first use)
 
 
 class TextEngine:
@@ -382,7 +433,9 @@ class TextEngine:
       "f16"    (default, round 5) every GEMM / attention operand IEEE half, fp32 residual stream, fp32 accumulation: three
                more mantissa bits on ALL four sources at the bf16 MFMA rate - 1.3-2.0e-4 emulated on four seeds.  (The
                reference converts CLIP to fp16 itself: convert_weights_to_fp16, model.py:393-419.)  Needs head dim 64 and a
-               width that is a multiple of 256 and >= 512 (every CLIP text tower); otherwise falls back to "bf16x2"
+               width that is a multiple of 256 and >= 512 (every CLIP text tower); otherwise falls back to "bf16x2".
+               This is the arithmetic that runs only the rows up to each caption's pooled position (engine.PACK_TEXT,
+               `plan_text`); "bf16x2" and "bf16" run every caption at the full context length
       "bf16x2" (round 4) weights as the sum of TWO bf16 terms, fp32 residual stream: 6.1-8.1e-4 measured at twice the GEMM
                flops and twice the LayerNorm passes (+17 ms per C3 step)
       "bf16"   the reference's amp_bf16 arithmetic."""
@@ -442,12 +495,102 @@ class TextEngine:
         ops.gemm_f16(ws.pooled, self.projT, None, out=f, res=f, epi=ops.EPI_RES_F32)
         return f[:B]
 
-    def encode_text(self, text: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+    def plan_text(self, text: torch.Tensor) -> Optional[TextPlan]:
+        """The packing plan of a token batch, or None where the batch runs dense (text_pack_mode).  For a token tensor on the
+        GPU this is the one place the host waits for the device: the plan kernel and a copy of two integers run on a stream of
+        the engine's own behind an event recorded on the current stream HERE, and the host waits for that stream alone -
+        request the plan before queueing other work (the fused steps do so first thing) and the wait is only for what was
+        already queued.  Pass the result to encode_text(text, plan=...); the token tensor must not change in between.
+        Stream order: the plan's device arrays are complete on the stream that is current HERE (a CPU token tensor's are
+        copied on it; a GPU one's are waited for by the host).  encode_text on ANOTHER stream must be ordered behind this
+        call by the caller - an event, or a join as the fused steps' `_side_by_side` does; encode_text only keeps the arrays'
+        memory alive for its stream (record_stream), it does not order the two."""
+        mode = text_pack_mode(self.arith, text, self.device)
+        if mode == "dense":
+            return None
+        B, L = text.shape
+        if mode == "host":
+            lens, start, last_row, (rows, max_len) = text_pack_plan_host(text.detach().long())
+            dv = lambda t: t.to(self.device)
+            return TextPlan(B, L, rows, max_len, dv(lens), dv(start), dv(last_row))
+        return self._plan_on_device(text, B, L)
+
+    def _plan_on_device(self, text, B, L) -> TextPlan:
+        dev = self.device
+        text = text.detach().to(dev, torch.int64).contiguous()
+        with torch.cuda.device(dev):
+            if getattr(self, "_plan_stream", None) is None:
+                self._plan_stream = torch.cuda.Stream(device=dev)
+                self._plan_pin = torch.empty(2, dtype=torch.int32).pin_memory()
+            cur = torch.cuda.current_stream(dev)
+            i32 = lambda n: torch.empty(n, device=dev, dtype=torch.int32)
+            lens, start, total = i32(B), i32(B + 1), i32(2)
+            last_row = torch.empty(B, device=dev, dtype=torch.int64)
+            asked = torch.cuda.Event()
+            asked.record(cur)                              # `text` and the four buffers exist on the current stream
+            side = self._plan_stream
+            side.wait_event(asked)
+            with torch.cuda.stream(side):
+                ops.text_pack_plan(text, lens, start, last_row, total)
+                self._plan_pin.copy_(total, non_blocking=True)
+            side.synchronize()                             # the host waits for this stream alone
+            rows, max_len = int(self._plan_pin[0]), int(self._plan_pin[1])
+        return TextPlan(B, L, rows, max_len, lens, start, last_row)
+
+    def _encode_f16_packed(self, text: torch.Tensor, plan: TextPlan) -> torch.Tensor:
+        cfg = self.cfg
+        B, L = text.shape
+        D, H = cfg.width, cfg.heads
+        if (plan.B, plan.L) != (B, L) or not (B <= plan.rows <= B * L) or not (1 <= plan.max_len <= L):
+            raise ValueError(f"encode_text: the plan was made for another batch ({plan.B} x {plan.L}, {plan.rows} rows, "
+                             f"longest {plan.max_len}; text {B} x {L})")
+        key = ("f16", B, L)
+        if key not in self._ws:
+            self._ws[key] = _WorkspaceF16(B, L, D, H, self.device)       # worst-case size: no allocation depends on the data
+        ws = self._ws[key]
+        E = self.projT.shape[0]
+        if ws.f is None:
+            ws.f = torch.empty(ws.Bp, E, device=self.device, dtype=torch.float32)
+        cur = torch.cuda.current_stream(self.device)
+        for t in (plan.lens, plan.start, plan.last_row):                 # (made on the stream the plan was requested on)
+            t.record_stream(cur)
+        rows = plan.rows
+        Mr = (rows + 255) // 256 * 256                                   # whole row tiles of the persistent GEMM
+        x, h, qkv, a, hid = ws.x[:Mr], ws.h[:Mr], ws.qkv[:Mr], ws.a[:Mr], ws.hid[:Mr]
+        # (rows [rows, Mr) of x are zeroed here; of h and a they hold whatever an earlier call left: GEMM rows are independent)
+        ops.text_embed_packed(text, plan.start, plan.lens, self.tok, self.pos, ws.x, rows, Mr)
+        qs = (D // H) ** -0.5 * ops.LOG2E
+        act = ops.mlp_act(cfg.quick_gelu)
+        for w in self.blocks:
+            ops.layernorm(x, w["ln1_w"], w["ln1_b"], h, rows, D)
+            ops.gemm_f16(h, w["in_w"], w["in_b"], out=qkv)
+            ops.attn_fwd_varlen(qkv, plan.start, plan.lens, a, H, plan.max_len, qscale=qs)
+            ops.gemm_f16(a, w["out_w"], w["out_b"], out=x, res=x, epi=ops.EPI_RES_F32)
+            ops.layernorm(x, w["ln2_w"], w["ln2_b"], h, rows, D)
+            ops.gemm_f16(h, w["fc_w"], w["fc_b"], out=hid, act=act)
+            ops.gemm_f16(hid, w["proj_w"], w["proj_b"], out=x, res=x, epi=ops.EPI_RES_F32)
+        # the pooled rows: src = r * 0 + last_row[r]
+        ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=plan.last_row, row_mul=0)
+        ws.f.zero_()
+        ops.gemm_f16(ws.pooled, self.projT, None, out=ws.f, res=ws.f, epi=ops.EPI_RES_F32)
+        return ws.f[:B]
+
+    def encode_text(self, text: torch.Tensor, normalize: bool = False, plan=None) -> torch.Tensor:
+        """plan: what plan_text(text) returned for THIS token tensor; None: made here where the batch runs packed; False: run
+        every caption at the full context length (no plan is made, the host never waits)."""
         cfg = self.cfg
         B, L = text.shape
         D = cfg.width
+        if plan is False:
+            plan = None
+        elif self.arith == "f16" and plan is None:
+            plan = self.plan_text(text)                    # (before the copy below: a CPU tensor gives its lengths on the host)
         text = text.to(self.device).contiguous()
         if self.arith == "f16":
+            # (not under a capture even with a plan in hand; the packed path's result lives in the workspace: hand out a copy)
+            if plan is not None and text_pack_mode(self.arith, text, self.device) != "dense":
+                f = self._encode_f16_packed(text if text.dtype == torch.int64 else text.long(), plan)
+                return ops.l2_normalize(f) if normalize else f.clone()
             f = self._encode_f16(text)
             return ops.l2_normalize(f) if normalize else f.contiguous()
         key = (B, L)

@@ -434,6 +434,61 @@ def attn_fwd(q, k, v, out, lse=None, causal=False, qscale=1.0):
     return out
 
 
+def attn_fwd_varlen(qkv, start, lens, out, H, max_len, lse=None, qscale=1.0):
+    """Causal self-attention of packed captions (vl_attn_fwd_varlen_f16): qkv fp16 [rows, 3*H*64] the packed in-projection output,
+    start int32 [B+1] / lens int32 [B] the packing plan on the device, max_len >= every length (host int, <= 288)
+    -> out fp16 [rows, H*64]; lse f32 [rows, H] optional."""
+    import ctypes
+    W = H * 64
+    if qkv.dtype != torch.float16 or out.dtype != torch.float16 or qkv.dim() != 2 or qkv.shape[1] != 3 * W or qkv.stride(1) != 1:
+        raise ValueError("attn_fwd_varlen: qkv must be an fp16 [rows, 3*H*64] matrix with unit column stride, out fp16")
+    if out.dim() != 2 or out.shape[1] != W or not out.is_contiguous() or out.shape[0] < qkv.shape[0]:
+        raise ValueError("attn_fwd_varlen: out must be a contiguous fp16 [rows, H*64] matrix")
+    for t, nm in ((start, "start"), (lens, "lens")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != qkv.device:
+            raise ValueError(f"attn_fwd_varlen: {nm} must be a contiguous int32 tensor on the operands' device")
+    B = lens.numel()
+    if start.numel() < B + 1:
+        raise ValueError("attn_fwd_varlen: start needs B + 1 entries")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < qkv.shape[0] * H):
+        raise ValueError("attn_fwd_varlen: lse must be a contiguous f32 [rows, H]")
+    ld = qkv.stride(0)
+    st = (ctypes.c_long * 6)(64, ld, 64, ld, 64, ld)
+    es = qkv.element_size()
+    base = qkv.data_ptr()
+    check(_lib.vl_attn_fwd_varlen_f16(base, base + W * es, base + 2 * W * es, st, _p(start), _p(lens), _p(out), _p(lse), B, H,
+                                      int(max_len), 64, float(qscale), _stream()))
+    return out
+
+
+def text_pack_plan(ids, lens, start, last_row, total):
+    """The packing plan of a batch of captions on the device (vl_text_pack_plan): ids int64 [B, L] -> lens int32 [B] =
+    argmax + 1, start int32 [B+1], last_row int64 [B], total int32 [2] = (rows, max_len)."""
+    B, L = ids.shape
+    if ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise ValueError("text_pack_plan: ids must be a contiguous int64 [B, L] tensor")
+    for t, dt, n, nm in ((lens, torch.int32, B, "lens"), (start, torch.int32, B + 1, "start"), (last_row, torch.int64, B, "last_row"),
+                         (total, torch.int32, 2, "total")):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < n or t.device != ids.device:
+            raise ValueError(f"text_pack_plan: {nm} must be a contiguous {dt} tensor of >= {n} entries on the ids' device")
+    check(_lib.vl_text_pack_plan(_p(ids), _p(lens), _p(start), _p(last_row), _p(total), B, L, _stream()))
+
+
+def text_embed_packed(ids, start, lens, tok_emb, pos, out, rows, rows_pad):
+    """Rows start[b] + t (t < lens[b]) of out f32 <- tok_emb[ids[b, t]] + pos[t]; rows [rows, rows_pad) <- 0 (vl_text_embed_packed)."""
+    B, L = ids.shape
+    D = tok_emb.shape[1]
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("text_embed_packed: ids contiguous int64 [B, L], out contiguous f32")
+    if out.dim() != 2 or out.shape[1] != D or out.shape[0] < rows_pad or pos.shape[0] < L or pos.shape[1] != D:
+        raise ValueError("text_embed_packed: out must hold rows_pad rows of the embedding width, pos L rows")
+    if start.dtype != torch.int32 or lens.dtype != torch.int32 or start.numel() < B + 1 or lens.numel() < B:
+        raise ValueError("text_embed_packed: start int32 [B+1], lens int32 [B]")
+    check(_lib.vl_text_embed_packed(_p(ids), _p(start), _p(lens), _p(tok_emb), _p(pos), _p(out), B, L, D, tok_emb.shape[0],
+                                    int(rows), int(rows_pad), _stream()))
+    return out
+
+
 def _q1_rows(t, H, name):
     if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.bfloat16 or t.shape[1] != H * 64:
         raise ValueError(f"{name}: need a bf16 [B, H*64] matrix with unit column stride, got {tuple(t.shape)} {t.dtype}")

@@ -243,6 +243,29 @@ class _StepState:
     def _overlap_active(self) -> bool:
         return self.overlap_frozen and self.dev.type == "cuda"
 
+    # Whether this step class runs its text tower packed (TextEngine.plan_text).  The plan request makes the host wait for the
+    # device once per step, so the host no longer queues the front of a step while the previous one drains; a step class whose
+    # front is bound by the host's launch rate turns it off (TriModalPCStep).
+    pack_text = True
+
+    def _text_plan(self, texts):
+        """The text tower's packing plan (TextEngine.plan_text), or None: a step class with `pack_text` off, an engine without
+        plan_text (a stand-in, a CPU device) or a batch that runs dense anyway.  Requested as the FIRST thing of a step, before
+        anything of this step is queued: the host then waits for what the previous step left in the queue, and nothing of this
+        one sits behind a blocked host."""
+        plan_text = getattr(self.text, "plan_text", None)
+        if plan_text is None or not self.pack_text:
+            return None
+        return plan_text(texts)
+
+    def _encode_text(self, texts, plan):
+        """The text features with the plan `_text_plan` gave.  No plan - whatever the reason - means dense: `plan=False` is the
+        only way a step keeps the engine from making a plan of its own (and waiting for the device in the middle of the step);
+        a direct `self.text.encode_text(texts)` packs whatever `pack_text` says."""
+        if not hasattr(self.text, "plan_text"):
+            return self.text.encode_text(texts)
+        return self.text.encode_text(texts, plan=plan if plan is not None else False)      # (False: dense, no plan made there)
+
     def _side_by_side(self, beside, here):
         """Run two closures of independent work: `beside()` on the step's second HIP stream, `here()` on the launch stream,
         joined by events on both ends (one after the other on a CPU device or with `overlap_frozen` off).  Two callers: the
@@ -665,6 +688,7 @@ class TriModalDepthStep(_StepState):
             self._reduced_upto = l
 
     def forward_backward(self, images: torch.Tensor, texts: torch.Tensor, depths: torch.Tensor) -> torch.Tensor:
+        tplan = self._text_plan(texts)
         B = images.shape[0]
         mb = min(self.mb, B)
         assert B % mb == 0, "per-GPU batch must be a multiple of the micro-batch"
@@ -684,7 +708,7 @@ class TriModalDepthStep(_StepState):
         # the frozen text tower sees the whole per-GPU batch in one pass: 77-token sequences give a micro-batch only 77 row
         # tiles (one uneven round of the persistent GEMM, 600-900 TF/s); four times the rows run whole rounds
         def frozen():
-            ops.l2_normalize(self.text.encode_text(texts), out=ft)
+            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)
             for i in range(nmb):
                 s = slice(i * mb, (i + 1) * mb)
                 ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
@@ -960,13 +984,14 @@ class DualAudioStep(_PerceiverLensStep):
         ops.cast_bf16(self.masters["visual.visual_adapter.conv1.weight_gemm"], out=self.lens.conv_w)
 
     def forward_backward(self, audio: torch.Tensor, texts: torch.Tensor) -> torch.Tensor:
+        tplan = self._text_plan(texts)
         B = audio.shape[0]
         mb, nmb = self._prepare(B)
         E = self.lens.tower.embed_dim
         ft = torch.empty(B, E, device=self.dev); fv = torch.empty(B, E, device=self.dev)
         vraw = torch.empty(B, E, device=self.dev); vnorm = torch.empty(B, device=self.dev)
         def frozen():
-            ops.l2_normalize(self.text.encode_text(texts), out=ft)          # (whole batch at once: see TriModalDepthStep)
+            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)       # (whole batch at once: see TriModalDepthStep)
 
         def trainable():
             for i in range(nmb):
@@ -1047,7 +1072,14 @@ class TriModalPCStep(_PerceiverLensStep):
         for t in self.trainers:
             t.tok.op = self.tok.op
 
+    # The point-cloud step's front (FPS, kNN grouping, the mini-PointNet with BatchNorm: hundreds of small launches) is bound
+    # by the host's launch rate and is queued while the previous step drains.  The plan's host wait exposes it: at the
+    # benchmark's shape the step came out 0.33 % SLOWER with the packed text tower than without (disjoint ranges,
+    # profiles/packed_text_ab.log), for a tower that saves 1.2 ms.  The text tower of this step class runs dense.
+    pack_text = False
+
     def forward_backward(self, images, texts, points, fps_start=None) -> torch.Tensor:
+        tplan = self._text_plan(texts)
         B = images.shape[0]
         mb, nmb = self._prepare(B)
         E = self.image.cfg.embed_dim
@@ -1055,7 +1087,7 @@ class TriModalPCStep(_PerceiverLensStep):
         fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
         vnorm = torch.empty(B, device=self.dev)
         def frozen():
-            ops.l2_normalize(self.text.encode_text(texts), out=ft)          # (whole batch at once: see TriModalDepthStep)
+            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)       # (whole batch at once: see TriModalDepthStep)
             for i in range(nmb):
                 s = slice(i * mb, (i + 1) * mb)
                 ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
