@@ -1,10 +1,12 @@
-"""CPU, 2 processes on gloo: the WHOLE host logic of the fused training steps (`TriModalDepthStep`, `DualAudioStep`)
-driven through the real `TorchComm` (torch.distributed), with the HIP `ops` replaced by a torch-CPU stand-in and the
+"""CPU, 2 processes on gloo: the WHOLE host logic of the fused training steps (`TriModalDepthStep`, `DualAudioStep`,
+`TriModalPCStep`) driven through the real `TorchComm` (torch.distributed), with the HIP `ops` replaced by a torch-CPU stand-in and the
 towers by small linear "towers" whose exact gradients are known.  What is asserted, per rank:
 
   * the collective sequence of one step and its payloads: exactly ONE all-gather of the packed [b, k*E] embeddings
     (k = 3 tri-modal, 2 dual), reduce-scatter(s) only under gather_with_grad, and the gradient all-reduce(s) covering the
-    flat gradient buffer exactly once (per-block async buckets + one call for the rest in the depth step);
+    flat gradient buffer exactly once (per-block async buckets + one call for the rest in the depth step) - with one, two
+    and three micro-batches per rank (no split, even halves, uneven halves of `_backward_all`), and after a
+    forward_backward whose gradients were never used (its bucket all-reduces are waited for, its sums are gone);
   * the numbers: every rank reports the GLOBAL loss, and after the all-reduce each rank holds W x the mean = the sum of the
     per-rank gradients, equal to torch autograd of the global-batch loss on the concatenated data.
 
@@ -99,8 +101,9 @@ class _LinearTower:
     def tower(self):          # the steps bind the shared gradient dictionary through `.tower.grads`
         return self
 
-    def forward(self, x):
+    def forward(self, x, fps_start=None):
         self.x = x.reshape(x.shape[0], -1)[:, :D_IN].float()
+        self.fps_start = fps_start          # (the point-cloud step hands each micro-batch its slice)
         return self.x @ self.W
 
     def backward(self, dfeat, on_block_done=None):
@@ -141,7 +144,7 @@ class _Rec:
         self.log.append(("reduce_scatter", tuple(inp.shape))); self.inner.reduce_scatter_sum(out, inp)
 
 
-def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
+def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False, nmb=2, twice=False):
     sys.path.insert(0, os.path.join(ROOT, "vit-lens_amd"))
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
@@ -150,7 +153,7 @@ def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
     ST.ops = _fake_ops(); TR.ops = ST.ops                      # the steps' host logic is what is under test
     g = torch.Generator().manual_seed(0)                        # same weights on every rank
     Wi, Wt, Wv = (torch.randn(D_IN, E_DIM, generator=g) * 0.3 for _ in range(3))
-    b, nblk = 4, 2
+    b, nblk = 2 * nmb, 2                                        # micro_batch = 2 below: nmb micro-batches per rank
     gd = torch.Generator().manual_seed(100)                     # same GLOBAL data on every rank; each takes its slice
     X = {k: torch.randn(world * b, D_IN + 3, generator=gd) for k in ("img", "txt", "vis")}
     mine = {k: v[rank * b:(rank + 1) * b] for k, v in X.items()}
@@ -188,19 +191,43 @@ def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
         def _bind_grads(self, t, grads=None):
             t.grads = self.grads if grads is None else grads
 
+    class PCHost(_HostMixin, ST.TriModalPCStep):
+        def _build(self, sd, tower, text, lens, **kw):
+            self.image, self.text = _Frozen(Wi), _Frozen(Wt)
+            self.masters["visual.W"] = Wv.clone()
+            self._mk = lambda: _LinearTower(self.masters["visual.W"], self.grads, "visual.W")
+
+        def _bind_grads(self, t, grads=None):
+            t.grads = self.grads if grads is None else grads
+
     kw = dict(micro_batch=2, lr=1e-2, rank=rank, world_size=world, comm=comm, local_loss=local_loss, gather_with_grad=gwg,
               overlap_frozen=overlap)
+    fps = torch.arange(rank * b, (rank + 1) * b)
     if recipe == "depth":
         st = DepthHost(sd0, None, None, "cpu", unlock_first_n=nblk, **kw)
         # a CPU device cannot run a second HIP stream: the request is recorded, the schedule is the serial one
         if st.overlap_frozen != overlap or st._overlap_active:
             errs.append(f"overlap_frozen={st.overlap_frozen} active={st._overlap_active} on a CPU device")
-        loss = st.forward_backward(mine["img"], mine["txt"], mine["vis"])
+        fb = lambda d: st.forward_backward(d["img"], d["txt"], d["vis"])
+        k = 3
+    elif recipe == "pc":
+        st = PCHost(sd0, None, None, None, "cpu", **kw)
+        fb = lambda d: st.forward_backward(d["img"], d["txt"], d["vis"], fps_start=fps)
         k = 3
     else:
         st = AudioHost(sd0, None, None, None, "cpu", **kw)
-        loss = st.forward_backward(mine["vis"], mine["txt"])
+        fb = lambda d: st.forward_backward(d["vis"], d["txt"])
         k = 2
+    if twice:
+        # a forward_backward on OTHER data whose gradients nobody asks for: the next one waits for the bucket all-reduces it
+        # left in flight, starts from zero, and everything asserted below is about the second call alone
+        fb({k_: -2.0 * v.flip(0) for k_, v in mine.items()})
+        del comm.log[:]
+    loss = fb(mine)
+    if recipe == "pc":
+        seen = torch.cat([t.fps_start for t in st.trainers])
+        if len(st.trainers) != nmb or not torch.equal(seen, fps):
+            errs.append(f"fps_start slices of the micro-batches {seen.tolist()} != {fps.tolist()}")
     # between forward_backward and optimizer_step the buffer is mixed (block buckets summed, the rest rank-local):
     # `finish_reduce()` / `reduced_grads()` is the accessor that makes it one state; idempotent (counted below: every
     # element is reduced exactly once although it is called twice and optimizer_step calls it again)
@@ -215,7 +242,7 @@ def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
     if ops_seen.count("all_gather") != 1 or comm.log[[e[0] for e in comm.log].index("all_gather")][1] != (b, k * E_DIM):
         errs.append(f"all_gather: {comm.log}")
     n_rs = ops_seen.count("reduce_scatter")
-    want_rs = 0 if not gwg else (2 if recipe == "depth" else 1)       # one per contrastive pair: only the visual side is trained
+    want_rs = 0 if not gwg else (1 if recipe == "audio" else 2)       # one per contrastive pair: only the visual side is trained
     if n_rs != want_rs:
         errs.append(f"reduce_scatter count {n_rs} != {want_rs}: {comm.log}")
     red = sum(e[1] for e in comm.log if e[0].startswith("all_reduce"))
@@ -237,7 +264,7 @@ def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
     def pair(x, y):
         lg = ls * x @ y.t()
         return (ce(lg, lab) + ce(lg.t(), lab)) / 2
-    ref = pair(fi, fv) + pair(ft, fv) if recipe == "depth" else pair(fv, ft)
+    ref = pair(fv, ft) if recipe == "audio" else pair(fi, fv) + pair(ft, fv)
     ref.backward()
     # reported loss: the global loss on every rank, or (local_loss) this rank's rows, whose mean over ranks is the global loss
     lt = [torch.zeros(1) for _ in range(world)]
@@ -269,19 +296,33 @@ def _worker(rank, world, port, recipe, local_loss, gwg, ret, overlap=False):
     dist.destroy_process_group()
 
 
-def _run(world, recipe, local_loss, gwg, overlap=False):
-    port = 29650 + (hash((world, recipe, local_loss, gwg, overlap)) % 300)
+def _run(world, recipe, local_loss, gwg, overlap=False, nmb=2, twice=False):
+    port = 29650 + (hash((world, recipe, local_loss, gwg, overlap, nmb, twice)) % 300)
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(_worker, args=(world, port, recipe, local_loss, gwg, ret, overlap), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, recipe, local_loss, gwg, ret, overlap, nmb, twice), nprocs=world, join=True)
     for r in range(world):
         assert ret[r] == [], (r, ret[r])
 
 
-@pytest.mark.parametrize("recipe", ["depth", "audio"])
+@pytest.mark.parametrize("recipe", ["depth", "audio", "pc"])
 @pytest.mark.parametrize("local_loss,gwg", [(False, False), (False, True), (True, True)])
 def test_step_host_logic_world2_gloo(recipe, local_loss, gwg):
     _run(2, recipe, local_loss, gwg)
+
+
+@pytest.mark.parametrize("nmb", [1, 3])
+@pytest.mark.parametrize("recipe", ["depth", "audio"])
+def test_step_host_logic_world2_gloo_micro_batch_counts(recipe, nmb):
+    """Per-rank batches of 2 and 6 at micro_batch = 2: one micro-batch (`_backward_all` does not split: no second buffer, the
+    bucket all-reduces start from the only backward) and three (halves of 1 and 2 micro-batches)."""
+    _run(2, recipe, False, False, nmb=nmb)
+
+
+def test_depth_step_world2_gloo_forward_backward_twice_before_the_reduce():
+    """Two forward_backward calls, then finish_reduce: the gradients are the second call's alone, and the all-reduces logged
+    during and after the second call cover the flat buffer exactly once."""
+    _run(2, "depth", False, False, twice=True)
 
 
 def test_depth_step_world2_gloo_with_overlap_frozen_requested():
@@ -289,7 +330,8 @@ def test_depth_step_world2_gloo_with_overlap_frozen_requested():
     _run(2, "depth", False, False, overlap=True)
 
 
-@pytest.mark.parametrize("recipe,local_loss,gwg", [("depth", False, False), ("depth", True, True), ("audio", False, True)])
+@pytest.mark.parametrize("recipe,local_loss,gwg", [("depth", False, False), ("depth", True, True), ("audio", False, True),
+                                                   ("pc", True, True)])
 def test_step_host_logic_world8_gloo(recipe, local_loss, gwg):
     """The node size the north_star names (8 ranks): bucket order, ONE packed gather of [b, k*E] per rank, reduce-scatter
     under gather_with_grad, every gradient element reduced exactly once, replicas identical after AdamW."""

@@ -180,7 +180,12 @@ def _master_to_sd(name: str, m: torch.Tensor, base_sd, cfg) -> Dict[str, torch.T
 
 
 class _StepState:
-    """state_dict / load_state_dict of a fused training step in the REFERENCE's names and layouts (a TriCLIP state_dict:
+    """What the fused training steps have in common, one copy of each piece: the step (`_forward_backward`, `finish_reduce`,
+    `optimizer_step`, `step`), the flat gradient buffers and their per-block buckets, the trainers of the micro-batches.  A
+    step class supplies what differs: `_build` (engines, masters, the trainer factory `_mk`), `_refresh_operands`, and
+    where needed `_share_operands`, `_bind_grads`, `_bucket_blocks`, `_loss`, `pack_text`.
+
+    state_dict / load_state_dict of a step in the REFERENCE's names and layouts (a TriCLIP state_dict:
     trained tensors from the fp32 masters, everything else as it was given), plus the AdamW moments - so training can be
     checkpointed, resumed, and handed back to `TriCLIP.load_state_dict` (training/train.py checkpoints `model.state_dict()`
     and `optimizer.state_dict()`)."""
@@ -204,6 +209,7 @@ class _StepState:
         self.overlap_frozen = bool(overlap_frozen)
         # with it: the two halves of a step's micro-batches run their BACKWARD on the two streams too (_backward_all)
         self.overlap_backward = bool(overlap_backward)
+        self._one_stream_backward = False      # a `_build` whose backward talks to the communicator (SyncBatchNorm) sets it
         self._side = None
         self._base_sd = {k: v.detach() for k, v in sd.items()}
         self.logit_scale = sd["logit_scale"].detach().float().reshape(1).to(device).clone()
@@ -290,6 +296,246 @@ class _StepState:
         trainable()
         main.wait_event(done)
 
+    # ------------------------------------------------------------------------------------------- construction, trainers, buffers
+    def _construct(self, host, adamw, *build, **build_kw):
+        """The tail of every step's `__init__`: the host state, the engines and masters of the trainable set, AdamW on them."""
+        self._init_host(*host)
+        self._build(*build, **build_kw)
+        self.opt = AdamW(self.masters, *adamw)
+
+    def _trainer(self, i):
+        while len(self.trainers) <= i:
+            t = self._mk()
+            if self.trainers:                      # share what is derived from the weights across micro-batches
+                self._share_operands(t, self.trainers[0])
+            self.trainers.append(t)
+        return self.trainers[i]
+
+    def _share_operands(self, t, first):
+        t.tower.wT, t.tower.proj = first.tower.wT, first.tower.proj
+
+    def _bind_grads(self, t, grads=None):
+        """Point every part of trainer `t` at one gradient dictionary (default: `self.grads`)."""
+        t.tower.grads = self.grads if grads is None else grads
+
+    def _alloc_flat_grads(self):
+        """All gradient buffers are views into ONE flat fp32 tensor -> a single all-reduce per step.  Master order and the
+        alignment of the views ARE the layout: the block buckets and the clipped AdamW's slot table rely on it."""
+        al = lambda n: (n + 3) // 4 * 4                       # every view starts 16-byte aligned
+        self.flat_grad = torch.zeros(sum(al(v.numel()) for v in self.masters.values()), device=self.dev, dtype=torch.float32)
+        self.flat_grad_b = torch.zeros_like(self.flat_grad)  # the first half of a step's micro-batches accumulates here (_backward_all)
+        self.grads_b, off = {}, 0
+        for k, v in self.masters.items():
+            self.grads[k] = self.flat_grad[off:off + v.numel()].view(v.shape)
+            self.grads_b[k] = self.flat_grad_b[off:off + v.numel()].view(v.shape)
+            off += al(v.numel())
+        for t in self.trainers:
+            self._bind_grads(t)
+
+    # ---- gradient buckets: the masters of one block are contiguous in the flat buffer ----
+    def _bucket_blocks(self):
+        """The transformer blocks whose gradients are a bucket of their own (merged and all-reduced as soon as the backward
+        has passed the block): the unlocked blocks of the depth step, none where every block is locked."""
+        return ()
+
+    def _block_range(self, l):
+        p = f"visual.transformer.resblocks.{l}."
+        names = [k for k in self.masters if k.startswith(p)]
+        base = self.flat_grad.data_ptr()
+        lo = min((self.grads[k].data_ptr() - base) // 4 for k in names)
+        hi = max((self.grads[k].data_ptr() - base) // 4 + self.grads[k].numel() for k in names)
+        return lo, min((hi + 3) // 4 * 4, self.flat_grad.numel())          # incl. the 16-byte alignment pad of the last view
+
+    def _rest_ranges(self):
+        """(lo, hi) of all buckets together: what lies outside it is merged / reduced at the end.  No buckets: everything."""
+        rs = [self._block_range(l) for l in self._bucket_blocks()]
+        return (min(r[0] for r in rs), max(r[1] for r in rs)) if rs else (0, 0)
+
+    def _start_block_reduce(self, l):
+        if self.dist and hasattr(self.comm, "all_reduce_sum_async"):
+            lo, hi = self._block_range(l)
+            self._pending.append(self.comm.all_reduce_sum_async(self.flat_grad[lo:hi]))
+            self._reduced_upto = l
+
+    # ------------------------------------------------------------------------------------------- the step
+    def step(self, *a, **kw) -> torch.Tensor:
+        loss = self.forward_backward(*a, **kw)
+        self.optimizer_step()
+        return loss
+
+    def finish_reduce(self):
+        """Bring `flat_grad` / `grads` to ONE state: the sum over ranks of every gradient, all collectives complete.
+
+        Between `forward_backward()` and this call the buffer is MIXED: the unlocked blocks' buckets were all-reduced
+        during the last micro-batch's backward (possibly still in flight on the collective's stream) while logit_scale
+        and the adapter - produced last - are still rank-local (a step without buckets: all of it is rank-local, and one
+        collective here sums it).  Anything that reads or rescales the gradients in between (clipping, norm logging, accumulation over several forward_backward calls) calls this first;
+        `optimizer_step()` does.  Idempotent; a no-op on one rank.  The values are SUMS: the 1/world of DDP's mean is
+        applied inside the optimizer step (`grad_scale`)."""
+        if not self.dist or self._reduce_done:
+            return
+        for h in self._pending:
+            h.wait()
+        self._pending = []
+        if self._reduced_upto is None:
+            self.comm.all_reduce_sum(self.flat_grad)
+        else:
+            lo, hi = self._rest_ranges()
+            for a, b in ((0, lo), (hi, self.flat_grad.numel())):
+                if b > a:
+                    self.comm.all_reduce_sum(self.flat_grad[a:b])
+        self._reduced_upto = None
+        self._reduce_done = True
+
+    def reduced_grads(self):
+        """The gradients by master name after `finish_reduce()` (sums over ranks)."""
+        self.finish_reduce()
+        return self.grads
+
+    def optimizer_step(self):
+        if self.grad_clip_norm is not None:
+            self._clipped_optimizer_step()
+        elif self.dist:
+            # DDP semantics: mean of per-rank gradients.  Block buckets were started during the last micro-batch's backward
+            # (reverse layer order); what is left - logit_scale and the adapter, produced last - goes in one more call.
+            self.finish_reduce()
+            self.opt.step(self.grads, grad_scale=1.0 / self.world)
+        else:
+            self.opt.step(self.grads)
+        self._refresh_operands()
+        ops.clamp_scalar(self.logit_scale, 0.0, math.log(100.0))
+
+    def _prepare(self, B):
+        """-> (micro-batch size, number of micro-batches); trainers and gradient buffers on the first call, `flat_grad` zero."""
+        mb = min(self.mb, B)
+        assert B % mb == 0, "per-GPU batch must be a multiple of the micro-batch"
+        nmb = B // mb
+        if self.flat_grad is None:
+            for i in range(nmb):
+                self._trainer(i)
+            self._alloc_flat_grads()
+        for h in self._pending:          # (a forward_backward without optimizer_step: finish what was started)
+            h.wait()
+        self._pending, self._reduced_upto, self._reduce_done = [], None, False
+        self.flat_grad.zero_()
+        return mb, nmb
+
+    def _forward_backward(self, texts, images, *inputs) -> torch.Tensor:
+        """One forward and backward over the per-GPU batch: the loss, and `flat_grad` = this rank's gradients (with the block
+        buckets, if any, already summed over ranks or on their way: `finish_reduce`).  `images` None: a step without the image
+        tower.  `inputs`: what the trainers' forward takes, each a per-sample tensor or None, cut into micro-batches here."""
+        tplan = self._text_plan(texts)
+        B = inputs[0].shape[0]
+        mb, nmb = self._prepare(B)
+        E = self.text.cfg.embed_dim
+        fi = None if images is None else torch.empty(B, E, device=self.dev)
+        ft = torch.empty(B, E, device=self.dev)
+        fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
+        vnorm = torch.empty(B, device=self.dev)
+        # the frozen text tower sees the whole per-GPU batch in one pass: 77-token sequences give a micro-batch only 77 row
+        # tiles (one uneven round of the persistent GEMM, 600-900 TF/s); four times the rows run whole rounds
+        def frozen():
+            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)
+            if images is None:
+                return
+            for i in range(nmb):
+                s = slice(i * mb, (i + 1) * mb)
+                ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
+
+        def trainable():
+            for i in range(nmb):
+                s = slice(i * mb, (i + 1) * mb)
+                vraw[s] = self._trainer(i).forward(*(None if x is None else x[s] for x in inputs))
+        self._side_by_side(frozen, trainable)
+        ops.l2_normalize(vraw, out=fv, norms=vnorm)
+        loss, dv, ds = self._loss(fi, ft, fv)
+        dvraw = ops.l2_normalize_bwd(fv, dv, vnorm)
+        self._backward_all(dvraw, nmb, mb)
+        # logit_scale is exp()'d in forward (model.py:619); with the device-side scale pair_backward returns d/d(log-scale).
+        # The pairs' parts are added here, after the backward has been enqueued
+        self.grads["logit_scale"] += sum(ds[1:], ds[0])
+        return loss
+
+    def _gather(self, *feats):
+        """The rank-major gathers [W*b, E] of the local features in ONE exchange: [b, k*E] per rank over xGMI (k*768 floats
+        a row).  The features themselves on one rank."""
+        if not self.dist:
+            return feats
+        E = feats[0].shape[1]
+        packed = torch.cat(feats, dim=1)
+        allp = torch.empty(self.world * packed.shape[0], len(feats) * E, device=self.dev)
+        self.comm.all_gather(allp, packed)
+        return [t.contiguous() for t in allp.split(E, dim=1)]
+
+    def _loss(self, fi, ft, fv):
+        """TriClipLoss, image and text towers frozen: (loss, d loss / d fv, the parts of d loss / d logit_scale).  The scale is
+        the log-temperature, on the device: exp() is applied inside the loss section."""
+        ai, at, av = self._gather(fi, ft, fv)
+        kw = dict(local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_x=False, dist=self.dist)
+        l1, _, dv1, ds1 = pair_loss_and_grads(self.comm, self.rank, self.world, fi, fv, ai, av, self.logit_scale, **kw)
+        l2, _, dv2, ds2 = pair_loss_and_grads(self.comm, self.rank, self.world, ft, fv, at, av, self.logit_scale, **kw)
+        return l1 + l2, dv1 + dv2, (ds1, ds2)
+
+    def _backward_all(self, dvraw, nmb, mb):
+        """Backward of every micro-batch; parameter gradients accumulate over them.
+
+        With two or more micro-batches the FIRST half accumulates into a second gradient buffer (`flat_grad_b`) and the second
+        half into `flat_grad`; a block's bucket is merged (and, across ranks, its all-reduce started) when the LAST micro-batch
+        of the second half has passed the block, the rest (adapter, position table; in a step without buckets: everything) at
+        the end.  That makes the two halves independent streams of work: with `overlap_frozen` on a GPU the first half runs on the second HIP stream beside the
+        second half - the backward is a chain of chip-filling GEMMs with latency-bound kernels between them (fused attention
+        backward, LayerNorm backward, leftover rows, the drain of every persistent launch), exactly what the forward's two
+        towers fill for each other.  The arithmetic - which products are added in which order - is the same on one stream
+        and on two: results are bit-identical (tests/test_hip_train.py).  Not on two streams with SyncBatchNorm (its backward
+        exchanges data on the communicator from inside the micro-batch: `_one_stream_backward`).  Reference: loss.backward()
+        over the micro-batches of the accumulation loop, training/train.py:154-210 (gradients of all summed into .grad)."""
+        blocks = self._bucket_blocks()
+        dist_cb = self.dist and len(blocks) > 0
+        dv = lambda i: dvraw[i * mb:(i + 1) * mb].contiguous()
+
+        def backward(i, on_block_done=None):
+            # (the trainers of a step without buckets take no callback, and none is passed to them)
+            self._trainer(i).backward(dv(i), *((on_block_done,) if blocks else ()))
+        half = nmb // 2
+        for i in range(nmb):
+            self._bind_grads(self._trainer(i), self.grads_b if i < half else self.grads)
+        if half == 0:
+            backward(0, self._start_block_reduce if dist_cb else None)
+            return
+        self.flat_grad_b.zero_()
+        two_streams = self._overlap_active and self.overlap_backward and not self._one_stream_backward
+        passed = {}          # block -> event on the first half's stream: its last micro-batch has passed the block
+
+        def first_done(l):
+            if two_streams:
+                passed[l] = torch.cuda.Event()
+                passed[l].record()
+
+        def second_done(l):
+            if two_streams:
+                torch.cuda.current_stream(self.dev).wait_event(passed[l])
+            lo, hi = self._block_range(l)
+            ops.axpy(self.flat_grad[lo:hi], self.flat_grad_b[lo:hi])
+            if dist_cb:
+                self._start_block_reduce(l)
+
+        def first_half():
+            for i in range(half):
+                backward(i, first_done if i == half - 1 else None)
+
+        def second_half():
+            for i in range(half, nmb):
+                backward(i, second_done if i == nmb - 1 else None)
+        if two_streams:
+            self._side_by_side(first_half, second_half)      # (first closure on the second stream, joined at the end)
+        else:
+            first_half(); second_half()
+        lo, hi = self._rest_ranges()
+        for a, b in ((0, lo), (hi, self.flat_grad.numel())):
+            if b > a:
+                ops.axpy(self.flat_grad[a:b], self.flat_grad_b[a:b])
+
+    # ------------------------------------------------------------------------------------------- checkpointing
     def state_dict(self) -> Dict[str, torch.Tensor]:
         out = {k: v.detach().clone() for k, v in self._base_sd.items()}
         cfg = getattr(self.lens, "lens", None)
@@ -544,13 +790,12 @@ class TriModalDepthStep(_StepState):
                  grad_clip_norm: Optional[float] = None):
         """overlap_frozen (default ON since round 6): the image / text towers' forwards run on a second HIP stream beside
         the trainable tower's forward (`_side_by_side`); results are bit-identical to the serial order."""
-        self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward, grad_clip_norm)
         self.grad_checkpointing = bool(grad_checkpointing)      # block recompute in the trainable tower (transformer.py:366-368)
         self.unlock_first_n = unlock_first_n
-        self._build(sd, tower, text, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
-                    text_wsplit=text_wsplit, text_arith=text_arith)
-        self.opt = AdamW(self.masters, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
+                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                        sd, tower, text, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
+                        text_wsplit=text_wsplit, text_arith=text_arith)
 
     def _build(self, sd, tower, text, gemm_cfg=-1, frozen_res_dtype=torch.float32, train_res_dtype=torch.float32,
                text_wsplit=None, text_arith="f16"):
@@ -582,33 +827,16 @@ class TriModalDepthStep(_StepState):
         self.masters["visual.visual_adapter.conv1.weight_gemm"] = conv_weight_as_gemm(       # from the fp32 weight, not the bf16 operand
             sd["visual.visual_adapter.conv1.weight"], device, torch.float32)
 
-    # -------------------------------------------------------------------------------------------
-    def _trainer(self, i):
-        while len(self.trainers) <= i:
-            t = DepthLensTrainer(self.lens, tower_kw=dict(train_blocks=range(self.unlock_first_n), checkpoint=self.grad_checkpointing))
-            if self.trainers:                      # share weight transposes + gradient buffers across micro-batches
-                t.tower.wT = self.trainers[0].tower.wT
-                t.tower.proj = self.trainers[0].tower.proj
-                t.tower.grads = self.trainers[0].tower.grads
-            self.trainers.append(t)
-        return self.trainers[i]
+    def _mk(self):
+        # (a method, not a closure kept on the instance: a step that holds itself in a reference cycle keeps its activations -
+        # 142 GB at the C3 shape - until the cycle collector runs, not until the last reference goes)
+        return DepthLensTrainer(self.lens, tower_kw=dict(train_blocks=range(self.unlock_first_n), checkpoint=self.grad_checkpointing))
 
-    def _alloc_flat_grads(self):
-        """All gradient buffers are views into ONE flat fp32 tensor -> a single all-reduce per step."""
-        al = lambda n: (n + 3) // 4 * 4                       # every view starts 16-byte aligned
-        self.flat_grad = torch.zeros(sum(al(v.numel()) for v in self.masters.values()), device=self.dev, dtype=torch.float32)
-        off = 0
-        for k, v in self.masters.items():
-            self.grads[k] = self.flat_grad[off:off + v.numel()].view(v.shape)
-            off += al(v.numel())
-        # a second buffer of the same layout: the first half of a step's micro-batches accumulates here (forward_backward)
-        self.flat_grad_b = torch.zeros_like(self.flat_grad)
-        self.grads_b, off = {}, 0
-        for k, v in self.masters.items():
-            self.grads_b[k] = self.flat_grad_b[off:off + v.numel()].view(v.shape)
-            off += al(v.numel())
-        for t in self.trainers:
-            t.tower.grads = self.grads
+    def _share_operands(self, t, first):      # weight transposes + gradient buffers
+        t.tower.wT, t.tower.proj, t.tower.grads = first.tower.wT, first.tower.proj, first.tower.grads
+
+    def _bucket_blocks(self):
+        return range(self.unlock_first_n)
 
     def _refresh_operands(self):
         eng = self.lens.vit
@@ -620,182 +848,14 @@ class TriModalDepthStep(_StepState):
             ops.transpose_to_bf16(m, ldo=m.shape[0], out=self.trainers[0].tower.wT[l][key])
         ops.cast_bf16(self.masters["visual.visual_adapter.conv1.weight_gemm"], out=self.lens.conv_w)
 
-    # -------------------------------------------------------------------------------------------
-    def step(self, images: torch.Tensor, texts: torch.Tensor, depths: torch.Tensor) -> torch.Tensor:
-        loss = self.forward_backward(images, texts, depths)
-        self.optimizer_step()
-        return loss
-
-    def finish_reduce(self):
-        """Bring `flat_grad` / `grads` to ONE state: the sum over ranks of every gradient, all collectives complete.
-
-        Between `forward_backward()` and this call the buffer is MIXED: the unlocked blocks' buckets were all-reduced
-        during the last micro-batch's backward (possibly still in flight on the collective's stream) while logit_scale
-        and the adapter - produced last - are still rank-local.  Anything that reads or rescales the gradients in
-        between (clipping, norm logging, accumulation over several forward_backward calls) calls this first;
-        `optimizer_step()` does.  Idempotent; a no-op on one rank.  The values are SUMS: the 1/world of DDP's mean is
-        applied inside the optimizer step (`grad_scale`)."""
-        if not self.dist or self._reduce_done:
-            return
-        for h in self._pending:
-            h.wait()
-        self._pending = []
-        if self._reduced_upto is None:
-            self.comm.all_reduce_sum(self.flat_grad)
-        else:
-            lo, hi = self._rest_ranges()
-            for a, b in ((0, lo), (hi, self.flat_grad.numel())):
-                if b > a:
-                    self.comm.all_reduce_sum(self.flat_grad[a:b])
-        self._reduced_upto = None
-        self._reduce_done = True
-
-    def reduced_grads(self):
-        """The gradients by master name after `finish_reduce()` (sums over ranks)."""
-        self.finish_reduce()
-        return self.grads
-
-    def optimizer_step(self):
-        if self.grad_clip_norm is not None:
-            self._clipped_optimizer_step()
-        elif self.dist:
-            # DDP semantics: mean of per-rank gradients.  Block buckets were started during the last micro-batch's backward
-            # (reverse layer order); what is left - logit_scale and the adapter, produced last - goes in one more call.
-            self.finish_reduce()
-            self.opt.step(self.grads, grad_scale=1.0 / self.world)
-        else:
-            self.opt.step(self.grads)
-        self._refresh_operands()
-        ops.clamp_scalar(self.logit_scale, 0.0, math.log(100.0))
-
-    # ---- gradient buckets: the masters of one block are contiguous in the flat buffer ----
-    def _block_range(self, l):
-        p = f"visual.transformer.resblocks.{l}."
-        names = [k for k in self.masters if k.startswith(p)]
-        base = self.flat_grad.data_ptr()
-        lo = min((self.grads[k].data_ptr() - base) // 4 for k in names)
-        hi = max((self.grads[k].data_ptr() - base) // 4 + self.grads[k].numel() for k in names)
-        return lo, min((hi + 3) // 4 * 4, self.flat_grad.numel())          # incl. the 16-byte alignment pad of the last view
-
-    def _rest_ranges(self):
-        rs = [self._block_range(l) for l in range(self.unlock_first_n)]
-        return min(r[0] for r in rs), max(r[1] for r in rs)
-
-    def _start_block_reduce(self, l):
-        if self.dist and hasattr(self.comm, "all_reduce_sum_async"):
-            lo, hi = self._block_range(l)
-            self._pending.append(self.comm.all_reduce_sum_async(self.flat_grad[lo:hi]))
-            self._reduced_upto = l
-
     def forward_backward(self, images: torch.Tensor, texts: torch.Tensor, depths: torch.Tensor) -> torch.Tensor:
-        tplan = self._text_plan(texts)
-        B = images.shape[0]
-        mb = min(self.mb, B)
-        assert B % mb == 0, "per-GPU batch must be a multiple of the micro-batch"
-        nmb = B // mb
-        if self.flat_grad is None:
-            for i in range(nmb):
-                self._trainer(i)
-            self._alloc_flat_grads()
-        for h in self._pending:          # (a forward_backward without optimizer_step: finish what was started)
-            h.wait()
-        self._pending, self._reduced_upto, self._reduce_done = [], None, False
-        self.flat_grad.zero_()
-        E = self.image.cfg.embed_dim
-        fi = torch.empty(B, E, device=self.dev); ft = torch.empty(B, E, device=self.dev)
-        fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
-        vnorm = torch.empty(B, device=self.dev)
-        # the frozen text tower sees the whole per-GPU batch in one pass: 77-token sequences give a micro-batch only 77 row
-        # tiles (one uneven round of the persistent GEMM, 600-900 TF/s); four times the rows run whole rounds
-        def frozen():
-            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)
-            for i in range(nmb):
-                s = slice(i * mb, (i + 1) * mb)
-                ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
-
-        def trainable():
-            for i in range(nmb):
-                s = slice(i * mb, (i + 1) * mb)
-                vraw[s] = self._trainer(i).forward(depths[s])
-        self._side_by_side(frozen, trainable)
-        ops.l2_normalize(vraw, out=fv, norms=vnorm)
-        scale = self.logit_scale          # the log-temperature, on the device: exp() is applied inside the loss section
-        if self.dist:
-            packed = torch.cat([fi, ft, fv], dim=1)
-            allp = torch.empty(self.world * B, 3 * E, device=self.dev)
-            self.comm.all_gather(allp, packed)                    # ONE exchange: [b, 3*768] per rank over xGMI
-            ai, at, av = [t.contiguous() for t in allp.split(E, dim=1)]
-        else:
-            ai, at, av = fi, ft, fv
-        kw = dict(local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_x=False, dist=self.dist)
-        l1, _, dv1, ds1 = pair_loss_and_grads(self.comm, self.rank, self.world, fi, fv, ai, av, scale, **kw)
-        l2, _, dv2, ds2 = pair_loss_and_grads(self.comm, self.rank, self.world, ft, fv, at, av, scale, **kw)
-        loss = l1 + l2
-        dvraw = ops.l2_normalize_bwd(fv, dv1 + dv2, vnorm)
-        self._backward_all(dvraw, nmb, mb)
-        # logit_scale is exp()'d in forward (model.py:619); with the device-side scale pair_backward returns d/d(log-scale)
-        self.grads["logit_scale"] += ds1 + ds2
-        return loss
-
-    def _backward_all(self, dvraw, nmb, mb):
-        """Backward of every micro-batch; parameter gradients accumulate over them.
-
-        With two or more micro-batches the FIRST half accumulates into a second gradient buffer (`flat_grad_b`) and the second
-        half into `flat_grad`; a block's bucket is merged (and, across ranks, its all-reduce started) when the LAST micro-batch
-        of the second half has passed the block, the rest (adapter, position table) at the end.  That makes the two halves
-        independent streams of work: with `overlap_frozen` on a GPU the first half runs on the second HIP stream beside the
-        second half - the backward is a chain of chip-filling GEMMs with latency-bound kernels between them (fused attention
-        backward, LayerNorm backward, leftover rows, the drain of every persistent launch), exactly what the forward's two
-        towers fill for each other.  The arithmetic - which products are added in which order - is the same on one stream
-        and on two: results are bit-identical (tests/test_hip_train.py).  Reference: loss.backward() over the micro-batches
-        of the accumulation loop, training/train.py:154-210 (gradients of all micro-batches summed into .grad)."""
-        dist_cb = self.dist and self.unlock_first_n > 0
-        dv = lambda i: dvraw[i * mb:(i + 1) * mb].contiguous()
-        half = nmb // 2
-        for i in range(nmb):
-            self._trainer(i).tower.grads = self.grads_b if i < half else self.grads
-        if half == 0:
-            self._trainer(0).backward(dv(0), self._start_block_reduce if dist_cb else None)
-            return
-        self.flat_grad_b.zero_()
-        two_streams = self._overlap_active and self.overlap_backward
-        passed = {}          # block -> event on the first half's stream: its last micro-batch has passed the block
-
-        def first_done(l):
-            if two_streams:
-                passed[l] = torch.cuda.Event()
-                passed[l].record()
-
-        def second_done(l):
-            if two_streams:
-                torch.cuda.current_stream(self.dev).wait_event(passed[l])
-            lo, hi = self._block_range(l)
-            ops.axpy(self.flat_grad[lo:hi], self.flat_grad_b[lo:hi])
-            if dist_cb:
-                self._start_block_reduce(l)
-
-        def first_half():
-            for i in range(half):
-                self._trainer(i).backward(dv(i), first_done if i == half - 1 else None)
-
-        def second_half():
-            for i in range(half, nmb):
-                self._trainer(i).backward(dv(i), second_done if i == nmb - 1 else None)
-        if two_streams:
-            self._side_by_side(first_half, second_half)      # (first closure on the second stream, joined at the end)
-        else:
-            first_half(); second_half()
-        n = self.flat_grad.numel()
-        lo, hi = self._rest_ranges() if self.unlock_first_n > 0 else (0, 0)
-        for a, b in ((0, lo), (hi, n)):
-            if b > a:
-                ops.axpy(self.flat_grad[a:b], self.flat_grad_b[a:b])
+        return self._forward_backward(texts, images, depths)
 
 
 class _PerceiverLensStep(_StepState):
-    """Shared plumbing of the steps whose trainable part is a Lens (tokenizer + Perceiver) in front of a locked ViT:
-    fp32 masters of the Perceiver under the reference's parameter names, one flat fp32 gradient buffer (a single
-    all-reduce per step = DDP's mean of per-rank gradients), AdamW, bf16 operand refresh, logit-scale clamp."""
+    """What the steps whose trainable part is a Lens (tokenizer + Perceiver) in front of a locked ViT add to the step:
+    fp32 masters of the Perceiver under the reference's parameter names and their bf16 operand refresh.  No block is
+    unlocked, so the flat gradient buffer has no buckets: a single all-reduce per step = DDP's mean of per-rank gradients."""
 
     def _collect_perceiver(self, sd):
         pe, P = self.lens.perceiver, "visual.perceiver."
@@ -833,73 +893,17 @@ class _PerceiverLensStep(_StepState):
         self.masters[p + "fn.net.2.weight"] = f32(p + "fn.net.2.weight"); self.refresh.append((p + "fn.net.2.weight", ff["w2"], path + ("w2",)))
         self.masters[p + "fn.net.2.bias"] = ff["b2"]
 
-    def _trainer(self, i):
-        while len(self.trainers) <= i:
-            t = self._mk()
-            if self.trainers:
-                t.tower.wT, t.tower.proj = self.trainers[0].tower.wT, self.trainers[0].tower.proj
-                t.perc.wT = self.trainers[0].perc.wT
-            self.trainers.append(t)
-        return self.trainers[i]
+    def _share_operands(self, t, first):
+        super()._share_operands(t, first)
+        t.perc.wT = first.perc.wT
 
     def _bind_grads(self, t, grads=None):
-        g = self.grads if grads is None else grads
-        t.tower.grads = g; t.perc.grads = g
-
-    def _alloc_flat_grads(self):
-        al = lambda n: (n + 3) // 4 * 4                       # every view starts 16-byte aligned
-        self.flat_grad = torch.zeros(sum(al(v.numel()) for v in self.masters.values()), device=self.dev, dtype=torch.float32)
-        self.flat_grad_b = torch.zeros_like(self.flat_grad)  # the first half of a step's micro-batches accumulates here (_backward_all)
-        self.grads_b, off = {}, 0
-        for k, v in self.masters.items():
-            self.grads[k] = self.flat_grad[off:off + v.numel()].view(v.shape)
-            self.grads_b[k] = self.flat_grad_b[off:off + v.numel()].view(v.shape)
-            off += al(v.numel())
-        for t in self.trainers:
-            self._bind_grads(t)
+        super()._bind_grads(t, grads)
+        t.perc.grads = t.tower.grads
 
     def reference_named_grads(self):
         """The step's gradients (all micro-batches, after `forward_backward`) under the reference's parameter names / layouts."""
         return self.trainers[0].perc.reference_named_grads(self.grads)
-
-    def _backward_all(self, dvraw, nmb, mb):
-        """Backward of every micro-batch (TriModalDepthStep._backward_all): the first half of the micro-batches accumulates into
-        `flat_grad_b`, the second into `flat_grad`, one merge at the end; with `overlap_frozen` on a GPU the two halves run on
-        two HIP streams.  Same arithmetic on one stream and on two.  Not with SyncBatchNorm (its backward exchanges data on the
-        communicator from inside the micro-batch: one stream)."""
-        dv = lambda i: dvraw[i * mb:(i + 1) * mb].contiguous()
-        half = nmb // 2
-        for i in range(nmb):
-            self._bind_grads(self._trainer(i), self.grads_b if i < half else self.grads)
-        if half == 0:
-            self._trainer(0).backward(dv(0))
-            return
-        self.flat_grad_b.zero_()
-
-        def first_half():
-            for i in range(half):
-                self._trainer(i).backward(dv(i))
-
-        def second_half():
-            for i in range(half, nmb):
-                self._trainer(i).backward(dv(i))
-        if getattr(self, "_one_stream_backward", False) or not self.overlap_backward:
-            first_half(); second_half()
-        else:
-            self._side_by_side(first_half, second_half)
-        ops.axpy(self.flat_grad, self.flat_grad_b)
-
-    def _prepare(self, B):
-        mb = min(self.mb, B)
-        assert B % mb == 0, "per-GPU batch must be a multiple of the micro-batch"
-        nmb = B // mb
-        if self.flat_grad is None:
-            for i in range(nmb):
-                self._trainer(i)
-            self._alloc_flat_grads()
-        self._reduce_done = False
-        self.flat_grad.zero_()
-        return mb, nmb
 
     def _refresh_perceiver(self):
         wT = self.trainers[0].perc.wT
@@ -913,29 +917,6 @@ class _PerceiverLensStep(_StepState):
 
     def _refresh_operands(self):
         self._refresh_perceiver()
-
-    def finish_reduce(self):
-        """Sum `flat_grad` over ranks (one collective, once per forward_backward).  Until this has run the gradients are
-        rank-local; clipping / logging / accumulation code calls it (or `reduced_grads()`) before touching them.  The 1/world
-        of DDP's mean is applied in the optimizer step."""
-        if self.dist and not self._reduce_done:
-            self.comm.all_reduce_sum(self.flat_grad)
-            self._reduce_done = True
-
-    def reduced_grads(self):
-        self.finish_reduce()
-        return self.grads
-
-    def optimizer_step(self):
-        if self.grad_clip_norm is not None:
-            self._clipped_optimizer_step()
-        elif self.dist:
-            self.finish_reduce()
-            self.opt.step(self.grads, grad_scale=1.0 / self.world)
-        else:
-            self.opt.step(self.grads)
-        self._refresh_operands()
-        ops.clamp_scalar(self.logit_scale, 0.0, math.log(100.0))
 
 
 class DualAudioStep(_PerceiverLensStep):
@@ -959,11 +940,10 @@ class DualAudioStep(_PerceiverLensStep):
             raise NotImplementedError(f"DualAudioStep: contra_loss_type is 'general' or 'sim_mask', got {contra_loss_type!r} "
                                       "(label_mask cannot run in the reference's drivers either)")
         self.contra_loss_type, self.sim_thres = contra_loss_type, float(sim_thres)
-        self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward, grad_clip_norm)
-        self._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
-                    text_wsplit=text_wsplit, text_arith=text_arith)
-        self.opt = AdamW(self.masters, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
+                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                        sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
+                        text_wsplit=text_wsplit, text_arith=text_arith)
 
     def _build(self, sd, tower, text, lens, gemm_cfg=-1, frozen_res_dtype=torch.float32, train_res_dtype=torch.float32,
                text_wsplit=None, text_arith="f16"):
@@ -984,42 +964,17 @@ class DualAudioStep(_PerceiverLensStep):
         ops.cast_bf16(self.masters["visual.visual_adapter.conv1.weight_gemm"], out=self.lens.conv_w)
 
     def forward_backward(self, audio: torch.Tensor, texts: torch.Tensor) -> torch.Tensor:
-        tplan = self._text_plan(texts)
-        B = audio.shape[0]
-        mb, nmb = self._prepare(B)
-        E = self.lens.tower.embed_dim
-        ft = torch.empty(B, E, device=self.dev); fv = torch.empty(B, E, device=self.dev)
-        vraw = torch.empty(B, E, device=self.dev); vnorm = torch.empty(B, device=self.dev)
-        def frozen():
-            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)       # (whole batch at once: see TriModalDepthStep)
+        return self._forward_backward(texts, None, audio)
 
-        def trainable():
-            for i in range(nmb):
-                s = slice(i * mb, (i + 1) * mb)
-                vraw[s] = self._trainer(i).forward(audio[s])
-        self._side_by_side(frozen, trainable)
-        ops.l2_normalize(vraw, out=fv, norms=vnorm)
-        scale = self.logit_scale          # device-side log-temperature (see TriModalDepthStep)
-        if self.dist:
-            allp = torch.empty(self.world * B, 2 * E, device=self.dev)
-            self.comm.all_gather(allp, torch.cat([fv, ft], dim=1))
-            av, at = [t.contiguous() for t in allp.split(E, dim=1)]
-        else:
-            av, at = fv, ft
+    def _loss(self, fi, ft, fv):
+        """ClipLossGeneral(x=visual, y=text), text tower frozen (the base's `_loss` with one pair and no image side)."""
+        av, at = self._gather(fv, ft)
         # sim_mask: the TEACHER is the text side, which sits in the y position of this call
         mk = dict(sim_teacher="y", sim_thres=self.sim_thres) if self.contra_loss_type == "sim_mask" else {}
-        loss, dv, _, ds = pair_loss_and_grads(self.comm, self.rank, self.world, fv, ft, av, at, scale,    # ClipLossGeneral(x=visual, y=text)
-                                              local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_y=False, dist=self.dist,
-                                              **mk)
-        dvraw = ops.l2_normalize_bwd(fv, dv, vnorm)
-        self._backward_all(dvraw, nmb, mb)
-        self.grads["logit_scale"] += ds
-        return loss
-
-    def step(self, audio, texts):
-        loss = self.forward_backward(audio, texts)
-        self.optimizer_step()
-        return loss
+        loss, dv, _, ds = pair_loss_and_grads(self.comm, self.rank, self.world, fv, ft, av, at, self.logit_scale,
+                                              local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_y=False,
+                                              dist=self.dist, **mk)
+        return loss, dv, (ds,)
 
 
 class TriModalPCStep(_PerceiverLensStep):
@@ -1038,11 +993,10 @@ class TriModalPCStep(_PerceiverLensStep):
                  train_res_dtype=torch.float32, bn_sync: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
                  grad_clip_norm: Optional[float] = None):
-        self._init_host(sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                        overlap_backward, grad_clip_norm)
-        self._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
-                    text_wsplit=text_wsplit, text_arith=text_arith, bn_training=bn_training, bn_sync=bn_sync, unlock_cls=unlock_cls)
-        self.opt = AdamW(self.masters, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
+                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                        sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
+                        text_wsplit=text_wsplit, text_arith=text_arith, bn_training=bn_training, bn_sync=bn_sync, unlock_cls=unlock_cls)
 
     def _build(self, sd, tower, text, lens, gemm_cfg=-1, frozen_res_dtype=torch.float32, train_res_dtype=torch.float32,
                text_wsplit=None, text_arith="f16", bn_training=True, bn_sync=False, unlock_cls=False):
@@ -1062,8 +1016,8 @@ class TriModalPCStep(_PerceiverLensStep):
         self._collect_perceiver(sd)
 
     def _bind_grads(self, t, grads=None):
-        g = self.grads if grads is None else grads
-        t.tower.grads = g; t.perc.grads = g; t.tok.grads = g
+        super()._bind_grads(t, grads)
+        t.tok.grads = t.tower.grads
         self.tok.grads = self.grads
 
     def _refresh_operands(self):
@@ -1079,41 +1033,4 @@ class TriModalPCStep(_PerceiverLensStep):
     pack_text = False
 
     def forward_backward(self, images, texts, points, fps_start=None) -> torch.Tensor:
-        tplan = self._text_plan(texts)
-        B = images.shape[0]
-        mb, nmb = self._prepare(B)
-        E = self.image.cfg.embed_dim
-        fi = torch.empty(B, E, device=self.dev); ft = torch.empty(B, E, device=self.dev)
-        fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
-        vnorm = torch.empty(B, device=self.dev)
-        def frozen():
-            ops.l2_normalize(self._encode_text(texts, tplan), out=ft)       # (whole batch at once: see TriModalDepthStep)
-            for i in range(nmb):
-                s = slice(i * mb, (i + 1) * mb)
-                ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
-
-        def trainable():
-            for i in range(nmb):
-                s = slice(i * mb, (i + 1) * mb)
-                vraw[s] = self._trainer(i).forward(points[s], None if fps_start is None else fps_start[s])
-        self._side_by_side(frozen, trainable)
-        ops.l2_normalize(vraw, out=fv, norms=vnorm)
-        scale = self.logit_scale          # device-side log-temperature (see TriModalDepthStep)
-        if self.dist:
-            allp = torch.empty(self.world * B, 3 * E, device=self.dev)
-            self.comm.all_gather(allp, torch.cat([fi, ft, fv], dim=1))
-            ai, at, av = [t.contiguous() for t in allp.split(E, dim=1)]
-        else:
-            ai, at, av = fi, ft, fv
-        kw = dict(local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_x=False, dist=self.dist)
-        l1, _, dv1, ds1 = pair_loss_and_grads(self.comm, self.rank, self.world, fi, fv, ai, av, scale, **kw)
-        l2, _, dv2, ds2 = pair_loss_and_grads(self.comm, self.rank, self.world, ft, fv, at, av, scale, **kw)
-        dvraw = ops.l2_normalize_bwd(fv, dv1 + dv2, vnorm)
-        self._backward_all(dvraw, nmb, mb)
-        self.grads["logit_scale"] += ds1 + ds2
-        return l1 + l2
-
-    def step(self, images, texts, points, fps_start=None):
-        loss = self.forward_backward(images, texts, points, fps_start)
-        self.optimizer_step()
-        return loss
+        return self._forward_backward(texts, images, points, fps_start)

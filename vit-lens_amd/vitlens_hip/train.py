@@ -893,6 +893,8 @@ class AudioLensTrainer:
     """`visual.` tower of the audio recipe (TRAIN_INFERENCE.md:283-299): AST tokenizer + Perceiver trainable,
     ViT blocks locked, class_embedding unlocked (--lock-visual --unlock-cls)."""
 
+    conv_w_name = "visual.visual_adapter.conv1.weight_gemm"
+
     def __init__(self, lens_engine, tower_kw=None):
         self.le = lens_engine
         kw = dict(train_blocks=(), train_cls=True) if tower_kw is None else dict(tower_kw)
@@ -905,39 +907,21 @@ class AudioLensTrainer:
     def grads(self):
         return self.tower.grads
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _tokens(self, x):
+        """-> (the im2col rows bf16 [B*T, Kp], which the backward keeps, and the tokenizer convolution's output [B*T, D])."""
         le, L = self.le, self.le.lens
         p = le.tower.patch
-        B = x.shape[0]
         cols, gh, gw = ops.im2col(x.contiguous().float().unsqueeze(1), p, p, L.audio_fstride, L.audio_tstride,
                                   le.conv_w.shape[1], transpose_hw=True)
-        tok = ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
-        T = tok.shape[0] // B
-        xin = torch.empty_like(tok)
-        ops.add_rows(tok, le.adapter_pos, xin, tok.shape[0], T, tok.shape[1])
-        lat = self.perc.forward(xin, B)
-        self.ctx = (cols, B, T)
-        return self.tower.forward(lat, B)
+        return cols, ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
 
-    def backward(self, dfeat: torch.Tensor):
-        cols, B, T = self.ctx
-        dlat = self.tower.backward(dfeat)
-        ddata = self.perc.backward(dlat)                          # f32 [B*T, D]
-        D = ddata.shape[1]
-        g = self.tower.grad_buffer("visual.visual_adapter.conv1.weight_gemm", torch.empty(D, cols.shape[1]))
-        conv_weight_grad(ddata, cols, g, self.le.gemm_cfg)
-        ops.batch_rowsum(ddata, self.tower.grad_buffer("visual.visual_adapter.pos_emb", self.le.adapter_pos), B, T, D, T, 0)
-
-
-class EEGLensTrainer(AudioLensTrainer):
-    """`visual.` tower of the EEG recipe (mm_vit_lens/model_cfg.py:153-178): PatchEmbed1D (Conv1d with bias over the
-    time axis) + pos_emb + Perceiver trainable in front of the locked ViT - the audio recipe with a 1-D tokenizer."""
+    def _conv_bias_grad(self, ddata):
+        pass                                          # (the AST convolution's bias is not in the trainable set)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         le = self.le
         B = x.shape[0]
-        cols = le.eeg_cols(x)
-        tok = ops.gemm(cols, le.conv_w, le.conv_b, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
+        cols, tok = self._tokens(x)
         T = tok.shape[0] // B
         xin = torch.empty_like(tok)
         ops.add_rows(tok, le.adapter_pos, xin, tok.shape[0], T, tok.shape[1])
@@ -950,10 +934,25 @@ class EEGLensTrainer(AudioLensTrainer):
         dlat = self.tower.backward(dfeat)
         ddata = self.perc.backward(dlat)                          # f32 [B*T, D]: gradient of tokens + pos
         D = ddata.shape[1]
-        g = self.tower.grad_buffer("visual.visual_adapter.proj.weight_gemm", torch.empty(D, cols.shape[1]))
+        g = self.tower.grad_buffer(self.conv_w_name, torch.empty(D, cols.shape[1]))
         conv_weight_grad(ddata, cols, g, self.le.gemm_cfg)
-        ops.colsum(ddata, self.tower.grad_buffer("visual.visual_adapter.proj.bias", self.le.conv_b))
+        self._conv_bias_grad(ddata)
         ops.batch_rowsum(ddata, self.tower.grad_buffer("visual.visual_adapter.pos_emb", self.le.adapter_pos), B, T, D, T, 0)
+
+
+class EEGLensTrainer(AudioLensTrainer):
+    """`visual.` tower of the EEG recipe (mm_vit_lens/model_cfg.py:153-178): PatchEmbed1D (Conv1d with bias over the
+    time axis) + pos_emb + Perceiver trainable in front of the locked ViT - the audio recipe with a 1-D tokenizer."""
+
+    conv_w_name = "visual.visual_adapter.proj.weight_gemm"
+
+    def _tokens(self, x):
+        le = self.le
+        cols = le.eeg_cols(x)
+        return cols, ops.gemm(cols, le.conv_w, le.conv_b, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
+
+    def _conv_bias_grad(self, ddata):
+        ops.colsum(ddata, self.tower.grad_buffer("visual.visual_adapter.proj.bias", self.le.conv_b))
 
 
 class PCLensTrainer:
