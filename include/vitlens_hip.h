@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 608
+#define VL_ABI_VERSION 609
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -262,6 +262,27 @@ int vl_layernorm_fwd(const void* x, int x_dtype, long x_row_stride, const int64_
 int vl_assemble_ln_pre(const void* tokens, int tok_dtype, const float* cls, const float* pos, const float* pos2,
                        const float* w, const float* b, void* y, int y_dtype, float* xpre, float* mean, float* rstd,
                        int B, int T, int D, float eps, hipStream_t stream);
+
+/* ---- patch dropout (PatchDropout, open_clip/transformer.py:53-90: train mode keeps the class token + K of the T tokens) ----
+ * The selection.  keep int32 [B,K]: keep[b,j] = the index of the j-th largest key of sample b, ties to the lower index (with
+ * distinct keys: torch.topk(keys, K).indices exactly); inv int32 [B,T]: inv[b,t] = j + 1 if keep[b,j] == t, else 0.
+ * keys f32 [B,T], which must be FINITE (a NaN has no place in the order; nothing is read or written out of bounds for one, but
+ * the selection is then unspecified) - or NULL: the kernel draws its own.  The key of (b, t) is then word t & 3 of
+ * Philox4x32-10 with counter (t >> 2, lo32(sample0 + b), hi32(sample0 + b), 0) and key (lo32(seed), hi32(seed)), compared as
+ * unsigned 32-bit integers.  Refused with a status: anything outside 1 <= K <= T <= 4096, B < 1. */
+int vl_patch_keep(const float* keys, uint64_t seed, int64_t sample0, int B, int T, int K, int* keep, int* inv,
+                  hipStream_t stream);
+/* vl_assemble_ln_pre on the kept rows only: y [B,K+1,D]; row 0 of a sample = cls + pos[0], row j >= 1 = tokens[b,t] + pos[1+t]
+ * (+ pos2[t]) with t = keep[b,j-1], then ln_pre.  tokens [B,T,D], keep int32 [B,K] with entries in [0, T) (clamped into it).
+ * The optional training outputs xpre [B,K+1,D], mean / rstd [B*(K+1)] and the dtype combinations are vl_assemble_ln_pre's; a
+ * row is bit-identical to the dense entry's row (b, 1+t) - the same code path computes it. */
+int vl_assemble_ln_pre_keep(const void* tokens, int tok_dtype, const int* keep, const float* cls, const float* pos,
+                            const float* pos2, const float* w, const float* b, void* y, int y_dtype, float* xpre,
+                            float* mean, float* rstd, int B, int T, int K, int D, float eps, hipStream_t stream);
+/* The backward of that gather, as a gather through inv: out f32 [B,T,D], row (b,t) = src[b, inv[b,t], :] if inv[b,t] > 0 else
+ * zeros; src f32 [B,K+1,D] (the ln_pre input gradient; row 0 = the class token's, never scattered).  Every output row is
+ * written once: no fill pass, no atomics, bit-reproducible.  16-byte accesses when D % 4 == 0 and both bases are aligned. */
+int vl_scatter_rows_keep(const float* src, const int* inv, float* out, int B, int T, int K, int D, hipStream_t stream);
 
 /* F.normalize(dim=-1, eps): y f32 and/or bf16 copy; norms[rows] optional (model.py:522-540). */
 int vl_l2_normalize(const float* x, float* y, void* y_bf16, float* norms, int rows, int D, float eps,

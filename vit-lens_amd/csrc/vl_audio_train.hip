@@ -18,6 +18,7 @@
 // torchaudio is not installed anywhere, so like the filterbank this path is "parity unpinned": restated from the published
 // algorithm and checked against a float64 numpy restatement (tests/resample_ref.py), not against the library.
 #include "vl_common.h"
+#include "vl_philox.h"
 #include "vitlens_hip.h"
 
 namespace {
@@ -70,20 +71,6 @@ __global__ void __launch_bounds__(RS_THREADS) resample_sinc_kernel(const float* 
     for (int k = 0; k < K; ++k) acc = fmaf(xp[k], tp[k], acc);
     y[r] = acc;
   }
-}
-
-// ---- Philox4x32-10 ----
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c;
 }
 
 struct AugParams {             // one per sample, written by the host (vitlens_hip/audio.py: AUGMENT_DTYPE)

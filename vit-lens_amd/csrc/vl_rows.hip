@@ -46,7 +46,10 @@ struct LnP {
   float* mean; float* rstd;  // optional [rows]
   int rows, D; float eps;
   // MODE 1 (assemble): row r = (bb, l) with l in [0, T]; l==0 -> cls + pos[0]; else tok[bb][l-1] + pos[l] (+ pos2[l-1])
+  // keep (optional, patch dropout): K kept token indices per sample, int32 [B, K]; the rows are then (bb, j) with j in [0, K]
+  // and l = 0 for j == 0, else 1 + keep[bb][j-1] - the row arithmetic below is the dense one for that (bb, l)
   const float* cls; const float* pos; const float* pos2; int T;
+  const int* keep; int K;
 };
 
 // NCH = number of 256-element chunks held in registers (0 = generic any-D path)
@@ -62,7 +65,14 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const LnP p) {
     const long src = p.ridx ? (long)row * p.rmul + p.ridx[row] : (long)row;
     x = (const TIN*)p.x + src * p.xs;
   } else {
-    const int bb = row / (p.T + 1); l = row - bb * (p.T + 1);
+    int bb;
+    if (p.keep) {
+      bb = row / (p.K + 1);
+      const int j = row - bb * (p.K + 1);
+      if (j > 0) { const int t = p.keep[(long)bb * p.K + j - 1]; l = 1 + (t < 0 ? 0 : (t >= p.T ? p.T - 1 : t)); }
+    } else {
+      bb = row / (p.T + 1); l = row - bb * (p.T + 1);
+    }
     x = (const TIN*)p.x + ((long)bb * p.T + (l > 0 ? l - 1 : 0)) * D;
   }
   TOUT* y = (TOUT*)p.y + (long)row * p.ys;
@@ -375,6 +385,17 @@ extern "C" int vl_assemble_ln_pre(const void* tokens, int tok_dtype, const float
   if (B <= 0 || T <= 0 || D <= 0) return vl_set_error("vl_assemble_ln_pre: empty problem");
   LnP p{}; p.x = tokens; p.xs = D; p.w = w; p.b = b; p.y = y; p.ys = D; p.rows = B * (T + 1); p.D = D; p.eps = eps;
   p.cls = cls; p.pos = pos; p.pos2 = pos2; p.T = T; p.y2 = xpre; p.mean = mean; p.rstd = rstd;
+  VL_HIP_OK(ln_dispatch<1>(p, tok_dtype, y_dtype, stream));
+  return 0;
+}
+
+extern "C" int vl_assemble_ln_pre_keep(const void* tokens, int tok_dtype, const int* keep, const float* cls, const float* pos,
+                                       const float* pos2, const float* w, const float* b, void* y, int y_dtype, float* xpre,
+                                       float* mean, float* rstd, int B, int T, int K, int D, float eps, hipStream_t stream) {
+  if (B <= 0 || T <= 0 || D <= 0 || K < 1 || K > T) return vl_set_error("vl_assemble_ln_pre_keep: bad shape (B, D >= 1, 1 <= K <= T)");
+  if (!keep) return vl_set_error("vl_assemble_ln_pre_keep: keep missing (vl_assemble_ln_pre is the dense form)");
+  LnP p{}; p.x = tokens; p.xs = D; p.w = w; p.b = b; p.y = y; p.ys = D; p.rows = B * (K + 1); p.D = D; p.eps = eps;
+  p.cls = cls; p.pos = pos; p.pos2 = pos2; p.T = T; p.y2 = xpre; p.mean = mean; p.rstd = rstd; p.keep = keep; p.K = K;
   VL_HIP_OK(ln_dispatch<1>(p, tok_dtype, y_dtype, stream));
   return 0;
 }

@@ -25,7 +25,8 @@ def _create(name, device, args):
     with warnings.catch_warnings():
         warnings.filterwarnings("ignore", message="precision='fp32'")
         return tri_create_model(name, None, precision="fp32", device=device, args=args,
-                                force_quick_gelu=bool(getattr(args, "force_quick_gelu", False)))
+                                force_quick_gelu=bool(getattr(args, "force_quick_gelu", False)),
+                                force_patch_dropout=False)          # (vitlens.py:47: the wrapper is an inference model)
 
 
 class ViTLens(nn.Module):

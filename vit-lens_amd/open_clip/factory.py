@@ -111,6 +111,9 @@ def tri_create_model(model_name: str, pretrained: Optional[str] = None, precisio
         cfg["quick_gelu"] = True          # override for use of QuickGELU on non-OpenAI transformer models (factory.py:224-226)
     if precision not in ("fp32", "amp", "amp_bf16", "amp_bfloat16", "bf16"):
         raise NotImplementedError(f"precision {precision!r}: the MI355X path computes GEMMs in bf16 with fp32 accumulation")
+    if force_patch_dropout is not None:
+        # override the default patch dropout value (factory.py:228-230); False (mm_vit_lens, openshape) is 0: off
+        cfg["vision_cfg"]["patch_dropout"] = force_patch_dropout
     if force_image_size is not None:
         cfg["vision_cfg"]["image_size"] = force_image_size
     if args is not None:

@@ -31,6 +31,9 @@ class CLIPVisionCfg:
     visual_adapter_cfg: Optional[dict] = None
     visual_arch: str = "perceiver_vit"
     exp_args: Optional[Any] = None
+    # fraction of the tokens in front of the ViT trunk that a tower in TRAIN mode drops (FLIP; model.py:44: "0.5 to 0.75
+    # recommended in the paper"); 0 (also None / False) = disabled
+    patch_dropout: float = 0.0
 
 
 @dataclass
@@ -143,6 +146,10 @@ class VisionTransformer(nn.Module):
         # `act_layer = QuickGELU if quick_gelu else nn.GELU` of the transformer blocks (model.py:130); the Perceiver's GEGLU and the
         # point tokenizer's MLP are erf-GELU whatever this says, as in the reference
         self.quick_gelu = bool(quick_gelu)
+        # PatchDropout(patch_dropout) if patch_dropout > 0.0 else nn.Identity() (transformer.py:518-521); the layer asserts its range
+        self.patch_dropout = float(cfg.patch_dropout or 0.0)
+        if self.patch_dropout > 0.0:
+            assert 0 <= self.patch_dropout < 1.0, f"patch_dropout must be in [0, 1), got {self.patch_dropout}"
         a = cfg.exp_args
         D, P = cfg.width, cfg.patch_size
         self.heads = D // cfg.head_width
@@ -455,21 +462,44 @@ class VisionTransformer(nn.Module):
                 out[k] = g.reshape(params[k].shape)
         return out
 
+    def _drop_tokens(self, batch: int):
+        """PatchDropout.forward in train mode (transformer.py:66-90) -> (keep int32 [B,K], inv int32 [B,T]) on the device, or
+        (None, None) when nothing is dropped (eval mode, patch_dropout 0).  The keys are the reference's own draw,
+        `torch.randn(batch, num_tokens)` from the CPU default generator, once per tower forward: with the same torch.manual_seed
+        and call order this tower keeps the tokens the reference keeps.  The selection (its topk) runs on the device."""
+        if not (self.training and self.patch_dropout > 0.0):
+            return None, None
+        if self.class_embedding.device.type != "cuda":
+            raise RuntimeError("the ViT-Lens towers run on the MI355X kernels only: move the model to a GPU")
+        from vitlens_hip import ops
+        T = self.positional_embedding.shape[0] - 1
+        keys = torch.randn(batch, T)
+        keys = keys.pin_memory().to(self.class_embedding.device, non_blocking=True)
+        return ops.patch_keep(keys, ops.patch_keep_count(T, self.patch_dropout))
+
     def forward(self, x: torch.Tensor, fwd_output_tokens: bool = False, **kwargs):
         if fwd_output_tokens:
             raise NotImplementedError("token outputs are only used by the video-distillation losses (out of scope)")
         x = x.to(self.class_embedding.device)
+        keep, inv = self._drop_tokens(x.shape[0])
+        if keep is not None:
+            kwargs = dict(kwargs, keep=keep)
+            return self._forward(x, kwargs, dict(kwargs, inv=inv))
+        return self._forward(x, kwargs, kwargs)
+
+    def _forward(self, x, kwargs, train_kwargs):
+        """kwargs: for the no-grad engines; train_kwargs: for the trainers (with patch dropout they also take `inv`)."""
         trainable = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
         if torch.is_grad_enabled() and trainable:
             names = tuple(n for n, _ in trainable)
-            return _TowerFn.apply(self, x, kwargs, names, *[p for _, p in trainable])
+            return _TowerFn.apply(self, x, train_kwargs, names, *[p for _, p in trainable])
         if self.modality == "pc" and self.training and not self._freeze_bn:
             # a no-grad forward in TRAIN mode (the feature-caching pass of the accumulation loop, training/train.py:154-178):
             # the reference's BatchNorm layers use the batch statistics there and update their running statistics, exactly
             # as in the pass with a graph - not the folded running statistics of the inference engine
             tr = self._trainer()
             self._gen += 1            # a pending backward of an earlier forward must not use the overwritten activations
-            feat = tr.forward(x, **kwargs)
+            feat = tr.forward(x, **train_kwargs)
             self._sync_bn_buffers(tr)
             return feat.clone()
         f32 = self._engine_f32() if (self.arith_f32 and not self.training) else None
@@ -477,7 +507,7 @@ class VisionTransformer(nn.Module):
             return f32.encode(x, **kwargs)
         eng = self.engine()
         if self.modality in ("image", "tactile"):
-            return eng.encode_image(x)
+            return eng.encode_image(x, keep=kwargs.get("keep"))
         return eng.encode(x, **kwargs)
 
     def _engine_f32(self):
@@ -630,7 +660,8 @@ class TriCLIP(nn.Module):
             raise NotImplementedError("only visual_arch='perceiver_vit' (Lens -> frozen ViT) is on the hot path")
         img_cfg = CLIPVisionCfg(layers=vision_cfg.layers, width=vision_cfg.width, head_width=vision_cfg.head_width,
                                 mlp_ratio=vision_cfg.mlp_ratio, patch_size=vision_cfg.patch_size,
-                                image_size=vision_cfg.image_size, exp_args=vision_cfg.exp_args)
+                                image_size=vision_cfg.image_size, exp_args=vision_cfg.exp_args,
+                                patch_dropout=vision_cfg.patch_dropout)     # (both towers are built from one vision cfg)
         self.image = VisionTransformer(embed_dim, img_cfg, quick_gelu=self.quick_gelu)      # module_cfg.set_default_image_cfg
         self.visual = VisionTransformer(embed_dim, vision_cfg, quick_gelu=self.quick_gelu)
         # text tower flattened into the root (model.py:435-443)

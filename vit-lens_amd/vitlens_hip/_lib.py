@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 608
+ABI_VERSION = 609
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -45,6 +45,9 @@ SIGNATURES = {
     "vl_gemm_res_rowstats_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "vl_ln_row_stats": [P, I, P, L, I, I, I, F, P, P, P, P, P, L, I, P],
     "vl_assemble_ln_pre": [P, I, P, P, P, P, P, P, I, P, P, P, I, I, I, F, P],
+    "vl_patch_keep": [P, C.c_uint64, C.c_int64, I, I, I, P, P, P],
+    "vl_assemble_ln_pre_keep": [P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, F, P],
+    "vl_scatter_rows_keep": [P, P, P, I, I, I, I, P],
     "vl_l2_normalize": [P, P, P, P, I, I, F, P],
     "vl_l2_normalize_bwd": [P, P, P, P, I, I, F, P],
     "vl_im2col_bf16": [P, P, I, I, I, I, I, I, I, I, I, I, P],

@@ -316,14 +316,20 @@ class VitEngine:
         cols, gh, gw = ops.im2col(image.contiguous().float(), p, p, p, p, self.conv_w.shape[1])
         return ops.gemm(cols, self.conv_w, None, epi=ops.EPI_BF16, cfg=self.gemm_cfg)
 
-    def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos=True):
-        """tokens [B*T, D] (bf16|f32) -> un-normalised features f32 [B, E]."""
+    def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos=True,
+              keep: Optional[torch.Tensor] = None):
+        """tokens [B*T, D] (bf16|f32) -> un-normalised features f32 [B, E].
+        keep int32 [B,K] (ops.patch_keep): patch dropout of a tower in train mode (PatchDropout, transformer.py:53-90) - the
+        trunk runs on the class token + the kept tokens, L = K + 1."""
         cfg = self.cfg
         D, T = cfg.width, tokens.shape[0] // B
-        L = T + 1
+        L = T + 1 if keep is None else keep.shape[1] + 1
         ws = self.workspace(B, L)
         pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
-        ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
+        if keep is None:
+            ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
+        else:
+            ops.assemble_ln_pre_keep(tokens, keep, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
         # (only the class-token rows are read below: the last block may run on them alone)
         run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu, pooled_only=True)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
@@ -334,9 +340,9 @@ class VitEngine:
             return pooled
         return ops.gemm(pooled, self.projT, None, epi=ops.EPI_F32, cfg=self.gemm_cfg)
 
-    def encode_image(self, image: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+    def encode_image(self, image: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         B = image.shape[0]
-        f = self.trunk(self.patch_tokens(image), B)
+        f = self.trunk(self.patch_tokens(image), B, keep=keep)
         return ops.l2_normalize(f) if normalize else f
 
 
@@ -837,7 +843,8 @@ class LensEngine:
         cols, gh, gw = ops.im2col(x.contiguous().float().unsqueeze(2), 1, L.eeg_window_size, 1, L.eeg_stride, self.conv_w.shape[1])
         return cols
 
-    def encode(self, x: torch.Tensor, normalize: bool = False, **kw) -> torch.Tensor:
+    def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
+        """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk)."""
         B = x.shape[0]
         if self.lens.modality == "pc":
             pend = getattr(self, "_points_pending", None)
@@ -847,15 +854,15 @@ class LensEngine:
                 self._points_pending = None
             tok = self.points.forward(x, **kw)                 # already x + pos, [B*G, C] bf16
             lat = self.perceiver.forward(tok, B)
-            f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos)
+            f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         else:
             tok, pos = self.tokens(x)
             if self.perceiver is None:
-                f = self.vit.trunk(tok, B, pos2=pos, use_orig_pos=self.lens.use_orig_pos)
+                f = self.vit.trunk(tok, B, pos2=pos, use_orig_pos=self.lens.use_orig_pos, keep=keep)
             else:
                 T = tok.shape[0] // B
                 xin = torch.empty_like(tok)
                 ops.add_rows(tok, pos, xin, tok.shape[0], T, tok.shape[1])
                 lat = self.perceiver.forward(xin, B)
-                f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos)
+                f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         return ops.l2_normalize(f) if normalize else f

@@ -523,6 +523,71 @@ def assemble_ln_pre(tokens, cls, pos, pos2, w, b, out, B, T, D, eps=1e-5, xpre=N
     return out
 
 
+# ------------------------------------------------------------------------------------------------ patch dropout
+PATCH_KEEP_MAX_T = 4096
+
+
+def patch_keep_count(T: int, p: float) -> int:
+    """Tokens a tower keeps of T at dropout probability p: the reference's `max(1, int(T * (1 - p)))` in Python floats
+    (PatchDropout.forward, open_clip/transformer.py:75-76), e.g. T=10, p=0.9 -> 1 because 10 * (1 - 0.9) < 1.0."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"patch dropout probability must be in [0, 1), got {p}")
+    return max(1, int(T * (1 - p)))
+
+
+def patch_keep(keys, K, B=None, T=None, seed=0, sample0=0, device=None):
+    """The kept tokens of a patch-dropout forward -> (keep int32 [B,K], inv int32 [B,T]): keep[b,j] = index of the j-th largest
+    key of sample b (ties to the lower index; torch.topk(keys, K).indices for distinct keys), inv[b,t] = j+1 where
+    keep[b,j] == t, else 0.  keys f32 [B,T] on the GPU (finite), or None: the kernel's own Philox4x32-10 keys for the samples
+    sample0 .. sample0+B-1 under `seed` (then B, T and device are needed)."""
+    if keys is not None:
+        if keys.dim() != 2 or keys.dtype != torch.float32 or not keys.is_contiguous():
+            raise ValueError("patch_keep: keys must be a contiguous f32 [B, T] tensor")
+        B, T = keys.shape
+        device = keys.device
+    elif B is None or T is None or device is None:
+        raise ValueError("patch_keep: without keys, B, T and device are needed")
+    K = int(K)
+    if B < 1 or not 1 <= K <= T <= PATCH_KEEP_MAX_T:      # (the entry refuses these too; no allocation of a negative size first)
+        raise RuntimeError(f"libvitlens_hip: vl_patch_keep: bad shape (B >= 1, 1 <= K <= T <= {PATCH_KEEP_MAX_T}): B={B} T={T} K={K}")
+    keep = torch.empty(B, K, device=device, dtype=torch.int32)
+    inv = torch.empty(B, T, device=device, dtype=torch.int32)
+    check(_lib.vl_patch_keep(_p(keys), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), B, T, K, _p(keep), _p(inv), _stream()))
+    return keep, inv
+
+
+def _chk_keep(keep, B, who):
+    if keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != B or not keep.is_contiguous():
+        raise ValueError(f"{who}: need a contiguous int32 [B, *] index tensor, got {tuple(keep.shape)} {keep.dtype}")
+
+
+def assemble_ln_pre_keep(tokens, keep, cls, pos, pos2, w, b, out, B, T, D, eps=1e-5, xpre=None, mean=None, rstd=None):
+    """assemble_ln_pre on the class token + the kept tokens only: out [B*(K+1), D] (keep int32 [B,K] from patch_keep)."""
+    _chk_keep(keep, B, "assemble_ln_pre_keep")
+    K = keep.shape[1]
+    check(_lib.vl_assemble_ln_pre_keep(_p(tokens), _dt(tokens), _p(keep), _p(cls), _p(pos), _p(pos2), _p(w), _p(b), _p(out),
+                                       _dt(out), _p(xpre), _p(mean), _p(rstd), B, T, K, D, float(eps), _stream()))
+    return out
+
+
+def scatter_rows_keep(src, inv, K, out=None):
+    """The backward of the kept-row gather: src f32 [B*(K+1), D] (rows of [class; kept tokens] per sample), inv int32 [B,T]
+    -> out f32 [B*T, D], row (b,t) = src[b*(K+1) + inv[b,t]] where inv[b,t] > 0, zeros elsewhere (every row written)."""
+    _chk2d(src, "src", torch.float32)
+    B, T = inv.shape
+    _chk_keep(inv, B, "scatter_rows_keep")
+    D = src.shape[1]
+    if not src.is_contiguous() or src.shape[0] != B * (K + 1):
+        raise ValueError(f"scatter_rows_keep: src must be a contiguous [B*(K+1), D] = [{B * (K + 1)}, D] matrix, got {tuple(src.shape)}")
+    if out is None:
+        out = torch.empty(B * T, D, device=src.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * T * D:
+        raise ValueError("scatter_rows_keep: out must be a contiguous f32 [B*T, D] tensor")
+    check(_lib.vl_scatter_rows_keep(_p(src), _p(inv), _p(out), B, T, K, D, _stream()))
+    return out
+
+
 def l2_normalize(x, out=None, out_bf16=None, norms=None, eps=1e-12):
     _chk2d(x, "x", torch.float32)
     if out is None:

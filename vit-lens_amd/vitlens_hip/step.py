@@ -179,6 +179,27 @@ def _master_to_sd(name: str, m: torch.Tensor, base_sd, cfg) -> Dict[str, torch.T
     return {name: m.reshape(base_sd[name].shape)}
 
 
+# ------------------------------------------------------------------------------------------------ patch dropout
+DROP_TOWER_VISUAL, DROP_TOWER_IMAGE = 0, 1      # tower ids of `drop_sample0`
+_DROP_OFFSET_BITS, _DROP_TOWER_BITS, _DROP_RANK_BITS, _DROP_STEP_BITS = 20, 2, 14, 27
+
+
+def drop_sample0(step: int, rank: int, tower: int, offset: int) -> int:
+    """The Philox sample number (vl_patch_keep's `sample0 + b`) of the sample at `offset` in the per-GPU batch, for tower
+    `tower` of rank `rank` at optimizer step count `step` - a 63-bit field layout, so no two of them share keys:
+
+        sample0 = (step mod 2^27) << 36  |  rank << 22  |  tower << 20  |  offset        rank < 2^14, tower < 4, offset < 2^20
+
+    A micro-batch that starts at `offset` passes this as sample0 and the kernel adds the row index: the kept set of a sample
+    depends on its place in the per-GPU batch, not on the micro-batch size."""
+    if not (0 <= rank < 1 << _DROP_RANK_BITS and 0 <= tower < 1 << _DROP_TOWER_BITS and 0 <= offset < 1 << _DROP_OFFSET_BITS):
+        raise ValueError(f"drop_sample0: rank {rank}, tower {tower} or sample offset {offset} outside the key layout "
+                         f"(rank < 2^{_DROP_RANK_BITS}, tower < 2^{_DROP_TOWER_BITS}, offset < 2^{_DROP_OFFSET_BITS})")
+    step = int(step) & ((1 << _DROP_STEP_BITS) - 1)
+    o, t = _DROP_OFFSET_BITS, _DROP_OFFSET_BITS + _DROP_TOWER_BITS
+    return (step << (t + _DROP_RANK_BITS)) | (rank << t) | (tower << o) | offset
+
+
 class _StepState:
     """What the fused training steps have in common, one copy of each piece: the step (`_forward_backward`, `finish_reduce`,
     `optimizer_step`, `step`), the flat gradient buffers and their per-block buckets, the trainers of the micro-batches.  A
@@ -188,10 +209,25 @@ class _StepState:
     state_dict / load_state_dict of a step in the REFERENCE's names and layouts (a TriCLIP state_dict:
     trained tensors from the fp32 masters, everything else as it was given), plus the AdamW moments - so training can be
     checkpointed, resumed, and handed back to `TriCLIP.load_state_dict` (training/train.py checkpoints `model.state_dict()`
-    and `optimizer.state_dict()`)."""
+    and `optimizer.state_dict()`).
+
+    patch_dropout / drop_seed (--force-patch-dropout; PatchDropout, open_clip/transformer.py:53-90): with patch_dropout > 0
+    every ViT tower of the step - the trainable `visual` tower and, where there is one, the frozen `image` tower, which the
+    reference's model.train() puts in train mode too - keeps the class token and K = max(1, int(T (1 - p))) of the T tokens
+    in front of its trunk, per micro-batch.  The keys are drawn on the device (vl_patch_keep with keys = NULL: Philox4x32-10,
+    no host round trip, no torch RNG): key words (lo32, hi32) of `drop_seed`, and for the sample at offset o of the per-GPU
+    batch the sample number `drop_sample0(self.opt.t, rank, tower, o)`,
+
+        ((opt.t mod 2^27) << 36) | (rank << 22) | (tower << 20) | o        tower: 0 = visual, 1 = image
+
+    with opt.t the number of optimizer steps taken so far (checkpointed by `optimizer_state_dict`).  So two towers, ranks,
+    steps or samples never share keys, a resumed run draws what the uninterrupted run would have drawn, and a sample's kept
+    set does not depend on the micro-batch size.  (Two forward_backward calls without an optimizer step between them draw the
+    same sets.)  The default 0.0 is the code path without the argument: no launch is added."""
 
     def _init_host(self, sd, device, micro_batch, rank, world_size, comm=None, local_loss=False, gather_with_grad=False,
-                   force_comm=False, overlap_frozen=False, overlap_backward=True, grad_clip_norm=None):
+                   force_comm=False, overlap_frozen=False, overlap_backward=True, grad_clip_norm=None,
+                   patch_dropout: float = 0.0, drop_seed: int = 0):
         """Everything of a step that is HOST state - flags, the communicator, the (still empty apart from logit_scale) master
         table, the gradient-bucket bookkeeping - and nothing that touches an engine or a kernel.  Every step's `__init__`
         runs this first and then its `_build()` (engines, masters of the trainable set); tests/test_step_gloo.py drives the
@@ -224,6 +260,12 @@ class _StepState:
             raise ValueError(f"grad_clip_norm must be positive (or None), got {grad_clip_norm}")
         self.grad_clip_norm = None if grad_clip_norm is None else float(grad_clip_norm)
         self._sumsq = None
+        # --force-patch-dropout: the fraction of tokens every ViT tower of the step drops (None / False: off, as in the factory)
+        self.patch_dropout = float(patch_dropout or 0.0)
+        if self.patch_dropout > 0.0:
+            assert 0 <= self.patch_dropout < 1.0, f"patch_dropout must be in [0, 1), got {self.patch_dropout}"
+            drop_sample0(0, rank, 0, 0)                # (a rank outside the key layout is refused here, not in the first step)
+        self.drop_seed = int(drop_seed)
 
     @property
     def last_grad_norm(self):
@@ -295,6 +337,13 @@ class _StepState:
             done.record(self._side)
         trainable()
         main.wait_event(done)
+
+    def drop_indices(self, tower: int, vit, offset: int, n: int):
+        """(keep int32 [n,K], inv int32 [n,T]) of the n samples from `offset` of the per-GPU batch for ViT tower `vit` (tower id
+        `tower`) at the current optimizer step count: what a forward of that micro-batch drops (class docstring)."""
+        T = vit.T
+        return ops.patch_keep(None, ops.patch_keep_count(T, self.patch_dropout), B=n, T=T, seed=self.drop_seed,
+                              sample0=drop_sample0(self.opt.t, self.rank, tower, offset), device=self.dev)
 
     # ------------------------------------------------------------------------------------------- construction, trainers, buffers
     def _construct(self, host, adamw, *build, **build_kw):
@@ -432,6 +481,7 @@ class _StepState:
         ft = torch.empty(B, E, device=self.dev)
         fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
         vnorm = torch.empty(B, device=self.dev)
+        drop = self.patch_dropout > 0.0
         # the frozen text tower sees the whole per-GPU batch in one pass: 77-token sequences give a micro-batch only 77 row
         # tiles (one uneven round of the persistent GEMM, 600-900 TF/s); four times the rows run whole rounds
         def frozen():
@@ -440,12 +490,14 @@ class _StepState:
                 return
             for i in range(nmb):
                 s = slice(i * mb, (i + 1) * mb)
-                ops.l2_normalize(self.image.encode_image(images[s]), out=fi[s])
+                kw = dict(keep=self.drop_indices(DROP_TOWER_IMAGE, self.image, i * mb, mb)[0]) if drop else {}
+                ops.l2_normalize(self.image.encode_image(images[s], **kw), out=fi[s])
 
         def trainable():
             for i in range(nmb):
                 s = slice(i * mb, (i + 1) * mb)
-                vraw[s] = self._trainer(i).forward(*(None if x is None else x[s] for x in inputs))
+                kw = dict(zip(("keep", "inv"), self.drop_indices(DROP_TOWER_VISUAL, self.lens.vit, i * mb, mb))) if drop else {}
+                vraw[s] = self._trainer(i).forward(*(None if x is None else x[s] for x in inputs), **kw)
         self._side_by_side(frozen, trainable)
         ops.l2_normalize(vraw, out=fv, norms=vnorm)
         loss, dv, ds = self._loss(fi, ft, fv)
@@ -787,13 +839,13 @@ class TriModalDepthStep(_StepState):
                  local_loss: bool = False, gather_with_grad: bool = False, train_res_dtype=torch.float32,
                  grad_checkpointing: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
-                 grad_clip_norm: Optional[float] = None):
+                 grad_clip_norm: Optional[float] = None, patch_dropout: float = 0.0, drop_seed: int = 0):
         """overlap_frozen (default ON since round 6): the image / text towers' forwards run on a second HIP stream beside
         the trainable tower's forward (`_side_by_side`); results are bit-identical to the serial order."""
         self.grad_checkpointing = bool(grad_checkpointing)      # block recompute in the trainable tower (transformer.py:366-368)
         self.unlock_first_n = unlock_first_n
         self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed), (lr, betas, eps, weight_decay),
                         sd, tower, text, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                         text_wsplit=text_wsplit, text_arith=text_arith)
 
@@ -935,13 +987,14 @@ class DualAudioStep(_PerceiverLensStep):
                  gemm_cfg: int = -1, comm=None, frozen_res_dtype=torch.float32, local_loss: bool = False,
                  gather_with_grad: bool = False, train_res_dtype=torch.float32, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
-                 grad_clip_norm: Optional[float] = None, contra_loss_type: str = "general", sim_thres: float = 0.8):
+                 grad_clip_norm: Optional[float] = None, contra_loss_type: str = "general", sim_thres: float = 0.8,
+                 patch_dropout: float = 0.0, drop_seed: int = 0):
         if contra_loss_type not in ("general", "sim_mask"):
             raise NotImplementedError(f"DualAudioStep: contra_loss_type is 'general' or 'sim_mask', got {contra_loss_type!r} "
                                       "(label_mask cannot run in the reference's drivers either)")
         self.contra_loss_type, self.sim_thres = contra_loss_type, float(sim_thres)
         self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed), (lr, betas, eps, weight_decay),
                         sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                         text_wsplit=text_wsplit, text_arith=text_arith)
 
@@ -992,9 +1045,9 @@ class TriModalPCStep(_PerceiverLensStep):
                  frozen_res_dtype=torch.float32, local_loss: bool = False, gather_with_grad: bool = False,
                  train_res_dtype=torch.float32, bn_sync: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
-                 grad_clip_norm: Optional[float] = None):
+                 grad_clip_norm: Optional[float] = None, patch_dropout: float = 0.0, drop_seed: int = 0):
         self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                         overlap_backward, grad_clip_norm), (lr, betas, eps, weight_decay),
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed), (lr, betas, eps, weight_decay),
                         sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                         text_wsplit=text_wsplit, text_arith=text_arith, bn_training=bn_training, bn_sync=bn_sync, unlock_cls=unlock_cls)
 

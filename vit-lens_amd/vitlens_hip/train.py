@@ -120,6 +120,7 @@ class TowerTrainer:
         self.grads: Dict[str, torch.Tensor] = {}
         self.ctx = None
         self._pruned = False                        # the decision of the last forward(), kept for its backward()
+        self._drop = None                           # (T, inv) of the last forward() when it dropped tokens, else None
 
     def refresh_derived(self, blocks=(), proj=False):
         """The engine's weights of `blocks` (and proj) were updated in place: redo their transposes."""
@@ -149,17 +150,30 @@ class TowerTrainer:
             g.zero_()
 
     # ------------------------------------------------------------------------------------------ forward
-    def forward(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """tokens [B*T, D] -> un-normalised features f32 [B, E]; keeps what backward() needs."""
+    def forward(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                inv: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tokens [B*T, D] -> un-normalised features f32 [B, E]; keeps what backward() needs.
+        keep / inv (ops.patch_keep; PatchDropout in train mode, open_clip/transformer.py:53-90, applied after the positional
+        add and before ln_pre, :770-771): the trunk runs on the class token + the K kept tokens of every sample - L = K + 1
+        everywhere behind the assembly, which gathers the kept rows itself and never writes the T + 1 row stream."""
         e, D, H = self.eng, self.D, self.H
         T = tokens.shape[0] // B
-        L = T + 1
+        if (keep is None) != (inv is None):
+            raise ValueError("TowerTrainer.forward: keep and inv come together (ops.patch_keep)")
+        if keep is not None and (tuple(inv.shape) != (B, T) or keep.shape[0] != B or not 1 <= keep.shape[1] <= T):
+            raise ValueError(f"TowerTrainer.forward: keep [B,K] / inv [B,T] do not fit B={B}, T={T}: {tuple(keep.shape)}, {tuple(inv.shape)}")
+        L = T + 1 if keep is None else keep.shape[1] + 1
         dh = D // H
         S = self.saved(B, L)
         cfg = e.gemm_cfg
         res_epi = ops.EPI_RES_F32 if e.res_dtype == torch.float32 else ops.EPI_RES_BF16
-        ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
-                            xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
+        if keep is None:
+            ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
+                                xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
+        else:
+            ops.assemble_ln_pre_keep(tokens, keep, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
+                                     xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
+        self._drop = None if keep is None else (T, inv)
         # only the class rows of the last block's output are read (ln_post below, and its backward)
         self._pruned = prunes_last_block(self.layers, self.train_blocks, self.checkpoint, self.causal, e.res_dtype, D, H, L)
         for l in range(self.layers):
@@ -261,13 +275,14 @@ class TowerTrainer:
         ops.gemm_dw(dyt, xt, g, cfg=self.eng.gemm_cfg)
 
     def backward(self, dfeat: torch.Tensor, on_block_done=None) -> torch.Tensor:
-        """dfeat f32 [B, E] -> gradient w.r.t. the input tokens, f32 [B*T, D]; fills self.grads.
+        """dfeat f32 [B, E] -> gradient w.r.t. the input tokens, f32 [B*T, D]; fills self.grads.  After a forward that dropped
+        tokens (keep / inv) the result is still the dense [B*T, D] gradient: the rows of dropped tokens are exact zeros.
         on_block_done(l) is called as soon as every gradient of trainable block l has been enqueued (the multi-GPU step
         starts that block's gradient all-reduce there, under the backward of the blocks below it)."""
         e, D, H = self.eng, self.D, self.H
         B, L, tokens, has_pos2 = self.ctx
         dh = D // H
-        T = L - 1
+        T = L - 1 if self._drop is None else self._drop[0]
         S = self.saved(B, L)
         rows = B * L
         cfg = e.gemm_cfg
@@ -302,9 +317,18 @@ class TowerTrainer:
         ops.layernorm_bwd(S.dx, S.xpre, S.pre_stats[0], S.pre_stats[1], e.ln_pre[0], rows, D, dx=dxpre)
         if self.train_cls:
             ops.batch_rowsum(dxpre, self.grad_buffer(P + "class_embedding", e.cls).view(1, D), B, 1, D, L, 0)
+        self.dxpre = dxpre
+        if self._drop is not None:
+            # the gather's backward: the compact rows back to their tokens' places, zeros for the dropped ones (one pass, every
+            # row written).  pos[0] takes the class rows of the compact gradient, pos[1:] the dense scattered rows
+            dtok = ops.scatter_rows_keep(dxpre, self._drop[1], L - 1)
+            if self.train_pos:
+                gpos = self.grad_buffer(P + "positional_embedding", e.pos)
+                ops.batch_rowsum(dxpre, gpos[:1], B, 1, D, L, 0)
+                ops.batch_rowsum(dtok, gpos[1:], B, T, D, T, 0)
+            return dtok
         if self.train_pos:
             ops.batch_rowsum(dxpre, self.grad_buffer(P + "positional_embedding", e.pos), B, L, D, L, 0)
-        self.dxpre = dxpre
         return dxpre.view(B, L, D)[:, 1:, :].reshape(B * T, D)
 
     def _cls_block_backward(self, S, l, B, L):
@@ -398,13 +422,14 @@ class DepthLensTrainer:
     def grads(self):
         return self.tower.grads
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, keep=None, inv=None) -> torch.Tensor:
+        """keep / inv: patch dropout in front of the ViT trunk (TowerTrainer.forward); the tokenizer stays dense."""
         le = self.le
         p = le.tower.patch
         cols, gh, gw = ops.im2col(x.contiguous().float(), p, p, p, p, le.conv_w.shape[1])
         tok = ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
         self.ctx = (cols, x.shape[0])
-        return self.tower.forward(tok, x.shape[0], pos2=le.adapter_pos)
+        return self.tower.forward(tok, x.shape[0], pos2=le.adapter_pos, keep=keep, inv=inv)
 
     def backward(self, dfeat: torch.Tensor, on_block_done=None):
         cols, B = self.ctx
@@ -413,7 +438,11 @@ class DepthLensTrainer:
         t = self.tower
         g = t.grad_buffer("visual.visual_adapter.conv1.weight_gemm", torch.empty(D, cols.shape[1]))
         conv_weight_grad(dtok, cols, g, self.le.gemm_cfg)
-        ops.batch_rowsum(t.dxpre, t.grad_buffer("visual.visual_adapter.pos_emb", self.le.adapter_pos), B, T, D, T + 1, 1)
+        gpos = t.grad_buffer("visual.visual_adapter.pos_emb", self.le.adapter_pos)
+        if t._drop is not None:          # (t.dxpre holds the K + 1 kept rows: the dense scattered gradient instead)
+            ops.batch_rowsum(dtok, gpos, B, T, D, T, 0)
+        else:
+            ops.batch_rowsum(t.dxpre, gpos, B, T, D, T + 1, 1)
 
 
 class ImageTowerTrainer:
@@ -430,13 +459,13 @@ class ImageTowerTrainer:
     def grads(self):
         return self.tower.grads
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, keep=None, inv=None) -> torch.Tensor:
         e = self.eng
         p = e.cfg.patch
         cols, gh, gw = ops.im2col(x.contiguous().float(), p, p, p, p, e.conv_w.shape[1])
         tok = ops.gemm(cols, e.conv_w, None, epi=ops.EPI_BF16, cfg=e.gemm_cfg)
         self.ctx = cols
-        return self.tower.forward(tok, x.shape[0])
+        return self.tower.forward(tok, x.shape[0], keep=keep, inv=inv)
 
     def backward(self, dfeat: torch.Tensor):
         dtok = self.tower.backward(dfeat)
@@ -918,7 +947,9 @@ class AudioLensTrainer:
     def _conv_bias_grad(self, ddata):
         pass                                          # (the AST convolution's bias is not in the trainable set)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, keep=None, inv=None) -> torch.Tensor:
+        """keep / inv: patch dropout on the Perceiver's latents, the tokens that enter the ViT trunk; tokenizer and Perceiver
+        stay dense."""
         le = self.le
         B = x.shape[0]
         cols, tok = self._tokens(x)
@@ -927,7 +958,7 @@ class AudioLensTrainer:
         ops.add_rows(tok, le.adapter_pos, xin, tok.shape[0], T, tok.shape[1])
         lat = self.perc.forward(xin, B)
         self.ctx = (cols, B, T)
-        return self.tower.forward(lat, B)
+        return self.tower.forward(lat, B, keep=keep, inv=inv)
 
     def backward(self, dfeat: torch.Tensor):
         cols, B, T = self.ctx
@@ -975,11 +1006,12 @@ class PCLensTrainer:
     def grads(self):
         return self.tower.grads
 
-    def forward(self, pts: torch.Tensor, fps_start=None, **kw) -> torch.Tensor:
-        """pts [B,N,3] (PointBERT tokenizer) or point features [B,N,in_dim] with xyz=[B,N,3] (pnsa tokenizer)."""
+    def forward(self, pts: torch.Tensor, fps_start=None, keep=None, inv=None, **kw) -> torch.Tensor:
+        """pts [B,N,3] (PointBERT tokenizer) or point features [B,N,in_dim] with xyz=[B,N,3] (pnsa tokenizer).
+        keep / inv: patch dropout on the Perceiver's latents (TowerTrainer.forward)."""
         B = pts.shape[0]
         ctx = self.tok.forward(pts, fps_start=fps_start, **kw)    # tokens (+ pos), bf16 [B*G, C]
-        return self.tower.forward(self.perc.forward(ctx, B), B)
+        return self.tower.forward(self.perc.forward(ctx, B), B, keep=keep, inv=inv)
 
     def backward(self, dfeat: torch.Tensor):
         self.tok.backward(self.perc.backward(self.tower.backward(dfeat)))
