@@ -66,7 +66,7 @@ const char* vl_last_error(void);
  * VL_F16 tag and the fp16 / fp32 entries without bumping it; round 6 starts counting: 600 = round 6, first revision).
  * vl_version() returns the library's value; a client built against this header must find them equal before its first
  * call - the Python binding (vitlens_hip/_lib.py) and tests/native/abi_c_client.c both refuse to run otherwise. */
-#define VL_ABI_VERSION 609
+#define VL_ABI_VERSION 610
 int vl_version(void);
 
 /* C[M,N] = A[M,K] · W[N,K]^T with fused epilogue.  A, W bf16.  K % 64 == 0, N % 4 == 0.
@@ -548,6 +548,60 @@ int vl_scale_exp_f32(const float* x, float* out, long n, const float* log_scale,
 /* out[t,:] += sum_b x[b*batch_stride_rows + row_offset + t, :]   (positional-embedding gradients) */
 int vl_batch_rowsum(const float* x, float* out, int B, int T, int D, long batch_stride_rows, long row_offset,
                     hipStream_t stream);
+
+/* ---- the linear probe (open_clip/linprobe_model.py ViTLensLP; training/optimizer.py LARS; csrc/vl_linprobe.hip) ----
+ * A frozen tower's pooled rows -> Dropout(p) -> BatchNorm1d(D, affine=False, eps) -> Linear(D, C), label cross-entropy, LARS.
+ * The Linear and its dW are vl_gemm_f32; these entries are the rest.  All fp32 in and out, fp64 accumulators, every reduction
+ * in a fixed order: two calls on the same input agree bit for bit.
+ *
+ * vl_lp_bn_fwd: x f32 [B, ldx >= D] -> xhat f32 [B, ldh >= D], and optionally its transpose xhatT f32 [D, ldt] (ldt % 4 == 0,
+ * ldt >= B, columns B .. ldt-1 written as zeros: dW is then one vl_gemm_f32 with K = ldt).  D % 4 == 0, ldx % 4 == ldh % 4 == 0,
+ * x and xhat 16-byte aligned; B up to 65536 and beyond.
+ *   train = 1: x' = dropout(x): a kept element is x * (1 / (1 - p)), a dropped one 0.  The mask is keep u8 [B, D] (contiguous,
+ *     4-byte aligned, non-zero = kept) when given; with keep == NULL and p > 0 element (b, d) is dropped when word d & 3 of
+ *     Philox4x32-10 with counter (d >> 2, lo32(sample0 + b), hi32(sample0 + b), 0) and key (lo32(seed), hi32(seed)) is below
+ *     (uint32_t)(p * 2^32) - a batch cut into pieces draws the same mask; with p == 0 no mask is read.  Then per column the batch
+ *     mean and the BIASED variance (two passes: mean, then squared deviations), xhat = (x' - mean) / sqrt(var + eps), mean[D]
+ *     and var[D] (optional outputs), and, when given, running = (1 - momentum) running + momentum {mean, var B / (B - 1)} as
+ *     nn.BatchNorm1d.  B < 2 is refused.
+ *   train = 0: no dropout; xhat = (x - running_mean) / sqrt(running_var + eps); nothing else is written. */
+int vl_lp_bn_fwd(const float* x, long ldx, const uint8_t* keep, float p, uint64_t seed, int64_t sample0, int train,
+                 float* running_mean, float* running_var, float momentum, float eps, float* xhat, long ldh, float* xhatT,
+                 long ldt, float* mean, float* var, int B, int D, hipStream_t stream);
+/* vl_ce_label: torch.nn.CrossEntropyLoss() (mean) over logits f32 [B, ld >= C] and target int64 [B], any C >= 1 (max-subtracted):
+ *   loss[0] = mean_b (lse_b - logits[b, target_b]);  optional G f32 [B, ldg >= C] = gscale (softmax - onehot) / B;  optional
+ *   GT f32 [C, ldgt] = its transpose (ldgt % 4 == 0, ldgt >= B, zeros behind column B);  optional dbias f32 [C] = sum_b G[b, :].
+ * The loss and dbias sums go through ws (vl_ce_label_ws_floats(B, C) floats) in two fixed-order stages.  A target outside
+ * [0, C) makes that row's loss term and gradient row NaN (hence the loss and dbias); the index is clamped before any read. */
+long vl_ce_label_ws_floats(int B, int C);
+int vl_ce_label(const float* logits, long ld, const int64_t* target, int B, int C, float gscale, float* loss, float* G,
+                long ldg, float* GT, long ldgt, float* dbias, float* ws, hipStream_t stream);
+/* One slot of vl_lars_multi_step's device table (40 bytes): one tensor of the optimizer. */
+typedef struct vl_lars_slot {
+  float* p; const float* g; float* mu;          /* parameter, gradient, momentum buffer: n contiguous floats each */
+  long n;
+  float weight_decay;
+  int adapt;                                    /* 1: the reference's p.ndim > 1 (weight decay + trust ratio); 0: bias */
+} vl_lars_slot;
+#define VL_LARS_MAX_SLOTS 1024
+/* LARS.step of the reference (training/optimizer.py, from MoCo v3) on every tensor of the table:
+ *   g' = g * grad_scale * clip,  clip = min(1, max_norm / (grad_scale * sqrt(sumsq[0]) + 1e-6)) if max_norm > 0 (sumsq as
+ *        vl_sumsq_f32 leaves it, as for vl_adamw_multi_step), else 1 (sumsq may be NULL)
+ *   adapt = 1:  dp = g' + weight_decay p;  q = trust_coefficient |p| / |dp| if both norms are > 0 else 1;  dp *= q
+ *   adapt = 0:  dp = g'                    (no weight decay and no trust ratio: the reference's rule for biases)
+ *   mu = momentum mu + dp;  p -= lr mu     (each operation rounded to fp32 on its own: no fused multiply-add)
+ * The norms are accumulated in fp64 per 2048-element tile and combined in a fixed order; the host reads neither them nor q.
+ * ws: vl_lars_ws_floats(total elements of the table, nslots) floats, 8-byte aligned; ws_floats = its size (tiles beyond it are
+ * left alone instead of written out of bounds). */
+long vl_lars_ws_floats(long total_elems, int nslots);
+int vl_lars_multi_step(const vl_lars_slot* slots, int nslots, float lr, float momentum, float trust_coefficient,
+                       float grad_scale, float max_norm, const float* sumsq, float* ws, long ws_floats, hipStream_t stream);
+/* Top-k hit counts (training/zero_shot.py test_linprob_single -> accuracy(topk=(1, 5))): rank_b = #{c: logits[b,c] >
+ * logits[b,t_b]} + #{c < t_b: logits[b,c] == logits[b,t_b]}; hits[0] += #{b: rank_b < k0}, hits[1] += #{b: rank_b < k1}
+ * (integer adds; the caller zeroes hits); optional correct u8 [B, 2].  A NaN logit counts as not greater; a target outside
+ * [0, C) is a miss (the index is clamped before the read). */
+int vl_topk_hits(const float* logits, long ld, const int64_t* target, int B, int C, int k0, int k1, int* hits,
+                 uint8_t* correct, hipStream_t stream);
 
 /* ---- the contrastive exchange over RCCL (csrc/vl_comm.cpp) ----
  * One process per GPU, one communicator per process; RCCL (librccl.so.1) is resolved at run time.  These are the three

@@ -176,3 +176,45 @@ def train_dual_one_epoch(model, data, loss, epoch, optimizer, scaler, scheduler,
     def loss_of(feats, logit_scale):
         return loss(feats["A_features"], feats["B_features"], logit_scale, output_dict=True, key=f"{args.align_to}-visual")
     _run_epoch(model, data, epoch, optimizer, scaler, scheduler, args, fetch, features, loss_of)
+
+
+def linprobe_train_one_epoch(model, data, loss, epoch, optimizer, scaler, scheduler, dist_model, args, tb_writer=None):
+    """One epoch of the linear probe (training/train.py:877-994): per batch scheduler(step) -> zero_grad -> logits = model(x) ->
+    loss(logits, label) -> backward -> optional gradient clipping -> optimizer.step.  `model` is an open_clip.linprobe_model
+    ViTLensLP (possibly under DistributedDataParallel: only lp_head's two tensors carry a gradient), `optimizer` a
+    training.optimizer.LARS, `loss` nn.CrossEntropyLoss() or - the same launches as vitlens_hip.linprobe.LinearProbeStep - a
+    LabelCrossEntropyLoss.  The loss is read on the host only at the logged steps, as in the reference."""
+    device = torch.device(args.device)
+    model.train()
+    data["train"].set_epoch(epoch)
+    dataloader = data["train"].dataloader
+    per_epoch = dataloader.num_batches // args.accum_freq
+    digits = math.ceil(math.log(dataloader.num_samples + 1, 10))
+    meters, batch_time, data_time = {}, AverageMeter(), AverageMeter()
+    end = time.time()
+    for i, batch in enumerate(dataloader):
+        step = per_epoch * epoch + i
+        if not args.skip_scheduler:
+            scheduler(step)
+        xs = batch[args.v_key].to(device=device, non_blocking=True)
+        targets = batch["label"].to(device=device, non_blocking=True)
+        data_time.update(time.time() - end)
+        optimizer.zero_grad()
+        lp_loss = loss(model(xs), targets)
+        losses = {"loss": lp_loss}
+        backward(lp_loss, scaler)
+        _optimizer_step(model, optimizer, scaler, args)
+        batch_time.update(time.time() - end)
+        end = time.time()
+        count = i + 1
+        if getattr(args, "rank", 0) == 0 and (i % args.log_every_n_steps == 0 or count == per_epoch):
+            bs = len(xs)
+            for k, v in losses.items():
+                meters.setdefault(k, AverageMeter()).update(v.item(), bs)
+            rate = args.batch_size * args.world_size / batch_time.val
+            logging.info(
+                f"Train Epoch: {epoch} [{count * bs * args.world_size:>{digits}}/{dataloader.num_samples} "
+                f"({100.0 * count / per_epoch:.0f}%)] Data (t): {data_time.avg:.3f} Batch (t): {batch_time.avg:.3f}, {rate:#g}/s, "
+                f"{rate / args.world_size:#g}/s/gpu LR: {optimizer.param_groups[0]['lr']:5f} "
+                + " ".join(f"{k.capitalize()}: {m.val:#.5g} ({m.avg:#.5g})" for k, m in meters.items()))
+            batch_time.reset(); data_time.reset()

@@ -17,7 +17,7 @@ def lib_path() -> str:
 P, I, L, F = C.c_void_p, C.c_int, C.c_long, C.c_float
 
 # include/vitlens_hip.h: VL_ABI_VERSION (tests/test_abi.py compares the two)
-ABI_VERSION = 609
+ABI_VERSION = 610
 
 # name -> argtypes (all functions return int status unless listed in _RET)
 SIGNATURES = {
@@ -108,6 +108,13 @@ SIGNATURES = {
     "vl_axpy_f32": [P, P, F, L, P],
     "vl_scale_exp_f32": [P, P, L, P, F, P],
     "vl_batch_rowsum": [P, P, I, I, I, L, L, P],
+    # the linear probe (csrc/vl_linprobe.hip)
+    "vl_lp_bn_fwd": [P, L, P, F, C.c_uint64, C.c_int64, I, P, P, F, F, P, L, P, L, P, P, I, I, P],
+    "vl_ce_label_ws_floats": [I, I],
+    "vl_ce_label": [P, L, P, I, I, F, P, P, L, P, L, P, P, P],
+    "vl_lars_ws_floats": [L, I],
+    "vl_lars_multi_step": [P, I, F, F, F, F, F, P, P, L, P],
+    "vl_topk_hits": [P, L, P, I, I, I, I, P, P, P],
     # RCCL exchange (csrc/vl_comm.cpp): comm handles are opaque pointers
     "vl_comm_unique_id": [P],
     "vl_comm_create": [C.POINTER(P), P, I, I],
@@ -119,7 +126,8 @@ SIGNATURES = {
 
 
 # functions that do not return a status code
-_RET = {"vl_colreduce_ws_floats": L, "vl_ce_grad_ws_floats": L, "vl_sumsq_ws_floats": L}
+_RET = {"vl_colreduce_ws_floats": L, "vl_ce_grad_ws_floats": L, "vl_sumsq_ws_floats": L, "vl_ce_label_ws_floats": L,
+        "vl_lars_ws_floats": L}
 
 
 def load_library():

@@ -1113,3 +1113,179 @@ def group_sum(x, M):
     return out
 
 
+
+
+# ---- the linear probe (csrc/vl_linprobe.hip): Dropout -> BatchNorm1d(affine=False) -> Linear, label cross-entropy, LARS ----
+LARS_MAX_SLOTS = 1024           # VL_LARS_MAX_SLOTS
+LARS_TILE = 2048                # elements per work tile of vl_lars_multi_step
+
+
+def _lp_pad4(n: int) -> int:
+    return (int(n) + 3) // 4 * 4
+
+
+def lp_bn_fwd(x, running_mean, running_var, train, p=0.0, keep=None, seed=0, sample0=0, momentum=0.1, eps=1e-6, xhat=None,
+              xhatT=None, mean=None, var=None):
+    """Dropout(p) -> BatchNorm1d(D, affine=False, eps) on pooled features x f32 [B, D] (row-major, any row stride that is a
+    multiple of 4) -> xhat f32 [B, D]; xhatT (optional, f32 [D, ldt], ldt % 4 == 0, ldt >= B) receives the transpose with zeros
+    behind column B.  train: the dropout mask is `keep` (u8 / bool [B, D], contiguous) when given, else the kernel's own
+    Philox4x32-10 draw for the samples sample0 .. sample0+B-1 under `seed` (p = 0: no mask at all); batch statistics normalise,
+    `mean` / `var` (f32 [D], optional) receive them and running_mean / running_var are updated as nn.BatchNorm1d does.
+    Eval: the running statistics normalise and nothing else is written."""
+    _chk2d(x, "lp_bn_fwd: x", torch.float32)
+    B, D = x.shape
+    p = float(p)
+    if D < 4 or D % 4 or x.stride(0) % 4:
+        raise ValueError(f"lp_bn_fwd: D and the row stride must be multiples of 4, got D={D} stride {x.stride(0)}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"lp_bn_fwd: dropout probability must be in [0, 1), got {p}")
+    if train and B < 2:
+        raise ValueError("lp_bn_fwd: Expected more than 1 value per channel when training (B >= 2)")
+    for name, t in (("running_mean", running_mean), ("running_var", running_var), ("mean", mean), ("var", var)):
+        if t is None:
+            if name.startswith("running") and not train:
+                raise ValueError("lp_bn_fwd: eval mode needs the running statistics")
+            continue
+        if t.dtype != torch.float32 or t.numel() != D or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"lp_bn_fwd: {name} must be a contiguous f32 [{D}] tensor on x's device")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("lp_bn_fwd: running_mean and running_var come together")
+    if keep is not None:
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        if keep.dtype != torch.uint8 or tuple(keep.shape) != (B, D) or not keep.is_contiguous() or keep.device != x.device:
+            raise ValueError(f"lp_bn_fwd: keep must be a contiguous u8 / bool [{B}, {D}] tensor on x's device")
+    if xhat is None:
+        xhat = torch.empty(B, D, device=x.device, dtype=torch.float32)
+    _chk2d(xhat, "lp_bn_fwd: xhat", torch.float32)
+    if tuple(xhat.shape) != (B, D) or xhat.stride(0) % 4:
+        raise ValueError("lp_bn_fwd: xhat must be f32 [B, D] with a row stride that is a multiple of 4")
+    ldt = 0
+    if xhatT is not None:
+        _chk2d(xhatT, "lp_bn_fwd: xhatT", torch.float32)
+        ldt = xhatT.shape[1]
+        if xhatT.shape[0] != D or ldt < B or ldt % 4 or not xhatT.is_contiguous():
+            raise ValueError(f"lp_bn_fwd: xhatT must be a contiguous f32 [{D}, ldt] tensor, ldt % 4 == 0 and >= {B}")
+    check(_lib.vl_lp_bn_fwd(_p(x), x.stride(0), _p(keep), p, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), 1 if train else 0,
+                            _p(running_mean), _p(running_var), float(momentum), float(eps), _p(xhat), xhat.stride(0), _p(xhatT),
+                            ldt, _p(mean), _p(var), B, D, _stream()))
+    return xhat
+
+
+def ce_label(logits, target, gscale=1.0, need_g=False, need_gt=False, need_dbias=False, loss=None, G=None, GT=None, dbias=None,
+             ws=None):
+    """torch.nn.CrossEntropyLoss() (mean) over logits f32 [B, C] (row-major, any row stride) and target int64 [B], and its
+    gradient -> (loss [1], G, GT, dbias), the last three None unless asked for (need_* or a given tensor):
+    G f32 [B, C] = gscale (softmax - onehot) / B, GT f32 [C, pad4(B)] = its transpose with zeros behind column B,
+    dbias f32 [C] = G's column sums.  A target outside [0, C) gives NaN in its row of G and a NaN loss."""
+    _chk2d(logits, "ce_label: logits", torch.float32)
+    B, Cc = logits.shape
+    if B < 1 or Cc < 1:
+        raise ValueError("ce_label: empty problem")
+    if target.dtype != torch.int64 or tuple(target.shape) != (B,) or not target.is_contiguous() or target.device != logits.device:
+        raise ValueError(f"ce_label: target must be a contiguous int64 [{B}] tensor on the logits' device")
+    dev = logits.device
+    if loss is None:
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+    elif loss.dtype != torch.float32 or loss.numel() != 1:
+        raise ValueError("ce_label: loss must be one f32 element")
+    if G is None and need_g:
+        G = torch.empty(B, Cc, device=dev, dtype=torch.float32)
+    if GT is None and need_gt:
+        GT = torch.empty(Cc, _lp_pad4(B), device=dev, dtype=torch.float32)
+    if dbias is None and need_dbias:
+        dbias = torch.empty(Cc, device=dev, dtype=torch.float32)
+    ldg = ldgt = 0
+    if G is not None:
+        _chk2d(G, "ce_label: G", torch.float32)
+        if tuple(G.shape) != (B, Cc):
+            raise ValueError(f"ce_label: G must be f32 [{B}, {Cc}]")
+        ldg = G.stride(0)
+    if GT is not None:
+        _chk2d(GT, "ce_label: GT", torch.float32)
+        ldgt = GT.shape[1]
+        if GT.shape[0] != Cc or ldgt < B or ldgt % 4 or (Cc > 1 and GT.stride(0) != ldgt):
+            raise ValueError(f"ce_label: GT must be a contiguous f32 [{Cc}, ldgt] tensor, ldgt % 4 == 0 and >= {B}")
+    if dbias is not None and (dbias.dtype != torch.float32 or dbias.numel() != Cc or not dbias.is_contiguous()):
+        raise ValueError(f"ce_label: dbias must be a contiguous f32 [{Cc}] tensor")
+    need = int(_lib.vl_ce_label_ws_floats(B, Cc))
+    if ws is None:
+        ws = torch.empty(need, device=dev, dtype=torch.float32)
+    elif ws.dtype != torch.float32 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError(f"ce_label: workspace of {need} f32 elements required")
+    check(_lib.vl_ce_label(_p(logits), logits.stride(0), _p(target), B, Cc, float(gscale), _p(loss), _p(G), ldg, _p(GT), ldgt,
+                           _p(dbias), _p(ws), _stream()))
+    return loss, G, GT, dbias
+
+
+def ce_label_ws_floats(B, C):
+    return int(_lib.vl_ce_label_ws_floats(int(B), int(C)))
+
+
+def pack_lars_slots(rows):
+    """rows of (p, g, mu, weight_decay, adapt) - three contiguous f32 tensors of one shape on the GPU, a float and a flag ->
+    the int64 [len, 5] image of `struct vl_lars_slot[]` (HOST tensor; 40 bytes per slot): (p, g, mu addresses, n, the f32 bits
+    of weight_decay in the low word and adapt in the high word).  The caller uploads it once and keeps the tensors alive."""
+    import struct
+    out = torch.empty(len(rows), 5, dtype=torch.int64)
+    for i, (p, g, mu, wd, adapt) in enumerate(rows):
+        for name, t in (("p", p), ("g", g), ("mu", mu)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise ValueError(f"pack_lars_slots: slot {i}: {name} must be a contiguous f32 tensor of p's size")
+            if not t.is_cuda:
+                raise RuntimeError("vitlens_hip ops need GPU tensors (no CPU fallback)")
+        lo = struct.unpack("<I", struct.pack("<f", float(wd)))[0]
+        word = lo | ((1 if adapt else 0) << 32)
+        out[i] = torch.tensor([p.data_ptr(), g.data_ptr(), mu.data_ptr(), p.numel(), word], dtype=torch.int64)
+    return out
+
+
+def lars_ws_floats(total_elems, nslots):
+    return int(_lib.vl_lars_ws_floats(int(total_elems), int(nslots)))
+
+
+def lars_multi_step(slots, nslots, lr, momentum=0.9, trust_coefficient=1e-3, grad_scale=1.0, max_norm=None, sumsq=None, ws=None,
+                    total_elems=None):
+    """The reference's LARS.step (training/optimizer.py) on every tensor of a device slot table (`pack_lars_slots`, uploaded) in
+    one call: weight decay and the trust ratio |p| / |dp| on the adapt slots only, momentum and the update on all; the norms
+    and the ratio stay on the device.  max_norm (with sumsq = `grad_sumsq` of all gradients of the table) folds
+    clip_grad_norm_ in, as `adamw_multi` does.  ws: f64 workspace of lars_ws_floats(total, nslots) / 2 elements (or
+    total_elems, from which it is allocated)."""
+    if slots.dtype != torch.int64 or slots.dim() != 2 or slots.shape[1] != 5 or not slots.is_contiguous():
+        raise ValueError("lars_multi_step: slots must be a contiguous int64 [nslots, 5] table")
+    if not 0 <= int(nslots) <= min(slots.shape[0], LARS_MAX_SLOTS):
+        raise ValueError(f"lars_multi_step: nslots {nslots} outside the table of {slots.shape[0]} rows (at most {LARS_MAX_SLOTS} per launch)")
+    clip = max_norm is not None and float(max_norm) > 0.0
+    if clip and (sumsq is None or sumsq.dtype != torch.float32 or sumsq.numel() != 1):
+        raise ValueError("lars_multi_step: max_norm needs sumsq, one f32 element (grad_sumsq of the gradients)")
+    if ws is None:
+        if total_elems is None:
+            raise ValueError("lars_multi_step: pass the workspace or total_elems")
+        ws = torch.empty(lars_ws_floats(total_elems, nslots) // 2 + 1, device=slots.device, dtype=torch.float64)
+    if ws.dtype != torch.float64 or not ws.is_contiguous() or ws.numel() < 2:
+        raise ValueError("lars_multi_step: the workspace is a contiguous f64 tensor of lars_ws_floats(total, nslots) / 2 elements")
+    check(_lib.vl_lars_multi_step(_p(slots), int(nslots), float(lr), float(momentum), float(trust_coefficient), float(grad_scale),
+                                  float(max_norm) if clip else 0.0, _p(sumsq) if clip else None, _p(ws), 2 * ws.numel(), _stream()))
+
+
+def topk_hits(logits, target, ks=(1, 5), hits=None, correct=None, need_correct=False):
+    """Top-k hit counts of logits f32 [B, C] against target int64 [B] for the two k of `ks`, ADDED into hits (int32 [2]; a new
+    zeroed tensor when None) -> (hits, correct u8 [B, 2] or None).  Ties: the lower class index ranks first."""
+    _chk2d(logits, "topk_hits: logits", torch.float32)
+    B, Cc = logits.shape
+    if B < 1 or Cc < 1:
+        raise ValueError("topk_hits: empty problem")
+    if target.dtype != torch.int64 or tuple(target.shape) != (B,) or not target.is_contiguous() or target.device != logits.device:
+        raise ValueError(f"topk_hits: target must be a contiguous int64 [{B}] tensor on the logits' device")
+    if len(ks) != 2 or min(int(k) for k in ks) < 1:
+        raise ValueError("topk_hits: two values of k, each >= 1")
+    if hits is None:
+        hits = torch.zeros(2, device=logits.device, dtype=torch.int32)
+    elif hits.dtype != torch.int32 or hits.numel() != 2 or not hits.is_contiguous():
+        raise ValueError("topk_hits: hits must be a contiguous int32 [2] tensor")
+    if correct is None and need_correct:
+        correct = torch.empty(B, 2, device=logits.device, dtype=torch.uint8)
+    if correct is not None and (correct.dtype != torch.uint8 or tuple(correct.shape) != (B, 2) or not correct.is_contiguous()):
+        raise ValueError(f"topk_hits: correct must be a contiguous u8 [{B}, 2] tensor")
+    check(_lib.vl_topk_hits(_p(logits), logits.stride(0), _p(target), B, Cc, int(ks[0]), int(ks[1]), _p(hits), _p(correct), _stream()))
+    return hits, correct
