@@ -1,0 +1,84 @@
+"""Records the library launches of a forward / backward that runs on CPU tensors instead of executing them: which kernels a
+host-side plan (engine.run_blocks, TowerTrainer.forward / backward, TextEngine.encode_text ...) enqueues, in which order and
+with which arguments - without a GPU.
+
+    with recording() as trace:
+        eng.trunk(tokens, B)
+    symbols(trace)            # ["vl_assemble_ln_pre", "vl_ln_row_stats", ...]
+    normalised(trace)         # comparable between two runs that allocate elsewhere
+
+`ops._lib` becomes a proxy that appends (symbol, arguments) for every call and reports success; the pure host functions
+(vl_gemm_main_rows, the *_ws_floats ...) go to the real library, so the row splits the plans branch on are the real ones.
+`ops._p` accepts CPU tensors, `ops._stream` and `torch.cuda.current_stream` are stubs.  The tensors' contents are whatever
+`torch.empty` left: only the plan is meaningful."""
+import contextlib
+import ctypes
+
+import torch
+
+HOST_FUNCTIONS = ("vl_version", "vl_last_error", "vl_gemm_main_rows", "vl_attn_bwd_fused_supported")
+
+
+class Ptr:
+    """A pointer argument: the tensor (kept alive, so that no two buffers of a trace share an address) and where it points."""
+
+    def __init__(self, t):
+        self.t = t
+        self.base = t.untyped_storage().data_ptr()
+        self.offset = t.data_ptr() - self.base
+
+
+class _Stream:
+    """What the wrappers read of the current stream."""
+    cuda_stream = 0
+
+
+class _Recorder:
+    def __init__(self, real, trace):
+        self._real, self._trace = real, trace
+
+    def __getattr__(self, name):
+        if name in HOST_FUNCTIONS or name.endswith("_ws_floats"):
+            return getattr(self._real, name)
+
+        def launch(*args):
+            self._trace.append((name, args))
+            return 0
+        return launch
+
+
+@contextlib.contextmanager
+def recording():
+    from vitlens_hip import ops
+    trace = []
+    saved = (ops._lib, ops._p, ops._stream, torch.cuda.current_stream)
+    ops._lib = _Recorder(saved[0], trace)
+    ops._p = lambda t: None if t is None else Ptr(t)
+    ops._stream = lambda: "stream"
+    torch.cuda.current_stream = lambda device=None: _Stream()
+    try:
+        yield trace
+    finally:
+        ops._lib, ops._p, ops._stream, torch.cuda.current_stream = saved
+
+
+def symbols(trace):
+    return [name for name, _ in trace]
+
+
+def normalised(trace):
+    """[(symbol, arguments)] with every pointer as (buffer numbered by first appearance in the trace, byte offset from that
+    buffer's storage base): two runs that allocate elsewhere compare equal, and aliasing is part of what is compared."""
+    number = {}
+    out = []
+    for name, args in trace:
+        row = []
+        for a in args:
+            if isinstance(a, Ptr):
+                row.append(("ptr", number.setdefault(a.base, len(number)), a.offset))
+            elif isinstance(a, ctypes.Array):
+                row.append(tuple(a))
+            else:
+                row.append(a)
+        out.append((name, tuple(row)))
+    return out

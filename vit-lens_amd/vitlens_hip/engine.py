@@ -8,10 +8,8 @@ pre-allocated workspaces (no allocation inside the block loop -> hipGraph-captur
 Precision contract (= the reference under torch autocast): GEMM operands bf16, accumulation fp32,
 LayerNorm / softmax statistics / residual stream / final features fp32 (residual dtype selectable).
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, Optional
-
-import os
 
 import torch
 
@@ -57,25 +55,24 @@ def prep_block(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.T
     """Device copies of one ResidualAttentionBlock: GEMM weights bf16, the rest f32; with the LayerNorm folding switched on
     also the operands of the two LayerNorm -> Linear pairs with the LayerNorm folded in (ops.fold_ln_linear; used for frozen
     blocks on a bf16 stream)."""
-    bf = torch.bfloat16
     dv = lambda k: sd[p + k].detach().to(device)
-    blk = _prep_block_plain(sd, p, device)
+    blk = block_operands(sd, p, device)
     if LN_FOLD:          # (read at call time: engines built while the switch is on carry the folded operands)
         blk["in_f"] = ops.fold_ln_linear(dv("attn.in_proj_weight"), dv("attn.in_proj_bias"), dv("ln_1.weight"), dv("ln_1.bias"))
         blk["fc_f"] = ops.fold_ln_linear(dv("mlp.c_fc.weight"), dv("mlp.c_fc.bias"), dv("ln_2.weight"), dv("ln_2.bias"))
     return blk
 
 
-def _prep_block_plain(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
-    bf = torch.bfloat16
-    return {
-        "ln1_w": _dev(sd[p + "ln_1.weight"], device), "ln1_b": _dev(sd[p + "ln_1.bias"], device),
-        "in_w": _dev(sd[p + "attn.in_proj_weight"], device, bf), "in_b": _dev(sd[p + "attn.in_proj_bias"], device),
-        "out_w": _dev(sd[p + "attn.out_proj.weight"], device, bf), "out_b": _dev(sd[p + "attn.out_proj.bias"], device),
-        "ln2_w": _dev(sd[p + "ln_2.weight"], device), "ln2_b": _dev(sd[p + "ln_2.bias"], device),
-        "fc_w": _dev(sd[p + "mlp.c_fc.weight"], device, bf), "fc_b": _dev(sd[p + "mlp.c_fc.bias"], device),
-        "proj_w": _dev(sd[p + "mlp.c_proj.weight"], device, bf), "proj_b": _dev(sd[p + "mlp.c_proj.bias"], device),
-    }
+_BLOCK_OPERANDS = {"ln1_w": "ln_1.weight", "ln1_b": "ln_1.bias", "in_w": "attn.in_proj_weight", "in_b": "attn.in_proj_bias",
+                   "out_w": "attn.out_proj.weight", "out_b": "attn.out_proj.bias", "ln2_w": "ln_2.weight", "ln2_b": "ln_2.bias",
+                   "fc_w": "mlp.c_fc.weight", "fc_b": "mlp.c_fc.bias", "proj_w": "mlp.c_proj.weight", "proj_b": "mlp.c_proj.bias"}
+
+
+def block_operands(sd: Dict[str, torch.Tensor], p: str, device, wdtype=torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """Device copies of the twelve operands of one ResidualAttentionBlock: the four GEMM weights in `wdtype` (bf16; IEEE half
+    for `TextEngine(arith="f16")`; f32 for the fp32 engines), LayerNorm parameters and biases f32."""
+    gemm_w = ("in_w", "out_w", "fc_w", "proj_w")
+    return {k: _dev(sd[p + n], device, wdtype if k in gemm_w else torch.float32) for k, n in _BLOCK_OPERANDS.items()}
 
 
 def conv_weight_as_gemm(w: torch.Tensor, device, dtype=torch.bfloat16) -> torch.Tensor:
@@ -102,6 +99,34 @@ def copy_tree(dst, src):
             copy_tree(d, s_)
 
 
+@dataclass
+class BlockSlots:
+    """Where block_forward reads and writes one ResidualAttentionBlock: built once with the buffers (one for an engine's
+    workspace, one per layer for a trainer's saved activations).  An optional output that is None is not written."""
+    x0: torch.Tensor                  # residual stream: block input, after the attention branch, block output (an engine
+    x1: torch.Tensor                  # passes one tensor three times: in place)
+    x2: torch.Tensor
+    h1: torch.Tensor                  # ln_1 / ln_2 output of a block that runs the LayerNorm passes
+    h2: torch.Tensor
+    h_left: torch.Tensor              # LayerNorm output of a folded GEMM's leftover rows
+    qkv: torch.Tensor                 # packed in-projection output and its q / k / v views by heads (ops.heads_view)
+    q: torch.Tensor
+    k: torch.Tensor
+    v: torch.Tensor
+    a: torch.Tensor                   # attention output
+    hid: torch.Tensor                 # MLP hidden
+    part: Optional[torch.Tensor]      # partial row sums between a gemm_res_rowstats and the ln_row_stats behind it
+    a1: torch.Tensor                  # the class rows of a pruned last block: attention output, ln_2 output, MLP hidden
+    h2c: torch.Tensor
+    hid1: torch.Tensor
+    stats: Optional[tuple] = None     # (mean1, rstd1, mean2, rstd2); a folded block needs them
+    lse: Optional[torch.Tensor] = None
+    u: Optional[torch.Tensor] = None  # the second output of c_fc (the activation's derivative, with a *_DSAVE act)
+    lse1: Optional[torch.Tensor] = None        # lse, (mean2, rstd2) and u of the class rows
+    stats2c: Optional[tuple] = None
+    u1: Optional[torch.Tensor] = None
+
+
 class _Workspace:
     def __init__(self, B, L, D, H, hidden, device, res_dtype):
         dh = D // H
@@ -122,6 +147,11 @@ class _Workspace:
         self.a1 = torch.empty(B, D, device=device, dtype=bf)
         self.h1 = torch.empty(B, D, device=device, dtype=bf)
         self.hid1 = torch.empty(B, hidden, device=device, dtype=bf)
+        # one in-place stream, one LayerNorm buffer.  A block that runs its LayerNorm passes keeps no statistics (slots); a
+        # folded one leaves both LayerNorms' in the one (mean, rstd) pair (slots_folded)
+        self.slots = BlockSlots(x0=self.x, x1=self.x, x2=self.x, h1=self.h, h2=self.h, h_left=self.h, qkv=self.qkv, q=self.q,
+                                k=self.k, v=self.v, a=self.a, hid=self.hid, part=self.part, a1=self.a1, h2c=self.h1, hid1=self.hid1)
+        self.slots_folded = replace(self.slots, stats=(self.mean, self.rstd, self.mean, self.rstd))
 
 
 # LayerNorm folding is ON by default since round 5 (the whole GPU suite is green with it: profiles/r05_pytest_gpu_lnfold_on_*.log;
@@ -155,71 +185,91 @@ def cls_rows(x2d, B, L):
     return x2d.as_strided((B, D), (L * D, 1), x2d.storage_offset())
 
 
-def _pooled_block_tail(w, ws, B, L, D, H, act, cfg):
-    """The last block behind its in-projection, on the class rows of ws.x only (see PRUNE_LAST_BLOCK)."""
-    xc = cls_rows(ws.x, B, L)
-    ops.attn_fwd_q1(ws.q, ws.k, ws.v, ws.a1, qrow=0, qscale=(D // H) ** -0.5 * ops.LOG2E)
-    ops.gemm(ws.a1, w["out_w"], w["out_b"], out=xc, res=xc, epi=ops.EPI_RES_BF16, cfg=cfg)
-    ops.layernorm(xc, w["ln2_w"], w["ln2_b"], ws.h1, B, D, x_row_stride=L * D)
-    ops.gemm(ws.h1, w["fc_w"], w["fc_b"], out=ws.hid1, epi=ops.EPI_BF16, act=act, cfg=cfg)
-    ops.gemm(ws.hid1, w["proj_w"], w["proj_b"], out=xc, res=xc, epi=ops.EPI_RES_BF16, cfg=cfg)
+def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, cfg):
+    """The pruned last block behind its in-projection (see PRUNE_LAST_BLOCK): single-query attention, out_proj + residual,
+    ln_2, c_fc + activation and c_proj + residual on the B class rows b*L of x0 / x1 / x2 (row-strided views, no copy); the
+    other rows of x1 and x2 and the full-size a / hid / u are neither written nor read."""
+    x0c, x1c, x2c = (cls_rows(x, B, L) for x in (s.x0, s.x1, s.x2))
+    m2, r2 = s.stats2c or (None, None)
+    ops.attn_fwd_q1(s.q, s.k, s.v, s.a1, lse=s.lse1, qrow=0, qscale=(D // H) ** -0.5 * ops.LOG2E)
+    ops.gemm(s.a1, w["out_w"], w["out_b"], out=x1c, res=x0c, epi=ops.EPI_RES_BF16, cfg=cfg)
+    ops.layernorm(x1c, w["ln2_w"], w["ln2_b"], s.h2c, B, D, x_row_stride=L * D, mean=m2, rstd=r2)
+    ops.gemm(s.h2c, w["fc_w"], w["fc_b"], out=s.hid1, epi=ops.EPI_BF16, act=act, cfg=cfg, out2=s.u1)
+    ops.gemm(s.hid1, w["proj_w"], w["proj_b"], out=x2c, res=x1c, epi=ops.EPI_RES_BF16, cfg=cfg)
+
+
+def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, cfg, folded, next_folded, cls_only=False, write_out=True, mm=0):
+    """One pre-LN ResidualAttentionBlock (transformer.py:254-272) with the operands `w` on the buffers `s`:
+    x1 = x0 + out_proj(attn(in_proj(ln_1(x0)))), x2 = x1 + c_proj(act(c_fc(ln_2(x1)))).  The one forward of the engines and
+    the trainers: it branches on what it is given, never on who calls.
+    folded: the LayerNorms are folded into the GEMMs either side of them (w carries "in_f" / "fc_f", bf16 stream, s.stats and
+    s.part given) - ln_1 / ln_2 are never materialised, the in-projection and c_fc read the residual rows and apply
+    (mean, rstd) in their epilogues, the out-projection leaves the partial row sums of what it stores (ops.gemm_lnfold /
+    gemm_res_rowstats).  Otherwise the LayerNorm passes run, and leave their statistics where s.stats is given.
+    next_folded: the consumer of x2 is a folded block - c_proj leaves the partial row sums too.
+    cls_only: the caller reads only the class-token rows b*L of x2 - dense up to the in-projection, then _cls_tail_forward.
+    write_out=False (the recompute in front of a block's backward, which does not need x2): c_proj is skipped.
+    mm: the rows of x0 whose partial sums are in s.part (what the block before returned; 0: the statistics come from the rows).
+    Returns the rows of x2 whose partial sums it left in s.part."""
+    rows = B * L
+    res_epi = ops.EPI_RES_F32 if s.x0.dtype == torch.float32 else ops.EPI_RES_BF16
+    m1, r1, m2, r2 = s.stats or (None,) * 4
+
+    def ln_linear(x, mm, mean, rstd, ln, lin, h, out, act=ops.ACT_NONE, out2=None):
+        """out = act(Linear(LayerNorm(x))) for the pair (ln, lin) of w; mm rows of x have their partial sums in s.part."""
+        ln_w, ln_b, lin_w, lin_b = w[ln + "_w"], w[ln + "_b"], w[lin + "_w"], w[lin + "_b"]
+        if not folded:
+            ops.layernorm(x, ln_w, ln_b, h, rows, D, mean=mean, rstd=rstd)
+            ops.gemm(h, lin_w, lin_b, out=out, epi=ops.EPI_BF16, act=act, cfg=cfg, out2=out2)
+            return
+        # (the row-statistics launch also writes the LayerNorm output of the GEMM's leftover rows into s.h_left - where all of
+        # them are rows whose statistics it computes from the rows themselves)
+        r = ops.fold_rows(x, out, out.shape[1])
+        k = dict(ln_w=ln_w, ln_b=ln_b, h_left=s.h_left, h_row0=r) if mm <= r else {}
+        ops.ln_row_stats(s.part, x, mm, mean, rstd, **k)
+        ops.gemm_lnfold(x, w[lin + "_f"], mean, rstd, out, lin_w, lin_b, ln_w, ln_b, s.h_left, act=act, out2=out2, cfg=cfg,
+                        h_ready=bool(k))
+
+    def linear_res(a, lin, out, res, leave_sums):
+        """out = res + Linear(a); returns the rows of out whose partial sums it left in s.part."""
+        if leave_sums:
+            return ops.gemm_res_rowstats(a, w[lin + "_w"], w[lin + "_b"], out, res, s.part, cfg=cfg)
+        ops.gemm(a, w[lin + "_w"], w[lin + "_b"], out=out, res=res, epi=res_epi, cfg=cfg)
+        return 0
+
+    ln_linear(s.x0, mm, m1, r1, "ln1", "in", s.h1, s.qkv)
+    if cls_only:
+        _cls_tail_forward(w, s, B, L, D, H, act, cfg)
+        return 0
+    ops.attn_fwd(s.q, s.k, s.v, s.a, lse=s.lse, causal=causal, qscale=(D // H) ** -0.5 * ops.LOG2E)
+    mm = linear_res(s.a, "out", s.x1, s.x0, folded)
+    # s.u = act'(fc output) under a *_DSAVE act: all the backward needs of the pre-activation, evaluated next to the activation
+    # from the same exp / rational pieces (+3 VALU per element here) - the dX GEMM's epilogue is then one multiplication,
+    # whichever activation (erf or QuickGELU) left the derivative
+    ln_linear(s.x1, mm, m2, r2, "ln2", "fc", s.h2, s.hid, act, s.u)
+    if not write_out:
+        return 0
+    return linear_res(s.hid, "proj", s.x2, s.x1, next_folded)
 
 
 def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None, quick_gelu=False, pooled_only=False):
-    """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:254-272, 364-371).
+    """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:364-371), each one block_forward in place.
     quick_gelu: the tower's MLP activation (TowerCfg / TextCfg.quick_gelu; `act_layer`, transformer.py:217-231).
-    fold (default: engine.LN_FOLD, bf16 stream only): the LayerNorms folded into the GEMMs either side of them - ln_1 / ln_2 are never
-    materialised, the in-projection and c_fc read the residual rows and apply (mean, rstd) in their epilogues, the
-    out-projection and c_proj leave the partial row sums of what they store (ops.gemm_lnfold / gemm_res_rowstats).
+    fold (default: engine.LN_FOLD, bf16 stream only): the LayerNorms folded into the GEMMs either side of them.
     pooled_only: the caller reads only the class-token rows b*L of the result (VitEngine.trunk) - the last block then runs on
     those rows alone where prune_last_ok() allows, and the other rows of ws.x are left as the block before it wrote them."""
-    dh = D // H
     prune = prune_last_ok(D, H, ws.x.dtype, L, pooled_only, causal)
     act = ops.mlp_act(quick_gelu)
-    res_epi = ops.EPI_RES_F32 if ws.x.dtype == torch.float32 else ops.EPI_RES_BF16
     if fold is None:
         fold = LN_FOLD
     can_fold = bool(fold) and ws.x.dtype == torch.bfloat16 and ws.part is not None
     # decided PER BLOCK: a block folds when it carries the folded operands (prep_block) - a fused training step removes them
     # from the blocks it trains (their LayerNorm parameters move every step) and those run the LayerNorm passes
-    folded = [can_fold and "in_f" in w for w in blocks]
+    folded = [can_fold and "in_f" in w for w in blocks] + [False]
     mm = 0                                            # rows of ws.x whose partial sums are in ws.part
-    r_in = r_fc = 0
-    if any(folded):
-        r_in, r_fc = ops.fold_rows(ws.x, ws.qkv, 3 * D), ops.fold_rows(ws.x, ws.hid, ws.hid.shape[1])
     for i, w in enumerate(blocks):
-        nxt = i + 1 < len(blocks) and folded[i + 1]   # the consumer of this block's output reads row statistics
-        pruned = prune and i + 1 == len(blocks)
-        if folded[i]:
-            # (the row-statistics launch also writes the LayerNorm output of the consuming GEMM's leftover rows into ws.h)
-            k_in = dict(ln_w=w["ln1_w"], ln_b=w["ln1_b"], h_left=ws.h, h_row0=r_in) if mm <= r_in else {}
-            ops.ln_row_stats(ws.part, ws.x, mm, ws.mean, ws.rstd, **k_in)
-            ops.gemm_lnfold(ws.x, w["in_f"], ws.mean, ws.rstd, ws.qkv, w["in_w"], w["in_b"], w["ln1_w"], w["ln1_b"], ws.h, cfg=cfg,
-                            h_ready=bool(k_in))
-            if pruned:
-                _pooled_block_tail(w, ws, B, L, D, H, act, cfg)
-                break
-            ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
-            mm = ops.gemm_res_rowstats(ws.a, w["out_w"], w["out_b"], ws.x, ws.x, ws.part, cfg=cfg)
-            k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=ws.h, h_row0=r_fc) if mm <= r_fc else {}
-            ops.ln_row_stats(ws.part, ws.x, mm, ws.mean, ws.rstd, **k_fc)
-            ops.gemm_lnfold(ws.x, w["fc_f"], ws.mean, ws.rstd, ws.hid, w["fc_w"], w["fc_b"], w["ln2_w"], w["ln2_b"], ws.h,
-                            act=act, cfg=cfg, h_ready=bool(k_fc))
-        else:
-            ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, B * L, D)
-            ops.gemm(ws.h, w["in_w"], w["in_b"], out=ws.qkv, epi=ops.EPI_BF16, cfg=cfg)
-            if pruned:
-                _pooled_block_tail(w, ws, B, L, D, H, act, cfg)
-                break
-            ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
-            ops.gemm(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=res_epi, cfg=cfg)
-            ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, B * L, D)
-            ops.gemm(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=act, cfg=cfg)
-        if nxt:
-            mm = ops.gemm_res_rowstats(ws.hid, w["proj_w"], w["proj_b"], ws.x, ws.x, ws.part, cfg=cfg)
-        else:
-            ops.gemm(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x, epi=res_epi, cfg=cfg)
-            mm = 0
+        mm = block_forward(w, ws.slots_folded if folded[i] else ws.slots, B, L, D, H, causal, act, cfg, folded[i], folded[i + 1],
+                           cls_only=prune and i + 1 == len(blocks), mm=mm)
 
 
 def _hi_lo(w: torch.Tensor, device):
@@ -391,19 +441,6 @@ class TextPlan:
     last_row: torch.Tensor    # int64 [B]: the pooled row of every caption
 
 
-def prep_block_f16(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
-    """One ResidualAttentionBlock with IEEE-half GEMM weights (`TextEngine(arith="f16")`): LayerNorm parameters and biases f32."""
-    hf = torch.float16
-    return {
-        "ln1_w": _dev(sd[p + "ln_1.weight"], device), "ln1_b": _dev(sd[p + "ln_1.bias"], device),
-        "in_w": _dev(sd[p + "attn.in_proj_weight"], device, hf), "in_b": _dev(sd[p + "attn.in_proj_bias"], device),
-        "out_w": _dev(sd[p + "attn.out_proj.weight"], device, hf), "out_b": _dev(sd[p + "attn.out_proj.bias"], device),
-        "ln2_w": _dev(sd[p + "ln_2.weight"], device), "ln2_b": _dev(sd[p + "ln_2.bias"], device),
-        "fc_w": _dev(sd[p + "mlp.c_fc.weight"], device, hf), "fc_b": _dev(sd[p + "mlp.c_fc.bias"], device),
-        "proj_w": _dev(sd[p + "mlp.c_proj.weight"], device, hf), "proj_b": _dev(sd[p + "mlp.c_proj.bias"], device),
-    }
-
-
 class _WorkspaceF16:
     """Activations of the fp16 text tower, sized for the dense run: B*L rows padded to whole 256-row tiles (vl_gemm_f16 is the
     persistent kernel only).  Rows beyond the ones a call owns - [B*L, Mp) of a dense call, [rows, roundup(rows, 256)) of a packed
@@ -465,37 +502,45 @@ class TextEngine:
         self.ln_final = (_dev(sd["ln_final.weight"], device), _dev(sd["ln_final.bias"], device))
         if arith == "f16":
             self.projT = _dev(sd["text_projection"].t(), device, torch.float16)       # [E, D]
-            self.blocks = [prep_block_f16(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+            self.blocks = [block_operands(sd, f"transformer.resblocks.{i}.", device, torch.float16) for i in range(cfg.layers)]
         elif self.wsplit:
             hi, lo = _hi_lo(sd["text_projection"].t(), device)
             self.projT = torch.cat([hi, lo], dim=1).contiguous()                      # [E, 2D]
             self.blocks = [prep_block_wsplit(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
         else:
             self.projT = _dev(sd["text_projection"].t(), device, torch.bfloat16)
-            self.blocks = [_prep_block_plain(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+            self.blocks = [block_operands(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
         self._ws = {}
 
-    def _encode_f16(self, text: torch.Tensor) -> torch.Tensor:
-        cfg = self.cfg
-        B, L = text.shape
-        D, H = cfg.width, cfg.heads
+    def _workspace_f16(self, B, L) -> _WorkspaceF16:
         key = ("f16", B, L)
         if key not in self._ws:
-            self._ws[key] = _WorkspaceF16(B, L, D, H, self.device)
-        ws = self._ws[key]
-        rows = ws.rows
-        ops.text_embed(text, self.tok, self.pos, ws.x[:rows])
+            self._ws[key] = _WorkspaceF16(B, L, self.cfg.width, self.cfg.heads, self.device)      # worst-case size: no allocation depends on the data
+        return self._ws[key]
+
+    def _blocks_f16(self, x, h, qkv, a, hid, rows, attn):
+        """x <- the blocks of the fp16 tower, on row views of a _WorkspaceF16 (whole 256-row tiles for the GEMMs): the
+        LayerNorms run on the first `rows` rows, attn() is the attention launch from qkv into a."""
+        D = self.cfg.width
+        act = ops.mlp_act(self.cfg.quick_gelu)
+        for w in self.blocks:
+            ops.layernorm(x, w["ln1_w"], w["ln1_b"], h, rows, D)
+            ops.gemm_f16(h, w["in_w"], w["in_b"], out=qkv)
+            attn()
+            ops.gemm_f16(a, w["out_w"], w["out_b"], out=x, res=x, epi=ops.EPI_RES_F32)
+            ops.layernorm(x, w["ln2_w"], w["ln2_b"], h, rows, D)
+            ops.gemm_f16(h, w["fc_w"], w["fc_b"], out=hid, act=act)
+            ops.gemm_f16(hid, w["proj_w"], w["proj_b"], out=x, res=x, epi=ops.EPI_RES_F32)
+
+    def _encode_f16(self, text: torch.Tensor) -> torch.Tensor:
+        B, L = text.shape
+        D, H = self.cfg.width, self.cfg.heads
+        ws = self._workspace_f16(B, L)
+        ops.text_embed(text, self.tok, self.pos, ws.x[:ws.rows])
         eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
         qs = (D // H) ** -0.5 * ops.LOG2E
-        act = ops.mlp_act(cfg.quick_gelu)
-        for w in self.blocks:
-            ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, rows, D)
-            ops.gemm_f16(ws.h, w["in_w"], w["in_b"], out=ws.qkv)
-            ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=True, qscale=qs)
-            ops.gemm_f16(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32)
-            ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, rows, D)
-            ops.gemm_f16(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=act)
-            ops.gemm_f16(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32)
+        self._blocks_f16(ws.x, ws.h, ws.qkv, ws.a, ws.hid, ws.rows,
+                         lambda: ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=True, qscale=qs))
         ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
         f = torch.zeros(ws.Bp, self.projT.shape[0], device=self.device, dtype=torch.float32)
         ops.gemm_f16(ws.pooled, self.projT, None, out=f, res=f, epi=ops.EPI_RES_F32)
@@ -550,10 +595,7 @@ class TextEngine:
         if (plan.B, plan.L) != (B, L) or not (B <= plan.rows <= B * L) or not (1 <= plan.max_len <= L):
             raise ValueError(f"encode_text: the plan was made for another batch ({plan.B} x {plan.L}, {plan.rows} rows, "
                              f"longest {plan.max_len}; text {B} x {L})")
-        key = ("f16", B, L)
-        if key not in self._ws:
-            self._ws[key] = _WorkspaceF16(B, L, D, H, self.device)       # worst-case size: no allocation depends on the data
-        ws = self._ws[key]
+        ws = self._workspace_f16(B, L)
         E = self.projT.shape[0]
         if ws.f is None:
             ws.f = torch.empty(ws.Bp, E, device=self.device, dtype=torch.float32)
@@ -566,15 +608,8 @@ class TextEngine:
         # (rows [rows, Mr) of x are zeroed here; of h and a they hold whatever an earlier call left: GEMM rows are independent)
         ops.text_embed_packed(text, plan.start, plan.lens, self.tok, self.pos, ws.x, rows, Mr)
         qs = (D // H) ** -0.5 * ops.LOG2E
-        act = ops.mlp_act(cfg.quick_gelu)
-        for w in self.blocks:
-            ops.layernorm(x, w["ln1_w"], w["ln1_b"], h, rows, D)
-            ops.gemm_f16(h, w["in_w"], w["in_b"], out=qkv)
-            ops.attn_fwd_varlen(qkv, plan.start, plan.lens, a, H, plan.max_len, qscale=qs)
-            ops.gemm_f16(a, w["out_w"], w["out_b"], out=x, res=x, epi=ops.EPI_RES_F32)
-            ops.layernorm(x, w["ln2_w"], w["ln2_b"], h, rows, D)
-            ops.gemm_f16(h, w["fc_w"], w["fc_b"], out=hid, act=act)
-            ops.gemm_f16(hid, w["proj_w"], w["proj_b"], out=x, res=x, epi=ops.EPI_RES_F32)
+        self._blocks_f16(x, h, qkv, a, hid, rows,
+                         lambda: ops.attn_fwd_varlen(qkv, plan.start, plan.lens, a, H, plan.max_len, qscale=qs))
         # the pooled rows: src = r * 0 + last_row[r]
         ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=plan.last_row, row_mul=0)
         ws.f.zero_()

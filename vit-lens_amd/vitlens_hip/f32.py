@@ -13,12 +13,12 @@ latent head dims are 32 or 64 (f32_lens_supported); anything else stays on the 1
 Reference ops: VisionTransformer.forward (open_clip/transformer.py:723-792), ResidualAttentionBlock (:254-272),
 TriCLIP.encode_text (open_clip/model.py:528-540), Perceiver.forward (open_clip/perceiver.py:289-328), PointTokenizer.forward
 (modal_3d/models/pointbert/point_encoder.py:350-362)."""
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from . import ops
-from .engine import LensCfg, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64
+from .engine import LensCfg, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64, block_operands
 
 
 def f32_head_dim_ok(dh: int) -> bool:
@@ -28,13 +28,6 @@ def f32_head_dim_ok(dh: int) -> bool:
 
 def f32_supported(width: int, heads: int) -> bool:
     return width % heads == 0 and f32_head_dim_ok(width // heads) and width % 4 == 0
-
-
-def _block(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
-    names = {"ln1_w": "ln_1.weight", "ln1_b": "ln_1.bias", "in_w": "attn.in_proj_weight", "in_b": "attn.in_proj_bias",
-             "out_w": "attn.out_proj.weight", "out_b": "attn.out_proj.bias", "ln2_w": "ln_2.weight", "ln2_b": "ln_2.bias",
-             "fc_w": "mlp.c_fc.weight", "fc_b": "mlp.c_fc.bias", "proj_w": "mlp.c_proj.weight", "proj_b": "mlp.c_proj.bias"}
-    return {k: _dev(sd[p + v], device) for k, v in names.items()}
 
 
 class _Ws:
@@ -68,9 +61,6 @@ def conv_as_gemm_f32(w: torch.Tensor, device="cpu") -> torch.Tensor:
     out = torch.zeros(O, _pad64(K), dtype=torch.float32, device=device)
     out[:, :K] = w.detach().reshape(O, K).float().to(device)
     return out
-
-
-_conv_as_gemm_f32 = conv_as_gemm_f32
 
 
 def fold_bn_f32(w, b, gamma, beta, running_mean, running_var, eps=1e-5):
@@ -132,15 +122,15 @@ class VitEngineF32:
         ln = lambda n: (_dev(sd[prefix + n + ".weight"], device), _dev(sd[prefix + n + ".bias"], device))
         self.ln_pre, self.ln_post = ln("ln_pre"), ln("ln_post")
         self.projT = _dev(sd[prefix + "proj"].t(), device) if prefix + "proj" in sd else None       # [E, D]
-        self.blocks = [_block(sd, f"{prefix}transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+        self.blocks = [block_operands(sd, f"{prefix}transformer.resblocks.{i}.", device, torch.float32) for i in range(cfg.layers)]
         self.pos2 = None
         self.conv_w = None
         if depth:
             a = prefix + "visual_adapter."
-            self.conv_w = _conv_as_gemm_f32(sd[a + "conv1.weight"], device)
+            self.conv_w = conv_as_gemm_f32(sd[a + "conv1.weight"], device)
             self.pos2 = _dev(sd[a + "pos_emb"].detach().float() * (0.0 if disable_adapter_pos else 1.0), device)
         elif prefix + "conv1.weight" in sd:
-            self.conv_w = _conv_as_gemm_f32(sd[prefix + "conv1.weight"], device)
+            self.conv_w = conv_as_gemm_f32(sd[prefix + "conv1.weight"], device)
         self._ws = {}
 
     def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos: bool = True) -> torch.Tensor:
@@ -184,7 +174,7 @@ class TextEngineF32:
         self.pos = _dev(sd["positional_embedding"], device)
         self.ln_final = (_dev(sd["ln_final.weight"], device), _dev(sd["ln_final.bias"], device))
         self.projT = _dev(sd["text_projection"].t(), device)                                          # [E, D]
-        self.blocks = [_block(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+        self.blocks = [block_operands(sd, f"transformer.resblocks.{i}.", device, torch.float32) for i in range(cfg.layers)]
         self.arith = "f32"
         self._ws = {}
 

@@ -69,9 +69,8 @@ class _Saved:
         else:
             self.h1 = {l: bf(T, D) for l in keep_blocks}; self.h2 = {l: bf(T, D) for l in keep_blocks}
             self.hidk = {l: bf(T, hidden) for l in keep_blocks}
-        # LayerNorm folding (frozen blocks, bf16 stream): partial row sums left by the GEMM that wrote `part_of`
+        # LayerNorm folding (frozen blocks, bf16 stream): partial row sums between a GEMM and the row statistics behind it
         self.part = f32(T * (D // 64) * 2) if (D % 64 == 0 and res_dtype == BF) else None
-        self.part_of, self.part_rows = None, 0
         self.xpre = f32(T, D); self.pre_stats = [f32(T), f32(T)]
         self.post_stats = [f32(B), f32(B)]
         self.pooled = bf(B, D)
@@ -88,6 +87,12 @@ class _Saved:
         self.a1 = bf(B, D); self.lse1 = f32(B, H); self.h2c = bf(B, D); self.stats2c = [f32(B), f32(B)]
         self.hid1 = bf(B, hidden); self.u1 = bf(B, hidden)
         self.dxc = bf(B, D); self.du1 = bf(B, hidden); self.dhc = bf(B, D); self.dO1 = bf(B, D)
+        # what engine.block_forward reads and writes for layer l: the shared temporaries, or the kept copies of a trainable block
+        self.slots = [_engine.BlockSlots(
+            x0=self.X[2 * l], x1=self.X[2 * l + 1], x2=self.X[2 * l + 2], h1=self.h1.get(l, self.h), h2=self.h2.get(l, self.h),
+            h_left=self.h, qkv=self.qkv[l], q=self.q[l], k=self.k[l], v=self.v[l], a=self.a[l], hid=self.hidk.get(l, self.hid),
+            part=self.part, stats=tuple(self.stats[l]), lse=self.lse[l], u=self.u[l], a1=self.a1, h2c=self.h2c, hid1=self.hid1,
+            lse1=self.lse1, stats2c=tuple(self.stats2c), u1=self.u1) for l in range(layers)]
 
 
 def prunes_last_block(layers, train_blocks, checkpoint, causal, res_dtype, D, H, L) -> bool:
@@ -163,10 +168,8 @@ class TowerTrainer:
         if keep is not None and (tuple(inv.shape) != (B, T) or keep.shape[0] != B or not 1 <= keep.shape[1] <= T):
             raise ValueError(f"TowerTrainer.forward: keep [B,K] / inv [B,T] do not fit B={B}, T={T}: {tuple(keep.shape)}, {tuple(inv.shape)}")
         L = T + 1 if keep is None else keep.shape[1] + 1
-        dh = D // H
         S = self.saved(B, L)
         cfg = e.gemm_cfg
-        res_epi = ops.EPI_RES_F32 if e.res_dtype == torch.float32 else ops.EPI_RES_BF16
         if keep is None:
             ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
                                 xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
@@ -176,8 +179,9 @@ class TowerTrainer:
         self._drop = None if keep is None else (T, inv)
         # only the class rows of the last block's output are read (ln_post below, and its backward)
         self._pruned = prunes_last_block(self.layers, self.train_blocks, self.checkpoint, self.causal, e.res_dtype, D, H, L)
+        mm = 0                                      # rows of X[2l] whose partial sums are in S.part
         for l in range(self.layers):
-            self._block_forward(S, l, B, L, cls_only=self._pruned and l == self.layers - 1)
+            mm = self._block_forward(S, l, B, L, cls_only=self._pruned and l == self.layers - 1, mm=mm)
         xl = S.X[2 * self.layers]
         ops.layernorm(xl, e.ln_post[0], e.ln_post[1], S.pooled, B, D, x_row_stride=L * D,
                       mean=S.post_stats[0], rstd=S.post_stats[1])
@@ -188,76 +192,20 @@ class TowerTrainer:
         self.ctx = (B, L, tokens, pos2 is not None)
         return feat
 
-    def _cls_tail_forward(self, S, l, B, L):
-        """The pruned last block behind its in-projection: single-query attention, out_proj + residual, ln_2, c_fc + activation
-        (act' saved) and c_proj + residual on the B class rows b*L of X[2l] / X[2l+1] / X[2l+2] (row-strided views, no copy);
-        the other rows of X[2l+1], X[2l+2] and the big a / hid / u slots of this layer are neither written nor read."""
-        e, D = self.eng, self.D
-        w, cfg = e.blocks[l], e.gemm_cfg
-        x0c, x1c, x2c = (_engine.cls_rows(S.X[i], B, L) for i in (2 * l, 2 * l + 1, 2 * l + 2))
-        ops.attn_fwd_q1(S.q[l], S.k[l], S.v[l], S.a1, lse=S.lse1, qrow=0, qscale=(D // self.H) ** -0.5 * ops.LOG2E)
-        ops.gemm(S.a1, w["out_w"], w["out_b"], out=x1c, res=x0c, epi=ops.EPI_RES_BF16, cfg=cfg)
-        ops.layernorm(x1c, w["ln2_w"], w["ln2_b"], S.h2c, B, D, x_row_stride=L * D, mean=S.stats2c[0], rstd=S.stats2c[1])
-        ops.gemm(S.h2c, w["fc_w"], w["fc_b"], out=S.hid1, epi=ops.EPI_BF16, act=self.act_dsave, cfg=cfg, out2=S.u1)
-        ops.gemm(S.hid1, w["proj_w"], w["proj_b"], out=x2c, res=x1c, epi=ops.EPI_RES_BF16, cfg=cfg)
-        S.part_of, S.part_rows = None, 0
-
-    def _block_forward(self, S, l, B, L, write_out=True, cls_only=False):
-        """One ResidualAttentionBlock forward (transformer.py:254-272) into the saved-activation slots of layer l.  With
-        write_out=False (the recompute in front of a block's backward) the block output X[2l+2] - already there from the
-        forward pass and not needed by the backward of block l - is not recomputed: the last GEMM is skipped.
-        cls_only (the last block of a class-token-pooled tower, prunes_last_block): dense up to the in-projection, then
-        _cls_tail_forward."""
-        e, D, H = self.eng, self.D, self.H
-        dh = D // H
-        cfg = e.gemm_cfg
-        res_epi = ops.EPI_RES_F32 if e.res_dtype == torch.float32 else ops.EPI_RES_BF16
-        w = e.blocks[l]
-        m1, r1, m2, r2 = S.stats[l]
-        h1, h2, hid = S.h1.get(l, S.h), S.h2.get(l, S.h), S.hidk.get(l, S.hid)
-        # LayerNorm folding (engine.run_blocks; round 4): a FROZEN block never materialises ln_1 / ln_2 - its backward needs
-        # only (mean, rstd), which ln_row_stats leaves in S.stats; a trainable block keeps its LayerNorm outputs (the operands
-        # of its weight gradients).  Either kind leaves the partial row sums of its output when the next block is folded.
-        fold_ok = _engine.LN_FOLD and S.part is not None
-        folded = fold_ok and "in_f" in w and l not in self.train_blocks
-        next_folded = (fold_ok and l + 1 < self.layers and "in_f" in e.blocks[l + 1] and (l + 1) not in self.train_blocks)
-        if folded:
-            x0, x1 = S.X[2 * l], S.X[2 * l + 1]
-            mm0 = S.part_rows if S.part_of is x0 else 0      # (a recompute in front of the backward finds none: from the rows)
-            S.part_of = None
-            # (the row-statistics launch also leaves the LayerNorm output of the consuming GEMM's leftover rows in S.h)
-            r_in, r_fc = ops.fold_rows(x0, S.qkv[l], 3 * D), ops.fold_rows(x1, hid, hid.shape[1])
-            k_in = dict(ln_w=w["ln1_w"], ln_b=w["ln1_b"], h_left=S.h, h_row0=r_in) if mm0 <= r_in else {}
-            ops.ln_row_stats(S.part, x0, mm0, m1, r1, **k_in)
-            ops.gemm_lnfold(x0, w["in_f"], m1, r1, S.qkv[l], w["in_w"], w["in_b"], w["ln1_w"], w["ln1_b"], S.h, cfg=cfg,
-                            h_ready=bool(k_in))
-            if cls_only:
-                return self._cls_tail_forward(S, l, B, L)
-            ops.attn_fwd(S.q[l], S.k[l], S.v[l], S.a[l], lse=S.lse[l], causal=self.causal, qscale=dh ** -0.5 * ops.LOG2E)
-            mm = ops.gemm_res_rowstats(S.a[l], w["out_w"], w["out_b"], x1, x0, S.part, cfg=cfg)
-            k_fc = dict(ln_w=w["ln2_w"], ln_b=w["ln2_b"], h_left=S.h, h_row0=r_fc) if mm <= r_fc else {}
-            ops.ln_row_stats(S.part, x1, mm, m2, r2, **k_fc)
-            ops.gemm_lnfold(x1, w["fc_f"], m2, r2, hid, w["fc_w"], w["fc_b"], w["ln2_w"], w["ln2_b"], S.h,
-                            act=self.act_dsave, out2=S.u[l], cfg=cfg, h_ready=bool(k_fc))
-        else:
-            ops.layernorm(S.X[2 * l], w["ln1_w"], w["ln1_b"], h1, B * L, D, mean=m1, rstd=r1)
-            ops.gemm(h1, w["in_w"], w["in_b"], out=S.qkv[l], epi=ops.EPI_BF16, cfg=cfg)
-            if cls_only:
-                return self._cls_tail_forward(S, l, B, L)
-            ops.attn_fwd(S.q[l], S.k[l], S.v[l], S.a[l], lse=S.lse[l], causal=self.causal, qscale=dh ** -0.5 * ops.LOG2E)
-            ops.gemm(S.a[l], w["out_w"], w["out_b"], out=S.X[2 * l + 1], res=S.X[2 * l], epi=res_epi, cfg=cfg)
-            ops.layernorm(S.X[2 * l + 1], w["ln2_w"], w["ln2_b"], h2, B * L, D, mean=m2, rstd=r2)
-            # S.u[l] = gelu'(fc output): all the backward needs of the pre-activation, evaluated next to gelu() from the same
-            # exp / rational pieces (+3 VALU per element here) - the dX GEMM's epilogue is then one multiplication, whichever
-            # activation (erf or QuickGELU) left the derivative
-            ops.gemm(h2, w["fc_w"], w["fc_b"], out=hid, epi=ops.EPI_BF16, act=self.act_dsave, cfg=cfg, out2=S.u[l])
-        if write_out:
-            S.part_of, S.part_rows = None, 0
-            if next_folded:
-                S.part_rows = ops.gemm_res_rowstats(hid, w["proj_w"], w["proj_b"], S.X[2 * l + 2], S.X[2 * l + 1], S.part, cfg=cfg)
-                S.part_of = S.X[2 * l + 2]
-            else:
-                ops.gemm(hid, w["proj_w"], w["proj_b"], out=S.X[2 * l + 2], res=S.X[2 * l + 1], epi=res_epi, cfg=cfg)
+    def _block_forward(self, S, l, B, L, write_out=True, cls_only=False, mm=0):
+        """engine.block_forward of layer l into its saved-activation slots; returns what that returns (the rows of X[2l+2] whose
+        partial sums are in S.part, for the next block's `mm`).  write_out=False: the recompute in front of a block's backward
+        (X[2l+2] is already there from the forward pass); cls_only: the last block of a class-token-pooled tower
+        (prunes_last_block)."""
+        e = self.eng
+        # LayerNorm folding (round 4): a FROZEN block never materialises ln_1 / ln_2 - its backward needs only (mean, rstd),
+        # which ln_row_stats leaves in S.stats; a trainable block keeps its LayerNorm outputs (the operands of its weight
+        # gradients).  Either kind leaves the partial row sums of its output when the next block is folded.
+        def folds(k):
+            return bool(_engine.LN_FOLD and S.part is not None and k < self.layers and "in_f" in e.blocks[k]
+                        and k not in self.train_blocks)
+        return _engine.block_forward(e.blocks[l], S.slots[l], B, L, self.D, self.H, self.causal, self.act_dsave, e.gemm_cfg,
+                                     folds(l), folds(l + 1), cls_only=cls_only, write_out=write_out, mm=mm)
 
     # ------------------------------------------------------------------------------------------ backward
     def _dw(self, name, dy, x, rows, bias_name=None):
@@ -332,7 +280,7 @@ class TowerTrainer:
         return dxpre.view(B, L, D)[:, 1:, :].reshape(B * T, D)
 
     def _cls_block_backward(self, S, l, B, L):
-        """Backward of the pruned last block (_cls_tail_forward): S.dxc [B, D] = the gradient of the class rows of its output
+        """Backward of the pruned last block (engine._cls_tail_forward): S.dxc [B, D] = the gradient of the class rows of its output
         (every other row's is zero) -> S.dx = the gradient of ALL rows of its input.  The MLP branch, ln_2, out_proj and the
         attention run on B rows; dK / dV, the dX GEMM of the in-projection and the ln_1 backward are dense.  Additions in the
         order of the full path: dLN_2 + dres on the class rows, then dLN_1 + that on the class rows, dLN_1 alone elsewhere."""
@@ -508,8 +456,9 @@ class TextTowerTrainer(TowerTrainer):
         S = self.saved(B, L)
         text = text.to(e.device).contiguous()
         ops.text_embed(text, e.tok, e.pos, S.X[0])
+        mm = 0
         for l in range(self.layers):
-            self._block_forward(S, l, B, L)
+            mm = self._block_forward(S, l, B, L, mm=mm)
         eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
         ops.layernorm(S.X[2 * self.layers], e.ln_post[0], e.ln_post[1], S.pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L,
                       mean=S.post_stats[0], rstd=S.post_stats[1])
