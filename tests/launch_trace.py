@@ -82,3 +82,25 @@ def normalised(trace):
                 row.append(a)
         out.append((name, tuple(row)))
     return out
+
+
+# what a trainer's launch may differ in from the engine's: the optional outputs it saves for the backward (argument indices of
+# mean / rstd, lse, out2) and the activation code (the same activation with its derivative saved)
+OPTIONAL_OUTPUTS = {"vl_layernorm_fwd": (10, 11), "vl_attn_fwd_bf16": (5,), "vl_attn_fwd_q1": (6,), "vl_gemm_bf16_ex": (5,),
+                    "vl_gemm_lnfold_bf16": (7,)}
+ACT_ARGUMENT = {"vl_gemm_bf16_ex": 14, "vl_gemm_lnfold_bf16": 14}
+
+
+def shape_of(call):
+    """A launch without its buffers: the symbol, every scalar, and of a pointer only whether it is there and its offset."""
+    from vitlens_hip import ops
+    plain_act = {ops.ACT_GELU_DSAVE: ops.ACT_GELU, ops.ACT_QGELU_DSAVE: ops.ACT_QGELU}
+    name, args = call
+    out = [name]
+    for i, a in enumerate(args):
+        if i in OPTIONAL_OUTPUTS.get(name, ()):
+            continue
+        if i == ACT_ARGUMENT.get(name):
+            a = plain_act.get(a, a)
+        out.append(("ptr", a.offset) if isinstance(a, Ptr) else (tuple(a) if hasattr(a, "_length_") else a))
+    return tuple(out)

@@ -5,7 +5,7 @@ ViT-L-width tower at L = 257 are written out below.  No GPU test reaches the B =
 import pytest
 import torch
 
-from launch_trace import Ptr, recording, symbols
+from launch_trace import recording, shape_of as _shape_of, symbols
 
 D, H, L, LAYERS = 1024, 16, 257, 3
 
@@ -29,27 +29,6 @@ FULL_50 = FULL_64[:8] + ["vl_layernorm_fwd"] + FULL_64[8:]
 PRUNED = ["vl_ln_row_stats", "vl_gemm_lnfold_bf16", "vl_gemm_bf16_ex",
           "vl_attn_fwd_q1", "vl_gemm_bf16_ex", "vl_layernorm_fwd", "vl_gemm_bf16_ex", "vl_gemm_bf16_ex"]
 HEAD = ["vl_layernorm_fwd", "vl_gemm_bf16_ex"]                               # ln_post of the class rows, the projection
-
-# what a trainer's launch may differ in from the engine's: the optional outputs it saves for the backward (argument indices of
-# mean / rstd, lse, out2) and the activation code (the same activation with its derivative saved)
-OPTIONAL_OUTPUTS = {"vl_layernorm_fwd": (10, 11), "vl_attn_fwd_bf16": (5,), "vl_attn_fwd_q1": (6,), "vl_gemm_bf16_ex": (5,),
-                    "vl_gemm_lnfold_bf16": (7,)}
-ACT_ARGUMENT = {"vl_gemm_bf16_ex": 14, "vl_gemm_lnfold_bf16": 14}
-
-
-def _shape_of(call):
-    """A launch without its buffers: the symbol, every scalar, and of a pointer only whether it is there and its offset."""
-    from vitlens_hip import ops
-    plain_act = {ops.ACT_GELU_DSAVE: ops.ACT_GELU, ops.ACT_QGELU_DSAVE: ops.ACT_QGELU}
-    name, args = call
-    out = [name]
-    for i, a in enumerate(args):
-        if i in OPTIONAL_OUTPUTS.get(name, ()):
-            continue
-        if i == ACT_ARGUMENT.get(name):
-            a = plain_act.get(a, a)
-        out.append(("ptr", a.offset) if isinstance(a, Ptr) else (tuple(a) if hasattr(a, "_length_") else a))
-    return tuple(out)
 
 
 @pytest.fixture(scope="module")

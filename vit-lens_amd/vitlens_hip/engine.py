@@ -701,106 +701,226 @@ def _interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     return wi, bi
 
 
-def prep_lens_attn(sd, p, device, packed_self: bool):
-    bf = torch.bfloat16
-    d = {"to_out_w": _dev(sd[p + "to_out.weight"], device, bf), "to_out_b": _dev(sd[p + "to_out.bias"], device)}
-    if packed_self:
-        d["qkv_w"] = _dev(torch.cat([sd[p + "to_q.weight"], sd[p + "to_kv.weight"]], 0), device, bf)
-    else:
-        d["q_w"] = _dev(sd[p + "to_q.weight"], device, bf)
-        d["kv_w"] = _dev(sd[p + "to_kv.weight"], device, bf)
-    return d
+def perceiver_operands(sd: Dict[str, torch.Tensor], prefix: str, cfg: LensCfg, device, wdtype=torch.bfloat16) -> list:
+    """Device copies of the Perceiver's layers: one dict per layer (cross attention "x_*", its FeedForward "x_ff*", the latent
+    "selfs"), GEMM weights in `wdtype` (bf16; f32 for the fp32 engine), LayerNorm parameters and biases f32.  to_q / to_kv of a
+    latent self-attention are one packed "qkv_w"; the GEGLU's first Linear is row-interleaved (_interleave_geglu)."""
+    dv = lambda k, dt=torch.float32: _dev(sd[k], device, dt)
+    ln = lambda q: (dv(q + ".weight"), dv(q + ".bias"))
+
+    def attn(p, packed):
+        d = {"to_out_w": dv(p + "to_out.weight", wdtype), "to_out_b": dv(p + "to_out.bias")}
+        if packed:
+            d["qkv_w"] = _dev(torch.cat([sd[p + "to_q.weight"], sd[p + "to_kv.weight"]], 0), device, wdtype)
+        else:
+            d["q_w"], d["kv_w"] = dv(p + "to_q.weight", wdtype), dv(p + "to_kv.weight", wdtype)
+        return d
+
+    def ff(p):
+        w0, b0 = _interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
+        return {"w0": _dev(w0, device, wdtype), "b0": _dev(b0, device), "w2": dv(p + "net.2.weight", wdtype), "b2": dv(p + "net.2.bias")}
+    layers = []
+    for i in range(cfg.depth):
+        if cfg.weight_tie_layers and i >= 2:
+            # perceiver.py:249-254 (`cache_fn`): layers 1 .. depth-1 ARE one set of modules; the state_dict repeats their
+            # tensors under every layer index.  Sharing the objects here makes an update of layer 1 an update of all.
+            layers.append(layers[1])
+            continue
+        q = f"{prefix}layers.{i}."
+        lay = {"x_norm": ln(q + "0.norm"), "x_norm_ctx": ln(q + "0.norm_context"), "x_attn": attn(q + "0.fn.", False),
+               "x_ff_norm": ln(q + "1.norm"), "x_ff": ff(q + "1.fn."), "selfs": []}
+        for j in range(cfg.self_per_cross):
+            r = f"{q}2.{j}."
+            lay["selfs"].append({"norm": ln(r + "0.norm"), "attn": attn(r + "0.fn.", True), "ff_norm": ln(r + "1.norm"),
+                                 "ff": ff(r + "1.fn.")})
+        layers.append(lay)
+    return layers
 
 
-def prep_lens_ff(sd, p, device):
-    w0, b0 = _interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
-    return {"w0": _dev(w0, device, torch.bfloat16), "b0": _dev(b0, device),
-            "w2": _dev(sd[p + "net.2.weight"], device, torch.bfloat16), "b2": _dev(sd[p + "net.2.bias"], device)}
+class Bf16Arith:
+    """The Perceiver's matrix products on bf16 operands with fp32 accumulation, on an fp32 residual stream (f32.F32Arith: the
+    same three in fp32)."""
+    dtype = torch.bfloat16
+
+    def __init__(self, gemm_cfg=-1):
+        self.cfg = gemm_cfg
+
+    def linear(self, a, w, b, out, res=None):
+        ops.gemm(a, w, b, out=out, res=res, epi=ops.EPI_BF16 if res is None else ops.EPI_RES_F32, cfg=self.cfg)
+
+    def geglu(self, a, w, b, out, out2=None):
+        ops.gemm(a, w, b, out=out, epi=ops.EPI_GEGLU, cfg=self.cfg, out2=out2)
+
+    def attn(self, q, k, v, out, lse, dh):
+        ops.attn_fwd(q, k, v, out, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
+
+
+@dataclass
+class LensAttnSlots:
+    """Where perceiver_forward reads and writes one attention sub-layer x1 = x0 + to_out(attn(...)).  Cross attention: q2 and
+    the context's kv2 apart, cn = LN_ctx(data); latent self-attention: q2 is the packed [q|k|v], kv2 and cn are None.  An
+    optional output that is None is not written (an engine's)."""
+    x0: torch.Tensor
+    x1: torch.Tensor
+    hn: torch.Tensor                           # LN(x0)
+    q2: torch.Tensor                           # token-major projection outputs and their views by heads (ops.heads_view)
+    kv2: Optional[torch.Tensor]
+    q: torch.Tensor
+    k: torch.Tensor
+    v: torch.Tensor
+    a: torch.Tensor                            # attention output
+    cn: Optional[torch.Tensor] = None
+    stats: Optional[tuple] = None              # (mean, rstd) of LN(x0), of LN_ctx(data)
+    cstats: Optional[tuple] = None
+    lse: Optional[torch.Tensor] = None
+    av: Optional[torch.Tensor] = None          # a trainer's backward: a by heads, the out-projection's input gradient, delta
+    dOm: Optional[torch.Tensor] = None
+    dO: Optional[torch.Tensor] = None
+    delta: Optional[torch.Tensor] = None
+
+
+@dataclass
+class LensFFSlots:
+    """One GEGLU FeedForward sub-layer x1 = x0 + W2 geglu(W0 LN(x0) + b0) + b2."""
+    x0: torch.Tensor
+    x1: torch.Tensor
+    hn: torch.Tensor                           # LN(x0)
+    hid: torch.Tensor                          # geglu(...)
+    stats: Optional[tuple] = None
+    h: Optional[torch.Tensor] = None           # the GEGLU's pre-activation
+
+
+def perceiver_residuals(c: LensCfg) -> int:
+    """How many residual snapshots a Perceiver has: one in front of the first sub-layer and one behind every sub-layer."""
+    return c.depth * (2 + 2 * c.self_per_cross) + 1
+
+
+def perceiver_slots(c: LensCfg, B, Tc, device, dtype, X=None):
+    """-> (X, layers): the residual snapshots in front of and behind every sub-layer and, per layer, the slots of its
+    sub-layers under the operand table's keys ("x_attn", "x_ff", "selfs"[j]["attn" | "ff"]).  An engine's workspace (X None):
+    ONE in-place fp32 stream and one set of `dtype` temporaries shared by all sub-layers, nothing optional.  A trainer's
+    (X: its perceiver_residuals(c) snapshots): saved operands, statistics and lse per sub-layer, and the backward's
+    per-attention buffers - allocated in the order the trainer's state has always had."""
+    n, D, C, f32 = c.num_latents, c.latent_dim, c.input_chan, torch.float32
+    R, save = B * n, X is not None
+    new = lambda *s, dt=dtype: torch.empty(*s, device=device, dtype=dt)
+    if not save:
+        X = [new(R, D, dt=f32)] * perceiver_residuals(c)
+    shared = {}
+
+    def tmp(name, *s):
+        """A trainer's buffer: a new one per sub-layer.  An engine's temporary: one per name, shared by the sub-layers."""
+        if save:
+            return new(*s)
+        if name not in shared:
+            shared[name] = new(*s)
+        return shared[name]
+    stats = lambda rows: (new(rows, dt=f32), new(rows, dt=f32)) if save else None
+    xi = iter(range(len(X)))
+
+    def attn(H, dh, cross):
+        i, inner = next(xi), H * dh
+        st, cst = stats(R), stats(B * Tc) if cross else None
+        if cross:
+            hn, cn, q2, kv2 = tmp("h", R, D), tmp("ctx", B * Tc, C), tmp("xq2", R, inner), tmp("xkv2", B * Tc, 2 * inner)
+            q, k, v = ops.heads_view(q2, B, n, H, dh), ops.heads_view(kv2, B, Tc, H, dh), ops.heads_view(kv2, B, Tc, H, dh, inner)
+        else:
+            q2, kv2, cn = tmp("sqkv2", R, 3 * inner), None, None
+            q, k, v = (ops.heads_view(q2, B, n, H, dh, j * inner) for j in range(3))
+        a = tmp("xa" if cross else "sa", R, inner)
+        lse, dOm, delta = (new(B, H, n, dt=f32), new(R, inner), new(B, H, n, dt=f32)) if save else (None, None, None)
+        if not cross:
+            hn = tmp("h", R, D)
+        by_heads = lambda m: ops.heads_view(m, B, n, H, dh) if save else None
+        return LensAttnSlots(x0=X[i], x1=X[i + 1], hn=hn, q2=q2, kv2=kv2, q=q, k=k, v=v, a=a, cn=cn, stats=st, cstats=cst, lse=lse,
+                             av=by_heads(a), dOm=dOm, dO=by_heads(dOm), delta=delta)
+
+    def ff():
+        i = next(xi)
+        st, h = stats(R), new(R, 8 * D) if save else None
+        return LensFFSlots(x0=X[i], x1=X[i + 1], hn=tmp("h", R, D), hid=tmp("hid", R, 4 * D), stats=st, h=h)
+    layers = [{"x_attn": attn(c.cross_heads, c.cross_dim_head, True), "x_ff": ff(),
+               "selfs": [{"attn": attn(c.latent_heads, c.latent_dim_head, False), "ff": ff()} for _ in range(c.self_per_cross)]}
+              for _ in range(c.depth)]
+    return X, layers
+
+
+def perceiver_forward(layers, slots, data, B, c: LensCfg, ar):
+    """Perceiver.forward(return_embeddings=True) behind the latents' broadcast (open_clip/perceiver.py:289-328,
+    fourier_encode_data=False) with the operands `layers` (perceiver_operands) on the buffers `slots` (perceiver_slots) in the
+    arithmetic `ar` (linear / geglu / attn: Bf16Arith, f32.F32Arith).  Per layer: cross attention of the latents over
+    data [B*Tc, C], FeedForward, then self_per_cross x (latent self-attention, FeedForward), each with its residual.  The one
+    forward of the engines and the trainer: it branches on what it is given, never on who calls."""
+    rows, D = B * c.num_latents, c.latent_dim
+
+    def attn(w, norm, s, dh, norm_ctx=None):
+        if ("qkv_w" in w) != (s.kv2 is None):
+            raise ValueError("perceiver_forward: packed (self) operands need packed slots, cross operands q2 / kv2 slots")
+        m, r = s.stats or (None, None)
+        ops.layernorm(s.x0, norm[0], norm[1], s.hn, rows, D, mean=m, rstd=r)
+        if s.kv2 is None:                      # latent self-attention: bias-free to_q / to_kv as one packed projection
+            ar.linear(s.hn, w["qkv_w"], None, s.q2)
+        else:
+            m, r = s.cstats or (None, None)
+            ops.layernorm(data, norm_ctx[0], norm_ctx[1], s.cn, data.shape[0], c.input_chan, mean=m, rstd=r)
+            ar.linear(s.hn, w["q_w"], None, s.q2)
+            ar.linear(s.cn, w["kv_w"], None, s.kv2)
+        ar.attn(s.q, s.k, s.v, s.a, s.lse, dh)
+        ar.linear(s.a, w["to_out_w"], w["to_out_b"], s.x1, res=s.x0)
+
+    def ff(w, norm, s):
+        m, r = s.stats or (None, None)
+        ops.layernorm(s.x0, norm[0], norm[1], s.hn, rows, D, mean=m, rstd=r)
+        ar.geglu(s.hn, w["w0"], w["b0"], s.hid, s.h)
+        ar.linear(s.hid, w["w2"], w["b2"], s.x1, res=s.x0)
+
+    for lay, S in zip(layers, slots):
+        attn(lay["x_attn"], lay["x_norm"], S["x_attn"], c.cross_dim_head, lay["x_norm_ctx"])
+        ff(lay["x_ff"], lay["x_ff_norm"], S["x_ff"])
+        for sl, T in zip(lay["selfs"], S["selfs"]):
+            attn(sl["attn"], sl["norm"], T["attn"], c.latent_dim_head)
+            ff(sl["ff"], sl["ff_norm"], T["ff"])
 
 
 class PerceiverEngine:
     """Perceiver.forward(return_embeddings=True) (open_clip/perceiver.py:289-328), fourier_encode_data=False."""
 
-    def __init__(self, sd, prefix: str, cfg: LensCfg, device, gemm_cfg=-1):
+    def __init__(self, sd, prefix: str, cfg: LensCfg, device, gemm_cfg=-1, arith=None):
         self.cfg, self.device, self.gemm_cfg = cfg, torch.device(device), gemm_cfg
+        self.arith = Bf16Arith(gemm_cfg) if arith is None else arith
         self.latents = _dev(sd[prefix + "latents"], device)
-        ln = lambda q: (_dev(sd[q + ".weight"], device), _dev(sd[q + ".bias"], device))
-        self.layers = []
-        for i in range(cfg.depth):
-            if cfg.weight_tie_layers and i >= 2:
-                # perceiver.py:249-254 (`cache_fn`): layers 1 .. depth-1 ARE one set of modules; the state_dict repeats their
-                # tensors under every layer index.  Sharing the objects here makes an update of layer 1 an update of all.
-                self.layers.append(self.layers[1])
-                continue
-            q = f"{prefix}layers.{i}."
-            lay = {"x_norm": ln(q + "0.norm"), "x_norm_ctx": ln(q + "0.norm_context"),
-                   "x_attn": prep_lens_attn(sd, q + "0.fn.", device, False),
-                   "x_ff_norm": ln(q + "1.norm"), "x_ff": prep_lens_ff(sd, q + "1.fn.", device), "selfs": []}
-            for j in range(cfg.self_per_cross):
-                r = f"{q}2.{j}."
-                lay["selfs"].append({"norm": ln(r + "0.norm"), "attn": prep_lens_attn(sd, r + "0.fn.", device, True),
-                                     "ff_norm": ln(r + "1.norm"), "ff": prep_lens_ff(sd, r + "1.fn.", device)})
-            self.layers.append(lay)
+        self.layers = perceiver_operands(sd, prefix, cfg, device, self.arith.dtype)
         self._ws = {}
 
     def update_params(self, sd, prefix: str):
         """All Perceiver operands re-derived from `sd`, in place (the Perceiver is trainable as a whole in every recipe)."""
-        fresh = PerceiverEngine(sd, prefix, self.cfg, self.device, self.gemm_cfg)
-        self.latents.copy_(fresh.latents)
-        copy_tree(self.layers, fresh.layers)
-
-    def _workspace(self, B, Tc):
-        key = (B, Tc)
-        if key in self._ws:
-            return self._ws[key]
-        c, dev, bf = self.cfg, self.device, torch.bfloat16
-        n, D = c.num_latents, c.latent_dim
-        f = lambda *s, dt=bf: torch.empty(*s, device=dev, dtype=dt)
-        ws = {
-            "x": f(B * n, D, dt=torch.float32), "h": f(B * n, D), "ctx": f(B * Tc, c.input_chan),
-            "xq2": f(B * n, c.cross_heads * c.cross_dim_head), "xkv2": f(B * Tc, 2 * c.cross_heads * c.cross_dim_head),
-            "xa": f(B * n, c.cross_heads * c.cross_dim_head),
-            "sqkv2": f(B * n, 3 * c.latent_heads * c.latent_dim_head),
-            "sa": f(B * n, c.latent_heads * c.latent_dim_head), "hid": f(B * n, 4 * D),
-        }
-        xi, si = c.cross_heads * c.cross_dim_head, c.latent_heads * c.latent_dim_head
-        ws["xq"] = ops.heads_view(ws["xq2"], B, n, c.cross_heads, c.cross_dim_head)
-        ws["xk"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head)
-        ws["xv"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head, xi)
-        for i, nm in enumerate(("sq", "sk", "sv")):
-            ws[nm] = ops.heads_view(ws["sqkv2"], B, n, c.latent_heads, c.latent_dim_head, i * si)
-        self._ws[key] = ws
-        return ws
-
-    def _ff(self, ws, norm, ff, rows, D):
-        ops.layernorm(ws["x"], norm[0], norm[1], ws["h"], rows, D)
-        ops.gemm(ws["h"], ff["w0"], ff["b0"], out=ws["hid"], epi=ops.EPI_GEGLU, cfg=self.gemm_cfg)
-        ops.gemm(ws["hid"], ff["w2"], ff["b2"], out=ws["x"], res=ws["x"], epi=ops.EPI_RES_F32, cfg=self.gemm_cfg)
+        self.latents.copy_(sd[prefix + "latents"].detach())
+        copy_tree(self.layers, perceiver_operands(sd, prefix, self.cfg, self.device, self.arith.dtype))
 
     def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
-        """data [B*Tc, C] (bf16|f32) -> latents [B*n, D] f32 (view of an internal workspace)."""
-        c = self.cfg
-        Tc, n, D = data.shape[0] // B, c.num_latents, c.latent_dim
-        ws = self._workspace(B, Tc)
-        ws["x"].view(B, n, D).copy_(self.latents)          # repeat(latents, 'n d -> b n d')
-        rows = B * n
-        for lay in self.layers:
-            a = lay["x_attn"]
-            ops.layernorm(ws["x"], lay["x_norm"][0], lay["x_norm"][1], ws["h"], rows, D)
-            ops.layernorm(data, lay["x_norm_ctx"][0], lay["x_norm_ctx"][1], ws["ctx"], B * Tc, c.input_chan)
-            ops.gemm(ws["h"], a["q_w"], None, out=ws["xq2"], epi=ops.EPI_BF16, cfg=self.gemm_cfg)
-            ops.gemm(ws["ctx"], a["kv_w"], None, out=ws["xkv2"], epi=ops.EPI_BF16, cfg=self.gemm_cfg)
-            ops.attn_fwd(ws["xq"], ws["xk"], ws["xv"], ws["xa"], qscale=c.cross_dim_head ** -0.5 * ops.LOG2E)
-            ops.gemm(ws["xa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"], epi=ops.EPI_RES_F32, cfg=self.gemm_cfg)
-            self._ff(ws, lay["x_ff_norm"], lay["x_ff"], rows, D)
-            for sl in lay["selfs"]:
-                a = sl["attn"]
-                ops.layernorm(ws["x"], sl["norm"][0], sl["norm"][1], ws["h"], rows, D)
-                ops.gemm(ws["h"], a["qkv_w"], None, out=ws["sqkv2"], epi=ops.EPI_BF16, cfg=self.gemm_cfg)
-                ops.attn_fwd(ws["sq"], ws["sk"], ws["sv"], ws["sa"], qscale=c.latent_dim_head ** -0.5 * ops.LOG2E)
-                ops.gemm(ws["sa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"], epi=ops.EPI_RES_F32, cfg=self.gemm_cfg)
-                self._ff(ws, sl["ff_norm"], sl["ff"], rows, D)
-        return ws["x"]
+        """data [B*Tc, C] (bf16|f32; f32 for the fp32 arithmetic) -> latents [B*n, D] f32 (view of an internal workspace)."""
+        c, key = self.cfg, (B, data.shape[0] // B)
+        if key not in self._ws:
+            self._ws[key] = perceiver_slots(c, *key, self.device, self.arith.dtype)
+        X, slots = self._ws[key]
+        X[0].view(B, c.num_latents, c.latent_dim).copy_(self.latents)          # repeat(latents, 'n d -> b n d')
+        perceiver_forward(self.layers, slots, data, B, c, self.arith)
+        return X[-1]
+
+
+def lens_cols(im2col, x: torch.Tensor, lens: LensCfg, patch: int, Kp: int) -> torch.Tensor:
+    """The GEMM rows [B*T, Kp] of a Lens tokenizer's convolution, by `im2col` (ops.im2col: bf16, ops.im2col_f32), column order
+    (c, i, j) = the conv weight's.  depth (DepthTokenizer.py:35-60): patch x patch, stride patch.  audio (AST_tokenizer.py:
+    44-57): [N,T,F] -> a conv over [N,1,F,T] with the f / t strides.  eeg (EEG_tokenizer.py:35-42, PatchEmbed1D): windows of the
+    time axis of [N, chans, time] = a conv over [N, chans, 1, time]."""
+    L, p = lens, patch
+    if L.modality not in ("depth", "audio", "eeg"):
+        raise NotImplementedError(L.modality)
+    kh, kw, sh, sw, transpose_hw, unsqueeze = {"depth": (p, p, p, p, False, None),
+                                               "audio": (p, p, L.audio_fstride, L.audio_tstride, True, 1),
+                                               "eeg": (1, L.eeg_window_size, 1, L.eeg_stride, False, 2)}[L.modality]
+    x = x.contiguous().float()
+    return im2col(x if unsqueeze is None else x.unsqueeze(unsqueeze), kh, kw, sh, sw, Kp, transpose_hw=transpose_hw)[0]
 
 
 class LensEngine:
@@ -814,7 +934,7 @@ class LensEngine:
         self.prefix_adapter = a
         self.adapter_pos = None
         if lens.modality in ("depth", "audio"):
-            self.conv_w = conv_weight_as_gemm(sd[a + "conv1.weight"], device)
+            self.conv_w, self.conv_b = conv_weight_as_gemm(sd[a + "conv1.weight"], device), None
             pos = sd[a + "pos_emb"].detach().float()
             self.adapter_pos = _dev(pos * (0.0 if lens.disable_adapter_pos else 1.0), device)      # (the product is a new tensor)
         elif lens.modality == "eeg":
@@ -856,27 +976,14 @@ class LensEngine:
         if self.perceiver is not None and any(n.startswith("perceiver.") for n in names):
             self.perceiver.update_params(sd, prefix + "perceiver.")
 
-    def tokens(self, x: torch.Tensor):
-        """-> (tokens [B*T, C] bf16, pos table [T, C] f32 or per-sample pos [B*T, C], B)."""
-        L = self.lens
-        p = self.tower.patch
-        if L.modality == "depth":       # DepthTokenizer.py:35-60
-            cols, gh, gw = ops.im2col(x.contiguous().float(), p, p, p, p, self.conv_w.shape[1])
-            return ops.gemm(cols, self.conv_w, None, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
-        if L.modality == "audio":       # AST_tokenizer.py:44-57: [N,T,F] -> conv over [N,1,F,T]
-            cols, gh, gw = ops.im2col(x.contiguous().float().unsqueeze(1), p, p, L.audio_fstride, L.audio_tstride,
-                                      self.conv_w.shape[1], transpose_hw=True)
-            return ops.gemm(cols, self.conv_w, None, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
-        if L.modality == "eeg":         # EEG_tokenizer.py:35-42: [N, chans, time] -> tokens [N*T', width]
-            cols = self.eeg_cols(x)
-            return ops.gemm(cols, self.conv_w, self.conv_b, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
-        raise NotImplementedError(L.modality)
+    def cols(self, x: torch.Tensor) -> torch.Tensor:
+        if not hasattr(self, "conv_w"):         # (no convolution tokenizer: the point cloud's is self.points)
+            raise NotImplementedError(self.lens.modality)
+        return lens_cols(ops.im2col, x, self.lens, self.tower.patch, self.conv_w.shape[1])
 
-    def eeg_cols(self, x: torch.Tensor) -> torch.Tensor:
-        """windows of the time axis as GEMM rows: [N*T', pad64(chans*window)], column order (chan, tap) = Conv1d's weight"""
-        L = self.lens
-        cols, gh, gw = ops.im2col(x.contiguous().float().unsqueeze(2), 1, L.eeg_window_size, 1, L.eeg_stride, self.conv_w.shape[1])
-        return cols
+    def tokens(self, x: torch.Tensor):
+        """-> (tokens [B*T, C] bf16, pos table [T, C] f32)."""
+        return ops.gemm(self.cols(x), self.conv_w, self.conv_b, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
 
     def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
         """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk)."""

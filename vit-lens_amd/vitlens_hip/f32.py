@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import LensCfg, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64, block_operands
+from .engine import LensCfg, PerceiverEngine, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64, block_operands, lens_cols
 
 
 def f32_head_dim_ok(dh: int) -> bool:
@@ -199,96 +199,30 @@ class TextEngineF32:
 # ------------------------------------------------------------------------------------------------
 # The Lenses with a Perceiver (audio, EEG, point cloud, depth): tokenizer -> (+pos) -> Perceiver -> trunk, all in fp32
 # ------------------------------------------------------------------------------------------------
-def _attn_f32(sd, p, device, packed_self: bool):
-    d = {"to_out_w": _dev(sd[p + "to_out.weight"], device), "to_out_b": _dev(sd[p + "to_out.bias"], device)}
-    if packed_self:
-        d["qkv_w"] = _dev(torch.cat([sd[p + "to_q.weight"].detach().float(), sd[p + "to_kv.weight"].detach().float()], 0), device)
-    else:
-        d["q_w"], d["kv_w"] = _dev(sd[p + "to_q.weight"], device), _dev(sd[p + "to_kv.weight"], device)
-    return d
+class F32Arith:
+    """engine.Bf16Arith in fp32: the Perceiver's matrix products on the fp32-input MFMA (the GEGLU FeedForward's first Linear as
+    ONE GEMM with the GEGLU epilogue, vl_gemm_f32_ex), attention on vl_attn_fwd_f32.  Inference only: no second outputs."""
+    dtype = torch.float32
+
+    def linear(self, a, w, b, out, res=None):
+        ops.gemm_f32(a, w, b, out=out, res=res)
+
+    def geglu(self, a, w, b, out, out2=None):
+        ops.gemm_f32_ex(a, w, b, out=out, geglu=True)
+
+    def attn(self, q, k, v, out, lse, dh):
+        ops.attn_fwd_f32(q, k, v, out, scale=dh ** -0.5)
 
 
-def _ff_f32(sd, p, device):
-    w0, b0 = interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
-    return {"w0": _dev(w0, device), "b0": _dev(b0, device),
-            "w2": _dev(sd[p + "net.2.weight"], device), "b2": _dev(sd[p + "net.2.bias"], device)}
-
-
-class PerceiverEngineF32:
-    """Perceiver.forward(return_embeddings=True) (open_clip/perceiver.py:289-328) in fp32: LayerNorm of latents and context,
-    bias-free to_q / to_kv, cross attention (Lq = num_latents, Lk = context length) and latent self-attention on
-    vl_attn_fwd_f32, to_out + residual, the GEGLU FeedForward as ONE GEMM with the GEGLU epilogue (vl_gemm_f32_ex) + the
-    down projection with the residual.  weight_tie_layers: layers 1 .. depth-1 are one set of operands (perceiver.py:249-254)."""
+class PerceiverEngineF32(PerceiverEngine):
+    """Perceiver.forward(return_embeddings=True) (open_clip/perceiver.py:289-328) in fp32: engine.perceiver_forward on fp32
+    operands and an fp32 workspace in F32Arith.  data f32 [B*Tc, C] -> latents f32 [B*n, D]."""
 
     def __init__(self, sd, prefix: str, cfg: LensCfg, device):
         for dh in (cfg.cross_dim_head, cfg.latent_dim_head):
             if dh not in (32, 64):
                 raise NotImplementedError("fp32 inference: Perceiver head dims must be 32 or 64")
-        self.cfg, self.device = cfg, torch.device(device)
-        self.latents = _dev(sd[prefix + "latents"], device)
-        ln = lambda q: (_dev(sd[q + ".weight"], device), _dev(sd[q + ".bias"], device))
-        self.layers = []
-        for i in range(cfg.depth):
-            if cfg.weight_tie_layers and i >= 2:
-                self.layers.append(self.layers[1])
-                continue
-            q = f"{prefix}layers.{i}."
-            lay = {"x_norm": ln(q + "0.norm"), "x_norm_ctx": ln(q + "0.norm_context"), "x_attn": _attn_f32(sd, q + "0.fn.", device, False),
-                   "x_ff_norm": ln(q + "1.norm"), "x_ff": _ff_f32(sd, q + "1.fn.", device), "selfs": []}
-            for j in range(cfg.self_per_cross):
-                r = f"{q}2.{j}."
-                lay["selfs"].append({"norm": ln(r + "0.norm"), "attn": _attn_f32(sd, r + "0.fn.", device, True),
-                                     "ff_norm": ln(r + "1.norm"), "ff": _ff_f32(sd, r + "1.fn.", device)})
-            self.layers.append(lay)
-        self._ws = {}
-
-    def _workspace(self, B, Tc):
-        key = (B, Tc)
-        if key in self._ws:
-            return self._ws[key]
-        c, dev = self.cfg, self.device
-        n, D = c.num_latents, c.latent_dim
-        xi, si = c.cross_heads * c.cross_dim_head, c.latent_heads * c.latent_dim_head
-        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        ws = {"x": f(B * n, D), "h": f(B * n, D), "ctx": f(B * Tc, c.input_chan), "xq2": f(B * n, xi), "xkv2": f(B * Tc, 2 * xi),
-              "xa": f(B * n, xi), "sqkv2": f(B * n, 3 * si), "sa": f(B * n, si), "hid": f(B * n, 4 * D)}
-        ws["xq"] = ops.heads_view(ws["xq2"], B, n, c.cross_heads, c.cross_dim_head)
-        ws["xk"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head)
-        ws["xv"] = ops.heads_view(ws["xkv2"], B, Tc, c.cross_heads, c.cross_dim_head, xi)
-        for i, nm in enumerate(("sq", "sk", "sv")):
-            ws[nm] = ops.heads_view(ws["sqkv2"], B, n, c.latent_heads, c.latent_dim_head, i * si)
-        self._ws[key] = ws
-        return ws
-
-    def _ff(self, ws, norm, ff, rows, D):
-        ops.layernorm(ws["x"], norm[0], norm[1], ws["h"], rows, D)
-        ops.gemm_f32_ex(ws["h"], ff["w0"], ff["b0"], out=ws["hid"], geglu=True)
-        ops.gemm_f32(ws["hid"], ff["w2"], ff["b2"], out=ws["x"], res=ws["x"])
-
-    def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
-        """data f32 [B*Tc, C] -> latents f32 [B*n, D] (a view of an internal workspace)."""
-        c = self.cfg
-        Tc, n, D = data.shape[0] // B, c.num_latents, c.latent_dim
-        ws = self._workspace(B, Tc)
-        ws["x"].view(B, n, D).copy_(self.latents)          # repeat(latents, 'n d -> b n d')
-        rows = B * n
-        for lay in self.layers:
-            a = lay["x_attn"]
-            ops.layernorm(ws["x"], lay["x_norm"][0], lay["x_norm"][1], ws["h"], rows, D)
-            ops.layernorm(data, lay["x_norm_ctx"][0], lay["x_norm_ctx"][1], ws["ctx"], B * Tc, c.input_chan)
-            ops.gemm_f32(ws["h"], a["q_w"], out=ws["xq2"])
-            ops.gemm_f32(ws["ctx"], a["kv_w"], out=ws["xkv2"])
-            ops.attn_fwd_f32(ws["xq"], ws["xk"], ws["xv"], ws["xa"], scale=c.cross_dim_head ** -0.5)
-            ops.gemm_f32(ws["xa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"])
-            self._ff(ws, lay["x_ff_norm"], lay["x_ff"], rows, D)
-            for sl in lay["selfs"]:
-                a = sl["attn"]
-                ops.layernorm(ws["x"], sl["norm"][0], sl["norm"][1], ws["h"], rows, D)
-                ops.gemm_f32(ws["h"], a["qkv_w"], out=ws["sqkv2"])
-                ops.attn_fwd_f32(ws["sq"], ws["sk"], ws["sv"], ws["sa"], scale=c.latent_dim_head ** -0.5)
-                ops.gemm_f32(ws["sa"], a["to_out_w"], a["to_out_b"], out=ws["x"], res=ws["x"])
-                self._ff(ws, sl["ff_norm"], sl["ff"], rows, D)
-        return ws["x"]
+        super().__init__(sd, prefix, cfg, device, arith=F32Arith())
 
 
 def point_tokenizer_operands_f32(sd, a: str, eps: float = 1e-5):
@@ -365,14 +299,7 @@ class LensEngineF32:
 
     def tokens(self, x: torch.Tensor) -> torch.Tensor:
         """-> tokens f32 [B*T, width] of the depth / audio / EEG tokenizer (without the adapter pos)."""
-        L, p = self.lens, self.tower.patch
-        x = x.to(self.device).contiguous().float()
-        if L.modality == "depth":       # DepthTokenizer.py:35-60
-            cols, _, _ = ops.im2col_f32(x, p, p, p, p, self.conv_w.shape[1])
-        elif L.modality == "audio":     # AST_tokenizer.py:44-57: [N,T,F] -> conv over [N,1,F,T]
-            cols, _, _ = ops.im2col_f32(x.unsqueeze(1), p, p, L.audio_fstride, L.audio_tstride, self.conv_w.shape[1], transpose_hw=True)
-        else:                           # EEG_tokenizer.py:35-42: windows of the time axis, column order (chan, tap)
-            cols, _, _ = ops.im2col_f32(x.unsqueeze(2), 1, L.eeg_window_size, 1, L.eeg_stride, self.conv_w.shape[1])
+        cols = lens_cols(ops.im2col_f32, x.to(self.device), self.lens, self.tower.patch, self.conv_w.shape[1])
         return ops.gemm_f32(cols, self.conv_w, self.conv_b)
 
     def encode(self, x: torch.Tensor, normalize: bool = False, fps_start=None, **kw) -> torch.Tensor:

@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .engine import LensCfg, LensEngine, TextCfg, TextEngine, TowerCfg, VitEngine
-from .train import AdamW, DepthLensTrainer
+from .train import AdamW, DepthLensTrainer, at_path
 
 
 class TorchComm:
@@ -962,10 +962,7 @@ class _PerceiverLensStep(_StepState):
         for name, fwd, path in self.refresh:
             m = self.masters[name]
             ops.cast_bf16(m, out=fwd)
-            node = wT[path[0]]
-            for k in path[1:-1]:
-                node = node[k]
-            ops.transpose_to_bf16(m, ldo=m.shape[0], out=node[path[-1]])
+            ops.transpose_to_bf16(m, ldo=m.shape[0], out=at_path(wT, path))
 
     def _refresh_operands(self):
         self._refresh_perceiver()

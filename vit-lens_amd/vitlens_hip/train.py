@@ -373,8 +373,7 @@ class DepthLensTrainer:
     def forward(self, x: torch.Tensor, keep=None, inv=None) -> torch.Tensor:
         """keep / inv: patch dropout in front of the ViT trunk (TowerTrainer.forward); the tokenizer stays dense."""
         le = self.le
-        p = le.tower.patch
-        cols, gh, gw = ops.im2col(x.contiguous().float(), p, p, p, p, le.conv_w.shape[1])
+        cols = le.cols(x)
         tok = ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
         self.ctx = (cols, x.shape[0])
         return self.tower.forward(tok, x.shape[0], pos2=le.adapter_pos, keep=keep, inv=inv)
@@ -619,65 +618,55 @@ class AdamW:
 # ------------------------------------------------------------------------------------------------
 # Perceiver ("Lens") training: autograd of Perceiver.forward (open_clip/perceiver.py:289-328)
 # ------------------------------------------------------------------------------------------------
-class _AttnSaved:
-    """Saved operands of one Perceiver attention.  The projections' outputs are kept as token-major matrices (packed
-    [q|k|v] for latent self-attention, q and [k|v] for cross-attention); the kernels read them by heads in place."""
-
-    def __init__(self, B, H, Lq, Lk, dh, device, packed: bool):
-        bf = lambda *s: torch.empty(*s, device=device, dtype=BF)
-        inner = H * dh
-        if packed:
-            self.qkv2 = bf(B * Lq, 3 * inner)
-            self.q2, self.kv2 = self.qkv2, None
-            self.q, self.k, self.v = (ops.heads_view(self.qkv2, B, Lq, H, dh, i * inner) for i in range(3))
-        else:
-            self.q2, self.kv2 = bf(B * Lq, inner), bf(B * Lk, 2 * inner)
-            self.q = ops.heads_view(self.q2, B, Lq, H, dh)
-            self.k, self.v = ops.heads_view(self.kv2, B, Lk, H, dh), ops.heads_view(self.kv2, B, Lk, H, dh, inner)
-        self.a = bf(B * Lq, inner)
-        self.av = ops.heads_view(self.a, B, Lq, H, dh)
-        self.lse = torch.empty(B, H, Lq, device=device, dtype=torch.float32)
-        self.dOm = bf(B * Lq, inner)
-        self.dO = ops.heads_view(self.dOm, B, Lq, H, dh)
-        self.delta = torch.empty(B, H, Lq, device=device, dtype=torch.float32)
-
-
 def deinterleave_geglu(g: torch.Tensor) -> torch.Tensor:
     """gradient / weight in the kernels' interleaved (a_j, gate_j) row order -> the reference's [a ; gate] order."""
     return torch.cat([g[0::2], g[1::2]], dim=0)
 
 
+def at_path(node, path):
+    """node[path[0]][path[1]]... of a nest of dicts and lists."""
+    for k in path:
+        node = node[k]
+    return node
+
+
 class PerceiverTrainer:
     def __init__(self, pe, param_prefix: str = "visual.perceiver."):
+        if pe.arith.dtype != BF:
+            raise ValueError("PerceiverTrainer needs a PerceiverEngine with bf16 operands")
         self.pe, self.P = pe, param_prefix
-        c = pe.cfg
         self.grads: Dict[str, torch.Tensor] = {}
-        t = lambda w: w.t().contiguous()
+        # transposed bf16 weights for the dX GEMMs (C = dY . W  ==  NT GEMM against W^T); tied layers
+        # (perceiver_weight_tie_layers) share one entry
         self.wT = []
         for li, lay in enumerate(pe.layers):
-            if li >= 2 and lay is pe.layers[1]:           # tied layers (perceiver_weight_tie_layers): one set of transposes too
+            if self.layer_name(li) != li:
                 self.wT.append(self.wT[1])
                 continue
-            d = {"x": {"q": t(lay["x_attn"]["q_w"]), "kv": t(lay["x_attn"]["kv_w"]), "out": t(lay["x_attn"]["to_out_w"])},
-                 "xff": {"w0": t(lay["x_ff"]["w0"]), "w2": t(lay["x_ff"]["w2"])}, "selfs": []}
-            for sl in lay["selfs"]:
-                d["selfs"].append({"qkv": t(sl["attn"]["qkv_w"]), "out": t(sl["attn"]["to_out_w"]),
-                                   "w0": t(sl["ff"]["w0"]), "w2": t(sl["ff"]["w2"])})
+            d = {"x": {}, "xff": {}, "selfs": [{} for _ in lay["selfs"]]}
+            for path, operand in self.wT_table(len(lay["selfs"])):
+                w = at_path(lay, operand)
+                at_path(d, path[:-1])[path[-1]] = w.new_empty(w.shape[1], w.shape[0])
             self.wT.append(d)
+        self.refresh_derived()
         self._st = {}
 
+    @staticmethod
+    def wT_table(n_selfs: int):
+        """(key path in wT[li], key path of the operand in pe.layers[li]) of every transposed weight of one layer."""
+        t = [(("x", "q"), ("x_attn", "q_w")), (("x", "kv"), ("x_attn", "kv_w")), (("x", "out"), ("x_attn", "to_out_w")),
+             (("xff", "w0"), ("x_ff", "w0")), (("xff", "w2"), ("x_ff", "w2"))]
+        for j in range(n_selfs):
+            t += [(("selfs", j, "qkv"), ("selfs", j, "attn", "qkv_w")), (("selfs", j, "out"), ("selfs", j, "attn", "to_out_w")),
+                  (("selfs", j, "w0"), ("selfs", j, "ff", "w0")), (("selfs", j, "w2"), ("selfs", j, "ff", "w2"))]
+        return t
+
     def refresh_derived(self):
-        """The Perceiver engine's operands were updated in place: redo the transposes."""
+        """The Perceiver engine's operands were set or updated in place: (re)do the transposes."""
         for li, lay in enumerate(self.pe.layers):
-            if li >= 2 and lay is self.pe.layers[1]:
-                continue
-            d = self.wT[li]
-            d["x"]["q"].copy_(lay["x_attn"]["q_w"].t()); d["x"]["kv"].copy_(lay["x_attn"]["kv_w"].t())
-            d["x"]["out"].copy_(lay["x_attn"]["to_out_w"].t())
-            d["xff"]["w0"].copy_(lay["x_ff"]["w0"].t()); d["xff"]["w2"].copy_(lay["x_ff"]["w2"].t())
-            for ds, sl in zip(d["selfs"], lay["selfs"]):
-                ds["qkv"].copy_(sl["attn"]["qkv_w"].t()); ds["out"].copy_(sl["attn"]["to_out_w"].t())
-                ds["w0"].copy_(sl["ff"]["w0"].t()); ds["w2"].copy_(sl["ff"]["w2"].t())
+            if self.layer_name(li) == li:
+                for path, operand in self.wT_table(len(lay["selfs"])):
+                    at_path(self.wT[li], path).copy_(at_path(lay, operand).t())
 
     def grad_buffer(self, name, shape):
         g = self.grads.get(name)
@@ -696,68 +685,29 @@ class PerceiverTrainer:
         if key in self._st:
             return self._st[key]
         c, dev = self.pe.cfg, self.pe.device
-        n, D = c.num_latents, c.latent_dim
-        R = B * n
+        R, D = B * c.num_latents, c.latent_dim
         f32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
         bf = lambda *s: torch.empty(*s, device=dev, dtype=BF)
-        nres = c.depth * (2 + 2 * c.self_per_cross) + 1
-        st = {"X": [f32(R, D) for _ in range(nres)],
+        st = {"X": [f32(R, D) for _ in range(_engine.perceiver_residuals(c))],
               "dx": f32(R, D), "dxb": bf(R, D), "dh8": bf(R, 8 * D), "dhn": bf(R, D), "dqkv": bf(R, 3 * c.latent_heads * c.latent_dim_head),
               "dq": bf(R, c.cross_heads * c.cross_dim_head), "dkv": bf(B * Tc, 2 * c.cross_heads * c.cross_dim_head),
-              "dctx": bf(B * Tc, c.input_chan), "ddata": f32(B * Tc, c.input_chan), "layers": []}
-        for _ in range(c.depth):
-            # (kept per sub-layer for the backward's weight gradients: every LayerNorm output `*_hn` / `c_n` and every GEGLU
-            #  output `*_hid` - recomputing them was 2 % of the C4 step's kernel time for 2-7 GB of a 288 GB card)
-            lay = {"x_stats": [f32(R), f32(R)], "c_stats": [f32(B * Tc), f32(B * Tc)], "x_hn": bf(R, D), "c_n": bf(B * Tc, c.input_chan),
-                   "x_attn": _AttnSaved(B, c.cross_heads, n, Tc, c.cross_dim_head, dev, packed=False),
-                   "xff_stats": [f32(R), f32(R)], "xff_h": bf(R, 8 * D), "xff_hn": bf(R, D), "xff_hid": bf(R, 4 * D), "selfs": []}
-            for _ in range(c.self_per_cross):
-                lay["selfs"].append({"stats": [f32(R), f32(R)], "attn": _AttnSaved(B, c.latent_heads, n, n, c.latent_dim_head, dev, packed=True),
-                                     "hn": bf(R, D), "ff_stats": [f32(R), f32(R)], "ff_h": bf(R, 8 * D), "ff_hn": bf(R, D),
-                                     "ff_hid": bf(R, 4 * D)})
-            st["layers"].append(lay)
+              "dctx": bf(B * Tc, c.input_chan), "ddata": f32(B * Tc, c.input_chan)}
+        # (kept per sub-layer for the backward's weight gradients: every LayerNorm output `hn` / `cn` and every GEGLU output
+        #  `hid` - recomputing them was 2 % of the C4 step's kernel time for 2-7 GB of a 288 GB card)
+        st["layers"] = _engine.perceiver_slots(c, B, Tc, dev, BF, X=st["X"])[1]
         self._st[key] = st
         return st
 
     # ---- forward ----------------------------------------------------------------------------------
-    def _ff_fwd(self, st, xi, norm, ff, stats, hsave, hn, hid, rows, D):
-        X, cfg = st["X"], self.pe.gemm_cfg
-        ops.layernorm(X[xi], norm[0], norm[1], hn, rows, D, mean=stats[0], rstd=stats[1])
-        ops.gemm(hn, ff["w0"], ff["b0"], out=hid, epi=ops.EPI_GEGLU, cfg=cfg, out2=hsave)
-        ops.gemm(hid, ff["w2"], ff["b2"], out=X[xi + 1], res=X[xi], epi=ops.EPI_RES_F32, cfg=cfg)
-
     def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
+        """engine.perceiver_forward into the per-sub-layer slots: residual snapshots, LayerNorm outputs and statistics,
+        projection outputs, lse, GEGLU pre-activation and output are what the backward reads."""
         pe, c = self.pe, self.pe.cfg
-        Tc, n, D = data.shape[0] // B, c.num_latents, c.latent_dim
-        st = self._state(B, Tc)
-        X, cfg, rows = st["X"], pe.gemm_cfg, B * n
-        X[0].view(B, n, D).copy_(pe.latents)
-        xi = 0
-        for li, lay in enumerate(pe.layers):
-            S = st["layers"][li]
-            a, A = lay["x_attn"], S["x_attn"]
-            ops.layernorm(X[xi], lay["x_norm"][0], lay["x_norm"][1], S["x_hn"], rows, D, mean=S["x_stats"][0], rstd=S["x_stats"][1])
-            ops.layernorm(data, lay["x_norm_ctx"][0], lay["x_norm_ctx"][1], S["c_n"], B * Tc, c.input_chan,
-                          mean=S["c_stats"][0], rstd=S["c_stats"][1])
-            ops.gemm(S["x_hn"], a["q_w"], None, out=A.q2, epi=ops.EPI_BF16, cfg=cfg)
-            ops.gemm(S["c_n"], a["kv_w"], None, out=A.kv2, epi=ops.EPI_BF16, cfg=cfg)
-            ops.attn_fwd(A.q, A.k, A.v, A.a, lse=A.lse, qscale=c.cross_dim_head ** -0.5 * ops.LOG2E)
-            ops.gemm(A.a, a["to_out_w"], a["to_out_b"], out=X[xi + 1], res=X[xi], epi=ops.EPI_RES_F32, cfg=cfg)
-            xi += 1
-            self._ff_fwd(st, xi, lay["x_ff_norm"], lay["x_ff"], S["xff_stats"], S["xff_h"], S["xff_hn"], S["xff_hid"], rows, D)
-            xi += 1
-            for sj, sl in enumerate(lay["selfs"]):
-                T = S["selfs"][sj]
-                a, A = sl["attn"], T["attn"]
-                ops.layernorm(X[xi], sl["norm"][0], sl["norm"][1], T["hn"], rows, D, mean=T["stats"][0], rstd=T["stats"][1])
-                ops.gemm(T["hn"], a["qkv_w"], None, out=A.qkv2, epi=ops.EPI_BF16, cfg=cfg)
-                ops.attn_fwd(A.q, A.k, A.v, A.a, lse=A.lse, qscale=c.latent_dim_head ** -0.5 * ops.LOG2E)
-                ops.gemm(A.a, a["to_out_w"], a["to_out_b"], out=X[xi + 1], res=X[xi], epi=ops.EPI_RES_F32, cfg=cfg)
-                xi += 1
-                self._ff_fwd(st, xi, sl["ff_norm"], sl["ff"], T["ff_stats"], T["ff_h"], T["ff_hn"], T["ff_hid"], rows, D)
-                xi += 1
-        self.ctx = (B, Tc, data)
-        return X[xi]
+        st = self._state(B, data.shape[0] // B)
+        st["X"][0].view(B, c.num_latents, c.latent_dim).copy_(pe.latents)
+        _engine.perceiver_forward(pe.layers, st["layers"], data, B, c, pe.arith)
+        self.ctx = (B, data.shape[0] // B, data)
+        return st["X"][-1]
 
     # ---- backward ---------------------------------------------------------------------------------
     def _dw(self, name, dy, x, rows):
@@ -772,81 +722,68 @@ class PerceiverTrainer:
         ops.layernorm_bwd_params(dy, x, stats[0], stats[1], self.grad_buffer(name + ".weight", (D,)),
                                  self.grad_buffer(name + ".bias", (D,)), rows, D)
 
-    def _ff_bwd(self, st, xi, norm, ff, wT, stats, hsave, hn, hid, rows, D, pname):
-        """x_{xi+1} = x_xi + W2 geglu(W0 LN(x_xi) + b0) + b2 ; st['dx'] holds dL/dx_{xi+1} on entry, dL/dx_xi on exit.
-        hn = LN(x_xi), hid = geglu(...) as the forward left them."""
-        X, cfg = st["X"], self.pe.gemm_cfg
+    def _ff_bwd(self, st, s, norm, wT, pname):
+        """x1 = x0 + W2 geglu(W0 LN(x0) + b0) + b2 on the slots `s` ; st['dx'] holds dL/dx1 on entry, dL/dx0 on exit.
+        s.hn = LN(x0), s.h = the GEGLU's pre-activation, s.hid = geglu(...) as the forward left them."""
+        cfg, (rows, D) = self.pe.gemm_cfg, s.x0.shape
         # (dy = the bf16 copy of the residual gradient the dX GEMMs read: token-major operands for the dW kernel - the fp32
         #  stream would be rounded to the same bf16 values on its way through a transposed copy)
-        self._dw(pname + "1.fn.net.2.weight", st["dxb"], hid, rows)
+        self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
         ops.colsum(st["dx"], self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
-        ops.gemm(st["dxb"], wT["w2"], None, out=st["dh8"], res=hsave, epi=ops.EPI_DGEGLU, cfg=cfg)     # d(pre-activation), interleaved
-        self._dw(pname + "1.fn.net.0.weight_il", st["dh8"], hn, rows)
+        ops.gemm(st["dxb"], wT["w2"], None, out=st["dh8"], res=s.h, epi=ops.EPI_DGEGLU, cfg=cfg)     # d(pre-activation), interleaved
+        self._dw(pname + "1.fn.net.0.weight_il", st["dh8"], s.hn, rows)
         ops.colsum(st["dh8"], self.grad_buffer(pname + "1.fn.net.0.bias_il", (8 * D,)))
         ops.gemm(st["dh8"], wT["w0"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
-        self._ln_params(pname + "1.norm", st["dhn"], X[xi], stats, rows, D)
-        ops.layernorm_bwd(st["dhn"], X[xi], stats[0], stats[1], norm[0], rows, D, dres=st["dx"], dx=st["dx"], dx_bf16=st["dxb"])
+        self._ln_params(pname + "1.norm", st["dhn"], s.x0, s.stats, rows, D)
+        ops.layernorm_bwd(st["dhn"], s.x0, s.stats[0], s.stats[1], norm[0], rows, D, dres=st["dx"], dx=st["dx"], dx_bf16=st["dxb"])
+
+    def _attn_bwd(self, st, s, norm, wT, pname, dq, dkv=None, data=None, norm_ctx=None):
+        """x1 = x0 + to_out(attn(to_q(LN(x0)), to_kv(context))) on the slots `s` ; st['dx'] holds dL/dx1 on entry, dL/dx0 on exit.
+        Latent self-attention (dkv None; the context is LN(x0) itself): dq is the packed [dq|dk|dv], one to_qkv gradient with
+        rows [to_q ; to_kv].  Cross attention: dq and dkv = [dk|dv] apart, and the context side LN_ctx(data) -> to_kv, whose
+        input gradient is ADDED to st['ddata'] (every cross layer reads the same data)."""
+        cfg, (rows, D), inner = self.pe.gemm_cfg, s.x0.shape, s.a.shape[1]
+        packed = dkv is None
+        self._dw(pname + "0.fn.to_out.weight", st["dxb"], s.a, rows)
+        ops.colsum(st["dx"], self.grad_buffer(pname + "0.fn.to_out.bias", (D,)))
+        ops.gemm(st["dxb"], wT["out"], None, out=s.dOm, epi=ops.EPI_BF16, cfg=cfg)
+        if packed:
+            ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dq[:, inner:], dq[:, 2 * inner:], 3 * inner, 3 * inner)
+        else:
+            ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dkv, dkv[:, inner:], inner, 2 * inner)
+        # query side: LN(x0) -> to_q (packed: -> [to_q ; to_kv])
+        self._dw(pname + ("0.fn.to_qkv.weight" if packed else "0.fn.to_q.weight"), dq, s.hn, rows)
+        ops.gemm(dq, wT["qkv" if packed else "q"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
+        self._ln_params(pname + "0.norm", st["dhn"], s.x0, s.stats, rows, D)
+        ops.layernorm_bwd(st["dhn"], s.x0, s.stats[0], s.stats[1], norm[0], rows, D, dres=st["dx"], dx=st["dx"], dx_bf16=st["dxb"])
+        if packed:
+            return
+        crows, C = data.shape
+        self._dw(pname + "0.fn.to_kv.weight", dkv, s.cn, crows)
+        ops.gemm(dkv, wT["kv"], None, out=st["dctx"], epi=ops.EPI_BF16, cfg=cfg)
+        self._ln_params(pname + "0.norm_context", st["dctx"], data, s.cstats, crows, C)
+        ops.layernorm_bwd(st["dctx"], data, s.cstats[0], s.cstats[1], norm_ctx[0], crows, C, dres=st["ddata"], dx=st["ddata"])
 
     def backward(self, dlat: torch.Tensor) -> torch.Tensor:
         """dlat f32 [B*n, D] = dL/d(latent output) -> returns dL/d(data) f32 [B*Tc, C]; fills self.grads
         (GEGLU first-layer gradients are kept in the kernels' interleaved row order under '*_il' names)."""
         pe, c = self.pe, self.pe.cfg
         B, Tc, data = self.ctx
-        n, D = c.num_latents, c.latent_dim
         st = self._state(B, Tc)
-        X, cfg, rows, P = st["X"], pe.gemm_cfg, B * n, self.P
         st["dx"].copy_(dlat)
         ops.cast_bf16(st["dx"], out=st["dxb"])
         st["ddata"].zero_()
-        xi = len(X) - 1
         for li in reversed(range(c.depth)):
             lay, S, wT = pe.layers[li], st["layers"][li], self.wT[li]
+            pn = f"{self.P}layers.{self.layer_name(li)}."
             for sj in reversed(range(c.self_per_cross)):
                 sl, T, w = lay["selfs"][sj], S["selfs"][sj], wT["selfs"][sj]
-                pn = f"{P}layers.{self.layer_name(li)}.2.{sj}."
-                xi -= 1
-                self._ff_bwd(st, xi, sl["ff_norm"], sl["ff"], w, T["ff_stats"], T["ff_h"], T["ff_hn"], T["ff_hid"], rows, D, pn)
-                xi -= 1
-                a, A = sl["attn"], T["attn"]
-                H, dh = c.latent_heads, c.latent_dim_head
-                inner = H * dh
-                self._dw(pn + "0.fn.to_out.weight", st["dxb"], A.a, rows)
-                ops.colsum(st["dx"], self.grad_buffer(pn + "0.fn.to_out.bias", (D,)))
-                ops.gemm(st["dxb"], w["out"], None, out=A.dOm, epi=ops.EPI_BF16, cfg=cfg)
-                dqkv = st["dqkv"]
-                ops.attn_bwd(A.q, A.k, A.v, A.dO, A.av, A.lse, A.delta, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:],
-                             3 * inner, 3 * inner)
-                self._dw(pn + "0.fn.to_qkv.weight", dqkv, T["hn"], rows)            # rows [to_q ; to_kv]
-                ops.gemm(dqkv, w["qkv"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
-                self._ln_params(pn + "0.norm", st["dhn"], X[xi], T["stats"], rows, D)
-                ops.layernorm_bwd(st["dhn"], X[xi], T["stats"][0], T["stats"][1], sl["norm"][0], rows, D, dres=st["dx"],
-                                  dx=st["dx"], dx_bf16=st["dxb"])
-            pn = f"{P}layers.{self.layer_name(li)}."
-            xi -= 1
-            self._ff_bwd(st, xi, lay["x_ff_norm"], lay["x_ff"], wT["xff"], S["xff_stats"], S["xff_h"], S["xff_hn"], S["xff_hid"], rows, D, pn)
-            xi -= 1
-            a, A, w = lay["x_attn"], S["x_attn"], wT["x"]
-            H, dh = c.cross_heads, c.cross_dim_head
-            inner = H * dh
-            self._dw(pn + "0.fn.to_out.weight", st["dxb"], A.a, rows)
-            ops.colsum(st["dx"], self.grad_buffer(pn + "0.fn.to_out.bias", (D,)))
-            ops.gemm(st["dxb"], w["out"], None, out=A.dOm, epi=ops.EPI_BF16, cfg=cfg)
-            dkv = st["dkv"]
-            ops.attn_bwd(A.q, A.k, A.v, A.dO, A.av, A.lse, A.delta, st["dq"], dkv, dkv[:, inner:], inner, 2 * inner)
-            # query side: LN(x) -> to_q
-            self._dw(pn + "0.fn.to_q.weight", st["dq"], S["x_hn"], rows)
-            ops.gemm(st["dq"], w["q"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
-            self._ln_params(pn + "0.norm", st["dhn"], X[xi], S["x_stats"], rows, D)
-            ops.layernorm_bwd(st["dhn"], X[xi], S["x_stats"][0], S["x_stats"][1], lay["x_norm"][0], rows, D, dres=st["dx"],
-                              dx=st["dx"], dx_bf16=st["dxb"])
-            # context side: LN_ctx(data) -> to_kv ; every cross layer reads the same data -> accumulate
-            C = c.input_chan
-            self._dw(pn + "0.fn.to_kv.weight", dkv, S["c_n"], B * Tc)
-            ops.gemm(dkv, w["kv"], None, out=st["dctx"], epi=ops.EPI_BF16, cfg=cfg)
-            self._ln_params(pn + "0.norm_context", st["dctx"], data, S["c_stats"], B * Tc, C)
-            ops.layernorm_bwd(st["dctx"], data, S["c_stats"][0], S["c_stats"][1], lay["x_norm_ctx"][0], B * Tc, C,
-                              dres=st["ddata"], dx=st["ddata"])
-        ops.batch_rowsum(st["dx"], self.grad_buffer(P + "latents", (n, D)), B, n, D, n, 0)
+                self._ff_bwd(st, T["ff"], sl["ff_norm"], w, f"{pn}2.{sj}.")
+                self._attn_bwd(st, T["attn"], sl["norm"], w, f"{pn}2.{sj}.", st["dqkv"])
+            self._ff_bwd(st, S["x_ff"], lay["x_ff_norm"], wT["xff"], pn)
+            self._attn_bwd(st, S["x_attn"], lay["x_norm"], wT["x"], pn, st["dq"], st["dkv"], data, lay["x_norm_ctx"])
+        n, D = c.num_latents, c.latent_dim
+        ops.batch_rowsum(st["dx"], self.grad_buffer(self.P + "latents", (n, D)), B, n, D, n, 0)
         return st["ddata"]
 
     def reference_named_grads(self, grads: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -855,9 +792,7 @@ class PerceiverTrainer:
         out = {}
         c = self.pe.cfg
         for k, g in (self.grads if grads is None else grads).items():
-            if k.endswith("net.0.weight_il"):
-                out[k[:-3]] = deinterleave_geglu(g)
-            elif k.endswith("net.0.bias_il"):
+            if k.endswith(("net.0.weight_il", "net.0.bias_il")):
                 out[k[:-3]] = deinterleave_geglu(g)
             elif k.endswith("to_qkv.weight"):
                 inner = c.latent_heads * c.latent_dim_head
@@ -887,11 +822,9 @@ class AudioLensTrainer:
 
     def _tokens(self, x):
         """-> (the im2col rows bf16 [B*T, Kp], which the backward keeps, and the tokenizer convolution's output [B*T, D])."""
-        le, L = self.le, self.le.lens
-        p = le.tower.patch
-        cols, gh, gw = ops.im2col(x.contiguous().float().unsqueeze(1), p, p, L.audio_fstride, L.audio_tstride,
-                                  le.conv_w.shape[1], transpose_hw=True)
-        return cols, ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
+        le = self.le
+        cols = le.cols(x)
+        return cols, ops.gemm(cols, le.conv_w, le.conv_b, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
 
     def _conv_bias_grad(self, ddata):
         pass                                          # (the AST convolution's bias is not in the trainable set)
@@ -925,11 +858,6 @@ class EEGLensTrainer(AudioLensTrainer):
     time axis) + pos_emb + Perceiver trainable in front of the locked ViT - the audio recipe with a 1-D tokenizer."""
 
     conv_w_name = "visual.visual_adapter.proj.weight_gemm"
-
-    def _tokens(self, x):
-        le = self.le
-        cols = le.eeg_cols(x)
-        return cols, ops.gemm(cols, le.conv_w, le.conv_b, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
 
     def _conv_bias_grad(self, ddata):
         ops.colsum(ddata, self.tower.grad_buffer("visual.visual_adapter.proj.bias", self.le.conv_b))
