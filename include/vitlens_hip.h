@@ -404,6 +404,45 @@ int vl_attn_fwd_q1(const void* q, const void* k, const void* v, const long* stri
 int vl_attn_bwd_q1(const void* q, const void* k, const void* v, const long* strides, const void* dO, long ld_do,
                    const void* o, long ld_o, const float* lse, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv,
                    int B, int H, int L, int dh, int qrow, float qscale, float scale, hipStream_t stream);
+/* ---- Perceiver dropout (csrc/vl_lens_drop.hip): the Lens's attn_dropout on the attention probabilities and ff_dropout behind the
+ * second Linear of a FeedForward (open_clip/perceiver.py:91-102, 105-154), train mode only.  The mask is a pure function of
+ * numbers and is never stored: element e is KEPT iff its Philox4x32-10 word is >= round(p * 2^32) as a uint32, a kept value is
+ * multiplied by 1 / (1 - p) computed in fp32.  Key (lo32(seed), hi32(seed)); counter
+ *     (group, lo32(sample0 + b), hi32(sample0 + b), sublayer)
+ * with b the sample (batch row) and `sublayer` the position of the sub-layer in the Perceiver's forward, counted from 0 over
+ * attentions and FeedForwards alike (so an attention and a FeedForward, or two calls of weight-tied modules, never share one).
+ * The element group inside the sample and the word of the four:
+ *     attention probability (head h, query i, key j):  group = (h * Lq + i) * ceil(Lk / 4) + j / 4,   word j % 4
+ *     FeedForward output (latent row i, column c):     group = i * (D / 4) + c / 4,                   word c % 4
+ * Refused with a status: p outside [0, 1), a group count beyond 2^32, a shape the kernels do not take - never a run without
+ * dropout.  tests/perceiver_drop_ref.py restates the layout in numpy.
+ * NOTE on the version: these four entries were added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py pins, so a
+ * library built before them reports the same number and does not have them.  A client that calls them must look the
+ * symbols up when it loads the library (the Python binding does: vitlens_hip/_lib.py names a library that lacks a symbol of its
+ * table as stale); the next change to this header bumps the number and ends the overlap.
+ *
+ * vl_attn_fwd_drop_bf16: vl_attn_fwd_bf16 (same operands, strides[9], qscale, token-major out, lse) with
+ * out = (P * M / (1 - p)) V.  The softmax normaliser is the sum over ALL keys and lse is what vl_attn_fwd_bf16 writes; the
+ * mask is applied to the unnormalised fp32 probabilities before they are rounded to bf16 for the P.V product.  Head dims 32,
+ * 64, or a multiple of 8 in (64, 128]; any Lq, Lk.
+ * vl_attn_bwd_drop_bf16: vl_attn_bwd_bf16 (same operands, strides[15], delta workspace, destinations) for that forward:
+ * dV = (P M / (1 - p))^T dO, dP = (dO V^T) M / (1 - p), dS = P (dP - delta), delta = rowsum(dO * O).  Two kernels. */
+int vl_attn_fwd_drop_bf16(const void* q, const void* k, const void* v, const long* strides, void* out, float* lse, int B, int H,
+                          int Lq, int Lk, int dh, float qscale, int causal, double p, uint64_t seed, int64_t sample0,
+                          int sublayer, hipStream_t stream);
+int vl_attn_bwd_drop_bf16(const void* q, const void* k, const void* v, const void* dO, const void* o, const long* strides,
+                          const float* lse, float* delta, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv, int B, int H,
+                          int Lq, int Lk, int dh, float qscale, int causal, float scale, double p, uint64_t seed,
+                          int64_t sample0, int sublayer, hipStream_t stream);
+/* x1 = x0 + y * M / (1 - p): y f32 [B*n, D] = the down-projection's output with its bias (dropped with it), x0 / x1 f32 [B*n, D]
+ * the residual stream (x1 may alias x0 or y), n rows per sample, D % 4 == 0. */
+int vl_ff_drop_fwd(const float* y, const float* x0, float* x1, int B, int n, int D, double p, uint64_t seed, int64_t sample0,
+                   int sublayer, hipStream_t stream);
+/* Its backward on the branch: dy bf16 [B*n, D] = dx1 * M / (1 - p) of the residual gradient dx1 f32 [B*n, D] (the residual
+ * branch itself keeps dx1) - the operand of the dW2 and dGEGLU products - and, optionally, the same products unrounded in
+ * dy_f32 f32 [B*n, D] (may alias dx1), whose column sum is db2. */
+int vl_ff_drop_bwd(const float* dx1, void* dy, float* dy_f32, int B, int n, int D, double p, uint64_t seed, int64_t sample0,
+                   int sublayer, hipStream_t stream);
 /* ---- audio front end (csrc/vl_audio.hip) ----
  * Kaldi-compatible log-mel filterbank = torchaudio.compliance.kaldi.fbank(htk_compat, 16 kHz, hanning window, 128 bins,
  * no dither, 25 ms / 10 ms frames, snip_edges) + zero-padding / truncation to target_len rows + Normalize(mean, std), i.e.

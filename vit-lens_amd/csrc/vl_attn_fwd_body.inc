@@ -1,7 +1,9 @@
 // Body of attn_fwd_kernel (vl_attn.hip), included by its two kernels: the dense one (the kernel arguments are `p`) and the packed
 // one (VARLEN: `p` is caption b's problem, built by the kernel in front of this text).  Expects in scope: the template
 // parameters DH, TAILQ, MULTI, F16, DMA, the constants VARLEN, KC, VSP, `const AttnP& p` (or the argument itself) and, for
-// VARLEN, `row0` = the caption's first row in the packed output / lse.
+// VARLEN, `row0` = the caption's first row in the packed output / lse.  An including file that defines the macro
+// VL_ATTN_FWD_DROP(pv, p, h, qidx, key0) gets it called on every tile's unnormalised probabilities (vl_lens_drop.hip); without
+// the macro the text is what it was.
   constexpr int RB = DH * 2;          // K row bytes in LDS
   constexpr int CH = RB / 16;         // 16-byte chunks per row
   constexpr int RSH = Rsh<DH>::v;     // rows per 256-B bank row = 2^RSH
@@ -289,6 +291,11 @@
         a0 += a2; a1 += a3;
         l2 += a0 + a1;
       }
+#ifdef VL_ATTN_FWD_DROP
+      // attention dropout (vl_lens_drop.hip): behind the running sum - the normaliser counts every key - and in front of the
+      // packing for P.V.  The lane's 16 values are four aligned groups of 4 keys: one Philox call each
+      VL_ATTN_FWD_DROP(pv, p, h, qidx, key0);
+#endif
       // ---- O^T += V^T . P^T ----
       bf16x8 vf1[DT];
 #pragma unroll

@@ -151,6 +151,12 @@ class VisionTransformer(nn.Module):
         if self.patch_dropout > 0.0:
             assert 0 <= self.patch_dropout < 1.0, f"patch_dropout must be in [0, 1), got {self.patch_dropout}"
         a = cfg.exp_args
+        # --perceiver_attn_dropout / --perceiver_ff_dropout (module_cfg.py:52-53 -> perceiver.py:91-102, 105-154): nn.Dropout on the
+        # attention probabilities and behind every FeedForward of the Lens, in train mode.  The masks are drawn on the device
+        # (Philox, csrc/vl_lens_drop.hip) from `drop_seed`, the rank and a count of this tower's train-mode forwards
+        self.perceiver_attn_dropout = self._dropout_p(_g(a, "perceiver_attn_dropout", 0.0), "perceiver_attn_dropout")
+        self.perceiver_ff_dropout = self._dropout_p(_g(a, "perceiver_ff_dropout", 0.0), "perceiver_ff_dropout")
+        self.drop_seed, self._drop_forwards = 0, 0
         D, P = cfg.width, cfg.patch_size
         self.heads = D // cfg.head_width
         self.modality = {"3dpc": "pc", "pointcloud": "pc", "point_cloud": "pc", "point cloud": "pc"}.get(
@@ -160,6 +166,7 @@ class VisionTransformer(nn.Module):
         self.perceiver_identity = bool(_g(a, "perceiver_as_identity", False)) or not self.use_perceiver
         if _g(a, "perceiver_as_transformer", False):
             raise NotImplementedError("perceiver_as_transformer is outside the hot path (SURVEY §8)")
+        self._check_lens_dropout()
         n_tok = _g(a, "perceiver_num_latents", grid) if self.use_perceiver else grid
         scale = D ** -0.5
         prm = {"class_embedding": scale * torch.randn(D), "positional_embedding": scale * torch.randn(n_tok + 1, D),
@@ -366,7 +373,8 @@ class VisionTransformer(nn.Module):
                 pc_radius=_g(a, "pc_radius", 0.2), pc_in_dim=_g(a, "pc_in_channel", 3),
                 use_orig_pos=not _g(a, "disable_orig_pos", False),
                 disable_adapter_pos=bool(_g(a, "disable_visual_adapter_pos", False)),
-                weight_tie_layers=bool(_g(a, "perceiver_weight_tie_layers", False)))
+                weight_tie_layers=bool(_g(a, "perceiver_weight_tie_layers", False)),
+                attn_dropout=self.perceiver_attn_dropout, ff_dropout=self.perceiver_ff_dropout)
         return tower, lens
 
     def engine(self):
@@ -477,10 +485,58 @@ class VisionTransformer(nn.Module):
         keys = keys.pin_memory().to(self.class_embedding.device, non_blocking=True)
         return ops.patch_keep(keys, ops.patch_keep_count(T, self.patch_dropout))
 
+    @staticmethod
+    def _dropout_p(p, name: str) -> float:
+        p = float(p or 0.0)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"{name} must be in [0, 1), got {p}")
+        return p
+
+    def set_perceiver_dropout(self, attn_dropout=None, ff_dropout=None):
+        """--perceiver_attn_dropout / --perceiver_ff_dropout after construction (the training drivers, from their `args`); None
+        leaves a value as it is.  A change rebuilds the tower's executors at their next use."""
+        pa = self.perceiver_attn_dropout if attn_dropout is None else self._dropout_p(attn_dropout, "perceiver_attn_dropout")
+        pf = self.perceiver_ff_dropout if ff_dropout is None else self._dropout_p(ff_dropout, "perceiver_ff_dropout")
+        if (pa, pf) != (self.perceiver_attn_dropout, self.perceiver_ff_dropout):
+            self.perceiver_attn_dropout, self.perceiver_ff_dropout = pa, pf
+            self._check_lens_dropout()
+            self._engine = self._trainer_obj = None
+
+    def _check_lens_dropout(self):
+        """A tower with a Perceiver that these executors do not run (image / tactile: their engines and trainers have no Lens)
+        refuses a positive probability - never a silent run without dropout.  A tower without a Perceiver has nothing to drop
+        in, as in the reference, whose Perceiver is then an identity."""
+        if (self.perceiver_attn_dropout > 0.0 or self.perceiver_ff_dropout > 0.0) and not self.perceiver_identity \
+                and self.modality in ("image", "tactile"):
+            raise NotImplementedError(f"perceiver_attn_dropout / perceiver_ff_dropout > 0 on a {self.modality!r} tower with a Perceiver: "
+                                      "this tower's executors run no Lens and would not drop")
+
+    def set_drop_seed(self, seed: int, forwards: int = 0):
+        """Seed of the Perceiver dropout's masks and the count of train-mode forwards drawn so far (the `step` of
+        vitlens_hip.step.drop_sample0 on the module path): the same pair reproduces the same sequence of masks."""
+        self.drop_seed, self._drop_forwards = int(seed), int(forwards)
+
+    def _lens_draw(self):
+        """The Perceiver's dropout draw of this forward (vitlens_hip.engine.LensDrop), or None: eval mode - nn.Dropout follows
+        .training, not requires_grad - no Perceiver, or both probabilities 0.  Every train-mode forward draws fresh masks."""
+        if not self.training or self.perceiver_identity or not (self.perceiver_attn_dropout > 0.0 or self.perceiver_ff_dropout > 0.0):
+            return None
+        import torch.distributed as dist
+        from vitlens_hip.engine import LensDrop
+        from vitlens_hip.step import DROP_TOWER_LENS, drop_sample0
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        d = LensDrop(self.drop_seed, drop_sample0(self._drop_forwards, rank, DROP_TOWER_LENS, 0), self.perceiver_attn_dropout,
+                     self.perceiver_ff_dropout)
+        self._drop_forwards += 1
+        return d
+
     def forward(self, x: torch.Tensor, fwd_output_tokens: bool = False, **kwargs):
         if fwd_output_tokens:
             raise NotImplementedError("token outputs are only used by the video-distillation losses (out of scope)")
         x = x.to(self.class_embedding.device)
+        drop = self._lens_draw()
+        if drop is not None:
+            kwargs = dict(kwargs, drop=drop)
         keep, inv = self._drop_tokens(x.shape[0])
         if keep is not None:
             kwargs = dict(kwargs, keep=keep)

@@ -8,6 +8,9 @@ def openclip_step(model, logit_scale_net, loss_fn, optimizer, data, device="cuda
                   fps_start=None):
     """data: dict with "xyz_dense" [B,N,3], "features_dense" [B,N,C], "text_feat" / "img_feat" lists of [1,E] (or [B,E]
     tensors).  Returns the loss dictionary of openshape.TriClipLoss (tensors)."""
+    # --perceiver_attn_dropout / --perceiver_ff_dropout of the run's config (param.py:335-344) onto the Lens tower
+    from training.train import _lens_dropout_from_args
+    _lens_dropout_from_args(getattr(model, "backbone", None), getattr(model, "args", None))
     optimizer.zero_grad()
     stack = lambda v: (torch.vstack(list(v)) if not torch.is_tensor(v) else v).to(device=device, dtype=torch.float32)
     text_feat, img_feat = stack(data["text_feat"]), stack(data["img_feat"])

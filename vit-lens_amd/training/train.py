@@ -63,6 +63,25 @@ def _refuse(args):
         raise NotImplementedError("Horovod is outside the hot path: one process per GPU on torch.distributed (RCCL)")
 
 
+def _lens_dropout_from_args(tower, args):
+    """--perceiver_attn_dropout / --perceiver_ff_dropout (params.py:739-748) of the driver's `args` onto the Lens tower.  Who wins:
+    a model built from the same args (tri_create_model(args=...)) already carries both, and a value the MODEL was built with is
+    never changed here - a missing key, None or a parser's default 0.0 in `args` switches nothing off.  A positive value in `args`
+    fills in a probability the model has at 0.0 (a model built without these args); two different positive values are a
+    ValueError.  Nothing is rebuilt when nothing changes, so calling this every epoch or step costs two comparisons."""
+    if tower is None or not hasattr(tower, "set_perceiver_dropout"):
+        return
+    new = {}
+    for key, field in (("perceiver_attn_dropout", "attn_dropout"), ("perceiver_ff_dropout", "ff_dropout")):
+        want, have = float(getattr(args, key, None) or 0.0), getattr(tower, key)
+        if want > 0.0 and have > 0.0 and want != have:
+            raise ValueError(f"{key}: the model was built with {have}, the driver's args say {want}")
+        if want > 0.0 and have == 0.0:
+            new[field] = want
+    if new:
+        tower.set_perceiver_dropout(**new)
+
+
 def _optimizer_step(model, optimizer, scaler, args):
     clip = getattr(args, "grad_clip_norm", None)
     if scaler is not None:
@@ -81,6 +100,7 @@ def _run_epoch(model, data, epoch, optimizer, scaler, scheduler, args, fetch, fe
     """fetch(batch) -> tuple of device inputs; features(inputs) -> ({name: feature tensor}, logit_scale);
     loss_of(feature dict, logit_scale) -> {name: loss tensor}."""
     _refuse(args)
+    _lens_dropout_from_args(getattr(unwrap_model(model), "visual", None), args)
     model.train()
     data["train"].set_epoch(epoch)
     dataloader = data["train"].dataloader

@@ -108,6 +108,11 @@ SIGNATURES = {
     "vl_axpy_f32": [P, P, F, L, P],
     "vl_scale_exp_f32": [P, P, L, P, F, P],
     "vl_batch_rowsum": [P, P, I, I, I, L, L, P],
+    # Perceiver dropout (csrc/vl_lens_drop.hip)
+    "vl_attn_fwd_drop_bf16": [P, P, P, P, P, P, I, I, I, I, I, F, I, C.c_double, C.c_uint64, C.c_int64, I, P],
+    "vl_attn_bwd_drop_bf16": [P, P, P, P, P, P, P, P, P, P, P, L, L, I, I, I, I, I, F, I, F, C.c_double, C.c_uint64, C.c_int64, I, P],
+    "vl_ff_drop_fwd": [P, P, P, I, I, I, C.c_double, C.c_uint64, C.c_int64, I, P],
+    "vl_ff_drop_bwd": [P, P, P, I, I, I, C.c_double, C.c_uint64, C.c_int64, I, P],
     # the linear probe (csrc/vl_linprobe.hip)
     "vl_lp_bn_fwd": [P, L, P, F, C.c_uint64, C.c_int64, I, P, P, F, F, P, L, P, L, P, P, I, I, P],
     "vl_ce_label_ws_floats": [I, I],
@@ -143,14 +148,22 @@ def load_library():
     lib = C.CDLL(path)
     lib.vl_last_error.restype = C.c_char_p
     lib.vl_last_error.argtypes = []
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
-        fn.argtypes = args
-        fn.restype = _RET.get(name, I)
+    # the version first, then every symbol: a library built from older sources is named as that, whether it reports another
+    # number or - entries can be ADDED under one number - lacks a symbol of the table (a bare AttributeError said nothing)
+    lib.vl_version.argtypes, lib.vl_version.restype = [], I
     got = int(lib.vl_version())
+    rebuild = "rebuild the library (`make -C vit-lens_amd/csrc`)"
     if got != ABI_VERSION:
         raise RuntimeError(f"{path} reports ABI version {got}, this binding was written for {ABI_VERSION} "
-                           "(include/vitlens_hip.h: VL_ABI_VERSION): rebuild the library (`make -C vit-lens_amd/csrc`)")
+                           f"(include/vitlens_hip.h: VL_ABI_VERSION): {rebuild}")
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f"{path} (ABI version {got}) does not export {', '.join(missing)}: it was built from older sources "
+                           f"than this binding - {rebuild}")
+    for name, args in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = _RET.get(name, I)
     _LIB = lib
     return lib
 

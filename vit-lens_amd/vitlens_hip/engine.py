@@ -690,6 +690,26 @@ class LensCfg:
     eeg_window_size: int = 1
     eeg_stride: int = 1
     weight_tie_layers: bool = False    # perceiver.py:249-254: layers >= 1 share one set of modules
+    attn_dropout: float = 0.0          # --perceiver_attn_dropout: on the probabilities of every cross / latent attention
+    ff_dropout: float = 0.0            # --perceiver_ff_dropout: behind the second Linear of every FeedForward (train mode only)
+
+
+@dataclass(frozen=True)
+class LensDrop:
+    """One train-mode forward's dropout draw in the Perceiver - numbers, never masks: the Philox seed, the per-sample number of
+    batch row 0 (step.drop_sample0 with DROP_TOWER_LENS) and the two probabilities.  The forward, the backward and any
+    recompute that are handed the same LensDrop draw the same bits (csrc/vl_lens_drop.hip has the counter layout)."""
+    seed: int
+    sample0: int
+    pa: float = 0.0
+    pf: float = 0.0
+
+
+def lens_sublayer(c: "LensCfg", li: int, sj: int = -1, ff: bool = False) -> int:
+    """The position of a sub-layer in the Perceiver's forward, the `sublayer` word of its dropout draw: layer li's cross
+    attention (sj = -1) or its sj-th latent self-attention, or the FeedForward behind it.  Weight-tied layers share modules,
+    not positions: every call draws a mask of its own, as nn.Dropout does."""
+    return li * (2 + 2 * c.self_per_cross) + 2 * (sj + 1) + (1 if ff else 0)
 
 
 def _interleave_geglu(w: torch.Tensor, b: torch.Tensor):
@@ -754,6 +774,14 @@ class Bf16Arith:
     def attn(self, q, k, v, out, lse, dh):
         ops.attn_fwd(q, k, v, out, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
 
+    # train mode with dropout (LensDrop): the attention with the mask on its probabilities, and a down-projection that leaves
+    # its fp32 output apart from the residual for ops.ff_drop_fwd
+    def attn_drop(self, q, k, v, out, lse, dh, drop, sublayer):
+        ops.attn_fwd_drop(q, k, v, out, drop.pa, drop.seed, drop.sample0, sublayer, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
+
+    def linear_f32(self, a, w, b, out):
+        ops.gemm(a, w, b, out=out, epi=ops.EPI_F32, cfg=self.cfg)
+
 
 @dataclass
 class LensAttnSlots:
@@ -788,6 +816,7 @@ class LensFFSlots:
     hid: torch.Tensor                          # geglu(...)
     stats: Optional[tuple] = None
     h: Optional[torch.Tensor] = None           # the GEGLU's pre-activation
+    y: Optional[torch.Tensor] = None           # ff_dropout > 0: the down-projection's fp32 output in front of the mask
 
 
 def perceiver_residuals(c: LensCfg) -> int:
@@ -835,23 +864,40 @@ def perceiver_slots(c: LensCfg, B, Tc, device, dtype, X=None):
         return LensAttnSlots(x0=X[i], x1=X[i + 1], hn=hn, q2=q2, kv2=kv2, q=q, k=k, v=v, a=a, cn=cn, stats=st, cstats=cst, lse=lse,
                              av=by_heads(a), dOm=dOm, dO=by_heads(dOm), delta=delta)
 
+    # ONE fp32 [R, D] buffer for every FeedForward of these slots, of a trainer too.  Forward: the down-projection's output, dead
+    # once the row kernel has added its masked copy to the residual - the backward redraws the mask and never reads it.
+    # Backward (PerceiverTrainer._ff_bwd): scratch for the unrounded branch gradient, written and column-summed within one
+    # sub-layer.  So nothing may expect y to hold a value across sub-layers; every trainer owns its own slots.
+    y = new(R, D, dt=f32) if c.ff_dropout > 0.0 else None
+
     def ff():
         i = next(xi)
         st, h = stats(R), new(R, 8 * D) if save else None
-        return LensFFSlots(x0=X[i], x1=X[i + 1], hn=tmp("h", R, D), hid=tmp("hid", R, 4 * D), stats=st, h=h)
+        return LensFFSlots(x0=X[i], x1=X[i + 1], hn=tmp("h", R, D), hid=tmp("hid", R, 4 * D), stats=st, h=h, y=y)
     layers = [{"x_attn": attn(c.cross_heads, c.cross_dim_head, True), "x_ff": ff(),
                "selfs": [{"attn": attn(c.latent_heads, c.latent_dim_head, False), "ff": ff()} for _ in range(c.self_per_cross)]}
               for _ in range(c.depth)]
     return X, layers
 
 
-def perceiver_forward(layers, slots, data, B, c: LensCfg, ar):
+def perceiver_forward(layers, slots, data, B, c: LensCfg, ar, drop: Optional[LensDrop] = None):
     """Perceiver.forward(return_embeddings=True) behind the latents' broadcast (open_clip/perceiver.py:289-328,
     fourier_encode_data=False) with the operands `layers` (perceiver_operands) on the buffers `slots` (perceiver_slots) in the
     arithmetic `ar` (linear / geglu / attn: Bf16Arith, f32.F32Arith).  Per layer: cross attention of the latents over
     data [B*Tc, C], FeedForward, then self_per_cross x (latent self-attention, FeedForward), each with its residual.  The one
-    forward of the engines and the trainer: it branches on what it is given, never on who calls."""
+    forward of the engines and the trainer: it branches on what it is given, never on who calls.
+
+    drop (a train-mode forward: LensDrop): with drop.pa > 0 every attention drops probabilities (ar.attn_drop), with
+    drop.pf > 0 every FeedForward's down-projection leaves its fp32 output in s.y and a row kernel adds its masked, scaled
+    copy to the residual (perceiver.py:91-102, 105-154).  None - eval mode, or both probabilities 0 - is the calls without
+    it, to the same symbols in the same order."""
     rows, D = B * c.num_latents, c.latent_dim
+    pa, pf = (drop.pa, drop.pf) if drop is not None else (0.0, 0.0)
+    if (pa > 0.0 or pf > 0.0) and not hasattr(ar, "attn_drop"):
+        raise ValueError("perceiver_forward: dropout runs on bf16 operands only (the fp32 engines are eval-only and never drop)")
+    if pf > 0.0 and any(S["x_ff"].y is None for S in slots):
+        raise ValueError("perceiver_forward: ff dropout needs slots built for a LensCfg with ff_dropout > 0")
+    sub = iter(range(perceiver_residuals(c) - 1))       # every sub-layer's position in this forward
 
     def attn(w, norm, s, dh, norm_ctx=None):
         if ("qkv_w" in w) != (s.kv2 is None):
@@ -865,14 +911,23 @@ def perceiver_forward(layers, slots, data, B, c: LensCfg, ar):
             ops.layernorm(data, norm_ctx[0], norm_ctx[1], s.cn, data.shape[0], c.input_chan, mean=m, rstd=r)
             ar.linear(s.hn, w["q_w"], None, s.q2)
             ar.linear(s.cn, w["kv_w"], None, s.kv2)
-        ar.attn(s.q, s.k, s.v, s.a, s.lse, dh)
+        k = next(sub)
+        if pa > 0.0:
+            ar.attn_drop(s.q, s.k, s.v, s.a, s.lse, dh, drop, k)
+        else:
+            ar.attn(s.q, s.k, s.v, s.a, s.lse, dh)
         ar.linear(s.a, w["to_out_w"], w["to_out_b"], s.x1, res=s.x0)
 
     def ff(w, norm, s):
         m, r = s.stats or (None, None)
         ops.layernorm(s.x0, norm[0], norm[1], s.hn, rows, D, mean=m, rstd=r)
         ar.geglu(s.hn, w["w0"], w["b0"], s.hid, s.h)
-        ar.linear(s.hid, w["w2"], w["b2"], s.x1, res=s.x0)
+        k = next(sub)
+        if pf > 0.0:
+            ar.linear_f32(s.hid, w["w2"], w["b2"], s.y)
+            ops.ff_drop_fwd(s.y, s.x0, s.x1, B, c.num_latents, pf, drop.seed, drop.sample0, k)
+        else:
+            ar.linear(s.hid, w["w2"], w["b2"], s.x1, res=s.x0)
 
     for lay, S in zip(layers, slots):
         attn(lay["x_attn"], lay["x_norm"], S["x_attn"], c.cross_dim_head, lay["x_norm_ctx"])
@@ -887,6 +942,7 @@ class PerceiverEngine:
 
     def __init__(self, sd, prefix: str, cfg: LensCfg, device, gemm_cfg=-1, arith=None):
         self.cfg, self.device, self.gemm_cfg = cfg, torch.device(device), gemm_cfg
+        ops.check_dropout_p(cfg.attn_dropout, "perceiver_attn_dropout"); ops.check_dropout_p(cfg.ff_dropout, "perceiver_ff_dropout")
         self.arith = Bf16Arith(gemm_cfg) if arith is None else arith
         self.latents = _dev(sd[prefix + "latents"], device)
         self.layers = perceiver_operands(sd, prefix, cfg, device, self.arith.dtype)
@@ -897,14 +953,23 @@ class PerceiverEngine:
         self.latents.copy_(sd[prefix + "latents"].detach())
         copy_tree(self.layers, perceiver_operands(sd, prefix, self.cfg, self.device, self.arith.dtype))
 
-    def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
-        """data [B*Tc, C] (bf16|f32; f32 for the fp32 arithmetic) -> latents [B*n, D] f32 (view of an internal workspace)."""
+    def draw(self, seed: int, sample0: int) -> Optional[LensDrop]:
+        """The dropout draw of ONE train-mode forward whose batch row 0 has the per-sample number `sample0`; None when the
+        configuration drops nothing, so that the default is the code path without the argument."""
+        c = self.cfg
+        if not (c.attn_dropout > 0.0 or c.ff_dropout > 0.0):
+            return None
+        return LensDrop(int(seed), int(sample0), float(c.attn_dropout), float(c.ff_dropout))
+
+    def forward(self, data: torch.Tensor, B: int, drop: Optional[LensDrop] = None) -> torch.Tensor:
+        """data [B*Tc, C] (bf16|f32; f32 for the fp32 arithmetic) -> latents [B*n, D] f32 (view of an internal workspace).
+        drop: a train-mode forward without autograd (nn.Dropout follows .training, not requires_grad)."""
         c, key = self.cfg, (B, data.shape[0] // B)
         if key not in self._ws:
             self._ws[key] = perceiver_slots(c, *key, self.device, self.arith.dtype)
         X, slots = self._ws[key]
         X[0].view(B, c.num_latents, c.latent_dim).copy_(self.latents)          # repeat(latents, 'n d -> b n d')
-        perceiver_forward(self.layers, slots, data, B, c, self.arith)
+        perceiver_forward(self.layers, slots, data, B, c, self.arith, drop)
         return X[-1]
 
 
@@ -985,8 +1050,10 @@ class LensEngine:
         """-> (tokens [B*T, C] bf16, pos table [T, C] f32)."""
         return ops.gemm(self.cols(x), self.conv_w, self.conv_b, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
 
-    def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None, **kw) -> torch.Tensor:
-        """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk)."""
+    def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None,
+               drop: Optional[LensDrop] = None, **kw) -> torch.Tensor:
+        """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk).
+        drop (PerceiverEngine.draw): the Perceiver's dropout of a train-mode forward without autograd."""
         B = x.shape[0]
         if self.lens.modality == "pc":
             pend = getattr(self, "_points_pending", None)
@@ -995,7 +1062,7 @@ class LensEngine:
                 self.points = PointTokenizerEngine(pend, self.prefix_adapter, self.lens, self.device, gemm_cfg=self.gemm_cfg)
                 self._points_pending = None
             tok = self.points.forward(x, **kw)                 # already x + pos, [B*G, C] bf16
-            lat = self.perceiver.forward(tok, B)
+            lat = self.perceiver.forward(tok, B, drop)
             f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         else:
             tok, pos = self.tokens(x)
@@ -1005,6 +1072,6 @@ class LensEngine:
                 T = tok.shape[0] // B
                 xin = torch.empty_like(tok)
                 ops.add_rows(tok, pos, xin, tok.shape[0], T, tok.shape[1])
-                lat = self.perceiver.forward(xin, B)
+                lat = self.perceiver.forward(xin, B, drop)
                 f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         return ops.l2_normalize(f) if normalize else f

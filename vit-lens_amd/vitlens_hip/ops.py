@@ -831,6 +831,67 @@ def attn_bwd(q, k, v, dO, o, lse, delta, dq, dk, dv, ld_dq, ld_dkv, causal=False
                                 ld_dq, ld_dkv, B, H, Lq, Lk, dh, float(qs), 1 if causal else 0, float(scale), _stream()))
 
 
+# ---- Perceiver dropout (csrc/vl_lens_drop.hip).  The draw is numbers, never a stored mask: p, the Philox seed, the per-sample
+# number of batch row 0 (step.drop_sample0 with DROP_TOWER_LENS) and the sub-layer's position in the forward.
+def check_dropout_p(p, name: str) -> float:
+    """A dropout probability of the Lens: a float in [0, 1), or a ValueError that names the knob."""
+    p = float(p or 0.0)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name} must be in [0, 1), got {p}")
+    return p
+
+
+def attn_fwd_drop(q, k, v, out, p, seed, sample0, sublayer, lse=None, causal=False, qscale=1.0):
+    """attn_fwd (bf16 operands) with dropout on the probabilities: out = (P * M / (1 - p)) V; the normaliser and lse are
+    attn_fwd's."""
+    B, H, Lq, dh = q.shape
+    st = _bhld_strides(q, k, v)
+    if q.dtype != torch.bfloat16:
+        raise TypeError("attn_fwd_drop: bf16 operands only")
+    check(_lib.vl_attn_fwd_drop_bf16(_p(q), _p(k), _p(v), st, _p(out), _p(lse), B, H, Lq, k.shape[2], dh, float(qscale),
+                                     1 if causal else 0, float(p), int(seed), int(sample0), int(sublayer), _stream()))
+    return out
+
+
+def attn_bwd_drop(q, k, v, dO, o, lse, delta, dq, dk, dv, ld_dq, ld_dkv, p, seed, sample0, sublayer, causal=False,
+                  softmax_scale=None, qscale=None):
+    """attn_bwd (the two-kernel path) for attn_fwd_drop: the mask is redrawn from the same numbers."""
+    B, H, Lq, dh = q.shape
+    scale = dh ** -0.5 if softmax_scale is None else softmax_scale
+    qs = scale * LOG2E if qscale is None else qscale
+    st = _bhld_strides(q, k, v, dO, o)
+    check(_lib.vl_attn_bwd_drop_bf16(_p(q), _p(k), _p(v), _p(dO), _p(o), st, _p(lse), _p(delta), _p(dq), _p(dk), _p(dv),
+                                     ld_dq, ld_dkv, B, H, Lq, k.shape[2], dh, float(qs), 1 if causal else 0, float(scale),
+                                     float(p), int(seed), int(sample0), int(sublayer), _stream()))
+
+
+def _chk_ff_drop(who, B, n, *ts):
+    for t in ts:
+        _chk2d(t, who)
+        if not t.is_contiguous() or t.shape != ts[0].shape or t.shape[0] != B * n:
+            raise ValueError(f"{who}: contiguous [B*n, D] operands of one shape, got {tuple(t.shape)} for B = {B}, n = {n}")
+
+
+def ff_drop_fwd(y, x0, x1, B, n, p, seed, sample0, sublayer):
+    """x1 = x0 + y * M / (1 - p) on f32 [B*n, D] rows (n rows per sample): ff_dropout behind a FeedForward's second Linear."""
+    _chk_ff_drop("ff_drop_fwd", B, n, y, x0, x1)
+    if not (y.dtype == x0.dtype == x1.dtype == torch.float32):
+        raise TypeError("ff_drop_fwd: f32 operands")
+    check(_lib.vl_ff_drop_fwd(_p(y), _p(x0), _p(x1), B, n, y.shape[1], float(p), int(seed), int(sample0), int(sublayer), _stream()))
+    return x1
+
+
+def ff_drop_bwd(dx1, dy, B, n, p, seed, sample0, sublayer, dy_f32=None):
+    """dy bf16 = dx1 f32 * M / (1 - p): the branch's share of the residual gradient, the operand of dW2 and the dGEGLU GEMM;
+    dy_f32 (optional, f32): the same products unrounded - db2 is their column sum."""
+    _chk_ff_drop("ff_drop_bwd", B, n, dx1, dy, *(() if dy_f32 is None else (dy_f32,)))
+    if dx1.dtype != torch.float32 or dy.dtype != torch.bfloat16 or (dy_f32 is not None and dy_f32.dtype != torch.float32):
+        raise TypeError("ff_drop_bwd: dx1 f32, dy bf16, dy_f32 f32")
+    check(_lib.vl_ff_drop_bwd(_p(dx1), _p(dy), _p(dy_f32), B, n, dx1.shape[1], float(p), int(seed), int(sample0), int(sublayer),
+                              _stream()))
+    return dy
+
+
 def attn_bwd_q1(q, k, v, dO, o, lse, dq, dk, dv, ld_dq, ld_dkv, qrow=0, softmax_scale=None):
     """Backward of attn_fwd_q1.  dO, o bf16 [B, H*64]; lse [B, H]; dq / dk / dv: the token-major destinations of attn_bwd.
     Writes dk, dv for every row, dq for row qrow and ZEROS to every other dq row."""

@@ -181,6 +181,7 @@ def _master_to_sd(name: str, m: torch.Tensor, base_sd, cfg) -> Dict[str, torch.T
 
 # ------------------------------------------------------------------------------------------------ patch dropout
 DROP_TOWER_VISUAL, DROP_TOWER_IMAGE = 0, 1      # tower ids of `drop_sample0`
+DROP_TOWER_LENS = 2                             # the Perceiver's own attention / FeedForward dropout (csrc/vl_lens_drop.hip)
 _DROP_OFFSET_BITS, _DROP_TOWER_BITS, _DROP_RANK_BITS, _DROP_STEP_BITS = 20, 2, 14, 27
 
 
@@ -223,11 +224,18 @@ class _StepState:
     with opt.t the number of optimizer steps taken so far (checkpointed by `optimizer_state_dict`).  So two towers, ranks,
     steps or samples never share keys, a resumed run draws what the uninterrupted run would have drawn, and a sample's kept
     set does not depend on the micro-batch size.  (Two forward_backward calls without an optimizer step between them draw the
-    same sets.)  The default 0.0 is the code path without the argument: no launch is added."""
+    same sets.)  The default 0.0 is the code path without the argument: no launch is added.
+
+    perceiver_attn_dropout / perceiver_ff_dropout (--perceiver_attn_dropout, --perceiver_ff_dropout; perceiver.py:91-102, 105-154;
+    the steps whose Lens has a Perceiver): nn.Dropout on the attention probabilities and behind every FeedForward of the Lens.
+    The masks are never stored - forward and backward of a micro-batch, on whichever stream, redraw them from numbers
+    (csrc/vl_lens_drop.hip): the same `drop_seed`, the sample number `drop_sample0(opt.t, rank, DROP_TOWER_LENS = 2, o)` and the
+    sub-layer's position in the forward.  The properties above hold for them in the same way; 0.0 adds no launch."""
 
     def _init_host(self, sd, device, micro_batch, rank, world_size, comm=None, local_loss=False, gather_with_grad=False,
                    force_comm=False, overlap_frozen=False, overlap_backward=True, grad_clip_norm=None,
-                   patch_dropout: float = 0.0, drop_seed: int = 0):
+                   patch_dropout: float = 0.0, drop_seed: int = 0, perceiver_attn_dropout: float = 0.0,
+                   perceiver_ff_dropout: float = 0.0):
         """Everything of a step that is HOST state - flags, the communicator, the (still empty apart from logit_scale) master
         table, the gradient-bucket bookkeeping - and nothing that touches an engine or a kernel.  Every step's `__init__`
         runs this first and then its `_build()` (engines, masters of the trainable set); tests/test_step_gloo.py drives the
@@ -266,6 +274,25 @@ class _StepState:
             assert 0 <= self.patch_dropout < 1.0, f"patch_dropout must be in [0, 1), got {self.patch_dropout}"
             drop_sample0(0, rank, 0, 0)                # (a rank outside the key layout is refused here, not in the first step)
         self.drop_seed = int(drop_seed)
+        # --perceiver_attn_dropout / --perceiver_ff_dropout: nn.Dropout inside the Lens's Perceiver (class docstring)
+        self.perceiver_attn_dropout, self.perceiver_ff_dropout = float(perceiver_attn_dropout or 0.0), float(perceiver_ff_dropout or 0.0)
+        self._lens_drop = False          # a `_build` with a Perceiver that drops sets it (_collect_perceiver)
+        for name in ("perceiver_attn_dropout", "perceiver_ff_dropout"):
+            if not 0.0 <= getattr(self, name) < 1.0:
+                raise ValueError(f"{name} must be in [0, 1), got {getattr(self, name)}")
+        if self.perceiver_attn_dropout > 0.0 or self.perceiver_ff_dropout > 0.0:
+            drop_sample0(0, rank, DROP_TOWER_LENS, 0)
+
+    def _lens_cfg(self, lens):
+        """The step's LensCfg: the caller's, with the step's own Perceiver dropout arguments where they are given."""
+        from dataclasses import replace
+        pa, pf = self.perceiver_attn_dropout, self.perceiver_ff_dropout
+        return replace(lens, attn_dropout=pa or lens.attn_dropout, ff_dropout=pf or lens.ff_dropout)
+
+    def lens_draw(self, offset: int):
+        """The Perceiver dropout draw (engine.LensDrop) of the micro-batch that starts at `offset` of the per-GPU batch at the
+        current optimizer step count, or None when the Lens drops nothing."""
+        return self.lens.perceiver.draw(self.drop_seed, drop_sample0(self.opt.t, self.rank, DROP_TOWER_LENS, offset))
 
     @property
     def last_grad_norm(self):
@@ -482,6 +509,7 @@ class _StepState:
         fv = torch.empty(B, E, device=self.dev); vraw = torch.empty(B, E, device=self.dev)
         vnorm = torch.empty(B, device=self.dev)
         drop = self.patch_dropout > 0.0
+        lens_drop = self._lens_drop
         # the frozen text tower sees the whole per-GPU batch in one pass: 77-token sequences give a micro-batch only 77 row
         # tiles (one uneven round of the persistent GEMM, 600-900 TF/s); four times the rows run whole rounds
         def frozen():
@@ -497,6 +525,8 @@ class _StepState:
             for i in range(nmb):
                 s = slice(i * mb, (i + 1) * mb)
                 kw = dict(zip(("keep", "inv"), self.drop_indices(DROP_TOWER_VISUAL, self.lens.vit, i * mb, mb))) if drop else {}
+                if lens_drop:
+                    kw["drop"] = self.lens_draw(i * mb)
                 vraw[s] = self._trainer(i).forward(*(None if x is None else x[s] for x in inputs), **kw)
         self._side_by_side(frozen, trainable)
         ops.l2_normalize(vraw, out=fv, norms=vnorm)
@@ -911,6 +941,7 @@ class _PerceiverLensStep(_StepState):
 
     def _collect_perceiver(self, sd):
         pe, P = self.lens.perceiver, "visual.perceiver."
+        self._lens_drop = pe.draw(0, 0) is not None
         f32 = lambda k: sd[k].detach().float().to(self.dev).contiguous().clone()
         self.masters[P + "latents"] = pe.latents
         for li, lay in enumerate(pe.layers):
@@ -985,13 +1016,15 @@ class DualAudioStep(_PerceiverLensStep):
                  gather_with_grad: bool = False, train_res_dtype=torch.float32, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
                  grad_clip_norm: Optional[float] = None, contra_loss_type: str = "general", sim_thres: float = 0.8,
-                 patch_dropout: float = 0.0, drop_seed: int = 0):
+                 patch_dropout: float = 0.0, drop_seed: int = 0, perceiver_attn_dropout: float = 0.0,
+                 perceiver_ff_dropout: float = 0.0):
         if contra_loss_type not in ("general", "sim_mask"):
             raise NotImplementedError(f"DualAudioStep: contra_loss_type is 'general' or 'sim_mask', got {contra_loss_type!r} "
                                       "(label_mask cannot run in the reference's drivers either)")
         self.contra_loss_type, self.sim_thres = contra_loss_type, float(sim_thres)
         self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed), (lr, betas, eps, weight_decay),
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed, perceiver_attn_dropout, perceiver_ff_dropout),
+                        (lr, betas, eps, weight_decay),
                         sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                         text_wsplit=text_wsplit, text_arith=text_arith)
 
@@ -1000,7 +1033,7 @@ class DualAudioStep(_PerceiverLensStep):
         from .train import AudioLensTrainer
         device = self.dev
         self.text = TextEngine(sd, text, device, gemm_cfg=gemm_cfg, res_dtype=frozen_res_dtype, wsplit=text_wsplit, arith=text_arith)
-        self.lens = LensEngine(sd, "visual.", tower, lens, device, gemm_cfg=gemm_cfg, res_dtype=train_res_dtype)
+        self.lens = LensEngine(sd, "visual.", tower, self._lens_cfg(lens), device, gemm_cfg=gemm_cfg, res_dtype=train_res_dtype)
         self._mk = lambda: AudioLensTrainer(self.lens)
         self.masters["visual.class_embedding"] = self.lens.vit.cls
         self.masters["visual.visual_adapter.pos_emb"] = self.lens.adapter_pos
@@ -1042,9 +1075,11 @@ class TriModalPCStep(_PerceiverLensStep):
                  frozen_res_dtype=torch.float32, local_loss: bool = False, gather_with_grad: bool = False,
                  train_res_dtype=torch.float32, bn_sync: bool = False, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
                  overlap_frozen: bool = True, overlap_backward: bool = True,
-                 grad_clip_norm: Optional[float] = None, patch_dropout: float = 0.0, drop_seed: int = 0):
+                 grad_clip_norm: Optional[float] = None, patch_dropout: float = 0.0, drop_seed: int = 0,
+                 perceiver_attn_dropout: float = 0.0, perceiver_ff_dropout: float = 0.0):
         self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
-                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed), (lr, betas, eps, weight_decay),
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed, perceiver_attn_dropout, perceiver_ff_dropout),
+                        (lr, betas, eps, weight_decay),
                         sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
                         text_wsplit=text_wsplit, text_arith=text_arith, bn_training=bn_training, bn_sync=bn_sync, unlock_cls=unlock_cls)
 
@@ -1055,6 +1090,7 @@ class TriModalPCStep(_PerceiverLensStep):
         device = self.dev
         self.image = VitEngine(sd, "image.", tower, device, gemm_cfg=gemm_cfg, res_dtype=frozen_res_dtype)
         self.text = TextEngine(sd, text, device, gemm_cfg=gemm_cfg, res_dtype=frozen_res_dtype, wsplit=text_wsplit, arith=text_arith)
+        lens = self._lens_cfg(lens)
         self.lens = LensEngine(sd, "visual.", tower, lens, device, gemm_cfg=gemm_cfg, res_dtype=train_res_dtype)
         self.tok = PointTokenizerTrainer(sd, "visual.visual_adapter.", lens, device, gemm_cfg=gemm_cfg, bn_training=bn_training,
                                          bn_sync=self.comm if bn_sync and self.dist else None, world_size=self.world)

@@ -650,6 +650,7 @@ class PerceiverTrainer:
             self.wT.append(d)
         self.refresh_derived()
         self._st = {}
+        self.drop = None          # the last forward's dropout draw (engine.LensDrop), redrawn by the backward
 
     @staticmethod
     def wT_table(n_selfs: int):
@@ -699,14 +700,16 @@ class PerceiverTrainer:
         return st
 
     # ---- forward ----------------------------------------------------------------------------------
-    def forward(self, data: torch.Tensor, B: int) -> torch.Tensor:
+    def forward(self, data: torch.Tensor, B: int, drop=None) -> torch.Tensor:
         """engine.perceiver_forward into the per-sub-layer slots: residual snapshots, LayerNorm outputs and statistics,
-        projection outputs, lse, GEGLU pre-activation and output are what the backward reads."""
+        projection outputs, lse, GEGLU pre-activation and output are what the backward reads.  drop (engine.LensDrop, from
+        PerceiverEngine.draw): this forward's dropout; the backward keeps the numbers and redraws the masks from them."""
         pe, c = self.pe, self.pe.cfg
         st = self._state(B, data.shape[0] // B)
         st["X"][0].view(B, c.num_latents, c.latent_dim).copy_(pe.latents)
-        _engine.perceiver_forward(pe.layers, st["layers"], data, B, c, pe.arith)
+        _engine.perceiver_forward(pe.layers, st["layers"], data, B, c, pe.arith, drop)
         self.ctx = (B, data.shape[0] // B, data)
+        self.drop = drop
         return st["X"][-1]
 
     # ---- backward ---------------------------------------------------------------------------------
@@ -722,14 +725,25 @@ class PerceiverTrainer:
         ops.layernorm_bwd_params(dy, x, stats[0], stats[1], self.grad_buffer(name + ".weight", (D,)),
                                  self.grad_buffer(name + ".bias", (D,)), rows, D)
 
-    def _ff_bwd(self, st, s, norm, wT, pname):
+    def _ff_bwd(self, st, s, norm, wT, pname, sub=0):
         """x1 = x0 + W2 geglu(W0 LN(x0) + b0) + b2 on the slots `s` ; st['dx'] holds dL/dx1 on entry, dL/dx0 on exit.
-        s.hn = LN(x0), s.h = the GEGLU's pre-activation, s.hid = geglu(...) as the forward left them."""
+        s.hn = LN(x0), s.h = the GEGLU's pre-activation, s.hid = geglu(...) as the forward left them.  With ff dropout
+        (sub = the sub-layer's position in the forward) the branch sees the masked, scaled gradient, the residual the whole."""
         cfg, (rows, D) = self.pe.gemm_cfg, s.x0.shape
         # (dy = the bf16 copy of the residual gradient the dX GEMMs read: token-major operands for the dW kernel - the fp32
         #  stream would be rounded to the same bf16 values on its way through a transposed copy)
-        self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
-        ops.colsum(st["dx"], self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
+        drop = self.drop
+        if drop is not None and drop.pf > 0.0:
+            # st['dxb'] becomes the branch gradient dx1 M / (1 - pf) (the LayerNorm backward below rewrites it): dW2 and the
+            # dGEGLU GEMM read that one; db2 is the column sum of its unrounded copy, in the forward's free s.y (p = 0 sums
+            # the fp32 residual gradient there, not a bf16 copy)
+            n = self.pe.cfg.num_latents
+            ops.ff_drop_bwd(st["dx"], st["dxb"], rows // n, n, drop.pf, drop.seed, drop.sample0, sub, dy_f32=s.y)
+            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
+            ops.colsum(s.y, self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
+        else:
+            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
+            ops.colsum(st["dx"], self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
         ops.gemm(st["dxb"], wT["w2"], None, out=st["dh8"], res=s.h, epi=ops.EPI_DGEGLU, cfg=cfg)     # d(pre-activation), interleaved
         self._dw(pname + "1.fn.net.0.weight_il", st["dh8"], s.hn, rows)
         ops.colsum(st["dh8"], self.grad_buffer(pname + "1.fn.net.0.bias_il", (8 * D,)))
@@ -737,7 +751,7 @@ class PerceiverTrainer:
         self._ln_params(pname + "1.norm", st["dhn"], s.x0, s.stats, rows, D)
         ops.layernorm_bwd(st["dhn"], s.x0, s.stats[0], s.stats[1], norm[0], rows, D, dres=st["dx"], dx=st["dx"], dx_bf16=st["dxb"])
 
-    def _attn_bwd(self, st, s, norm, wT, pname, dq, dkv=None, data=None, norm_ctx=None):
+    def _attn_bwd(self, st, s, norm, wT, pname, dq, dkv=None, data=None, norm_ctx=None, sub=0):
         """x1 = x0 + to_out(attn(to_q(LN(x0)), to_kv(context))) on the slots `s` ; st['dx'] holds dL/dx1 on entry, dL/dx0 on exit.
         Latent self-attention (dkv None; the context is LN(x0) itself): dq is the packed [dq|dk|dv], one to_qkv gradient with
         rows [to_q ; to_kv].  Cross attention: dq and dkv = [dk|dv] apart, and the context side LN_ctx(data) -> to_kv, whose
@@ -747,10 +761,13 @@ class PerceiverTrainer:
         self._dw(pname + "0.fn.to_out.weight", st["dxb"], s.a, rows)
         ops.colsum(st["dx"], self.grad_buffer(pname + "0.fn.to_out.bias", (D,)))
         ops.gemm(st["dxb"], wT["out"], None, out=s.dOm, epi=ops.EPI_BF16, cfg=cfg)
-        if packed:
-            ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dq[:, inner:], dq[:, 2 * inner:], 3 * inner, 3 * inner)
+        dk, dv, lds = (dq[:, inner:], dq[:, 2 * inner:], (3 * inner, 3 * inner)) if packed else (dkv, dkv[:, inner:], (inner, 2 * inner))
+        drop = self.drop
+        if drop is not None and drop.pa > 0.0:
+            # (the two-kernel backward also where p = 0 has the one-kernel one: sub = the sub-layer's position in the forward)
+            ops.attn_bwd_drop(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dk, dv, *lds, drop.pa, drop.seed, drop.sample0, sub)
         else:
-            ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dkv, dkv[:, inner:], inner, 2 * inner)
+            ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dk, dv, *lds)
         # query side: LN(x0) -> to_q (packed: -> [to_q ; to_kv])
         self._dw(pname + ("0.fn.to_qkv.weight" if packed else "0.fn.to_q.weight"), dq, s.hn, rows)
         ops.gemm(dq, wT["qkv" if packed else "q"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
@@ -778,10 +795,11 @@ class PerceiverTrainer:
             pn = f"{self.P}layers.{self.layer_name(li)}."
             for sj in reversed(range(c.self_per_cross)):
                 sl, T, w = lay["selfs"][sj], S["selfs"][sj], wT["selfs"][sj]
-                self._ff_bwd(st, T["ff"], sl["ff_norm"], w, f"{pn}2.{sj}.")
-                self._attn_bwd(st, T["attn"], sl["norm"], w, f"{pn}2.{sj}.", st["dqkv"])
-            self._ff_bwd(st, S["x_ff"], lay["x_ff_norm"], wT["xff"], pn)
-            self._attn_bwd(st, S["x_attn"], lay["x_norm"], wT["x"], pn, st["dq"], st["dkv"], data, lay["x_norm_ctx"])
+                self._ff_bwd(st, T["ff"], sl["ff_norm"], w, f"{pn}2.{sj}.", sub=_engine.lens_sublayer(c, li, sj, ff=True))
+                self._attn_bwd(st, T["attn"], sl["norm"], w, f"{pn}2.{sj}.", st["dqkv"], sub=_engine.lens_sublayer(c, li, sj))
+            self._ff_bwd(st, S["x_ff"], lay["x_ff_norm"], wT["xff"], pn, sub=_engine.lens_sublayer(c, li, ff=True))
+            self._attn_bwd(st, S["x_attn"], lay["x_norm"], wT["x"], pn, st["dq"], st["dkv"], data, lay["x_norm_ctx"],
+                           sub=_engine.lens_sublayer(c, li))
         n, D = c.num_latents, c.latent_dim
         ops.batch_rowsum(st["dx"], self.grad_buffer(self.P + "latents", (n, D)), B, n, D, n, 0)
         return st["ddata"]
@@ -829,16 +847,16 @@ class AudioLensTrainer:
     def _conv_bias_grad(self, ddata):
         pass                                          # (the AST convolution's bias is not in the trainable set)
 
-    def forward(self, x: torch.Tensor, keep=None, inv=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, keep=None, inv=None, drop=None) -> torch.Tensor:
         """keep / inv: patch dropout on the Perceiver's latents, the tokens that enter the ViT trunk; tokenizer and Perceiver
-        stay dense."""
+        stay dense.  drop (PerceiverEngine.draw): the Perceiver's own attention / FeedForward dropout."""
         le = self.le
         B = x.shape[0]
         cols, tok = self._tokens(x)
         T = tok.shape[0] // B
         xin = torch.empty_like(tok)
         ops.add_rows(tok, le.adapter_pos, xin, tok.shape[0], T, tok.shape[1])
-        lat = self.perc.forward(xin, B)
+        lat = self.perc.forward(xin, B, drop)
         self.ctx = (cols, B, T)
         return self.tower.forward(lat, B, keep=keep, inv=inv)
 
@@ -883,12 +901,13 @@ class PCLensTrainer:
     def grads(self):
         return self.tower.grads
 
-    def forward(self, pts: torch.Tensor, fps_start=None, keep=None, inv=None, **kw) -> torch.Tensor:
+    def forward(self, pts: torch.Tensor, fps_start=None, keep=None, inv=None, drop=None, **kw) -> torch.Tensor:
         """pts [B,N,3] (PointBERT tokenizer) or point features [B,N,in_dim] with xyz=[B,N,3] (pnsa tokenizer).
-        keep / inv: patch dropout on the Perceiver's latents (TowerTrainer.forward)."""
+        keep / inv: patch dropout on the Perceiver's latents (TowerTrainer.forward); drop: the Perceiver's own dropout
+        (PerceiverEngine.draw)."""
         B = pts.shape[0]
         ctx = self.tok.forward(pts, fps_start=fps_start, **kw)    # tokens (+ pos), bf16 [B*G, C]
-        return self.tower.forward(self.perc.forward(ctx, B), B, keep=keep, inv=inv)
+        return self.tower.forward(self.perc.forward(ctx, B, drop), B, keep=keep, inv=inv)
 
     def backward(self, dfeat: torch.Tensor):
         self.tok.backward(self.perc.backward(self.tower.backward(dfeat)))
