@@ -419,7 +419,8 @@ int vl_attn_bwd_q1(const void* q, const void* k, const void* v, const long* stri
  * NOTE on the version: these four entries were added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py pins, so a
  * library built before them reports the same number and does not have them.  A client that calls them must look the
  * symbols up when it loads the library (the Python binding does: vitlens_hip/_lib.py names a library that lacks a symbol of its
- * table as stale); the next change to this header bumps the number and ends the overlap.
+ * table as stale).  vl_pc_augment below was added under 610 in the same way; the next change of an EXISTING entry bumps the
+ * number and ends the overlap.
  *
  * vl_attn_fwd_drop_bf16: vl_attn_fwd_bf16 (same operands, strides[9], qscale, token-major out, lse) with
  * out = (P * M / (1 - p)) V.  The softmax normaliser is the sum over ALL keys and lse is what vl_attn_fwd_bf16 writes; the
@@ -475,6 +476,34 @@ int vl_fps(const float* xyz, const int64_t* start, int64_t* idx, float* centers,
 /* pc_norm after a gather (modal_3d/processors/pc_processor.py:32-38, PCProcessorEval :60-88): out [B,G,C] f32 =
  * (pts[b, idx[b,g], :] - centroid) / max distance from the centroid over the G selected points; idx NULL = all N points. */
 int vl_pc_gather_normalize(const float* pts, const int64_t* idx, float* out, int B, int N, int G, int C, hipStream_t stream);
+/* The training transform of the 3D recipes after the sampling (csrc/vl_pc_augment.hip), one launch per batch, out of place:
+ * ViT-Lens' pc_norm + random_point_dropout + random_scale / shift / rotate_perturbation / rotate_point_cloud
+ * (open_clip/modal_3d/datasets.py:97-204, 471-479) and OpenShape's normalize_pc + augment_pc + random_rotate_z + colour drop
+ * (VitLens-OpenShape/src/data.py:74-88).  pts [B,N,C] f32, 3 <= C <= 8, xyz first; idx [B,G] int64 (vl_fps' result or a
+ * random subset; an index outside [0, N) is clamped into it), NULL = all points (then G == N); out [B,G,C] f32.
+ * params: DEVICE array of one 64-byte record per sample, 16 little-endian 32-bit words:
+ *     words  0 ..  8   float A[9]       row-major 3x3
+ *     words  9 .. 11   float t[3]
+ *     word  12         float drop_ratio in [0, 1], or -1: nothing is dropped (0 still drops a point whose u is 0)
+ *     word  13         int32 flags      1 = normalise, 2 = normalize_pc's guard, 4 = fill the feature channels
+ *     words 14 .. 15   uint64 seed
+ * Output point j of sample b, in this order:
+ *   1. p = pts[b, idx[b,j], :]
+ *   2. flags & 1: xyz = (xyz - mean) / r, mean and r = largest distance from it over the G selected points; with flags & 2
+ *      as well r < 1e-6 gives xyz = 0 (normalize_pc), without it the division is done as it comes (pc_norm)
+ *   3. u_j = (w >> 8) 2^-24, w = word j % 4 of Philox4x32-10 with key (lo32(seed), hi32(seed)), counter (j / 4, 0, 0, 0);
+ *      u_j <= drop_ratio (fp32, the reference's <=): the point takes the xyz of output point 0 after step 2
+ *   4. xyz_out[c] = fma(x, A[c], fma(y, A[3 + c], fma(z, A[6 + c], t[c])))      (xyz . A + t)
+ *   5. channels 3 .. C-1 are copied, or all set to feat_fill with flags & 4
+ * Refused with a status, nothing launched: a bad shape, a null pts / out / params, idx NULL with G != N, pts == out.  The
+ * records live in device memory, where the entry cannot look at them without a read-back: a drop_ratio outside [0, 1] (but
+ * -1) is refused where the records are packed on the host (vitlens_hip.ops.pc_augment_params); the kernel's comparison is
+ * defined for every value.  Stream-ordered, no global state, no host synchronisation.
+ * NOTE on the version: like the four Perceiver-dropout entries above, this entry was added under VL_ABI_VERSION 610, which
+ * tests/test_linprobe_host.py pins: a library built before it reports the same number and lacks the symbol, and a client must
+ * look it up when it loads the library (vitlens_hip/_lib.py does, and names such a library as stale). */
+int vl_pc_augment(const float* pts, const int64_t* idx, float* out, int B, int N, int G, int C, const void* params,
+                  float feat_fill, hipStream_t stream);
 /* ---- evaluation-time image / depth preprocessing (csrc/vl_preproc.hip) ----
  * Separable bicubic resampling restricted to a crop window, tables built by the host (vitlens_hip/preproc.py):
  * bounds [n_out,2] int32 = (first tap, tap count) and coefficients [n_out,ksize] per OUTPUT index of the full resized

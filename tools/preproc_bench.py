@@ -4,6 +4,8 @@ GPU side: bytes already resident in HBM (the image transform's two kernels per i
 host->device copy of each decoded image inside the timed region.  CPU side ("port" of what the reference's data-loader
 workers run): Pillow bicubic resize + crop + torch ToTensor/Normalize for images, F.interpolate for disparity maps,
 one thread.  Prints one JSON object; `python tools/preproc_bench.py > gpurun_out/preproc_bench.json`."""
+# `--pc-train-only` prints the row of the 3D training transform alone (PCProcessorTrain against the numpy restatement of the
+# reference's five passes on the host's cores)
 import json
 import os
 import sys
@@ -31,7 +33,50 @@ def gpu_time(fn, n_warm=1):
     return e0.elapsed_time(e1) * 1e-3
 
 
+def pc_train_row(B=1024, N=8192, threads=16):
+    """PCProcessorTrain.process_batch at B x N points, every point selected (a permutation per cloud, already on the GPU), next
+    to the reference's loader-side work on the same clouds: pc_norm + random_point_dropout + scale + shift + the two
+    rotations in numpy (tests/pc_augment_ref.py, pinned to the reference), on one thread and on a pool of `threads`."""
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pc_augment_ref as R
+    from open_clip.modal_3d.processors.pc_processor import PCProcessorTrain
+    from vitlens_hip import ops
+    host = np.random.default_rng(1).normal(size=(B, N, 3)).astype(np.float32)
+    pcs = torch.from_numpy(host).cuda()
+    sub = torch.stack([torch.randperm(N) for _ in range(B)]).cuda()
+    proc = PCProcessorTrain(npoint=N, uniform=True, seed=0)
+    row = {"n": B, "in": [N, 3], "npoint": N}
+    params = ops.pc_augment_params(proc.draw_records(B), "cuda")
+    s = min(gpu_time(lambda: ops.pc_augment(pcs, sub, params), n_warm=2) for _ in range(5))
+    row["gpu_kernel_us_per_batch"] = round(s * 1e6, 1)
+    row["gpu_kernel_gb_per_s"] = round(B * N * (12 + 12 + 8) / s / 1e9, 1)          # points read, points written, indices read
+    proc.process_batch(pcs, subset=sub); torch.cuda.synchronize()
+    t0 = time.perf_counter(); proc.process_batch(pcs, subset=sub); torch.cuda.synchronize()
+    row["gpu_process_batch_ms"] = round((time.perf_counter() - t0) * 1e3, 2)         # with the host's B draws and their upload
+    t0 = time.perf_counter(); proc.draw_records(B)
+    row["host_draws_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3, 2)
+
+    def one(b):
+        rng = np.random.RandomState(b)
+        return R.vitlens_pipeline(R.pc_norm(host[b]), R.draw_reference(N, "vitlens", rng))
+
+    n_cpu = min(B, 256)
+    t0 = time.perf_counter()
+    for b in range(n_cpu):
+        one(b)
+    row["cpu_1thread_ms_per_batch"] = round((time.perf_counter() - t0) / n_cpu * B * 1e3, 1)
+    with ThreadPoolExecutor(threads) as pool:
+        t0 = time.perf_counter(); list(pool.map(one, range(B)))
+        row[f"cpu_{threads}threads_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3, 1)
+    row[f"cpu_1thread_over_{threads}_ms_per_batch"] = round(row["cpu_1thread_ms_per_batch"] / threads, 1)   # perfect scaling
+    return row
+
+
 def main():
+    if "--pc-train-only" in sys.argv[1:]:
+        print(json.dumps({"pc_train": pc_train_row()}))
+        return
     N, H, W = 256, 375, 500                                                       # ImageNet-typical decoded size
     rng = np.random.default_rng(0)
     host = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(N)]
@@ -108,6 +153,7 @@ def main():
     start = np.zeros(B, dtype=np.int64)
     s = gpu_time(lambda: pp.process_batch(pcs, start=start))
     res["pc"] = {"n": B, "in": [10000, 3], "npoint": 8192, "gpu_resident_clouds_per_s": round(B / s, 1)}
+    res["pc_train"] = pc_train_row()
     print(json.dumps(res))
 
 

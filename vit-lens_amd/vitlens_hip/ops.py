@@ -3,6 +3,7 @@ torch stream and returns immediately.  Inputs must live on a GPU: there is no CP
 import ctypes as C
 import threading
 
+import numpy as np
 import torch
 
 from ._lib import load_library, check
@@ -1003,6 +1004,52 @@ def pc_gather_normalize(pts, idx=None):
     out = torch.empty(B, G, Cc, device=pts.device, dtype=torch.float32)
     check(_lib.vl_pc_gather_normalize(_p(pts.contiguous()), _p(idx.contiguous() if idx is not None else None), _p(out), B, N, G, Cc,
                                       _stream()))
+    return out
+
+
+# one record per sample, as csrc/vl_pc_augment.hip reads it (64 bytes; include/vitlens_hip.h spells the layout out)
+PC_AUGMENT_DTYPE = np.dtype([("A", "<f4", (9,)), ("t", "<f4", (3,)), ("drop_ratio", "<f4"), ("flags", "<i4"), ("seed", "<u8")])
+PC_NORMALIZE, PC_NORM_GUARD, PC_FEAT_FILL = 1, 2, 4          # bits of `flags`
+
+
+def pc_augment_pack(rows) -> np.ndarray:
+    """rows: a PC_AUGMENT_DTYPE array (or per sample (A[9], t[3], drop_ratio, flags, seed)) -> int32 [B, 16], the words of the
+    records.  A drop_ratio outside [0, 1] is refused here, on the host, where the records can still be looked at; -1 is
+    admitted and means that nothing is dropped (0 still drops a point whose u is exactly 0, as the reference's <= does)."""
+    a = rows if isinstance(rows, np.ndarray) and rows.dtype == PC_AUGMENT_DTYPE else np.array([tuple(r) for r in rows], dtype=PC_AUGMENT_DTYPE)
+    a = np.ascontiguousarray(a.reshape(-1))
+    r = a["drop_ratio"]
+    if not np.all(((r >= 0) & (r <= 1)) | (r == -1)):
+        raise ValueError(f"pc_augment_params: drop_ratio must be in [0, 1] (or -1: drop nothing), got {r.tolist()}")
+    return a.view(np.int32).reshape(len(a), 16)
+
+
+def pc_augment_params(rows, device) -> torch.Tensor:
+    """The device array vl_pc_augment reads (int32 [B, 16]) from the records of `pc_augment_pack`, uploaded from pinned
+    memory without waiting for the copy."""
+    words = torch.from_numpy(pc_augment_pack(rows))
+    device = torch.device(device)
+    if device.type == "cuda":
+        words = words.pin_memory()
+    return words.to(device, non_blocking=True)
+
+
+def pc_augment(pts, idx, params, feat_fill=0.4):
+    """The 3D training transform in one launch (vl_pc_augment): pts [B,N,C] f32, idx [B,G] int64 or None (all points), params
+    int32 [B,16] from `pc_augment_params` -> [B,G,C] f32 = gather, normalise, point dropout, xyz . A + t, feature fill."""
+    if pts.dim() != 3 or pts.dtype != torch.float32:
+        raise ValueError(f"pc_augment: pts must be f32 [B, N, C], got {tuple(pts.shape)} {pts.dtype}")
+    B, N, Cc = pts.shape
+    if idx is not None and (idx.dim() != 2 or idx.shape[0] != B or idx.dtype != torch.int64 or idx.device != pts.device):
+        raise ValueError(f"pc_augment: idx must be int64 [B, G] on the device of pts, got {tuple(idx.shape)} {idx.dtype}")
+    if params.shape != (B, 16) or params.dtype != torch.int32 or params.device != pts.device:
+        raise ValueError(f"pc_augment: params must be int32 [B, 16] on the device of pts, got {tuple(params.shape)} {params.dtype}")
+    G = N if idx is None else idx.shape[1]
+    if B < 1 or N < 1 or G < 1:      # (the entry refuses these too; nothing of size 0 is allocated first)
+        raise RuntimeError(f"libvitlens_hip: vl_pc_augment: bad shape (B, N, G >= 1, 3 <= C <= 8): B={B} N={N} G={G} C={Cc}")
+    out = torch.empty(B, G, Cc, device=pts.device, dtype=torch.float32)
+    check(_lib.vl_pc_augment(_p(pts.contiguous()), _p(idx.contiguous() if idx is not None else None), _p(out), B, N, G, Cc,
+                             _p(params.contiguous()), float(feat_fill), _stream()))
     return out
 
 
