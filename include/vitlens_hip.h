@@ -504,6 +504,44 @@ int vl_pc_gather_normalize(const float* pts, const int64_t* idx, float* out, int
  * look it up when it loads the library (vitlens_hip/_lib.py does, and names such a library as stale). */
 int vl_pc_augment(const float* pts, const int64_t* idx, float* out, int B, int N, int G, int C, const void* params,
                   float feat_fill, hipStream_t stream);
+/* The training transform of the depth recipe (csrc/vl_rgbd_augment.hip), one call per batch of n RGB-D samples of any sizes:
+ * ToTensor + DepthNorm + RandomResizedCrop(S, bilinear) + RandomHorizontalFlip + ColorJitter3d + RandomErasing + Normalize
+ * (modal_depth/processors/vt_processor.py:94-207; RandAugment3d leaves a 4-channel tensor as it is).  out_rgb [n,3,S,S] and
+ * out_depth [n,1,S,S] f32.  Every random scalar is drawn by the host and arrives in the sample's record.
+ * records: DEVICE array of one 136-byte record per sample, 34 little-endian 32-bit words:
+ *     words  0 ..  1   uint64 rgb          device pointer, uint8 [H,W,3]
+ *     words  2 ..  3   uint64 depth        device pointer, float32 [H,W]
+ *     word   4         int32 rgb_stride    bytes per row of rgb
+ *     word   5         int32 depth_stride  floats per row of depth
+ *     words  6 ..  7   int32 H, W
+ *     words  8 .. 11   int32 top, left, bh, bw     the crop box, inside the image
+ *     words 12 .. 13   int32 row0, nrows   the rows of the box, counted from top, that the vertical taps touch
+ *     words 14 .. 16   int32 hb, hw, hks   horizontal table (bw -> S): offsets of its bounds [S,2] int32 and weights [S,hks]
+ *                                          f32 in `tables`, counted in 32-bit words, and the taps per row
+ *     words 17 .. 19   int32 vb, vw, vks   the same for the vertical table (bh -> S)
+ *     words 20 .. 21   int64 tmp           offset of the sample's [nrows,S] intermediate in `tmp`, counted in float4
+ *     word  22         int32 flags         1 flip, 2 brightness, 4 contrast, 8 saturation, 16 hue (the term is applied),
+ *                                          32 erase; bits 8 .. 15: the order of the four terms, two bits per position,
+ *                                          first position lowest (0 brightness, 1 contrast, 2 saturation, 3 hue)
+ *     words 23 .. 28   float b, 1-b, c, 1-c, s, 1-s        the factors; 1 - f is formed in double on the host
+ *     word  29         float hue           the hue shift
+ *     words 30 .. 33   int32 ei, ej, eh, ew        the erase rectangle: rows [ei, ei+eh), columns [ej, ej+ew) of the output
+ * Taps are relative to the box and clamped into it; tables: the packed per-axis tables of the distinct (size -> S) pairs;
+ * tmp: sum of nrows * S float4, 16-byte aligned; max_nrows: the largest nrows; mean / stdv: HOST arrays of 4 floats (RGB,
+ * depth); depth is read as min(max(d, depth_lo), depth_hi) / depth_div.  Per sample, in this order: resample (a flipped
+ * sample's output column x takes the table row of S-1-x), the enabled jitter terms in the record's order (contrast blends
+ * with the mean of 0.2989 R + 0.587 G + 0.114 B over the sample as it is at that point, summed in a fixed order), the erase
+ * (all four channels become 0), (x - mean[c]) / stdv[c].  A sample's result does not depend on its place in the batch.
+ * Refused with a status, nothing launched: n outside [1, 65535], S outside [1, 4096], max_nrows < 1, a null operand, records
+ * not 8-byte or tmp not 16-byte aligned, a zero stdv or depth_div.  The records live in device memory: their contents are
+ * checked where they are packed on the host (vitlens_hip.ops.rgbd_augment_pack); in the kernels a row or column outside
+ * the image is clamped into it.  Stream-ordered, three launches, no global state, no host synchronisation.
+ * NOTE on the version: like vl_pc_augment, this entry was added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before it reports the same number and lacks the symbol, and a client must look it up when it loads
+ * the library (vitlens_hip/_lib.py does, and names such a library as stale). */
+int vl_rgbd_augment(const void* records, int n, int S, int max_nrows, const void* tables, float* tmp, const float* mean,
+                    const float* stdv, float depth_lo, float depth_hi, float depth_div, float* out_rgb, float* out_depth,
+                    hipStream_t stream);
 /* ---- evaluation-time image / depth preprocessing (csrc/vl_preproc.hip) ----
  * Separable bicubic resampling restricted to a crop window, tables built by the host (vitlens_hip/preproc.py):
  * bounds [n_out,2] int32 = (first tap, tap count) and coefficients [n_out,ksize] per OUTPUT index of the full resized

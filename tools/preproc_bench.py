@@ -5,7 +5,8 @@ host->device copy of each decoded image inside the timed region.  CPU side ("por
 workers run): Pillow bicubic resize + crop + torch ToTensor/Normalize for images, F.interpolate for disparity maps,
 one thread.  Prints one JSON object; `python tools/preproc_bench.py > gpurun_out/preproc_bench.json`."""
 # `--pc-train-only` prints the row of the 3D training transform alone (PCProcessorTrain against the numpy restatement of the
-# reference's five passes on the host's cores)
+# reference's five passes on the host's cores); `--rgbd-train-only` the row of the depth training transform alone
+# (RGBD_Processor_Train against the torch restatement of the reference's pipeline on the host's cores)
 import json
 import os
 import sys
@@ -73,9 +74,61 @@ def pc_train_row(B=1024, N=8192, threads=16):
     return row
 
 
+def rgbd_train_row(B=1024, H=480, W=640, threads=16, distinct=64):
+    """RGBD_Processor_Train.process_batch at B samples of H x W (`distinct` different sources, each used B / distinct times),
+    next to the reference's loader-side work on the same samples: the torch restatement of its pipeline
+    (tests/rgbd_augment_ref.py, float32, per-sample draws included) on one thread and on a pool of `threads`."""
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rgbd_augment_ref as R
+    from open_clip.modal_depth.processors.vt_processor import RGBD_Processor_Train
+    src = [R.sample(H, W, 100 + i) for i in range(distinct)]
+    images, depths = [src[i % distinct][0] for i in range(B)], [src[i % distinct][1] for i in range(B)]
+    dev = [(a.cuda(), b.cuda()) for a, b in src]
+    images_d, depths_d = [dev[i % distinct][0] for i in range(B)], [dev[i % distinct][1] for i in range(B)]
+    proc = RGBD_Processor_Train.from_config()
+    row = {"n": B, "in": [H, W], "size": proc.size, "source_mb_per_batch": round(B * H * W * 7 / 1e6, 1)}
+    torch.manual_seed(0)
+    draws = [proc.draw(H, W) for _ in range(B)]
+    plan = preproc.plan_rgbd(images_d, depths_d, draws, proc.size, proc.mean, proc.std, proc.depth_clamp, antialias=proc.antialias)
+    row["intermediate_mb"] = round(plan.tmp.numel() * 4 / 1e6, 1)
+    s = min(gpu_time(plan.launch, n_warm=2) for _ in range(5))
+    row["gpu_kernels_ms_per_batch"] = round(s * 1e3, 3)                              # the three launches, sources resident
+
+    def timed(fn):
+        fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3, 2)
+    row["gpu_process_batch_ms_resident_sources"] = timed(lambda: proc.process_batch(images_d, depths_d))   # draws, records, launch
+    row["gpu_process_batch_ms_host_sources"] = timed(lambda: proc.process_batch(images, depths))           # + packing and upload
+    t0 = time.perf_counter(); [proc.draw(H, W) for _ in range(B)]
+    row["host_draws_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3, 2)
+
+    def one(b):
+        return R.apply(images[b], depths[b], R.draw(H, W, proc.size), proc.size, proc.mean, proc.std, proc.antialias, torch.float32)
+
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    n_cpu = min(B, 64)
+    t0 = time.perf_counter()
+    for b in range(n_cpu):
+        one(b)
+    row["cpu_1thread_ms_per_batch"] = round((time.perf_counter() - t0) / n_cpu * B * 1e3, 1)
+    n_pool = min(B, 256)
+    with ThreadPoolExecutor(threads) as pool:
+        t0 = time.perf_counter(); list(pool.map(one, range(n_pool)))
+        row[f"cpu_{threads}threads_ms_per_batch"] = round((time.perf_counter() - t0) / n_pool * B * 1e3, 1)
+    torch.set_num_threads(nt)
+    row[f"cpu_1thread_over_{threads}_ms_per_batch"] = round(row["cpu_1thread_ms_per_batch"] / threads, 1)   # perfect scaling
+    return row
+
+
 def main():
     if "--pc-train-only" in sys.argv[1:]:
         print(json.dumps({"pc_train": pc_train_row()}))
+        return
+    if "--rgbd-train-only" in sys.argv[1:]:
+        print(json.dumps({"rgbd_train": rgbd_train_row()}))
         return
     N, H, W = 256, 375, 500                                                       # ImageNet-typical decoded size
     rng = np.random.default_rng(0)
@@ -154,6 +207,7 @@ def main():
     s = gpu_time(lambda: pp.process_batch(pcs, start=start))
     res["pc"] = {"n": B, "in": [10000, 3], "npoint": 8192, "gpu_resident_clouds_per_s": round(B / s, 1)}
     res["pc_train"] = pc_train_row()
+    res["rgbd_train"] = rgbd_train_row()
     print(json.dumps(res))
 
 

@@ -1053,6 +1053,68 @@ def pc_augment(pts, idx, params, feat_fill=0.4):
     return out
 
 
+# one record per sample, as csrc/vl_rgbd_augment.hip reads it (136 bytes; include/vitlens_hip.h spells the layout out)
+RGBD_AUGMENT_DTYPE = np.dtype(
+    [("rgb", "<u8"), ("depth", "<u8"), ("rgb_stride", "<i4"), ("depth_stride", "<i4"), ("H", "<i4"), ("W", "<i4"),
+     ("top", "<i4"), ("left", "<i4"), ("bh", "<i4"), ("bw", "<i4"), ("row0", "<i4"), ("nrows", "<i4"),
+     ("hb", "<i4"), ("hw", "<i4"), ("hks", "<i4"), ("vb", "<i4"), ("vw", "<i4"), ("vks", "<i4"), ("tmp", "<i8"), ("flags", "<i4"),
+     ("b", "<f4"), ("b1", "<f4"), ("c", "<f4"), ("c1", "<f4"), ("s", "<f4"), ("s1", "<f4"), ("hue", "<f4"),
+     ("ei", "<i4"), ("ej", "<i4"), ("eh", "<i4"), ("ew", "<i4")])
+RGBD_FLIP, RGBD_BRIGHTNESS, RGBD_CONTRAST, RGBD_SATURATION, RGBD_HUE, RGBD_ERASE, RGBD_ORDER_SHIFT = 1, 2, 4, 8, 16, 32, 8
+
+
+def rgbd_augment_pack(rows, S) -> np.ndarray:
+    """rows: a RGBD_AUGMENT_DTYPE array -> int32 [n, 34], the words of the records.  The records are read on the device, where
+    the entry cannot look at them, so their contents are checked here: the box inside the image, the touched rows inside
+    the box, the strides, the order field a permutation of the four terms, the erase rectangle inside the S x S output."""
+    a = np.ascontiguousarray(np.asarray(rows, dtype=RGBD_AUGMENT_DTYPE).reshape(-1))
+
+    def need(ok, what):
+        if not np.all(ok):
+            raise ValueError(f"rgbd_augment_pack: {what} (sample {int(np.argmin(ok))})")
+    need((a["rgb"] != 0) & (a["depth"] != 0), "null source pointer")
+    need((a["H"] >= 1) & (a["W"] >= 1) & (a["rgb_stride"] >= 3 * a["W"]) & (a["depth_stride"] >= a["W"]), "bad source size or stride")
+    need((a["top"] >= 0) & (a["bh"] >= 1) & (a["top"] + a["bh"] <= a["H"]) & (a["left"] >= 0) & (a["bw"] >= 1)
+         & (a["left"] + a["bw"] <= a["W"]), "the crop box must lie inside the image")
+    need((a["row0"] >= 0) & (a["nrows"] >= 1) & (a["row0"] + a["nrows"] <= a["bh"]), "the touched rows must lie inside the box")
+    need((a["hks"] >= 1) & (a["vks"] >= 1) & (a["hb"] >= 0) & (a["hw"] >= 0) & (a["vb"] >= 0) & (a["vw"] >= 0) & (a["tmp"] >= 0),
+         "bad table or intermediate offset")
+    order = (a["flags"] >> RGBD_ORDER_SHIFT) & 0xFF
+    need(sum(1 << ((order >> (2 * k)) & 3) for k in range(4)) == 15, "the order field must hold each of the four terms once")
+    need((a["flags"] >> (RGBD_ORDER_SHIFT + 8)) == 0, "unknown flag bits")
+    e = (a["flags"] & RGBD_ERASE) != 0
+    need(~e | ((a["ei"] >= 0) & (a["eh"] >= 0) & (a["ei"] + a["eh"] <= S) & (a["ej"] >= 0) & (a["ew"] >= 0) & (a["ej"] + a["ew"] <= S)),
+         "the erase rectangle must lie inside the output")
+    return a.view(np.int32).reshape(len(a), RGBD_AUGMENT_DTYPE.itemsize // 4)
+
+
+def rgbd_augment(records, tables, tmp, S, max_nrows, mean, std, depth_clamp, out_rgb=None, out_depth=None):
+    """The depth recipe's training transform for a batch (vl_rgbd_augment, three launches): records int32 [n, 34] (the words
+    of `rgbd_augment_pack`), tables int32 [*] and tmp f32 [*, 4] on the device; mean / std: 4 numbers (RGB, depth);
+    depth_clamp = (lo, hi, divide_by) = DepthNorm -> (out_rgb [n,3,S,S], out_depth [n,1,S,S]) f32."""
+    if records.dim() != 2 or records.shape[1] != RGBD_AUGMENT_DTYPE.itemsize // 4 or records.dtype != torch.int32 or not records.is_cuda:
+        raise ValueError(f"rgbd_augment: records must be int32 [n, 34] on the GPU, got {tuple(records.shape)} {records.dtype} {records.device}")
+    n, dev = records.shape[0], records.device
+    if tables.dtype != torch.int32 or tables.device != dev or tmp.dtype != torch.float32 or tmp.device != dev:
+        raise ValueError("rgbd_augment: tables must be int32 and tmp float32 on the device of the records")
+    if len(mean) != 4 or len(std) != 4:
+        raise ValueError("rgbd_augment: mean and std hold four numbers (RGB, depth)")
+    if n < 1 or S < 1:                   # (the entry refuses these too; nothing of size 0 is allocated first)
+        raise RuntimeError(f"libvitlens_hip: vl_rgbd_augment: bad shape: n={n} S={S}")
+    if out_rgb is None:
+        out_rgb = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
+    if out_depth is None:
+        out_depth = torch.empty(n, 1, S, S, device=dev, dtype=torch.float32)
+    for o, c in ((out_rgb, 3), (out_depth, 1)):
+        if o.dtype != torch.float32 or not o.is_contiguous() or tuple(o.shape) != (n, c, S, S) or o.device != dev:
+            raise ValueError(f"rgbd_augment: outputs must be contiguous f32 [n, {c}, S, S] on the device of the records")
+    lo, hi, div = depth_clamp
+    fl = lambda v: (C.c_float * 4)(*[float(x) for x in v])
+    check(_lib.vl_rgbd_augment(_p(records.contiguous()), n, int(S), int(max_nrows), _p(tables), _p(tmp), fl(mean), fl(std), float(lo),
+                               float(hi), float(div), _p(out_rgb), _p(out_depth), _stream()))
+    return out_rgb, out_depth
+
+
 def knn_group(xyz, center_idx, k, Kp=64, want_idx=False):
     B, N, _ = xyz.shape
     G = center_idx.shape[1]

@@ -8,7 +8,9 @@ ATen build theirs - cached, and kept on the device.
     kernel a = -0.5, support scaled when shrinking, 22-bit fixed point rounded half away from zero);
   * `aten_bicubic_tables` = ATen `UpSampleKernel.cpp` weights: antialiased (`_compute_indices_min_size_weights_aa`,
     float32, a = -0.5, normalised) or plain (`get_cubic_upsample_coefficients`, a = -0.75, 4 taps from floor(src) - 1,
-    border-clamped in the kernel).
+    border-clamped in the kernel);
+  * `aten_bilinear_tables` = the bilinear weights of the same ATen file (antialiased triangle filter, or the two plain
+    taps), for the crop boxes of the depth training transform (`plan_rgbd`, csrc/vl_rgbd_augment.hip).
 
 `image_to_tensor` / `depth_to_tensor` run Resize(shorter edge) -> CenterCrop -> Normalize restricted to the crop
 window (torchvision `_compute_resized_output_size`, `center_crop`); see open_clip/transform.py and
@@ -97,6 +99,40 @@ def aten_bicubic_tables(in_size, out_size, antialias=True):
     w = np.stack([c2(t + 1.0), c1(t), c1(1.0 - t), c2(2.0 - t)], 1).astype(np.float32)
     bounds = np.stack([i0.astype(np.int64) - 1, np.full(out_size, 4, np.int64)], 1).astype(np.int32)
     return bounds, np.ascontiguousarray(w), 4
+
+
+@functools.lru_cache(maxsize=1024)
+def aten_bilinear_tables(in_size, out_size, antialias=True):
+    """-> (bounds [out,2] int32, weights [out,ksize] float32, ksize) of F.interpolate(mode="bilinear", align_corners=False)
+    on a float input.  Antialiased: the triangle filter max(0, 1 - |x|) over the support `scale` (1 when enlarging), index
+    arithmetic and float32 normalisation as the antialiased branch of `aten_bicubic_tables`.  Plain: two taps from
+    src = max(scale (i + 0.5) - 0.5, 0), i0 = floor(src) and i0 + 1, which the kernel clamps to the last index."""
+    f = np.float32
+    scale = f(in_size) / f(out_size)
+    i = np.arange(out_size, dtype=np.float32)
+    if antialias:
+        support = scale if scale >= 1.0 else f(1.0)
+        invscale = f(1.0) / scale if scale >= 1.0 else f(1.0)
+        ksize = int(math.ceil(float(support))) * 2 + 1
+        center = scale * (i + f(0.5))
+        xmin = np.maximum((center - support + f(0.5)).astype(np.int64), 0)
+        xsize = np.minimum((center + support + f(0.5)).astype(np.int64), in_size) - xmin
+        j = np.arange(ksize, dtype=np.int64)[None, :]
+        arg = (((j + xmin[:, None]).astype(np.float32) - center[:, None] + f(0.5)) * invscale).astype(np.float32)
+        w = np.maximum(f(1.0) - np.abs(arg), f(0.0)).astype(np.float32)
+        w = np.where(j < xsize[:, None], w, f(0.0)).astype(np.float32)
+        tot = np.cumsum(w, axis=1, dtype=np.float32)[:, -1:]
+        w = np.where(tot != 0, w / np.where(tot != 0, tot, f(1.0)), w).astype(np.float32)
+        return np.stack([xmin, xsize], 1).astype(np.int32), np.ascontiguousarray(w), ksize
+    # one rounding to float32 of scale * (i + 0.5) - 0.5, as in the plain branch of aten_bicubic_tables
+    src = (np.float64(scale) * (np.arange(out_size, dtype=np.float64) + 0.5) - 0.5).astype(np.float32)
+    src = np.maximum(src, f(0.0))
+    i0 = np.floor(src)                                          # src <= in - 0.5: i0 <= in - 1
+    t = (src - i0).astype(np.float32)
+    t = np.where(i0 >= in_size - 1, f(0.0), t)                  # both taps are the last sample there: (1, 0) returns it exactly
+    w = np.stack([f(1.0) - t, t], 1).astype(np.float32)
+    bounds = np.stack([i0.astype(np.int64), np.full(out_size, 2, np.int64)], 1).astype(np.int32)
+    return bounds, np.ascontiguousarray(w), 2
 
 
 _DEVICE_TABLES = collections.OrderedDict()      # (kind, in, out[, antialias], device) -> tables; LRU, a data set has few distinct sizes
@@ -305,3 +341,117 @@ def images_to_tensor(images, size, mean, std, out=None, boxes=None):
     in two kernel launches (vl_resample_batch_u8_norm): same arithmetic and bits as `image_to_tensor` per image.
     boxes[i] = (top, left, h, w): crop-then-resize (training)."""
     return plan_images(images, size, mean, std, out=out, boxes=boxes).launch()
+
+
+def rgbd_record_scalars(rec, draw):
+    """Write a draw's scalars into one RGBD_AUGMENT_DTYPE row: the box, the flip, the jitter order, the enabled terms with
+    factor and 1 - factor (the difference formed in double, as torchvision's _blend forms it, then rounded to float32),
+    the erase rectangle.  draw: {"box": (top, left, h, w), "flip": bool, "order": 4 ids (0 brightness, 1 contrast,
+    2 saturation, 3 hue), "brightness" / "contrast" / "saturation" / "hue": a float or None (term off),
+    "erase": (i, j, h, w) or None}."""
+    from . import ops
+    rec["top"], rec["left"], rec["bh"], rec["bw"] = draw["box"]
+    order = [int(k) for k in draw["order"]]
+    if sorted(order) != [0, 1, 2, 3]:
+        raise ValueError(f"the jitter order must be a permutation of 0..3, got {order}")
+    flags = (ops.RGBD_FLIP if draw["flip"] else 0) | sum(k << (ops.RGBD_ORDER_SHIFT + 2 * pos) for pos, k in enumerate(order))
+    for name, bit, f, f1 in (("brightness", ops.RGBD_BRIGHTNESS, "b", "b1"), ("contrast", ops.RGBD_CONTRAST, "c", "c1"),
+                             ("saturation", ops.RGBD_SATURATION, "s", "s1")):
+        v = draw.get(name)
+        if v is not None:
+            flags |= bit
+            rec[f], rec[f1] = float(v), 1.0 - float(v)
+    if draw.get("hue") is not None:
+        flags |= ops.RGBD_HUE
+        rec["hue"] = float(draw["hue"])
+    if draw.get("erase") is not None:
+        flags |= ops.RGBD_ERASE
+        rec["ei"], rec["ej"], rec["eh"], rec["ew"] = draw["erase"]
+    rec["flags"] = flags
+
+
+class RgbdPlan:
+    """Device-side description of one batch of the depth training transform: the packed buffer (records, tables, host
+    sources), the intermediate and the tensors that keep device sources alive.  `launch()` enqueues vl_rgbd_augment; it can
+    be repeated (same inputs, same outputs)."""
+
+    def __init__(self, records, tables, tmp, n, S, max_nrows, mean, std, depth_clamp, keep):
+        self.records, self.tables, self.tmp, self.keep = records, tables, tmp, keep
+        self.n, self.S, self.max_nrows, self.mean, self.std, self.depth_clamp = n, S, max_nrows, mean, std, depth_clamp
+
+    def launch(self, out_rgb=None, out_depth=None):
+        from . import ops
+        return ops.rgbd_augment(self.records, self.tables, self.tmp, self.S, self.max_nrows, self.mean, self.std, self.depth_clamp,
+                                out_rgb=out_rgb, out_depth=out_depth)
+
+
+def plan_rgbd(images, depths, draws, size, mean, std, depth_clamp, antialias=True, device="cuda"):
+    """Host side of the depth training transform.  images[i]: uint8 [H, W, 3] tensor, depths[i]: float32 [H, W] tensor of
+    the same H, W (host or device; sizes differ between samples), draws[i]: the sample's scalars (`rgbd_record_scalars`).
+    Everything the host provides - records, the packed bilinear tables of the distinct (box edge -> size) pairs, host
+    depth maps and host image bytes - is laid out in ONE pinned buffer and travels in ONE copy; device sources are read
+    where they are."""
+    from . import ops
+    n, S, dev = len(images), int(size), torch.device(device)
+    if n < 1 or len(depths) != n or len(draws) != n:
+        raise ValueError(f"plan_rgbd: {n} images, {len(depths)} depth maps, {len(draws)} draws")
+    rec = np.zeros(n, dtype=ops.RGBD_AUGMENT_DTYPE)
+    parts, offsets, cursor = [], {}, 0
+
+    def table(in_size):
+        nonlocal cursor
+        if in_size not in offsets:
+            b, w, ks = aten_bilinear_tables(in_size, S, antialias)
+            offsets[in_size] = (cursor, cursor + b.size, ks, b)
+            parts.extend((b.reshape(-1), w.reshape(-1).view(np.int32)))
+            cursor += b.size + w.size
+        return offsets[in_size]
+    tmp_vec, keep, host = 0, [], []                    # host: (record field, source tensor) to be packed
+    for i, (im, dp, draw) in enumerate(zip(images, depths, draws)):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f"plan_rgbd: image {i} must be uint8 [H, W, 3], got {tuple(im.shape)} {im.dtype}")
+        H, W = im.shape[:2]
+        if dp.dtype != torch.float32 or tuple(dp.shape) != (H, W):
+            raise ValueError(f"plan_rgbd: depth {i} must be float32 [{H}, {W}] like its image, got {tuple(dp.shape)} {dp.dtype}")
+        r = rec[i]
+        r["H"], r["W"], r["rgb_stride"], r["depth_stride"] = H, W, 3 * W, W
+        for field, t in (("rgb", im), ("depth", dp)):
+            if t.is_cuda:
+                t = t.contiguous()
+                keep.append(t)
+                r[field] = t.data_ptr()
+            else:
+                host.append((i, field, t))
+        rgbd_record_scalars(r, draw)
+        top, left, bh, bw = (int(v) for v in draw["box"])
+        if not (0 <= top and 1 <= bh and top + bh <= H and 0 <= left and 1 <= bw and left + bw <= W):
+            raise ValueError(f"plan_rgbd: box {draw['box']} of sample {i} is not inside its {H} x {W} image")
+        r["hb"], r["hw"], r["hks"], _ = table(bw)
+        r["vb"], r["vw"], r["vks"], vb_host = table(bh)
+        r["row0"], r["nrows"] = _window(vb_host, 0, S, bh)
+        r["tmp"] = tmp_vec
+        tmp_vec += int(r["nrows"]) * S
+    tables = np.concatenate(parts)
+    # layout: records | tables | host depth maps (4-byte aligned) | host image bytes
+    off_tables = (rec.nbytes + 15) & ~15
+    cursor = off_tables + tables.nbytes
+    place = {}
+    for i, field, t in sorted(host, key=lambda h: h[1] != "depth"):
+        place[(i, field)] = cursor
+        cursor += t.numel() * t.element_size()
+    packed = torch.empty(max(cursor, 1), device=dev, dtype=torch.uint8)
+    for (i, field), off in place.items():
+        rec[i][field] = packed.data_ptr() + off
+    stage = torch.empty(cursor, dtype=torch.uint8, pin_memory=dev.type == "cuda")
+    buf = stage.numpy()
+    buf[:rec.nbytes] = ops.rgbd_augment_pack(rec, S).view(np.uint8).reshape(-1)
+    buf[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
+    for i, field, t in host:
+        off = place[(i, field)]
+        stage[off:off + t.numel() * t.element_size()].copy_(t.contiguous().view(torch.uint8).reshape(-1))
+    packed.copy_(stage, non_blocking=True)
+    records = packed[:rec.nbytes].view(torch.int32).view(n, -1)
+    tables_d = packed[off_tables:off_tables + tables.nbytes].view(torch.int32)
+    tmp = torch.empty(tmp_vec, 4, device=dev, dtype=torch.float32)
+    keep.append(packed)
+    return RgbdPlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), list(mean), list(std), tuple(depth_clamp), keep)
