@@ -404,8 +404,8 @@ int vl_attn_fwd_q1(const void* q, const void* k, const void* v, const long* stri
 int vl_attn_bwd_q1(const void* q, const void* k, const void* v, const long* strides, const void* dO, long ld_do,
                    const void* o, long ld_o, const float* lse, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv,
                    int B, int H, int L, int dh, int qrow, float qscale, float scale, hipStream_t stream);
-/* ---- Perceiver dropout (csrc/vl_lens_drop.hip): the Lens's attn_dropout on the attention probabilities and ff_dropout behind the
- * second Linear of a FeedForward (open_clip/perceiver.py:91-102, 105-154), train mode only.  The mask is a pure function of
+/* ---- Perceiver dropout (csrc/vl_lens_drop.hip; the attention backward in csrc/vl_attn_bwd.hip): the Lens's attn_dropout on
+ * the attention probabilities and ff_dropout behind the second Linear of a FeedForward (open_clip/perceiver.py:91-102, 105-154), train mode only.  The mask is a pure function of
  * numbers and is never stored: element e is KEPT iff its Philox4x32-10 word is >= round(p * 2^32) as a uint32, a kept value is
  * multiplied by 1 / (1 - p) computed in fp32.  Key (lo32(seed), hi32(seed)); counter
  *     (group, lo32(sample0 + b), hi32(sample0 + b), sublayer)

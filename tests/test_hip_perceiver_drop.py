@@ -1,5 +1,6 @@
-"""GPU: Perceiver dropout (csrc/vl_lens_drop.hip) - the attention forward and backward with the mask on the probabilities per
-(b, h, 32-row) block against float64 under the numpy mask of tests/perceiver_drop_ref.py, the FeedForward row kernels exactly,
+"""GPU: Perceiver dropout (csrc/vl_lens_drop.hip, the attention backward in csrc/vl_attn_bwd.hip) - the attention forward and
+backward with the mask on the probabilities per (b, h, 32-row) block against float64 under the numpy mask of
+tests/perceiver_drop_ref.py, the dropout backward at p = 0.0 against the p = 0 backward, the FeedForward row kernels exactly,
 p = 0 as today's path bit for bit, a whole tiny Perceiver through PerceiverTrainer and through the drop-in model, and the
 fused audio step under micro-batching and resume.
 
@@ -51,11 +52,13 @@ def relerr(a, b):
 _CASE = {}
 
 
-def attn_case(name):
-    """Inputs, mask, the float64 reference (forward and autograd) and the CPU emulations of one case - computed once."""
-    if name in _CASE:
-        return _CASE[name]
-    B, H, Lq, Lk, dh, p, seed = R.ATTN_CASES[name]
+def attn_case(name, p=None):
+    """Inputs, mask, the float64 reference (forward and autograd) and the CPU emulations of one case (at another probability
+    than its own if `p` is given) - computed once."""
+    if (name, p) in _CASE:
+        return _CASE[name, p]
+    B, H, Lq, Lk, dh, p_case, seed = R.ATTN_CASES[name]
+    key, p = (name, p), p_case if p is None else p
     q, k, v, qscale = A.make_scores("normal", B, H, Lq, Lk, dh, seed=seed)
     dO = torch.randn(B, H, Lq, dh, generator=torch.Generator().manual_seed(seed + 1000)).to(BF)
     keep = R.attn_keep(seed, R.ATTN_SAMPLE0, R.ATTN_SUB, p, B, H, Lq, Lk)
@@ -84,8 +87,8 @@ def attn_case(name):
         scale = dh ** -0.5
         emu = dict(out=emu_out, dv=(Pt.transpose(-1, -2) @ dO.double()).to(BF), dq=(scale * (dS @ k.double())).to(BF),
                    dk=(LN2 * (dS.transpose(-1, -2) @ q2)).to(BF))
-    _CASE[name] = SimpleNamespace(B=B, H=H, Lq=Lq, Lk=Lk, dh=dh, p=p, seed=seed, q=q, k=k, v=v, dO=dO, qscale=qscale, ref=ref, emu=emu)
-    return _CASE[name]
+    _CASE[key] = SimpleNamespace(B=B, H=H, Lq=Lq, Lk=Lk, dh=dh, p=p, seed=seed, q=q, k=k, v=v, dO=dO, qscale=qscale, ref=ref, emu=emu)
+    return _CASE[key]
 
 
 def _tol(c, what, L):
@@ -155,6 +158,41 @@ def test_attention_backward_with_dropout_per_block(name):
         print(f"bwd {name} {what}: kernel worst block {kw:.3e} (b={b} h={h} {rows} {r0}:{r1}), emulation worst block {emu:.3e}, tol {tol:.3e}")
         ERRORS[f"attn_bwd/{name}/{what}"] = dict(kernel=kw, emulation=emu, tol=tol)
         assert kw <= tol, f"{what} b={b} h={h} {rows} {r0}:{r1}: {kw:.3e} > {tol:.3e}"
+
+
+@pytest.mark.parametrize("name", ["b", "c"])
+def test_backward_dropout_entry_at_p0_is_the_two_kernel_backward(name):
+    """One body for both entries (csrc/vl_attn_bwd.hip): at p = 0.0 the threshold is 0 and the scale 1, so every element is kept
+    and the dropout instantiation computes what attn_bwd(fused=False) computes.  delta is the same code; dq: (dp - delta) P and
+    P fma(dp, 1, -delta) round identically; dv: P * 1 = P - all three bit-equal.  dk sums the same dS, but -delta enters dP's
+    accumulation in front of the products in one kernel and behind them in the other: the per-block rule against float64."""
+    ops = _ops()
+    c = attn_case(name, p=0.0)
+    out, lse = _run_fwd(c, drop=False)
+    q, k, v, dO = c.q.cuda(), c.k.cuda(), c.v.cuda(), c.dO.cuda()
+    inner = c.H * c.dh
+    o = ops.heads_view(out, c.B, c.Lq, c.H, c.dh)
+
+    def run(drop):
+        dq = torch.full((c.B * c.Lq, inner), float("nan"), device="cuda", dtype=BF)
+        dkv = torch.full((c.B * c.Lk, 2 * inner), float("nan"), device="cuda", dtype=BF)
+        delta = torch.full((c.B, c.H, c.Lq), float("nan"), device="cuda")
+        args = (q, k, v, dO, o, lse, delta, dq, dkv, dkv[:, inner:], inner, 2 * inner)
+        if drop:
+            ops.attn_bwd_drop(*args, 0.0, c.seed, R.ATTN_SAMPLE0, R.ATTN_SUB)
+        else:
+            ops.attn_bwd(*args, fused=False)
+        return delta, dq, dkv[:, :inner].contiguous(), dkv[:, inner:].contiguous()
+    delta0, dq0, dk0, dv0 = run(False)
+    delta1, dq1, dk1, dv1 = run(True)
+    assert torch.isfinite(delta1).all() and torch.equal(delta1, delta0)
+    assert torch.isfinite(dq1.float()).all() and torch.equal(dq1, dq0)
+    assert torch.isfinite(dv1.float()).all() and torch.equal(dv1, dv0)
+    tol, emu = _tol(c, "dk", c.Lk)
+    for which, dk in (("p = 0 entry", dk0), ("dropout entry", dk1)):
+        kw, (b, h, r0, r1) = attn_block_relerr(dk.cpu(), c.ref["dk"], c.B, c.H, c.Lk)
+        print(f"bwd {name} at p = 0, dk of the {which}: worst block {kw:.3e} (b={b} h={h} keys {r0}:{r1}), emulation {emu:.3e}, tol {tol:.3e}")
+        assert kw <= tol, f"dk ({which}) b={b} h={h} keys {r0}:{r1}: {kw:.3e} > {tol:.3e}"
 
 
 def test_attention_entries_refuse_what_they_do_not_take():

@@ -419,33 +419,42 @@ def test_step_host_state_and_defaults():
 
 
 def test_vl_lens_drop_kernels_no_scratch_no_spills(tmp_path):
-    """The recipe of test_f32_wide_heads_host.py on csrc/vl_lens_drop.hip, with the flags csrc/Makefile gives it."""
+    """The recipe of test_f32_wide_heads_host.py on csrc/vl_lens_drop.hip (forward, FeedForward rows) and on the dropout
+    instantiations of csrc/vl_attn_bwd.hip's two kernels (template arguments ..., TAIL = false, DROP = true), with the flags
+    csrc/Makefile gives both files."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans", "-I" + CSRC,
-                        "-I" + os.path.join(ROOT, "include"), "-x", "hip", "-c", os.path.join(CSRC, "vl_lens_drop.hip"), "-o",
-                        str(tmp_path / "o.o"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    name, bad, vgprs = None, [], {}
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and int(m.group(1)) > 0:
-            bad.append((name, "scratch", int(m.group(1))))
-        m = re.search(r"([SV]GPRs) Spill: (\d+)", line)
-        if m and int(m.group(2)) > 0:
-            bad.append((name, m.group(1) + " spill", int(m.group(2))))
-        m = re.search(r" VGPRs: (\d+)", line)
-        if m and name:
-            vgprs[name] = int(m.group(1))
+    bad, vgprs = [], {}
+    for src in ("vl_lens_drop.hip", "vl_attn_bwd.hip"):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans", "-I" + CSRC,
+                            "-I" + os.path.join(ROOT, "include"), "-x", "hip", "-c", os.path.join(CSRC, src), "-o",
+                            str(tmp_path / "o.o"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        name = None
+        for line in r.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+            if name and src == "vl_attn_bwd.hip" and not re.search(r"_kernelILi\d+ELi\d+ELb0ELb1E", name):
+                continue                                     # a p = 0 instantiation: tests/test_kernel_resources.py
+            m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+            if m and int(m.group(1)) > 0:
+                bad.append((name, "scratch", int(m.group(1))))
+            m = re.search(r"([SV]GPRs) Spill: (\d+)", line)
+            if m and int(m.group(2)) > 0:
+                bad.append((name, m.group(1) + " spill", int(m.group(2))))
+            m = re.search(r" VGPRs: (\d+)", line)
+            if m and name:
+                vgprs[name] = int(m.group(1))
     for n, v in sorted(vgprs.items()):
         print(f"{n}: {v} VGPRs")
     # head dims 32 / 64 / padded 128 of the forward and of both backward kernels, and the two row kernels
     assert len([n for n in vgprs if "attn_fwd_drop_kernel" in n]) == 3
-    assert len([n for n in vgprs if "attn_bwd_dq_drop_kernel" in n]) == 3 and len([n for n in vgprs if "attn_bwd_dkv_drop_kernel" in n]) == 3
+    for kern, inst in (("attn_bwd_dq_kernel", [(32, 160), (64, 160), (128, 160)]), ("attn_bwd_dkv_kernel", [(32, 288), (64, 288), (128, 96)])):
+        got = [re.search(kern + r"ILi(\d+)ELi(\d+)ELb0ELb1E", n).groups() for n in vgprs if kern in n]
+        assert sorted((int(dh), int(nc)) for dh, nc in got) == sorted(inst), sorted(vgprs)
     assert len([n for n in vgprs if "ff_drop_kernel" in n]) == 2
+    assert len(vgprs) == 11
     assert not bad, bad

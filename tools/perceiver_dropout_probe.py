@@ -6,7 +6,7 @@ against 0.0, alternated step by step, and the attention kernels of the Lens alon
 entries, forward and backward.  Prints a log (profiles/perceiver_dropout_ab.log holds one).  No fallback: without a GPU this
 fails.
 
-usage: python tools/perceiver_dropout_probe.py [--p 0.1] [--steps 6] [--warmup 2] [--batch 256] [--reps 20]"""
+usage: python tools/perceiver_dropout_probe.py [--p 0.1] [--steps 6] [--warmup 2] [--batch 256] [--reps 20] [--digest]"""
 import argparse
 import os
 import statistics
@@ -31,27 +31,59 @@ def kernel_ms(fn, reps):
     return statistics.median(ts)
 
 
+class AttnProblem:
+    """Seeded bf16 operands of one attention shape in the trainer's layout (q, dO token-major, k | v packed) and the buffers of
+    its forward and backward."""
+
+    def __init__(self, B, H, Lq, Lk, dh, seed=1):
+        import torch
+        from vitlens_hip import ops
+        BF, dev, self.inner = torch.bfloat16, "cuda", H * dh
+        g = torch.Generator().manual_seed(seed)
+        q2 = torch.randn(B * Lq, self.inner, generator=g).to(BF).to(dev)
+        kv2 = torch.randn(B * Lk, 2 * self.inner, generator=g).to(BF).to(dev)
+        dO2 = torch.randn(B * Lq, self.inner, generator=g).to(BF).to(dev)
+        hv = lambda t, L, *off: ops.heads_view(t, B, L, H, dh, *off)
+        self.q, self.k, self.v, self.dO = hv(q2, Lq), hv(kv2, Lk), hv(kv2, Lk, self.inner), hv(dO2, Lq)
+        self.out, self.lse = torch.empty(B * Lq, self.inner, device=dev, dtype=BF), torch.empty(B, H, Lq, device=dev)
+        self.delta, self.dq, self.dkv = torch.empty(B, H, Lq, device=dev), torch.empty_like(q2), torch.empty_like(kv2)
+        self.o, self.qs, self.ops = hv(self.out, Lq), dh ** -0.5 * ops.LOG2E, ops
+
+    def fwd(self, p=0.0):
+        if p:
+            return self.ops.attn_fwd_drop(self.q, self.k, self.v, self.out, p, 1, 2, 3, lse=self.lse, qscale=self.qs)
+        return self.ops.attn_fwd(self.q, self.k, self.v, self.out, lse=self.lse, qscale=self.qs)
+
+    def bwd(self, p=0.0, **kw):
+        i = self.inner
+        args = (self.q, self.k, self.v, self.dO, self.o, self.lse, self.delta, self.dq, self.dkv, self.dkv[:, i:], i, 2 * i)
+        return self.ops.attn_bwd_drop(*args, p, 1, 2, 3) if p else self.ops.attn_bwd(*args, **kw)
+
+
 def attention_times(B, H, Lq, Lk, dh, p, reps):
     """(forward p = 0, forward dropout, backward p = 0 as the trainer runs it, backward two-kernel p = 0, backward dropout) in ms."""
+    a = AttnProblem(B, H, Lq, Lk, dh)
+    a.fwd()
+    return (kernel_ms(a.fwd, reps), kernel_ms(lambda: a.fwd(p), reps), kernel_ms(a.bwd, reps),
+            kernel_ms(lambda: a.bwd(fused=False), reps), kernel_ms(lambda: a.bwd(p), reps))
+
+
+def digests(shapes):
+    """sha256 of dq, dk, dv, delta of the two-kernel backward, under dropout and at p = 0, for every (name, B, H, Lq, Lk, dh, p):
+    what two builds of the library must agree on bit for bit."""
+    import hashlib
     import torch
-    from vitlens_hip import ops
-    BF, dev, inner = torch.bfloat16, "cuda", H * dh
-    g = torch.Generator().manual_seed(1)
-    q2 = torch.randn(B * Lq, inner, generator=g).to(BF).to(dev)
-    kv2 = torch.randn(B * Lk, 2 * inner, generator=g).to(BF).to(dev)
-    dO2 = torch.randn(B * Lq, inner, generator=g).to(BF).to(dev)
-    q, k, v = ops.heads_view(q2, B, Lq, H, dh), ops.heads_view(kv2, B, Lk, H, dh), ops.heads_view(kv2, B, Lk, H, dh, inner)
-    out, lse = torch.empty(B * Lq, inner, device=dev, dtype=BF), torch.empty(B, H, Lq, device=dev)
-    delta = torch.empty(B, H, Lq, device=dev)
-    dq, dkv = torch.empty_like(q2), torch.empty_like(kv2)
-    o, dO = ops.heads_view(out, B, Lq, H, dh), ops.heads_view(dO2, B, Lq, H, dh)
-    qs = dh ** -0.5 * ops.LOG2E
-    ops.attn_fwd(q, k, v, out, lse=lse, qscale=qs)
-    bwd = lambda **kw: ops.attn_bwd(q, k, v, dO, o, lse, delta, dq, dkv, dkv[:, inner:], inner, 2 * inner, **kw)
-    return (kernel_ms(lambda: ops.attn_fwd(q, k, v, out, lse=lse, qscale=qs), reps),
-            kernel_ms(lambda: ops.attn_fwd_drop(q, k, v, out, p, 1, 2, 3, lse=lse, qscale=qs), reps),
-            kernel_ms(lambda: bwd(), reps), kernel_ms(lambda: bwd(fused=False), reps),
-            kernel_ms(lambda: ops.attn_bwd_drop(q, k, v, dO, o, lse, delta, dq, dkv, dkv[:, inner:], inner, 2 * inner, p, 1, 2, 3), reps))
+    for name, B, H, Lq, Lk, dh, p in shapes:
+        a = AttnProblem(B, H, Lq, Lk, dh)
+        for pp, kw in ((p, {}), (0.0, dict(fused=False))):
+            for t in (a.dq, a.dkv, a.delta):
+                t.fill_(float("nan"))
+            a.fwd(pp); a.bwd(pp, **kw)
+            torch.cuda.synchronize()
+            i = a.inner
+            sha = lambda t: hashlib.sha256(t.contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()[:16]
+            print(f"digest {name} B{B} H{H} {Lq}x{Lk} dh{dh} p={pp:.2f}: dq {sha(a.dq)} dk {sha(a.dkv[:, :i])} dv {sha(a.dkv[:, i:])} "
+                  f"delta {sha(a.delta)}")
 
 
 def main():
@@ -61,6 +93,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20, help="timed launches per kernel")
+    ap.add_argument("--digest", action="store_true", help="digests of the attention backward's results (the ATTN_CASES of "
+                    "tests/perceiver_drop_ref.py and the two C4 shapes) and the kernel rows; no training step")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -72,12 +106,19 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     print(f"device: {torch.cuda.get_device_name(dev)}; C4 step, per-GPU batch {a.batch} in one micro-batch, bf16 streams, p = {a.p}")
-    for name, (H, Lq, Lk) in (("cross attention, 1 head, 256 x 600", (1, 256, 600)), ("latent self-attention, 16 heads, 256 x 256", (16, 256, 256))):
+    c4 = (("cross attention, 1 head, 256 x 600", (1, 256, 600)), ("latent self-attention, 16 heads, 256 x 256", (16, 256, 256)))
+    if a.digest:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from perceiver_drop_ref import ATTN_CASES
+        digests([(n, *c[:6]) for n, c in ATTN_CASES.items()] + [(f"C4 {n.split(',')[0]}", a.batch, H, Lq, Lk, 64, a.p) for n, (H, Lq, Lk) in c4])
+    for name, (H, Lq, Lk) in c4:
         f0, fd, b0, b2, bd = attention_times(a.batch, H, Lq, Lk, 64, a.p, a.reps)
         print(f"{name}, B = {a.batch}, median of {a.reps} launches:")
         print(f"  forward   p = 0 {f0:8.3f} ms   dropout {fd:8.3f} ms   x{fd / f0:.2f}")
         print(f"  backward  p = 0 {b0:8.3f} ms (as the trainer runs it)   two-kernel p = 0 {b2:8.3f} ms   dropout {bd:8.3f} ms   "
               f"x{bd / b0:.2f} of the trainer's, x{bd / b2:.2f} of the two-kernel")
+    if a.digest:
+        return
     g = torch.Generator().manual_seed(1234)
     torch.manual_seed(1234)
     model = open_clip.tri_create_model("ViT-L-14", None, device="cpu", args=fetch_model_cfg(modality="audio"))

@@ -29,11 +29,22 @@
 // alongside their own tiles - wave w takes tile w with the MFMA operand roles swapped (the lone row is row 0 of the A
 // operand), pushes p / dS through a 128-byte LDS scratch to make them an A operand, and the per-wave partial dQ (or
 // dK, dV) rows are summed in a fixed order through LDS.
+//
+// Perceiver dropout (vl_attn_bwd_drop_bf16, the backward of vl_lens_drop.hip's forward) is the DROP = true instantiation of the
+// same two bodies, without the shared last row; the mask is recomputed from vl_drop.h's Philox counters, never read.
+//   A: a lane owns one query and four aligned groups of four keys per tile: four Philox calls, dS = P (dP M / (1 - p) - delta).
+//   B: a lane owns ONE key and 16 queries, i.e. 16 groups: 16 calls per lane per tile, one word of each used.  The mask
+//      multiplies dO V^T alone, so -delta is read beside the dP product instead of entering it as the C operand; dV accumulates
+//      (P M / (1 - p))^T dO, dK the same dS.  (Left open: four neighbouring lanes need the four words of the same calls - a quad
+//      transpose would cut the calls to four.)
+#include <type_traits>
 #include "vl_attn_common.h"
+#include "vl_drop.h"
 #include "vitlens_hip.h"
 
 namespace {
 using namespace vlattn;
+using namespace vldrop;
 
 constexpr int NC = 288;        // queries per LDS chunk of kernel B: 9 tiles of 32
 constexpr int NCA = 160;       // keys per LDS chunk of kernel A: 5 tiles (two workgroups per CU)
@@ -53,6 +64,7 @@ struct AttnBwdP {
   VL_PROF_FIELD
   int l_main;               // queries (A) / keys (B) handled by per-wave tiles (L, or L-1 when the last row is shared)
 };
+struct AttnBwdPD : AttnBwdP { DropArgs drop; };
 
 __device__ __forceinline__ bf16x8 load_frag(const bf16_t* row, int ks, int fg, float scale) {
   u32x4 raw = *(const u32x4*)(row + ks * 16 + fg * 8);
@@ -81,8 +93,9 @@ __device__ __forceinline__ void wave_lds_sync() {
 // NCA keys per LDS chunk.  NCA = 160 (62 KB of LDS, <= 128 VGPRs) puts TWO workgroups on a CU, so one workgroup's staging
 // (a memory round trip that is bandwidth-bound chip-wide: every workgroup asks for its 40 KB at once) overlaps the
 // other's MFMA work; measured against the single-chunk 1-workgroup-per-CU version (load + compute strictly serial).
-template <int DH, int NCA, bool TAILQ>
-__global__ void __launch_bounds__(NWMAX * 64, DH == 128 ? 2 : 4) attn_bwd_dq_kernel(const AttnBwdP p) {
+template <int DH, int NCA, bool TAILQ, bool DROP = false, class P = AttnBwdP>
+__global__ void __launch_bounds__(NWMAX * 64, DH == 128 ? 2 : 4) attn_bwd_dq_kernel(const P p) {
+  static_assert(!(DROP && TAILQ), "dropout has no shared-last-row variant");
   constexpr int RB = DH * 2, KS = DH / 16, DT = DH / 32, TS = NCA + 8, CH = DH / 8;
   constexpr bool PAD = DH == 128;                 // head dims 72..128 run zero-padded to 128
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -108,6 +121,11 @@ __global__ void __launch_bounds__(NWMAX * 64, DH == 128 ? 2 : 4) attn_bwd_dq_ker
   const int qidx = q0 + fr;
   const int qrow = qidx < p.l_main ? qidx : p.l_main - 1;
   const int dhr = PAD ? p.dh : DH, nch = dhr >> 3;        // real head dim, valid 16-byte chunks per operand row
+  [[maybe_unused]] uint32_t slo = 0u, shi = 0u;           // (DROP) the sample's number: counter words 1, 2
+  if constexpr (DROP) {
+    const uint64_t samp = p.drop.sample0 + (uint64_t)b;
+    slo = (uint32_t)samp; shi = (uint32_t)(samp >> 32);
+  }
 
   VL_PROF_STAMP(p, 0);
   // one memory round trip for everything the workgroup needs first: the per-lane q / dO / O rows and the log-sum-exp
@@ -193,13 +211,30 @@ __global__ void __launch_bounds__(NWMAX * 64, DH == 128 ? 2 : 4) attn_bwd_dq_ker
           }
         }
         float ds[16];
+        if constexpr (DROP) {
+          // dS = P (dP M / (1 - p) - delta), one group of four keys at a time (the scheduling barrier keeps the four Philox
+          // chains from being interleaved: their temporaries would not fit beside the accumulators)
+          const uint32_t g0 = ((uint32_t)h * (uint32_t)p.Lq + (uint32_t)qidx) * p.drop.kg4 + ((uint32_t)key0 >> 2);
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) {          // packed adds / multiplies: (s - lse2), (dp - delta), p * (dp - delta)
-          vl_f32x2 sv = {s[r], s[r + 1]}, dv = {dp[r], dp[r + 1]};
-          sv -= lse2; dv -= dlt;
-          const vl_f32x2 pv = {__builtin_amdgcn_exp2f(sv[0]), __builtin_amdgcn_exp2f(sv[1])};
-          dv *= pv;
-          ds[r] = dv[0]; ds[r + 1] = dv[1];
+          for (int gq = 0; gq < 4; ++gq) {
+            float m[4];
+            drop_mul4(p.drop, slo, shi, g0 + 2u * gq, m);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int r = gq * 4 + e;
+              ds[r] = __builtin_amdgcn_exp2f(s[r] - lse2) * fmaf(dp[r], m[e], -dlt);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; r += 2) {        // packed adds / multiplies: (s - lse2), (dp - delta), p * (dp - delta)
+            vl_f32x2 sv = {s[r], s[r + 1]}, dv = {dp[r], dp[r + 1]};
+            sv -= lse2; dv -= dlt;
+            const vl_f32x2 pv = {__builtin_amdgcn_exp2f(sv[0]), __builtin_amdgcn_exp2f(sv[1])};
+            dv *= pv;
+            ds[r] = dv[0]; ds[r + 1] = dv[1];
+          }
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -274,8 +309,9 @@ __global__ void __launch_bounds__(NWMAX * 64, DH == 128 ? 2 : 4) attn_bwd_dq_ker
 // NCB queries per LDS chunk (288 = the whole 257-token sequence; 96 for the padded 128-wide head dims, whose images are
 // twice as large).  The padded instantiation also walks its 4 output d-tiles in two passes of TPP = 2 (dK, dV, K, V for 128
 // columns would need 256 accumulator / operand registers): S and dP are recomputed per pass.
-template <int DH, int NCB, bool TAILK>
-__global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnBwdP p) {
+template <int DH, int NCB, bool TAILK, bool DROP = false, class P = AttnBwdP>
+__global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const P p) {
+  static_assert(!(DROP && TAILK), "dropout has no shared-last-row variant");
   constexpr int RB = DH * 2, KS = DH / 16, DT = DH / 32, TS = NCB + 8;
   constexpr bool PAD = DH == 128;
   constexpr int TPP = PAD ? 2 : DT;              // output d-tiles per pass
@@ -305,6 +341,13 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
   const int kidx = k0 + fr;
   const int krow = kidx < p.l_main ? kidx : p.l_main - 1;
   const int dhr = PAD ? p.dh : DH, nch = dhr >> 3;        // real head dim, valid 16-byte chunks per operand row
+  [[maybe_unused]] uint32_t slo = 0u, shi = 0u;           // (DROP) the sample's number: counter words 1, 2
+  if constexpr (DROP) {
+    const uint64_t samp = p.drop.sample0 + (uint64_t)b;
+    slo = (uint32_t)samp; shi = (uint32_t)(samp >> 32);
+  }
+  [[maybe_unused]] const uint32_t kgrp = (uint32_t)kidx >> 2;      // (DROP) this lane's key: its group of four and word
+  [[maybe_unused]] const int kword = kidx & 3;
 
   VL_PROF_STAMP(p, 0);
   [[maybe_unused]] u32x4 tailraw = {0u, 0u, 0u, 0u};
@@ -333,9 +376,11 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
 
   for (int qc0 = 0; qc0 < p.Lq; qc0 += NCB) {
     __syncthreads();
-    // (log-sum-exp / delta of the chunk requested before the staging loads: one round trip)
+    // (log-sum-exp / delta of the chunk requested before the staging loads: one round trip - except under dropout, where
+    //  holding them across the staging costs 8 registers and the dh = 32 instantiation a wave of occupancy)
+    const bool ahead = !DROP && nthr == NWMAX * 64;
     float lraw[(NCB + NWMAX * 64 - 1) / (NWMAX * 64)], draw[(NCB + NWMAX * 64 - 1) / (NWMAX * 64)];
-    if (nthr == NWMAX * 64) {
+    if (ahead) {
 #pragma unroll
       for (int j = 0; j < (NCB + NWMAX * 64 - 1) / (NWMAX * 64); ++j) {
         const int i = tid + j * NWMAX * 64;
@@ -349,7 +394,7 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
     if constexpr (TAILK) {
       if (qc0 == 0 && tid < 2 * CH) *(u32x4*)(sTail + tid * 8) = tailraw;
     }
-    if (nthr == NWMAX * 64) {
+    if (ahead) {
 #pragma unroll
       for (int j = 0; j < (NCB + NWMAX * 64 - 1) / (NWMAX * 64); ++j) {
         const int i = tid + j * NWMAX * 64;
@@ -371,23 +416,41 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
       if (p.causal) t0 = max(0, (k0 - qc0) >> 5);      // queries before this key tile never see it
       for (int qt = t0; qt < ntile; ++qt) {
         // rows of the accumulator = queries (r&3) + 8*(r>>2) + 4*fg of this tile; column = this lane's key
-        f32x16 s, dp;
+        [[maybe_unused]] uint32_t keep = 0u;
+        if constexpr (DROP) {
+          // The 16 keep bits first, while neither score tile is live, in a loop that stays rolled: unrolled, the sixteen
+          // Philox chains are interleaved and their temporaries spill beside the accumulators (the padded instantiation: 39
+          // registers).  The group of query row r = one per-lane base + a wave-uniform multiple of ceil(Lk / 4)
+          const uint32_t gq0 = ((uint32_t)h * (uint32_t)p.Lq + (uint32_t)(qc0 + qt * 32 + 4 * fg)) * p.drop.kg4 + kgrp;
+#pragma unroll 1
+          for (int r = 0; r < 16; ++r) {
+            const uint32_t g = gq0 + (uint32_t)((r & 3) + 8 * (r >> 2)) * p.drop.kg4;
+            keep |= (drop_mul1(p.drop, slo, shi, g, kword) != 0.f ? 1u : 0u) << r;
+          }
+        }
+        // -lse2 and (p = 0) -delta as the C operands; under dropout the mask multiplies dO V^T alone, so dP starts from zero
+        f32x16 s, dp = zero16();
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
           const f32x4 l4 = *(const f32x4*)(sNegL + qt * 32 + qd * 8 + fg * 4);
-          const f32x4 d4 = *(const f32x4*)(sNegD + qt * 32 + qd * 8 + fg * 4);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { s[qd * 4 + e] = l4[e]; dp[qd * 4 + e] = d4[e]; }
+          for (int e = 0; e < 4; ++e) s[qd * 4 + e] = l4[e];
+          if constexpr (!DROP) {
+            const f32x4 d4 = *(const f32x4*)(sNegD + qt * 32 + qd * 8 + fg * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dp[qd * 4 + e] = d4[e];
+          }
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(sQ, qt * 32 + fr, ks, fg), kf[ks], s, 0, 0, 0);
           dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<DH>(sdO, qt * 32 + fr, ks, fg), vf[ks], dp, 0, 0, 0);
         }
-        // (fragments of the transposed images requested ahead of the exponentials - except in the padded instantiation,
-        //  which has no registers to hold them)
+        // (fragments of the transposed images requested ahead of the exponentials - except in the padded and the dropout
+        //  instantiations, which have no registers to hold them)
+        constexpr bool AHEAD = !PAD && !DROP;
         [[maybe_unused]] bf16x8 gtf[2][TPP], qtf[2][TPP];
-        if constexpr (!PAD) {
+        if constexpr (AHEAD) {
 #pragma unroll
           for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -404,15 +467,30 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
           }
         }
         float pv[16], ds[16];
+        if constexpr (DROP) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { pv[r] = __builtin_amdgcn_exp2f(s[r]); ds[r] = pv[r] * dp[r]; }
+          for (int qd = 0; qd < 4; ++qd) {
+            const f32x4 d4 = *(const f32x4*)(sNegD + qt * 32 + qd * 8 + fg * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int r = qd * 4 + e;
+              const float m = (keep >> r) & 1u ? p.drop.inv_keep : 0.f;
+              const float pr = __builtin_amdgcn_exp2f(s[r]);       // (padded query rows: -inf -> 0)
+              ds[r] = pr * fmaf(dp[r], m, d4[e]);                  // dS = P (dP M / (1 - p) - delta)
+              pv[r] = pr * m;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { pv[r] = __builtin_amdgcn_exp2f(s[r]); ds[r] = pv[r] * dp[r]; }
+        }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const bf16x8 pf = pack8(pv + c * 8), df = pack8(ds + c * 8);
 #pragma unroll
           for (int t = 0; t < TPP; ++t) {
-            dv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(PAD ? frag_t<NCB>(sdOt, (tp + t) * 32 + fr, qt, c, fg) : gtf[c][t], pf, dv[t], 0, 0, 0);
-            dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(PAD ? frag_t<NCB>(sQt, (tp + t) * 32 + fr, qt, c, fg) : qtf[c][t], df, dk[t], 0, 0, 0);
+            dv[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AHEAD ? gtf[c][t] : frag_t<NCB>(sdOt, (tp + t) * 32 + fr, qt, c, fg), pf, dv[t], 0, 0, 0);
+            dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AHEAD ? qtf[c][t] : frag_t<NCB>(sQt, (tp + t) * 32 + fr, qt, c, fg), df, dk[t], 0, 0, 0);
           }
         }
       }
@@ -493,65 +571,97 @@ __global__ void __launch_bounds__(NWMAX * 64, 2) attn_bwd_dkv_kernel(const AttnB
 
 }  // namespace
 
-extern "C" int vl_set_error(const char* msg);
-
-template <int DH, bool TQ, bool TK>
-static int launch_bwd(const AttnBwdP& pin, int lq_main, int lk_main, hipStream_t stream) {
+// LDS bytes and grids of both kernels.  The p = 0 instantiations are given their shared-last-row arrays whether or not they use
+// them; the dropout ones have none.
+template <int DH, bool TQ, bool TK, bool DROP>
+static int launch_bwd(const std::conditional_t<DROP, AttnBwdPD, AttnBwdP>& pin, int lq_main, int lk_main, hipStream_t stream) {
+  using P = std::conditional_t<DROP, AttnBwdPD, AttnBwdP>;
   constexpr int NCB = DH == 128 ? 96 : NC;
-  const size_t smA = (size_t)2 * NCA * DH * 2 + (size_t)DH * (NCA + 8) * 2 + (size_t)NWMAX * 32 * 4 + (size_t)NWMAX * DH * 4 +
-                     (size_t)3 * DH * 2;
-  const size_t smB = (size_t)2 * NCB * DH * 2 + (size_t)2 * DH * (NCB + 8) * 2 + (size_t)2 * NCB * 4 + (size_t)NWMAX * 64 * 4 +
-                     (size_t)NWMAX * 2 * DH * 4 + (size_t)2 * DH * 2;
-  static const hipError_t attrA = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DH, NCA, TQ>,
+  const size_t smA = (size_t)2 * NCA * DH * 2 + (size_t)DH * (NCA + 8) * 2 +
+                     (DROP ? 0 : (size_t)NWMAX * 32 * 4 + (size_t)NWMAX * DH * 4 + (size_t)3 * DH * 2);
+  const size_t smB = (size_t)2 * NCB * DH * 2 + (size_t)2 * DH * (NCB + 8) * 2 + (size_t)2 * NCB * 4 +
+                     (DROP ? 0 : (size_t)NWMAX * 64 * 4 + (size_t)NWMAX * 2 * DH * 4 + (size_t)2 * DH * 2);
+  static const hipError_t attrA = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<DH, NCA, TQ, DROP, P>,
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smA);
-  static const hipError_t attrB = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DH, NCB, TK>,
+  static const hipError_t attrB = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<DH, NCB, TK, DROP, P>,
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smB);
   if (attrA != hipSuccess) return vl_set_error(hipGetErrorString(attrA));
   if (attrB != hipSuccess) return vl_set_error(hipGetErrorString(attrB));
-  AttnBwdP p = pin;
+  P p = pin;
   const int qtiles = (lq_main + 31) / 32, ktiles = (lk_main + 31) / 32;
   const int nwq = qtiles < NWMAX ? qtiles : NWMAX, nwk = ktiles < NWMAX ? ktiles : NWMAX;
   p.l_main = lq_main;
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, NCA, TQ>), dim3((qtiles + nwq - 1) / nwq, p.H, p.B), dim3(nwq * 64), smA, stream, p);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, NCA, TQ, DROP, P>), dim3((qtiles + nwq - 1) / nwq, p.H, p.B), dim3(nwq * 64), smA, stream, p);
   p.l_main = lk_main;
 #ifdef VL_ATTN_PROF
   if (p.prof) p.prof += (size_t)p.B * p.H * ((qtiles + nwq - 1) / nwq) * 8;     // kernel B's stamps follow kernel A's
 #endif
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, NCB, TK>), dim3((ktiles + nwk - 1) / nwk, p.H, p.B), dim3(nwk * 64), smB, stream, p);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, NCB, TK, DROP, P>), dim3((ktiles + nwk - 1) / nwk, p.H, p.B), dim3(nwk * 64), smB, stream, p);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e));
+}
+
+// the checks of both entries (`who` names the entry in the error text) and the operands into *p; 0 on success
+static int bwd_params(const char* who, const void* q, const void* k, const void* v, const void* dO, const void* o, const long* s,
+                      const float* lse, float* delta, void* dq, void* dk, void* dv, long ld_dq, long ld_dkv, int B, int H, int Lq,
+                      int Lk, int dh, float qscale, int causal, float scale, AttnBwdP* p) {
+  const auto fail = [who](const char* what) {
+    static thread_local char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return vl_set_error(msg);
+  };
+  if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return fail("empty problem");
+  if (dh != 32 && dh != 64 && !(dh > 64 && dh <= 128 && (dh & 7) == 0))
+    return fail("head dim must be 32, 64, or a multiple of 8 in (64, 128] (run zero-padded to 128)");
+  if (!s || !delta || !lse) return fail("strides, lse and the delta workspace are required");
+  if (!q || !k || !v || !dO || !o || !dq || !dk || !dv) return fail("operands and destinations required");
+  for (int i = 0; i < 15; ++i)
+    if (s[i] & 7) return fail("operand strides must be multiples of 8 elements (16-byte rows)");
+  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dO) | ((uintptr_t)o)) & 15)
+    return fail("operands must be 16-byte aligned");
+  if ((((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15 || (ld_dq & 7) || (ld_dkv & 7))
+    return fail("gradient destinations must be 16-byte aligned with row strides multiple of 8");
+  *p = AttnBwdP{TV{(const bf16_t*)q, s[0], s[1], s[2]},   TV{(const bf16_t*)k, s[3], s[4], s[5]},
+                TV{(const bf16_t*)v, s[6], s[7], s[8]},   TV{(const bf16_t*)dO, s[9], s[10], s[11]},
+                TV{(const bf16_t*)o, s[12], s[13], s[14]}, lse, delta, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv,
+                ld_dq, ld_dkv, B, H, Lq, Lk, causal, dh, qscale, scale,
+#ifdef VL_ATTN_PROF
+                vl_attn_prof_buf,
+#endif
+                0};
+  return 0;
 }
 
 extern "C" int vl_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* dO, const void* o,
                                 const long* strides, const float* lse, float* delta, void* dq, void* dk, void* dv,
                                 long ld_dq, long ld_dkv, int B, int H, int Lq, int Lk, int dh, float qscale, int causal,
                                 float scale, hipStream_t stream) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return vl_set_error("vl_attn_bwd_bf16: empty problem");
-  if (dh != 32 && dh != 64 && !(dh > 64 && dh <= 128 && (dh & 7) == 0))
-    return vl_set_error("vl_attn_bwd_bf16: head dim must be 32, 64, or a multiple of 8 in (64, 128] (run zero-padded to 128)");
-  if (!strides || !delta || !lse) return vl_set_error("vl_attn_bwd_bf16: strides, lse and the delta workspace are required");
-  for (int i = 0; i < 15; ++i)
-    if (strides[i] & 7) return vl_set_error("vl_attn_bwd_bf16: operand strides must be multiples of 8 elements (16-byte rows)");
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dO) | ((uintptr_t)o)) & 15)
-    return vl_set_error("vl_attn_bwd_bf16: operands must be 16-byte aligned");
-  if ((((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15 || (ld_dq & 7) || (ld_dkv & 7))
-    return vl_set_error("vl_attn_bwd_bf16: gradient destinations must be 16-byte aligned with row strides multiple of 8");
-  const long* s = strides;
-  AttnBwdP p{TV{(const bf16_t*)q, s[0], s[1], s[2]},   TV{(const bf16_t*)k, s[3], s[4], s[5]},
-             TV{(const bf16_t*)v, s[6], s[7], s[8]},   TV{(const bf16_t*)dO, s[9], s[10], s[11]},
-             TV{(const bf16_t*)o, s[12], s[13], s[14]}, lse, delta, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv,
-             ld_dq, ld_dkv, B, H, Lq, Lk, causal, dh, qscale, scale,
-#ifdef VL_ATTN_PROF
-             vl_attn_prof_buf,
-#endif
-             0};
+  AttnBwdP p;
+  if (bwd_params("vl_attn_bwd_bf16", q, k, v, dO, o, strides, lse, delta, dq, dk, dv, ld_dq, ld_dkv, B, H, Lq, Lk, dh, qscale, causal,
+                 scale, &p))
+    return 1;
   // one row beyond whole tiles (257 tokens): shared by the 8 waves of the single workgroup instead of a ninth wave
   const bool tq = (Lq % 32 == 1) && Lq > 32 && Lq - 1 <= NWMAX * 32 && (!causal || Lk <= Lq);
   const bool tk = (Lk % 32 == 1) && Lk > 32 && Lk - 1 <= NWMAX * 32;      // (the query chunks are walked inside the kernel)
   const int lqm = tq ? Lq - 1 : Lq, lkm = tk ? Lk - 1 : Lk;
 #define VL_BWD(DHV)                                                                       \
-  (tq ? (tk ? launch_bwd<DHV, true, true>(p, lqm, lkm, stream) : launch_bwd<DHV, true, false>(p, lqm, lkm, stream)) \
-      : (tk ? launch_bwd<DHV, false, true>(p, lqm, lkm, stream) : launch_bwd<DHV, false, false>(p, lqm, lkm, stream)))
+  (tq ? (tk ? launch_bwd<DHV, true, true, false>(p, lqm, lkm, stream) : launch_bwd<DHV, true, false, false>(p, lqm, lkm, stream)) \
+      : (tk ? launch_bwd<DHV, false, true, false>(p, lqm, lkm, stream) : launch_bwd<DHV, false, false, false>(p, lqm, lkm, stream)))
   return dh == 64 ? VL_BWD(64) : (dh == 32 ? VL_BWD(32) : VL_BWD(128));
 #undef VL_BWD
+}
+
+extern "C" int vl_attn_bwd_drop_bf16(const void* q, const void* k, const void* v, const void* dO, const void* o,
+                                     const long* strides, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                     long ld_dq, long ld_dkv, int B, int H, int Lq, int Lk, int dh, float qscale, int causal,
+                                     float scale, double pdrop, uint64_t seed, int64_t sample0, int sublayer,
+                                     hipStream_t stream) {
+  AttnBwdPD p;
+  if (bwd_params("vl_attn_bwd_drop_bf16", q, k, v, dO, o, strides, lse, delta, dq, dk, dv, ld_dq, ld_dkv, B, H, Lq, Lk, dh, qscale,
+                 causal, scale, &p))
+    return 1;
+  const uint32_t kg4 = (uint32_t)((Lk + 3) / 4);
+  if (drop_args("vl_attn_bwd_drop_bf16", pdrop, seed, sample0, sublayer, (uint64_t)H * (uint64_t)Lq * kg4, kg4, &p.drop)) return 1;
+  return dh == 64 ? launch_bwd<64, false, false, true>(p, Lq, Lk, stream)
+                  : (dh == 32 ? launch_bwd<32, false, false, true>(p, Lq, Lk, stream) : launch_bwd<128, false, false, true>(p, Lq, Lk, stream));
 }
