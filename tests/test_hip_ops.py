@@ -104,6 +104,55 @@ def test_gemm_epilogues(cfg):
     assert out.shape == (M, N // 2) and relerr(out, ref) < 4e-3
 
 
+def test_gemm_epilogues_fp32_transpose_fallback():
+    """The round-1 persistent kernel (cfg 5) with N % 8 == 4: bf16 rows are not 16-byte aligned, so every epilogue takes the
+    fp32 LDS transpose with 8-byte stores.  Partial row tile (300 = 256 + 44), partial column block (196 = 6 x 32 + 4).
+    References: fp32 PyTorch on the same bf16 operands, the tolerances of test_gemm_epilogues."""
+    ops = _ops()
+    M, N, K, cfg = 300, 196, 128, 5
+    a = rnd(M, K, seed=41).bfloat16().cuda(); w = rnd(N, K, seed=42, scale=0.1).bfloat16().cuda()
+    bias = rnd(N, seed=43).cuda()
+    prod = a.float().cpu() @ w.float().cpu().t()
+    acc = prod + bias.cpu()
+    accb = acc.bfloat16().float().requires_grad_(True)            # the rounding point of the epilogues that act on the bf16 value
+    torch.nn.functional.gelu(accb).sum().backward()
+    dgelu = accb.grad
+    sig = torch.sigmoid(1.702 * accb.detach())
+
+    def bf16_out():
+        return torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+
+    def check(got, ref, what, tol=4e-3):
+        assert bool(torch.isfinite(got).all()), what
+        e = relerr(got, ref)
+        print(f"{what}: relerr {e:.2e} (allowed {tol:.0e})")
+        assert e < tol, (what, e)
+
+    check(ops.gemm(a, w, bias, epi=ops.EPI_BF16, cfg=cfg, out=bf16_out()), acc, "bf16")
+    check(ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg, out=bf16_out()), torch.nn.functional.gelu(acc), "gelu")
+    pre = bf16_out()
+    out = ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg, out=bf16_out(), out2=pre)
+    check(out, torch.nn.functional.gelu(acc), "gelu + pre: out"); check(pre, acc, "gelu + pre: out2")
+    d = bf16_out()
+    out = ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_GELU_DSAVE, cfg=cfg, out=bf16_out(), out2=d)
+    check(out, torch.nn.functional.gelu(acc), "gelu_dsave: out"); check(d, dgelu, "gelu_dsave: out2")
+    dq = bf16_out()
+    out = ops.gemm(a, w, bias, epi=ops.EPI_BF16, act=ops.ACT_QGELU_DSAVE, cfg=cfg, out=bf16_out(), out2=dq)
+    check(out, acc * torch.sigmoid(1.702 * acc), "qgelu_dsave: out")
+    check(dq, sig + 1.702 * accb.detach() * sig * (1 - sig), "qgelu_dsave: out2")
+    resb = rnd(M, N, seed=44).bfloat16().cuda()
+    check(ops.gemm(a, w, bias, res=resb, epi=ops.EPI_RES_BF16, cfg=cfg, out=bf16_out()), resb.float().cpu() + acc, "res_bf16")
+    # dX through GELU: the saved derivative (one multiplication) and the recomputed one (res = the pre-activation)
+    check(ops.gemm(a, w, None, res=d, epi=ops.EPI_DGELU, act=ops.ACT_GELU_DSAVE, cfg=cfg, out=bf16_out()), prod * d.float().cpu(), "dgelu saved")
+    u = rnd(M, N, seed=45, scale=1.5).bfloat16().cuda()
+    uf = u.float().cpu().requires_grad_(True)
+    torch.nn.functional.gelu(uf).sum().backward()
+    check(ops.gemm(a, w, None, res=u, epi=ops.EPI_DGELU, cfg=cfg, out=bf16_out()), prod * uf.grad, "dgelu recomputed")
+    check(ops.gemm(a, w, bias, epi=ops.EPI_F32, cfg=cfg), acc, "f32", tol=1e-5)
+    res = rnd(M, N, seed=46).cuda()
+    check(ops.gemm(a, w, bias, res=res, epi=ops.EPI_RES_F32, cfg=cfg), res.cpu() + acc, "res_f32", tol=1e-5)
+
+
 def test_gelu_erf_accuracy():
     """The A&S erf used in the epilogue: |gelu_hip - gelu_exact| <= 1e-6 before bf16 rounding; checked
     through the f32 path by feeding x through an identity GEMM is not possible (GELU is bf16-out only),

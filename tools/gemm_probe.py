@@ -15,7 +15,9 @@ T = 256 * 256
 SHAPES = {"qkv": (T, 3072, 1024), "out": (T, 1024, 1024), "fc": (T, 4096, 1024), "proj": (T, 1024, 4096),
           "sq8k": (8192, 8192, 8192), "dfc": (T, 1024, 4096), "dproj": (T, 4096, 1024),
           # text tower (ViT-L/14 text: width 768, 77 tokens x 256 captions = 77 row tiles: no whole round of 256 workgroups)
-          "tqkv": (19712, 2304, 768), "tout": (19712, 768, 768), "tfc": (19712, 3072, 768), "tproj": (19712, 768, 3072)}
+          "tqkv": (19712, 2304, 768), "tout": (19712, 768, 768), "tfc": (19712, 3072, 768), "tproj": (19712, 768, 3072),
+          # the rows a whole number of rounds leaves over (M = B * 257: one row per image) - the 64x64-tile and split-K tail kernels (cfg 11, 9)
+          "lfc": (256, 4096, 1024), "lproj": (256, 1024, 4096)}
 
 
 def main():
@@ -45,6 +47,10 @@ def main():
                 return lambda: ops.gemm(a, w, bias, out=out, epi=ops.EPI_BF16, cfg=cfg)
             if label == "gelu":
                 return lambda: ops.gemm(a, w, bias, out=out, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg)
+            if label == "qgelu":
+                return lambda: ops.gemm(a, w, bias, out=out, epi=ops.EPI_BF16, act=ops.ACT_QGELU, cfg=cfg)
+            if label == "qgelu+dsave":
+                return lambda: ops.gemm(a, w, bias, out=out, epi=ops.EPI_BF16, act=ops.ACT_QGELU_DSAVE, cfg=cfg, out2=u2)
             if label == "gelu+save":
                 return lambda: ops.gemm(a, w, bias, out=out, epi=ops.EPI_BF16, act=ops.ACT_GELU, cfg=cfg, out2=u2)
             if label == "gelu+dsave":      # forward of a trained MLP: gelu and gelu' (VL_ACT_GELU_DSAVE)
@@ -72,7 +78,7 @@ def main():
                 ts[c].append(e0.elapsed_time(e1) / 2)
         for c in cfgs:
             v = sorted(ts[c]); med = v[len(v) // 2]
-            print(f"{tag:14s} {name:5s} {label:10s} cfg{c:3d}  med {med:7.4f} ms  min {v[0]:7.4f}  {2.0 * M * N * K / med / 1e9:7.1f} TF/s", flush=True)
+            print(f"{tag:14s} {name:5s} {label:11s} cfg{c:3d}  med {med:7.4f} ms  min {v[0]:7.4f}  {2.0 * M * N * K / med / 1e9:7.1f} TF/s", flush=True)
         del a, w, out, resb, u2
 
 

@@ -12,15 +12,16 @@
 //   * staging is either LDS-DMA (global_load_lds_dwordx4, swizzle applied on the per-lane SOURCE
 //     address, LDS image lane-linear) or plain register staging; selected by template flag.
 //   * XCD-aware bijective block remap keeps consecutive N-tiles of one M-tile on one XCD's L2.
-#include "vl_gemm_common.h"
+//   * epilogue arithmetic (activations, residual adds, dGELU, GEGLU) is vl_gemm_epi.h's, shared with vl_gemm_pp.hip and
+//     vl_gemm_park.hip; this file keeps the three ways of getting values to memory: direct (store_tile), fp32 LDS transpose
+//     (store_tile_lds) and bf16 LDS transpose with 16-byte stores (store_tile_lds16).
+#include "vl_gemm_epi.h"
 
 namespace {
 
 // ---- epilogue: lane owns row m = mrow0 + 32*i + fr, columns n = ncol0 + 32*j + 8*q + 4*fg + {0..3} ----
 template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL], int mrow0, int ncol0, int fr, int fg) {
-  constexpr int EPI = epi_base(EPI_);            // EPI_BF16_QG: EPI_BF16 + the QuickGELU codes (vl_gemm_common.h)
-  constexpr bool QG = (EPI_ == EPI_BF16_QG);
   // rows OUTER: a lane writes the 8 column groups of one row back to back, so the 128-byte lines of that row
   // are completed while still in the write-combining window (columns-outer order cost the fc GEMM 40 %).
 #pragma unroll
@@ -41,86 +42,7 @@ __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += bv[e];
         }
-        if constexpr (EPI == EPI_BF16) {
-          if (p.act == 4) {          // GELU of the bf16-rounded pre-activation, out2 = gelu' of the same (bf16)
-            unsigned int y0, g0, y1, g1;
-            gelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
-            gelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
-            const u32x2 o = {y0, y1}, d = {g0, g1};
-            *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
-            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-            continue;
-          }
-          if (QG && p.act == VL_ACT_QGELU_DSAVE) {   // the QuickGELU twin: out2 = qgelu' of the bf16-rounded pre-activation
-            unsigned int y0, g0, y1, g1;
-            qgelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
-            qgelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
-            const u32x2 o = {y0, y1}, d = {g0, g1};
-            *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
-            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-            continue;
-          }
-          if (p.act == 1) {
-            if (p.out2) {
-              u32x2 o2; o2[0] = pack2bf(v[0], v[1]); o2[1] = pack2bf(v[2], v[3]);
-              *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = o2;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-          } else if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          } else if (QG && p.act == VL_ACT_QGELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
-          }
-          u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-          *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-        } else if constexpr (EPI == EPI_F32) {
-          f32x4 o = {v[0], v[1], v[2], v[3]};
-          *(f32x4*)((float*)p.out + (size_t)m * p.ldo + n) = o;
-        } else if constexpr (EPI == EPI_RES_F32) {
-          const f32x4 r = *(const f32x4*)((const float*)p.res + (size_t)m * p.ldo + n);
-          f32x4 o = {v[0] + r[0], v[1] + r[1], v[2] + r[2], v[3] + r[3]};
-          *(f32x4*)((float*)p.out + (size_t)m * p.ldo + n) = o;
-        } else if constexpr (EPI == EPI_RES_BF16) {
-          const u32x2 r = *(const u32x2*)((const bf16_t*)p.res + (size_t)((m + p.m_off) / p.res_div) * p.ldo + n);
-          v[0] += bf2f((bf16_t)(r[0] & 0xffff)); v[1] += bf2f((bf16_t)(r[0] >> 16));
-          v[2] += bf2f((bf16_t)(r[1] & 0xffff)); v[3] += bf2f((bf16_t)(r[1] >> 16));
-          if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          }
-          u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-          *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-        } else if constexpr (EPI == EPI_DGELU) {
-          const u32x2 r = *(const u32x2*)((const bf16_t*)p.res + (size_t)m * p.ldo + n);
-          const bool saved = p.act == 4;          // res = gelu' itself (left by a VL_ACT_GELU_DSAVE forward)
-          const float r0 = bf2f((bf16_t)(r[0] & 0xffff)), r1 = bf2f((bf16_t)(r[0] >> 16));
-          const float r2 = bf2f((bf16_t)(r[1] & 0xffff)), r3 = bf2f((bf16_t)(r[1] >> 16));
-          v[0] *= saved ? r0 : gelu_erf_grad(r0); v[1] *= saved ? r1 : gelu_erf_grad(r1);
-          v[2] *= saved ? r2 : gelu_erf_grad(r2); v[3] *= saved ? r3 : gelu_erf_grad(r3);
-          u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-          *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-        } else if constexpr (EPI == EPI_GEGLU) {
-          // interleaved rows: (a_j, gate_j, a_j+1, gate_j+1)
-          if (p.out2) {   // pre-activation kept for the backward: bf16 [M, N], row stride 2*ldo
-            u32x2 o2; o2[0] = pack2bf(v[0], v[1]); o2[1] = pack2bf(v[2], v[3]);
-            *(u32x2*)((bf16_t*)p.out2 + (size_t)m * (2 * p.ldo) + n) = o2;
-          }
-          const float o0 = v[0] * gelu_erf(v[1]);
-          const float o1 = v[2] * gelu_erf(v[3]);
-          *(unsigned int*)((bf16_t*)p.out + (size_t)m * p.ldo + (n >> 1)) = pack2bf(o0, o1);
-        } else if constexpr (EPI == EPI_DGEGLU) {
-          const u32x4 hv = *(const u32x4*)((const bf16_t*)p.res + (size_t)m * p.ldo + 2 * n);
-          u32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float a = bf2f((bf16_t)(hv[e] & 0xffff)), g = bf2f((bf16_t)(hv[e] >> 16));
-            o[e] = pack2bf(v[e] * gelu_erf(g), v[e] * a * gelu_erf_grad(g));
-          }
-          *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + 2 * n) = o;
-        }
+        epi_direct4<EPI_>(p, v, m, n);
       }
     }
   }
@@ -134,7 +56,8 @@ __device__ __forceinline__ void store_tile(const GemmP& p, f32x16 (&acc)[MT][NTL
 // transpose.  Arithmetic that needs another tensor of the output's shape (bf16 residual, saved pre-activation for
 // dGELU, GELU when the pre-activation is also kept) runs after the read-back on the bf16-rounded values, with
 // coalesced 16-byte loads - the same rounding points as the reference's autocast (bf16 linear output, then the add /
-// activation); bias, alpha, the q scale and GELU-without-save are applied in fp32 before packing.
+// activation); bias, alpha, the q scale and GELU-without-save are applied in fp32 before packing.  The arithmetic on either side
+// of the transpose is epi_prepack / epi_post8 (vl_gemm_epi.h); the runtime act picks the templated step.
 template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[MT][NTL], int j0, int mrow0, int ncol0, int fr, int fg,
                                                  int lane, unsigned char* wl) {
@@ -157,18 +80,9 @@ __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[M
         f32x4 v = {acc[i][j0 + j][q * 4 + 0], acc[i][j0 + j][q * 4 + 1], acc[i][j0 + j][q * 4 + 2], acc[i][j0 + j][q * 4 + 3]};
         v = v * p.alpha;
         if (p.bias && n < p.N) v = v + *(const f32x4*)(p.bias + n);
-        if constexpr (EPI == EPI_BF16) {
-          if (gelu_pre) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-          } else if (p.act == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          } else if (QG && p.act == VL_ACT_QGELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
-          }
-        }
+        if (gelu_pre) epi_prepack<EPI, 1>(v);
+        else if (p.act == 2) epi_prepack<EPI, 2>(v);
+        else if (QG && p.act == VL_ACT_QGELU) epi_prepack<EPI, 5, false>(v);
         u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
         *(u32x2*)(wr + (((j * 4 + q) ^ wsw) << 4)) = o;
       }
@@ -181,47 +95,21 @@ __device__ __forceinline__ void store_tile_lds16(const GemmP& p, f32x16 (&acc)[M
       const int m = mb + r;
       u32x4 w = *(const u32x4*)(wl + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
       if (m >= p.M || !col_ok) continue;
+      // the runtime act picks the templated step (template ACT codes: vl_gemm_epi.h)
+      [[maybe_unused]] u32x4 rr, d;
       if constexpr (EPI == EPI_BF16) {
-        if (p.act == 1 && p.out2) {
-          *(u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8) = w;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            w[e] = pack2bf(gelu_erf(bf2f((bf16_t)(w[e] & 0xffff))), gelu_erf(bf2f((bf16_t)(w[e] >> 16))));
-        } else if (p.act == 4) {
-          u32x4 d;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
-          *(u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8) = d;
-        } else if (QG && p.act == VL_ACT_QGELU_DSAVE) {
-          u32x4 d;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
-          *(u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8) = d;
-        }
-        *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + n8) = w;
+        u32x4* const out2 = (u32x4*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n8);
+        if (p.act == 1 && p.out2) { *out2 = w; epi_post8<EPI, 3>(w, rr, d); }
+        else if (p.act == 4) { epi_post8<EPI, 4>(w, rr, d); *out2 = d; }
+        else if (QG && p.act == VL_ACT_QGELU_DSAVE) { epi_post8<EPI, 6>(w, rr, d); *out2 = d; }
       } else if constexpr (EPI == EPI_RES_BF16) {
-        const u32x4 rr = *(const u32x4*)((const bf16_t*)p.res + (size_t)((m + p.m_off) / p.res_div) * p.ldo + n8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float lo = bf2f((bf16_t)(w[e] & 0xffff)) + bf2f((bf16_t)(rr[e] & 0xffff));
-          float hi = bf2f((bf16_t)(w[e] >> 16)) + bf2f((bf16_t)(rr[e] >> 16));
-          if (p.act == 2) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-          w[e] = pack2bf(lo, hi);
-        }
-        *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + n8) = w;
+        rr = *(const u32x4*)((const bf16_t*)p.res + (size_t)((m + p.m_off) / p.res_div) * p.ldo + n8);
+        if (p.act == 2) epi_post8<EPI, 2>(w, rr, d); else epi_post8<EPI, 0>(w, rr, d);
       } else if constexpr (EPI == EPI_DGELU) {
-        const u32x4 rr = *(const u32x4*)((const bf16_t*)p.res + (size_t)m * p.ldo + n8);
-        if (p.act == 4) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w[e] = mul_pk_bf16(w[e], rr[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            w[e] = pack2bf(bf2f((bf16_t)(w[e] & 0xffff)) * gelu_erf_grad(bf2f((bf16_t)(rr[e] & 0xffff))),
-                           bf2f((bf16_t)(w[e] >> 16)) * gelu_erf_grad(bf2f((bf16_t)(rr[e] >> 16))));
-        }
-        *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + n8) = w;
+        rr = *(const u32x4*)((const bf16_t*)p.res + (size_t)m * p.ldo + n8);
+        if (p.act == 4) epi_post8<EPI, 4>(w, rr, d); else epi_post8<EPI, 0>(w, rr, d);
       }
+      *(u32x4*)((bf16_t*)p.out + (size_t)m * p.ldo + n8) = w;
     }
     asm volatile("" ::: "memory");
   }
@@ -242,7 +130,6 @@ template <int EPI_, int MT, int NTL>
 __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT][NTL], int mrow0, int ncol0, int fr, int fg,
                                                int lane, unsigned char* wl) {
   constexpr int EPI = epi_base(EPI_);            // EPI_BF16_QG: EPI_BF16 + the QuickGELU codes (vl_gemm_common.h)
-  constexpr bool QG = (EPI_ == EPI_BF16_QG);
   if constexpr (EPI == EPI_GEGLU || EPI == EPI_DGEGLU) {
     store_tile<EPI_, MT, NTL>(p, acc, mrow0, ncol0, fr, fg);
     return;
@@ -291,66 +178,8 @@ __device__ __forceinline__ void store_tile_lds(const GemmP& p, f32x16 (&acc)[MT]
           f32x4 v = *(const f32x4*)(wl + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
           if (m >= p.M || !col_ok) continue;
           v = v * p.alpha + bv;
-          if constexpr (EPI == EPI_BF16) {
-            if (p.act == 4) {
-              unsigned int y0, g0, y1, g1;
-              gelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
-              gelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
-              const u32x2 o = {y0, y1}, d = {g0, g1};
-              *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
-              *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-              continue;
-            }
-            if (QG && p.act == VL_ACT_QGELU_DSAVE) {
-              unsigned int y0, g0, y1, g1;
-              qgelu_and_grad_pk(pack2bf(v[0], v[1]), y0, g0);
-              qgelu_and_grad_pk(pack2bf(v[2], v[3]), y1, g1);
-              const u32x2 o = {y0, y1}, d = {g0, g1};
-              *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = d;
-              *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-              continue;
-            }
-            if (p.act == 1) {
-              if (p.out2) {
-                u32x2 o2; o2[0] = pack2bf(v[0], v[1]); o2[1] = pack2bf(v[2], v[3]);
-                *(u32x2*)((bf16_t*)p.out2 + (size_t)m * p.ldo + n) = o2;
-              }
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-            } else if (p.act == 2) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if (QG && p.act == VL_ACT_QGELU) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
-            }
-            u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-          } else if constexpr (EPI == EPI_F32) {
-            *(f32x4*)((float*)p.out + (size_t)m * p.ldo + n) = v;
-          } else if constexpr (EPI == EPI_RES_F32) {
-            const f32x4 rr = *(const f32x4*)((const float*)p.res + (size_t)m * p.ldo + n);
-            *(f32x4*)((float*)p.out + (size_t)m * p.ldo + n) = v + rr;
-          } else if constexpr (EPI == EPI_RES_BF16) {
-            const u32x2 rr = *(const u32x2*)((const bf16_t*)p.res + (size_t)((m + p.m_off) / p.res_div) * p.ldo + n);
-            v[0] += bf2f((bf16_t)(rr[0] & 0xffff)); v[1] += bf2f((bf16_t)(rr[0] >> 16));
-            v[2] += bf2f((bf16_t)(rr[1] & 0xffff)); v[3] += bf2f((bf16_t)(rr[1] >> 16));
-            if (p.act == 2) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-          } else if constexpr (EPI == EPI_DGELU) {
-            const u32x2 rr = *(const u32x2*)((const bf16_t*)p.res + (size_t)m * p.ldo + n);
-            const bool saved = p.act == 4;
-            const float r0 = bf2f((bf16_t)(rr[0] & 0xffff)), r1 = bf2f((bf16_t)(rr[0] >> 16));
-            const float r2 = bf2f((bf16_t)(rr[1] & 0xffff)), r3 = bf2f((bf16_t)(rr[1] >> 16));
-            v[0] *= saved ? r0 : gelu_erf_grad(r0); v[1] *= saved ? r1 : gelu_erf_grad(r1);
-            v[2] *= saved ? r2 : gelu_erf_grad(r2); v[3] *= saved ? r3 : gelu_erf_grad(r3);
-            u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-            *(u32x2*)((bf16_t*)p.out + (size_t)m * p.ldo + n) = o;
-          }
+          float t[4] = {v[0], v[1], v[2], v[3]};
+          epi_direct4<EPI_>(p, t, m, n);
         }
         asm volatile("" ::: "memory");
       }

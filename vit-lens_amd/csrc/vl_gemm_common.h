@@ -1,5 +1,6 @@
 // Shared definitions of the NT GEMM kernels (vl_gemm.hip: tile / tail / split-K kernels and the dispatcher, vl_gemm_park.hip:
-// the persistent 256x256 kernel, vl_gemm_pp.hip: 256x128 tiles, vl_gemm_tn.hip: token-major weight gradients).
+// the persistent 256x256 kernel, vl_gemm_pp.hip: 256x128 tiles, vl_gemm_tn.hip: token-major weight gradients).  The epilogue
+// arithmetic of the first three and their shared host-side rules: vl_gemm_epi.h.
 #pragma once
 #include "vl_common.h"
 #include "vitlens_hip.h"

@@ -13,7 +13,8 @@
 //  * The two waves of a SIMD (wave w and w+4) issue their 8 DMA instructions half a k-step apart (group A right after
 //    the barrier, group B at the top of the next step): an LDS-DMA issue blocks its wave for tens of cycles and with
 //    both partners blocked at once the matrix pipe idles.  Main loop alone: 1231 TF/s (round 1) -> 1300-1350 TF/s.
-//  * Epilogue = arithmetic in the accumulator layout -> bf16 -> wave-private 4 KB LDS slab (XOR-swizzled, no barrier)
+//  * Epilogue = arithmetic in the accumulator layout (epi_act2) -> bf16 -> wave-private 4 KB LDS slab (XOR-swizzled, no barrier)
+//    -> arithmetic that needs a second operand or the rounded value (epi_post8; both vl_gemm_epi.h, shared with the other GEMM files)
 //    -> 16-byte NON-TEMPORAL stores, 8 lanes per 128-byte line, issued as ONE burst per wave; the next tile's main
 //    loop starts while they drain.  Plain (L2-allocating) stores cost +0.10 ms here: the 0.5 GB output evicts the
 //    operand slabs from the 4 MB L2s.  Trickling the stores through the next tile's k-loop from parked registers
@@ -51,7 +52,7 @@
 // (open_clip/transformer.py:215,226-234,252-272) in forward and dX-backward at ViT-L sizes.
 #include <type_traits>
 
-#include "vl_gemm_common.h"
+#include "vl_gemm_epi.h"
 
 namespace {
 
@@ -81,10 +82,7 @@ using IC = std::integral_constant<int, I>;
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// ACT (EPI_BF16 only): 0 none, 1 GELU, 2 ReLU, 3 GELU with the pre-activation also written to out2 (saved for backward),
-// 4 GELU with gelu'(pre-activation) written to out2, 5 QuickGELU, 6 QuickGELU with qgelu'(pre-activation) written to out2
-// (VL_ACT_QGELU / VL_ACT_QGELU_DSAVE: the twins of 1 and 4, same stores, other arithmetic).  EPI_DGELU: ACT 4 = the aux operand
-// is the saved derivative (of either activation).
+// ACT: the epilogue's template code (vl_gemm_epi.h): 0-6, 10 + code with LayerNorm folded in, 20 = row statistics.
 // The main loop runs on `v_mfma_f32_16x16x32_*` (32 MFMAs of 16 384 flop per 32-deep half k-step from 8 + 4 fragments): against
 // `v_mfma_f32_32x32x16_*` (rounds 2-3a; removed in round 5 with its A/B switch) the same LDS traffic and accumulator registers,
 // a quarter of the accumulator read-modify-write per flop.  The board is power-limited on real data (profiles/
@@ -467,19 +465,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             } else {
               v = scale_bias(v, pe.alpha, bvq[q]);
             }
-            if constexpr (EPI == EPI_BF16 && ACTB == 1) {
+            if constexpr (EPI == EPI_BF16 && (ACTB == 1 || ACTB == 2 || ACTB == 5)) {
+              // (epi_prepack's loop, spelled out: behind the call two instantiations came out with other register numbers)
 #pragma unroll
               for (int e = 0; e < 4; e += 2) {
-                const vl_f32x2 y = gelu_erf2(vl_f32x2{v[e], v[e + 1]});
-                v[e] = y[0]; v[e + 1] = y[1];
-              }
-            } else if constexpr (EPI == EPI_BF16 && ACTB == 2) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if constexpr (EPI == EPI_BF16 && ACTB == 5) {
-#pragma unroll
-              for (int e = 0; e < 4; e += 2) {
-                const vl_f32x2 y = qgelu2(vl_f32x2{v[e], v[e + 1]});
+                const vl_f32x2 y = epi_act2<EPI, ACTB>(vl_f32x2{v[e], v[e + 1]});
                 v[e] = y[0]; v[e + 1] = y[1];
               }
             }
@@ -530,31 +520,23 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             __builtin_nontemporal_store(o2[0], (u32x4*)dst);
             __builtin_nontemporal_store(o2[1], (u32x4*)(dst + 16));
             continue;
-          } else if constexpr (EPI == EPI_BF16 && ACTB == 3) {
-            __builtin_nontemporal_store(w, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = pack2bf(gelu_erf2(unpack2bf(w[e])));
-          } else if constexpr (EPI == EPI_BF16 && ACTB == 4) {
-            u32x4 d;                                              // out2 = gelu'(pre) for the dX GEMM of the backward
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
-            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-          } else if constexpr (EPI == EPI_BF16 && ACTB == 6) {
-            u32x4 d;                                              // out2 = qgelu'(pre)
+          }
+          // out2: the pre-activation as it came back (ACT 3), or the derivative for the dX GEMM of the backward (ACT 4, 6)
+          [[maybe_unused]] auto out2 = [&]() { return (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out); };
+          [[maybe_unused]] u32x4 d;
+          if constexpr (EPI == EPI_BF16 && ACTB == 3) __builtin_nontemporal_store(w, out2());
+          if constexpr (LNF && ACTB == 6) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g;
-              if constexpr (LNF) __builtin_amdgcn_sched_barrier(0);      // one pair at a time: with the four interleaved the folded variant spills (256 VGPRs + scratch)
+              __builtin_amdgcn_sched_barrier(0);      // one pair at a time: with the four interleaved the folded variant spills (256 VGPRs + scratch)
             }
-            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-          } else if constexpr (EPI == EPI_RES_BF16) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float lo = bf2f((bf16_t)(w[e] & 0xffff)) + bf2f((bf16_t)(rr[e] & 0xffff));
-              const float hi = bf2f((bf16_t)(w[e] >> 16)) + bf2f((bf16_t)(rr[e] >> 16));
-              w[e] = pack2bf(lo, hi);
-            }
-            if constexpr (STATS) {
+          } else {
+            epi_post8<EPI, STATS ? 0 : ACTB>(w, rr, d);
+          }
+          if constexpr (EPI == EPI_BF16 && (ACTB == 4 || ACTB == 6)) __builtin_nontemporal_store(d, out2());
+          if constexpr (STATS) {
+            {
               // (sum, sum of squares) of the 8 STORED values (bf16-rounded: what the next LayerNorm will read) of this lane:
               // two bf16 dot products per dword; the cross-lane part waits for the end of the row block (below)
               // (inline assembly: through __builtin_amdgcn_fdot2_f32_bf16 hipcc 7.2 fed all four dot products of this loop
@@ -569,13 +551,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
               }
               st1[pass] = s1; st2[pass] = s2;
             }
-          } else if constexpr (EPI == EPI_DGELU && ACT == 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = mul_pk_bf16(w[e], rr[e]);     // aux = gelu' saved by the forward
-          } else if constexpr (EPI == EPI_DGELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              w[e] = pack2bf(unpack2bf(w[e]) * gelu_erf_grad2(unpack2bf(rr[e])));
           }
           __builtin_nontemporal_store(w, (u32x4*)(out_base + (size_t)((i * 32 + pass * 8) * ldo2)));
         }
@@ -640,17 +615,8 @@ bool vl_gemm_park_supported(int epi, const void* params) {
   if (epi == EPI_GEGLU && p.act != 0) return false;
   if (epi == EPI_DGEGLU && (p.bias || !p.res)) return false;
   // whole tiles; the DMA prologue issues two k-steps of tile 0 up front
-  if ((p.M & 255) || (p.N & 255) || (p.K & 63) || p.K < 512 || p.M <= 0 || p.N <= 0) return false;
-  if (p.res_div != 1) return false;
-  if (epi == EPI_RES_BF16 && p.act != 0) return false;
-  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4 && p.act != VL_ACT_QGELU_DSAVE) return false;
-  if (epi == EPI_BF16 && (p.act == 4 || p.act == VL_ACT_QGELU_DSAVE) && !p.out2) return false;
-  if (epi == EPI_DGELU && (p.act == VL_ACT_QGELU || p.act == VL_ACT_QGELU_DSAVE)) return false;   // (the dispatcher passes the saved form as 4)
-  if (p.ldo & 7) return false;
-  // 16-byte accesses on every operand
-  if (((uintptr_t)p.A | (uintptr_t)p.W) & 15) return false;
-  if (((uintptr_t)p.out | (uintptr_t)p.res | (uintptr_t)p.out2) & 15) return false;
-  return true;
+  if ((p.M & 255) || (p.N & 255) || p.K < 512) return false;
+  return epi_bf16_family_ok(epi, p);
 }
 
 int vl_gemm_park_launch(int epi, const void* params, int ncu, hipStream_t s) {
@@ -663,28 +629,15 @@ int vl_gemm_park_launch(int epi, const void* params, int ncu, hipStream_t s) {
     if (epi == EPI_RES_F32) return (int)launch_pk<EPI_RES_F32, 0, true>(p, ncu, s);
     return (int)hipErrorInvalidValue;
   }
-  switch (epi) {
-    case EPI_BF16:
-      if (p.ln_mean) {        // LayerNorm folded into the epilogue (vl_gemm_lnfold_bf16 checked the rest)
-        if (p.act == 1) return (int)launch_pk<EPI_BF16, 11>(p, ncu, s);
-        if (p.act == 4) return (int)launch_pk<EPI_BF16, 14>(p, ncu, s);
-        if (p.act == VL_ACT_QGELU) return (int)launch_pk<EPI_BF16, 15>(p, ncu, s);
-        if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pk<EPI_BF16, 16>(p, ncu, s);
-        return p.act == 0 ? (int)launch_pk<EPI_BF16, 10>(p, ncu, s) : (int)hipErrorInvalidValue;
-      }
-      if (p.act == 1) return p.out2 ? (int)launch_pk<EPI_BF16, 3>(p, ncu, s) : (int)launch_pk<EPI_BF16, 1>(p, ncu, s);
-      if (p.act == 4) return (int)launch_pk<EPI_BF16, 4>(p, ncu, s);
-      if (p.act == VL_ACT_QGELU) return (int)launch_pk<EPI_BF16, 5>(p, ncu, s);
-      if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pk<EPI_BF16, 6>(p, ncu, s);
-      return p.act == 2 ? (int)launch_pk<EPI_BF16, 2>(p, ncu, s) : (int)launch_pk<EPI_BF16, 0>(p, ncu, s);
-    case EPI_RES_BF16:
-      if (p.row_part) return (int)launch_pk<EPI_RES_BF16, 20>(p, ncu, s);
-      return (int)launch_pk<EPI_RES_BF16, 0>(p, ncu, s);
-    case EPI_DGELU: return p.act == 4 ? (int)launch_pk<EPI_DGELU, 4>(p, ncu, s) : (int)launch_pk<EPI_DGELU, 0>(p, ncu, s);
-    case EPI_GEGLU: return (int)launch_pk<EPI_GEGLU, 0>(p, ncu, s);
-    case EPI_DGEGLU: return (int)launch_pk<EPI_DGEGLU, 0>(p, ncu, s);
-    case EPI_F32: return (int)launch_pk<EPI_F32, 0>(p, ncu, s);
-    case EPI_RES_F32: return (int)launch_pk<EPI_RES_F32, 0>(p, ncu, s);
+#define PK_CASE(E, A) case (E) * 32 + (A): return (int)launch_pk<E, A>(p, ncu, s)
+  switch (epi * 32 + epi_act_code(epi, p.act, p.out2 != nullptr, p.ln_mean != nullptr, p.row_part != nullptr)) {
+    PK_CASE(EPI_BF16, 0); PK_CASE(EPI_BF16, 1); PK_CASE(EPI_BF16, 2); PK_CASE(EPI_BF16, 3); PK_CASE(EPI_BF16, 4); PK_CASE(EPI_BF16, 5); PK_CASE(EPI_BF16, 6);
+    // LayerNorm folded into the epilogue (vl_gemm_lnfold_bf16 checked the rest)
+    PK_CASE(EPI_BF16, 10); PK_CASE(EPI_BF16, 11); PK_CASE(EPI_BF16, 14); PK_CASE(EPI_BF16, 15); PK_CASE(EPI_BF16, 16);
+    PK_CASE(EPI_RES_BF16, 0); PK_CASE(EPI_RES_BF16, 20);
+    PK_CASE(EPI_DGELU, 0); PK_CASE(EPI_DGELU, 4);
+    PK_CASE(EPI_GEGLU, 0); PK_CASE(EPI_DGEGLU, 0); PK_CASE(EPI_F32, 0); PK_CASE(EPI_RES_F32, 0);
     default: return (int)hipErrorInvalidValue;
   }
+#undef PK_CASE
 }

@@ -22,7 +22,7 @@
 // the MFMAs across tile boundaries.
 //
 // Epilogue: as round 2 (arithmetic in the accumulator layout -> bf16 -> wave-private 4 KB LDS slab -> 16-byte non-temporal
-// stores, 8 lanes per 128-byte line).  The slab needs no LDS of its own: it is the four 1 KB pieces of the just-consumed
+// stores, 8 lanes per 128-byte line; the arithmetic itself is epi_prepack / epi_post8 of vl_gemm_epi.h, shared with round 2).  The slab needs no LDS of its own: it is the four 1 KB pieces of the just-consumed
 // stage that THIS wave's next DMA batch overwrites (program order inside one wave), so no other wave ever touches it.
 //
 // Replaces: nn.Linear / MultiheadAttention in/out projections of ResidualAttentionBlock
@@ -30,7 +30,7 @@
 // products of the weight gradients.
 #include <type_traits>
 
-#include "vl_gemm_common.h"
+#include "vl_gemm_epi.h"
 
 namespace {
 
@@ -43,8 +43,7 @@ using IC = std::integral_constant<int, I>;
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// ACT (EPI_BF16 only): 0 none, 1 GELU, 2 ReLU, 3 GELU with the pre-activation also written to out2 (saved for backward),
-// 4 GELU with gelu'(pre-activation) written to out2, 5 QuickGELU, 6 QuickGELU with qgelu'(pre-activation) written to out2
+// ACT: the epilogue's template code, 0-6 (vl_gemm_epi.h)
 template <int EPI, int ACT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
     gemm_nt_pp_kernel(const GemmP p) {
@@ -265,16 +264,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
             for (int e = 0; e < 4; ++e) bv[e] = has_bias ? bv[e] : 0.f;
             v = scale_bias(v, pe.alpha, bv);
-            if constexpr (EPI == EPI_BF16 && ACT == 1) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-            } else if constexpr (EPI == EPI_BF16 && ACT == 2) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            } else if constexpr (EPI == EPI_BF16 && ACT == 5) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = qgelu(v[e]);
-            }
+            epi_prepack<EPI, ACT>(v);
             u32x2 o; o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
             *(u32x2*)(wr + (((j * 4 + q) ^ wsw) << 4)) = o;
           }
@@ -285,37 +275,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
           u32x4 w = *(const u32x4*)(slab + pass * 4096 + prow * 128 + (((lane & 7) ^ prow) << 4));
           [[maybe_unused]] u32x4 rr;
           if constexpr (HAS_AUX) rr = aux[i * 4 + pass];
-          if constexpr (EPI == EPI_BF16 && ACT == 3) {
-            __builtin_nontemporal_store(w, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              w[e] = pack2bf(gelu_erf(bf2f((bf16_t)(w[e] & 0xffff))), gelu_erf(bf2f((bf16_t)(w[e] >> 16))));
-          } else if constexpr (EPI == EPI_BF16 && ACT == 4) {
-            u32x4 d;                                              // out2 = gelu'(pre) for the dX GEMM of the backward
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { unsigned int y, g; gelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
-            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-          } else if constexpr (EPI == EPI_BF16 && ACT == 6) {
-            u32x4 d;                                              // out2 = qgelu'(pre)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { unsigned int y, g; qgelu_and_grad_pk(w[e], y, g); w[e] = y; d[e] = g; }
-            __builtin_nontemporal_store(d, (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out));
-          } else if constexpr (EPI == EPI_RES_BF16) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float lo = bf2f((bf16_t)(w[e] & 0xffff)) + bf2f((bf16_t)(rr[e] & 0xffff));
-              const float hi = bf2f((bf16_t)(w[e] >> 16)) + bf2f((bf16_t)(rr[e] >> 16));
-              w[e] = pack2bf(lo, hi);
-            }
-          } else if constexpr (EPI == EPI_DGELU && ACT == 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = mul_pk_bf16(w[e], rr[e]);     // aux = gelu' saved by the forward
-          } else if constexpr (EPI == EPI_DGELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              w[e] = pack2bf(bf2f((bf16_t)(w[e] & 0xffff)) * gelu_erf_grad(bf2f((bf16_t)(rr[e] & 0xffff))),
-                             bf2f((bf16_t)(w[e] >> 16)) * gelu_erf_grad(bf2f((bf16_t)(rr[e] >> 16))));
-          }
+          // out2: the pre-activation as it came back (ACT 3), or the derivative for the dX GEMM of the backward (ACT 4, 6)
+          [[maybe_unused]] auto out2 = [&]() { return (u32x4*)((unsigned char*)pe.out2 + ((size_t)(mrow0 + i * 32 + pass * 8) * pe.ldo + ncol0) * 2 + lo_out); };
+          [[maybe_unused]] u32x4 d;
+          if constexpr (EPI == EPI_BF16 && ACT == 3) __builtin_nontemporal_store(w, out2());
+          epi_post8<EPI, ACT>(w, rr, d);
+          if constexpr (EPI == EPI_BF16 && (ACT == 4 || ACT == 6)) __builtin_nontemporal_store(d, out2());
           __builtin_nontemporal_store(w, (u32x4*)(out_base + (size_t)((i * 32 + pass * 8) * ldo2)));
         }
       }
@@ -354,29 +319,18 @@ bool vl_gemm_pp_supported(int epi, const void* params) {
   }
   if (!(epi == EPI_BF16 || epi == EPI_RES_BF16 || epi == EPI_DGELU)) return false;
   if (p.K < 128) return false;                  // the DMA prologue issues two steps of tile 0 up front
-  if (p.res_div != 1) return false;
-  if (epi == EPI_RES_BF16 && p.act != 0) return false;
-  if (epi == EPI_BF16 && p.out2 && p.act != 1 && p.act != 4 && p.act != VL_ACT_QGELU_DSAVE) return false;
-  if (epi == EPI_BF16 && (p.act == 4 || p.act == VL_ACT_QGELU_DSAVE) && !p.out2) return false;
-  if (epi == EPI_DGELU && (p.act == VL_ACT_QGELU || p.act == VL_ACT_QGELU_DSAVE)) return false;   // (the dispatcher passes the saved form as 4)
-  if (p.ldo & 7) return false;
-  if (((uintptr_t)p.A | (uintptr_t)p.W) & 15) return false;
-  if (((uintptr_t)p.out | (uintptr_t)p.res | (uintptr_t)p.out2) & 15) return false;
-  return true;
+  return epi_bf16_family_ok(epi, p);
 }
 
 int vl_gemm_pp_launch(int epi, const void* params, int ncu, hipStream_t s) {
   const GemmP& p = *(const GemmP*)params;
-  switch (epi) {
-    case EPI_BF16:
-      if (p.act == 1) return p.out2 ? (int)launch_pp<EPI_BF16, 3>(p, ncu, s) : (int)launch_pp<EPI_BF16, 1>(p, ncu, s);
-      if (p.act == 4) return (int)launch_pp<EPI_BF16, 4>(p, ncu, s);
-      if (p.act == VL_ACT_QGELU) return (int)launch_pp<EPI_BF16, 5>(p, ncu, s);
-      if (p.act == VL_ACT_QGELU_DSAVE) return (int)launch_pp<EPI_BF16, 6>(p, ncu, s);
-      return p.act == 2 ? (int)launch_pp<EPI_BF16, 2>(p, ncu, s) : (int)launch_pp<EPI_BF16, 0>(p, ncu, s);
-    case EPI_RES_BF16: return (int)launch_pp<EPI_RES_BF16, 0>(p, ncu, s);
-    case EPI_DGELU: return p.act == 4 ? (int)launch_pp<EPI_DGELU, 4>(p, ncu, s) : (int)launch_pp<EPI_DGELU, 0>(p, ncu, s);
-    case EPI_F32: return (int)launch_pp<EPI_F32, 0>(p, ncu, s);
+#define PP_CASE(E, A) case (E) * 32 + (A): return (int)launch_pp<E, A>(p, ncu, s)
+  switch (epi * 32 + epi_act_code(epi, p.act, p.out2 != nullptr, false, false)) {
+    PP_CASE(EPI_BF16, 0); PP_CASE(EPI_BF16, 1); PP_CASE(EPI_BF16, 2); PP_CASE(EPI_BF16, 3); PP_CASE(EPI_BF16, 4); PP_CASE(EPI_BF16, 5); PP_CASE(EPI_BF16, 6);
+    PP_CASE(EPI_RES_BF16, 0);
+    PP_CASE(EPI_DGELU, 0); PP_CASE(EPI_DGELU, 4);
+    PP_CASE(EPI_F32, 0);
     default: return (int)hipErrorInvalidValue;
   }
+#undef PP_CASE
 }
