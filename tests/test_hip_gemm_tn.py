@@ -95,6 +95,44 @@ def test_bias_gradient_column_sum(R, C, stride):
         assert torch.equal(outf, again)                       # deterministic two-stage reduction
 
 
+def _colsum_per_column(a, what):
+    """ops.colsum of `a` into a pre-filled destination (a missed or doubled finalize shows) against the fp64 sums, per column;
+    a second call into a fresh buffer must add exactly the same numbers."""
+    from errloc import assert_blocks
+    ops = _ops()
+    out = torch.full((a.shape[1],), -1.0, device="cuda")
+    ops.colsum(a, out, 0.5)
+    assert_blocks(out[None], (-1.0 + 0.5 * a.double().sum(0))[None], 6e-7, 1, 1, what=what)
+    again = torch.full((a.shape[1],), -1.0, device="cuda")
+    ops.colsum(a, again, 0.5)
+    assert torch.equal(out, again), what
+
+
+def test_bias_gradient_bf16_unaligned_base():
+    """A bf16 view shifted by ONE column of a wider tensor (C % 8 == 0, stride % 8 == 0, base 2 bytes off a 16-byte boundary): the
+    one-column-per-thread form must be chosen.  The same numbers through an aligned copy take the 8-column form; both against
+    fp64 (not each other: they add in different orders)."""
+    R, C = 263, 72
+    g = torch.Generator().manual_seed(26372)
+    a = torch.randn(R, C + 8, generator=g).bfloat16().cuda()[:, 1:1 + C]
+    assert a.data_ptr() % 16 == 2 and a.stride(0) % 8 == 0
+    _colsum_per_column(a, "shifted view")
+    _colsum_per_column(a.contiguous(), "aligned copy")
+
+
+@pytest.mark.parametrize("R", [257, 261, 3])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_bias_gradient_slab_and_lane_edges(R, dtype):
+    """The two vector forms (8 bf16 / 4 fp32 columns per thread) at the edges of the row split, C = 64 (8 / 16 of the 64 column
+    groups live): 257 rows = a second slab of one row, lane 0 alone has work; 261 = lanes 0-3 of the second slab hold 2, 1, 1, 1
+    rows (no four-row batch, a short remainder); 3 = fewer rows than lanes.
+    The fp32 operand holds bf16-representable values: the 6e-7 bound is the one measured on such data, whose partial sums fp32
+    holds (nearly) exactly; 257 fp32 additions of values with 24 random mantissa bits round by more in any kernel (0.9e-6 to
+    1.5e-6 in an emulation of this summation order on the host)."""
+    g = torch.Generator().manual_seed(R * 7 + (dtype == torch.float32))
+    _colsum_per_column(torch.randn(R, 64, generator=g).bfloat16().to(dtype).cuda(), f"{R} rows, {dtype}")
+
+
 @pytest.mark.parametrize("R,M,N", [(256 * 64, 64, 1024),      # Perceiver to_q / to_k gradient: 64 output columns
                                    (512 * 64, 1024, 128),     # to_out: a 128-column operand on the x side
                                    (196 * 64, 1024, 384),     # a 384-wide context (1.5 tiles)

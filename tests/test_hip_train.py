@@ -501,6 +501,79 @@ def test_layernorm_param_gradients_bf16_dy_fp32_x(rows, D):
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
+def _ln_param_gradients(dy, x, what):
+    """ops.layernorm_bwd_params on (dy, x) - any dtypes, column windows of wider tensors included - into pre-filled dgamma /
+    dbeta (a missed or doubled finalize shows), against fp64 sums, per column; a second call into fresh buffers must add exactly
+    the same numbers.  Returns (dgamma, dbeta) without the pre-fill's share removed."""
+    from vitlens_hip import ops
+    rows, D = dy.shape
+    xd = x.double()
+    mean = xd.mean(1).float(); rstd = (xd.var(1, unbiased=False) + 1e-5).rsqrt().float()
+    xh = (xd - mean.double()[:, None]) * rstd.double()[:, None]
+    ref_w, ref_b = 2.0 + (dy.double() * xh).sum(0), -1.0 + dy.double().sum(0)
+    got = []
+    for _ in range(2):
+        dw = torch.full((D,), 2.0, device="cuda"); db = torch.full((D,), -1.0, device="cuda")
+        ops.layernorm_bwd_params(dy, x, mean, rstd, dw, db, rows, D, x_row_stride=x.stride(0), dy_row_stride=dy.stride(0))
+        got.append((dw, db))
+    (dw, db), (dw2, db2) = got
+    assert_blocks(dw[None], ref_w[None], 4e-6, 1, 1, what=what + " dgamma")
+    assert_blocks(db[None], ref_b[None], 6e-7, 1, 1, what=what + " dbeta")
+    assert torch.equal(dw, dw2) and torch.equal(db, db2), what
+    return dw, db
+
+
+@pytest.mark.parametrize("x_dtype", [torch.float32, torch.bfloat16])
+def test_layernorm_param_gradients_fp32_dy(x_dtype):
+    """An fp32 dy (ln_pre on an fp32 gradient stream) against an fp32 and a bf16 x: the two one-column-per-thread forms no
+    other test reaches.  Two slabs (256 + 7 rows), a partly filled column block.
+    dy holds bf16-representable values in fp32, as the dy of every neighbouring test does: the 6e-7 bound on dbeta is the one
+    measured on such data, whose partial sums fp32 holds (nearly) exactly.  On dy with 24 random mantissa bits the 256 sequential
+    fp32 additions of a slab alone round by more (1.9e-6 in an emulation of this summation order on the host), in any kernel."""
+    rows, D = 263, 72
+    g = torch.Generator().manual_seed(263 + 72 + (x_dtype == torch.bfloat16))
+    x = (torch.randn(rows, D, generator=g) * 2 + 0.5).to(x_dtype).cuda()
+    dy = torch.randn(rows, D, generator=g).bfloat16().float().cuda()
+    _ln_param_gradients(dy, x, f"fp32 dy, {x_dtype} x")
+
+
+def test_layernorm_param_gradients_bf16_unaligned_base():
+    """bf16 dy and bf16 x as views shifted by ONE column of wider tensors (D % 8 == 0, strides % 8 == 0, but the base is 2 bytes
+    off a 16-byte boundary): the one-column-per-thread form must be chosen.  The same numbers through aligned copies take the
+    8-column form; both against fp64 (not each other: they add in different orders)."""
+    rows, D = 263, 72
+    g = torch.Generator().manual_seed(7263)
+    wx = (torch.randn(rows, D + 8, generator=g) * 2 + 0.5).bfloat16().cuda()
+    wdy = torch.randn(rows, D + 8, generator=g).bfloat16().cuda()
+    x, dy = wx[:, 1:1 + D], wdy[:, 1:1 + D]
+    assert x.data_ptr() % 16 == 2 and dy.data_ptr() % 16 == 2 and x.stride(0) % 8 == 0
+    _ln_param_gradients(dy, x, "shifted views")
+    _ln_param_gradients(dy.contiguous(), x.contiguous(), "aligned copies")
+
+
+@pytest.mark.parametrize("rows", [257, 261, 3])
+@pytest.mark.parametrize("x_dtype", [torch.bfloat16, torch.float32])
+def test_layernorm_param_gradients_slab_and_lane_edges(rows, x_dtype):
+    """The two vector forms (bf16 dy with a bf16 / an fp32 x) at the edges of the row split, D = 64 (8 / 16 of the 64 column
+    groups live): 257 rows = a second slab of one row, lane 0 alone has work; 261 = lanes 0-3 of the second slab hold 2, 1, 1, 1
+    rows (the two-row batch and the single-row remainder both run short); 3 = fewer rows than lanes."""
+    D = 64
+    g = torch.Generator().manual_seed(rows * 5 + (x_dtype == torch.bfloat16))
+    x = (torch.randn(rows, D, generator=g) * 2 + 0.5).to(x_dtype).cuda()
+    dy = torch.randn(rows, D, generator=g).bfloat16().cuda()
+    _ln_param_gradients(dy, x, f"{rows} rows, {x_dtype} x")
+
+
+def test_layernorm_param_gradients_strided_dy():
+    """bf16 dy = a 16-byte aligned column window of a wider tensor (dy_row_stride > D) with a dense bf16 x: the 8-column form."""
+    rows, D = 50, 64
+    g = torch.Generator().manual_seed(5064)
+    x = (torch.randn(rows, D, generator=g) * 2 + 0.5).bfloat16().cuda()
+    dy = torch.randn(rows, D + 16, generator=g).bfloat16().cuda()[:, 8:8 + D]
+    assert dy.stride(0) == D + 16 and dy.data_ptr() % 16 == 0
+    _ln_param_gradients(dy, x, "strided dy")
+
+
 def test_adamw_matches_torch():
     from vitlens_hip import train as TR
     g = torch.Generator().manual_seed(7)

@@ -2,7 +2,8 @@
 """Do two builds of a .hip file hold the same kernels?  Compares two device-assembly files
 (hipcc --offload-arch=gfx950 --cuda-device-only -S, with the flags csrc/Makefile gives the file) kernel by kernel, as text.
 
-Kernels are paired by instantiation: `name<integer and bool template arguments>`.  A kernel of OLD pairs with the kernel of NEW
+Kernels are paired by instantiation: `name<template arguments>`, integers and bools as digits, builtin types as their mangled
+letters (f = float, t = the 16-bit storage type of bf16).  A kernel of OLD pairs with the kernel of NEW
 that has the same key, or its key extended by zeros (template parameters added later with a false / 0 default);
 --alias 'REGEX=REPLACEMENT' rewrites OLD keys first, for kernels that were renamed.  Inside a kernel the symbol's own name and
 the numbers of local labels are normalised; everything else, register numbers included, must match for `identical`.  Prints
@@ -13,6 +14,21 @@ usage: python tools/kernel_text_diff.py OLD.s NEW.s [--only REGEX] [--alias 'dq_
 import argparse
 import re
 import sys
+
+
+def template_args(rest):
+    """The template arguments of a mangled kernel name, `rest` = what follows the name: integers and bools as their digits,
+    builtin types as their mangled letters (f = float, t = unsigned short, the bf16 storage type), in order.  Instantiations
+    that differ only in a type (ln_bwd_kernel<4, bf16, float, float> / <4, float, float, float>) thereby get keys of their own.
+    An argument of any other kind ends the walk: the integers and bools of the whole symbol, as before types were read."""
+    args, i = [], 1
+    while rest.startswith("I") and i < len(rest) and rest[i] != "E":
+        m = re.match(r"L[ib](\d+)E|(DF16b|D[fdhe]|[a-z])", rest[i:])
+        if not m:
+            return re.findall(r"L[ib](\d+)E", rest)
+        args.append(m.group(1) or m.group(2))
+        i += m.end()
+    return args
 
 
 def kernels(path):
@@ -38,7 +54,7 @@ def kernels(path):
                 while sym[i].isdigit():                        # the last length-prefixed component of the mangled name
                     n = re.match(r"\d+", sym[i:]).group()
                     name, i = sym[i + len(n):i + len(n) + int(n)], i + len(n) + int(n)
-                key = name + "<" + ",".join(re.findall(r"L[ib](\d+)E", sym)) + ">"
+                key = name + "<" + ",".join(template_args(sym[i:])) + ">"
                 out[key] = (lines, (res["NumVgprs"], res["ScratchSize"], *spills[sym], res["LDSByteSize"], res["Occupancy"]))
                 sym = None
     return out

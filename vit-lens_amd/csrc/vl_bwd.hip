@@ -1,7 +1,6 @@
 // Row-wise backward kernels + optimizer for the trainable part of the path (HBM-bound, wave-per-row).
 //   vl_layernorm_bwd      dx = LN'(dy) (+ upstream residual gradient), f32 and optional bf16 copy
-//   vl_layernorm_bwd_params   dw += sum_r dy*xhat, db += sum_r dy          (trainable LayerNorms only)
-//   vl_colsum             out[j] += sum_r a[r,j]                            (bias gradients)
+//   (the LayerNorm parameter gradients and the bias gradients - column reductions over the rows - are vl_colreduce.hip)
 //   vl_gelu_bf16          y = gelu(u)                                       (recompute of the MLP hidden)
 //   vl_adamw_step         torch.optim.AdamW update (decoupled weight decay), one launch per tensor
 //   vl_sumsq_f32          squared 2-norm of the flat gradient buffer: two stages, fp64 partials, bit-reproducible
@@ -105,216 +104,6 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdP p) {
       if (dx) { if constexpr (sizeof(TG) == 4) dx[e] = v; else dx[e] = f2bf(v); }
       if (dxb) dxb[e] = f2bf(v);
     }
-  }
-}
-
-// LayerNorm weight / bias gradients, deterministic two-stage column reduction (no atomics):
-// stage 1: block (column block, row slab) -> partial sums ws[slab][2][D]; stage 2: fixed-order sum over slabs, += into dw / db.
-template <typename TDY, typename TX>
-__global__ void __launch_bounds__(256) ln_bwd_params_kernel(const TDY* dy, long dys, const TX* x, long xs, const float* mean,
-                                                            const float* rstd, float* ws, int rows, int D, int slab) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= D) return;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  float a = 0.f, b = 0.f;
-  for (int r = r0; r < r1; ++r) {
-    const float g = ld1(dy + (long)r * dys + j);
-    a = fmaf(g, (ld1(x + (long)r * xs + j) - mean[r]) * rstd[r], a);
-    b += g;
-  }
-  ws[((long)blockIdx.y * 2) * D + j] = a; ws[((long)blockIdx.y * 2 + 1) * D + j] = b;
-}
-
-// bf16 dy and bf16 x with 16-byte friendly rows: 8 columns per thread, four row lanes per block (as colsum8_bf16_kernel; the
-// one-column-per-thread kernel above ran at 2 TB/s: 132 us per call on [65 792, 1 024]).  Same partial layout, same finalize.
-__global__ void __launch_bounds__(256) ln_bwd_params8_bf16_kernel(const bf16_t* dy, long dys, const bf16_t* x, long xs, const float* mean,
-                                                                  const float* rstd, float* ws, int rows, int D, int slab) {
-  __shared__ float sh[3][64][16];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int j = (blockIdx.x * 64 + cx) * 8;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  float a[8], b[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { a[e] = 0.f; b[e] = 0.f; }
-  if (j < D) {
-    for (int r = r0 + ry; r < r1; r += 8) {
-      const bool two = r + 4 < r1;
-      const int r2 = two ? r + 4 : r;
-      const u32x4 g0 = *(const u32x4*)(dy + (long)r * dys + j), x0 = *(const u32x4*)(x + (long)r * xs + j);
-      const u32x4 g1 = *(const u32x4*)(dy + (long)r2 * dys + j), x1 = *(const u32x4*)(x + (long)r2 * xs + j);
-      const float m0 = mean[r], s0 = rstd[r], m1 = mean[r2], s1 = two ? rstd[r2] : 0.f;
-      const float k1 = two ? 1.f : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float gl = bf2f((bf16_t)(g0[e] & 0xffff)), gh = bf2f((bf16_t)(g0[e] >> 16));
-        a[2 * e] = fmaf(gl, (bf2f((bf16_t)(x0[e] & 0xffff)) - m0) * s0, a[2 * e]);
-        a[2 * e + 1] = fmaf(gh, (bf2f((bf16_t)(x0[e] >> 16)) - m0) * s0, a[2 * e + 1]);
-        b[2 * e] += gl; b[2 * e + 1] += gh;
-        const float hl = bf2f((bf16_t)(g1[e] & 0xffff)), hh = bf2f((bf16_t)(g1[e] >> 16));
-        a[2 * e] = fmaf(hl, (bf2f((bf16_t)(x1[e] & 0xffff)) - m1) * s1, a[2 * e]);
-        a[2 * e + 1] = fmaf(hh, (bf2f((bf16_t)(x1[e] >> 16)) - m1) * s1, a[2 * e + 1]);
-        b[2 * e] = fmaf(hl, k1, b[2 * e]); b[2 * e + 1] = fmaf(hh, k1, b[2 * e + 1]);
-      }
-    }
-  }
-  if (ry) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sh[ry - 1][cx][e] = a[e]; sh[ry - 1][cx][8 + e] = b[e]; }
-  }
-  __syncthreads();
-  if (ry == 0 && j < D) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      ws[((long)blockIdx.y * 2) * D + j + e] = (a[e] + sh[0][cx][e]) + (sh[1][cx][e] + sh[2][cx][e]);
-      ws[((long)blockIdx.y * 2 + 1) * D + j + e] = (b[e] + sh[0][cx][8 + e]) + (sh[1][cx][8 + e] + sh[2][cx][8 + e]);
-    }
-  }
-}
-
-// fp32 rows that are 16-byte friendly (the Perceiver's fp32 residual-gradient stream: bias gradients of to_out / FF w2): 4 columns
-// per thread, four row lanes with four loads each in flight - the one-column-per-thread kernel ran at 2.3 TB/s (116 us on
-// [65 536, 1 024] in the C4 step).  Same partial layout, same finalize.
-__global__ void __launch_bounds__(256) colsum4_f32_kernel(const float* a, long lda, float* ws, int rows, int cols, int slab) {
-  __shared__ float sh[3][64][4];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int j = (blockIdx.x * 64 + cx) * 4;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (j < cols) {
-    const float* ptr = a + j;
-    int r = r0 + ry;
-    for (; r + 12 < r1; r += 16) {
-      const f32x4 v0 = *(const f32x4*)(ptr + (long)r * lda), v1 = *(const f32x4*)(ptr + (long)(r + 4) * lda);
-      const f32x4 v2 = *(const f32x4*)(ptr + (long)(r + 8) * lda), v3 = *(const f32x4*)(ptr + (long)(r + 12) * lda);
-      s += v0; s += v1; s += v2; s += v3;
-    }
-    for (; r < r1; r += 4) s += *(const f32x4*)(ptr + (long)r * lda);
-  }
-  if (ry) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sh[ry - 1][cx][e] = s[e];
-  }
-  __syncthreads();
-  if (ry == 0 && j < cols) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ws[(long)blockIdx.y * cols + j + e] = (s[e] + sh[0][cx][e]) + (sh[1][cx][e] + sh[2][cx][e]);
-  }
-}
-
-// bf16 dy with fp32 x (the Perceiver's LayerNorms: bf16 gradient of the normalised rows, fp32 residual stream), 8- / 16-byte
-// friendly rows: 4 columns per thread, four row lanes, two rows per iteration (the generic kernel: 139 us on [65 536, 1 024]).
-__global__ void __launch_bounds__(256) ln_bwd_params4_bf16_f32_kernel(const bf16_t* dy, long dys, const float* x, long xs, const float* mean,
-                                                                      const float* rstd, float* ws, int rows, int D, int slab) {
-  __shared__ float sh[3][64][8];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int j = (blockIdx.x * 64 + cx) * 4;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  float a[4], b[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { a[e] = 0.f; b[e] = 0.f; }
-  if (j < D) {
-    for (int r = r0 + ry; r < r1; r += 8) {
-      const bool two = r + 4 < r1;
-      const int r2 = two ? r + 4 : r;
-      const u32x2 g0 = *(const u32x2*)(dy + (long)r * dys + j), g1 = *(const u32x2*)(dy + (long)r2 * dys + j);
-      const f32x4 x0 = *(const f32x4*)(x + (long)r * xs + j), x1 = *(const f32x4*)(x + (long)r2 * xs + j);
-      const float m0 = mean[r], s0 = rstd[r], m1 = mean[r2], s1 = two ? rstd[r2] : 0.f;
-      const float k1 = two ? 1.f : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float gl = bf2f((bf16_t)((e & 1) ? (g0[e >> 1] >> 16) : (g0[e >> 1] & 0xffff)));
-        const float hl = bf2f((bf16_t)((e & 1) ? (g1[e >> 1] >> 16) : (g1[e >> 1] & 0xffff)));
-        a[e] = fmaf(gl, (x0[e] - m0) * s0, a[e]);
-        b[e] += gl;
-        a[e] = fmaf(hl, (x1[e] - m1) * s1, a[e]);
-        b[e] = fmaf(hl, k1, b[e]);
-      }
-    }
-  }
-  if (ry) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { sh[ry - 1][cx][e] = a[e]; sh[ry - 1][cx][4 + e] = b[e]; }
-  }
-  __syncthreads();
-  if (ry == 0 && j < D) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      ws[((long)blockIdx.y * 2) * D + j + e] = (a[e] + sh[0][cx][e]) + (sh[1][cx][e] + sh[2][cx][e]);
-      ws[((long)blockIdx.y * 2 + 1) * D + j + e] = (b[e] + sh[0][cx][4 + e]) + (sh[1][cx][4 + e] + sh[2][cx][4 + e]);
-    }
-  }
-}
-
-// out_k[j] += scale * sum_s ws[s][k][j]   (k < K planes), fixed summation order.
-// One block = 64 columns of one plane x 16 slab groups: thread (j, g) adds the slabs s = g, g+16, ... in order, the 16
-// group sums are combined by a fixed tree through LDS.  (The first version gave every column ONE thread and the whole
-// grid 4 blocks: 514 dependent loads per thread, 120 us per call = 4 ms of the C3 step.)
-__global__ void __launch_bounds__(1024) slab_finalize_kernel(const float* ws, int nslab, int K, int D, float scale, float* out0, float* out1) {
-  __shared__ float sh[16][64];
-  const int jl = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + jl, k = blockIdx.y;
-  float s = 0.f;
-  if (j < D)
-    for (int t = g; t < nslab; t += 16) s += ws[((long)t * K + k) * D + j];
-  sh[g][jl] = s;
-  __syncthreads();
-  if (g == 0 && j < D) {
-    float a[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = sh[i][jl];
-#pragma unroll
-    for (int w = 8; w > 0; w >>= 1)
-#pragma unroll
-      for (int i = 0; i < w; ++i) a[i] += a[i + w];
-    float* o = k == 0 ? out0 : out1;
-    o[j] += a[0] * scale;
-  }
-}
-
-// bias gradients: stage 1 of the same deterministic two-stage column reduction (partials ws[slab][cols])
-template <typename T>
-__global__ void __launch_bounds__(256) colsum_kernel(const T* a, long lda, float* ws, int rows, int cols, int slab) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= cols) return;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  float s = 0.f;
-  for (int r = r0; r < r1; ++r) s += ld1(a + (long)r * lda + j);
-  ws[(long)blockIdx.y * cols + j] = s;
-}
-
-// the same for bf16 inputs whose rows are 16-byte friendly: 8 columns per thread (one 16-byte load per row), four row lanes
-// per block with four loads each in flight, reduced through LDS.  (The one-column-per-thread kernel moves 128 bytes per wave
-// load: 1.6 TB/s on a [65 792, 4 096] gradient, 0.33 ms - more than both transposes of the path it now stands beside.)
-__global__ void __launch_bounds__(256) colsum8_bf16_kernel(const bf16_t* a, long lda, float* ws, int rows, int cols, int slab) {
-  __shared__ float sh[3][64][8];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int j = (blockIdx.x * 64 + cx) * 8;
-  const int r0 = blockIdx.y * slab, r1 = min(rows, r0 + slab);
-  float s[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = 0.f;
-  auto add = [&](const u32x4 v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { s[2 * e] += bf2f((bf16_t)(v[e] & 0xffff)); s[2 * e + 1] += bf2f((bf16_t)(v[e] >> 16)); }
-  };
-  if (j < cols) {
-    const bf16_t* ptr = a + j;
-    int r = r0 + ry;
-    for (; r + 12 < r1; r += 16) {
-      const u32x4 v0 = *(const u32x4*)(ptr + (long)r * lda), v1 = *(const u32x4*)(ptr + (long)(r + 4) * lda);
-      const u32x4 v2 = *(const u32x4*)(ptr + (long)(r + 8) * lda), v3 = *(const u32x4*)(ptr + (long)(r + 12) * lda);
-      add(v0); add(v1); add(v2); add(v3);
-    }
-    for (; r < r1; r += 4) add(*(const u32x4*)(ptr + (long)r * lda));
-  }
-  if (ry) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[ry - 1][cx][e] = s[e];
-  }
-  __syncthreads();
-  if (ry == 0 && j < cols) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ws[(long)blockIdx.y * cols + j + e] = (s[e] + sh[0][cx][e]) + (sh[1][cx][e] + sh[2][cx][e]);
   }
 }
 
@@ -585,52 +374,6 @@ extern "C" int vl_layernorm_bwd(const void* dy, int dy_dtype, long dy_stride, co
                                 const float* mean, const float* rstd, const float* w, const float* dres, float* dx,
                                 void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream) {
   return vl_layernorm_bwd_g(dy, dy_dtype, dy_stride, x, x_dtype, x_stride, mean, rstd, w, dres, dx, VL_F32, dx_bf16, dx_stride, rows, D, stream);
-}
-
-static const int kSlabRows = 256;
-extern "C" long vl_colreduce_ws_floats(int rows, int cols, int planes) {
-  return (long)((rows + kSlabRows - 1) / kSlabRows) * planes * cols;
-}
-
-extern "C" int vl_layernorm_bwd_params(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
-                                       const float* mean, const float* rstd, float* dw, float* db, int rows, int D,
-                                       float* ws, hipStream_t stream) {
-  if (rows <= 0 || D <= 0) return vl_set_error("vl_layernorm_bwd_params: empty problem");
-  if (!ws) return vl_set_error("vl_layernorm_bwd_params: workspace of vl_colreduce_ws_floats(rows, D, 2) floats required");
-  const int slab = kSlabRows, nslab = (rows + slab - 1) / slab;
-  const dim3 g((D + 255) / 256, nslab), b(256);
-  if (dy_dtype == VL_BF16 && x_dtype == VL_F32 && (D & 3) == 0 && (dy_stride & 3) == 0 && (x_stride & 3) == 0 &&
-      ((uintptr_t)dy & 7) == 0 && ((uintptr_t)x & 15) == 0)
-    hipLaunchKernelGGL(ln_bwd_params4_bf16_f32_kernel, dim3((D + 255) / 256, nslab), b, 0, stream, (const bf16_t*)dy, dy_stride, (const float*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  else if (dy_dtype == VL_BF16 && x_dtype == VL_F32)
-    hipLaunchKernelGGL((ln_bwd_params_kernel<bf16_t, float>), g, b, 0, stream, (const bf16_t*)dy, dy_stride, (const float*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  else if (dy_dtype == VL_BF16 && (D & 7) == 0 && (dy_stride & 7) == 0 && (x_stride & 7) == 0 && (((uintptr_t)dy | (uintptr_t)x) & 15) == 0)
-    hipLaunchKernelGGL(ln_bwd_params8_bf16_kernel, dim3((D + 511) / 512, nslab), b, 0, stream, (const bf16_t*)dy, dy_stride, (const bf16_t*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  else if (dy_dtype == VL_BF16)
-    hipLaunchKernelGGL((ln_bwd_params_kernel<bf16_t, bf16_t>), g, b, 0, stream, (const bf16_t*)dy, dy_stride, (const bf16_t*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  else if (x_dtype == VL_F32)
-    hipLaunchKernelGGL((ln_bwd_params_kernel<float, float>), g, b, 0, stream, (const float*)dy, dy_stride, (const float*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  else
-    hipLaunchKernelGGL((ln_bwd_params_kernel<float, bf16_t>), g, b, 0, stream, (const float*)dy, dy_stride, (const bf16_t*)x, x_stride, mean, rstd, ws, rows, D, slab);
-  hipLaunchKernelGGL(slab_finalize_kernel, dim3((D + 63) / 64, 2), dim3(1024), 0, stream, ws, nslab, 2, D, 1.0f, dw, db);
-  VL_HIP_OK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int vl_colsum(const void* a, int a_dtype, long lda, float* out, int rows, int cols, float scale, float* ws, hipStream_t stream) {
-  if (rows <= 0 || cols <= 0) return vl_set_error("vl_colsum: empty problem");
-  if (!ws) return vl_set_error("vl_colsum: workspace of vl_colreduce_ws_floats(rows, cols, 1) floats required");
-  const int slab = kSlabRows, nslab = (rows + slab - 1) / slab;
-  const dim3 g((cols + 255) / 256, nslab), b(256);
-  if (a_dtype == VL_BF16 && (cols & 7) == 0 && (lda & 7) == 0 && ((uintptr_t)a & 15) == 0)
-    hipLaunchKernelGGL(colsum8_bf16_kernel, dim3((cols + 511) / 512, nslab), b, 0, stream, (const bf16_t*)a, lda, ws, rows, cols, slab);
-  else if (a_dtype == VL_BF16) hipLaunchKernelGGL(colsum_kernel<bf16_t>, g, b, 0, stream, (const bf16_t*)a, lda, ws, rows, cols, slab);
-  else if (a_dtype == VL_F32 && (cols & 3) == 0 && (lda & 3) == 0 && ((uintptr_t)a & 15) == 0)
-    hipLaunchKernelGGL(colsum4_f32_kernel, g, b, 0, stream, (const float*)a, lda, ws, rows, cols, slab);
-  else hipLaunchKernelGGL(colsum_kernel<float>, g, b, 0, stream, (const float*)a, lda, ws, rows, cols, slab);
-  hipLaunchKernelGGL(slab_finalize_kernel, dim3((cols + 63) / 64, 1), dim3(1024), 0, stream, ws, nslab, 1, cols, scale, out, out);
-  VL_HIP_OK(hipGetLastError());
-  return 0;
 }
 
 extern "C" int vl_gelu_bf16(const void* u, void* y, long n, hipStream_t stream) {

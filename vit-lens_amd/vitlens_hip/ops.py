@@ -401,6 +401,20 @@ def gemm_dw_tn_any(dy, x, g, alpha=1.0):
     return True
 
 
+def weight_grad(dy, x, g, bias_grad=None, narrow=True, cfg=-1):
+    """g[N_out, K_in] += dy^T x on the operands as the backward holds them (dy [R, N_out], x [R, K_in], row = token) and, if
+    bias_grad is given, bias_grad += the column sums of dy.  Token-major operands where the shape fits the dW kernel (narrow:
+    column counts that are not whole 256-column tiles too, through gemm_dw_tn_any's zero-padded copies; otherwise gemm_dw_tn
+    alone), the bias gradient from colsum; else both operands transposed to bf16 with the token axis padded to whole 64-token
+    steps - the transpose of dy reads all of dy anyway and produces the bias gradient - and gemm_dw (kernel configuration cfg)."""
+    if (gemm_dw_tn_any if narrow else gemm_dw_tn)(dy, x, g):
+        if bias_grad is not None:
+            colsum(dy, bias_grad)
+        return g
+    rp = (dy.shape[0] + 63) // 64 * 64
+    return gemm_dw(transpose_colsum(dy, rp, colsum_out=bias_grad), transpose_to_bf16(x, ldo=rp), g, cfg=cfg)
+
+
 def _bhld_strides(*views):
     """(batch, head, row) element strides of [B,H,L,dh] views (last stride 1) as a ctypes long array."""
     import ctypes

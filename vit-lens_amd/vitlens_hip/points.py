@@ -193,10 +193,7 @@ class PointTokenizerTrainer:
         """g += dy^T x (bf16 [rows, *] operands): token-major operands for the dW kernel (narrow channel counts zero-padded to
         whole tiles, ops.gemm_dw_tn_any) - the rows are B * groups * points, two transposed copies of them per weight were
         3 % of the C5 step; the transposing NT path where the row count is not a multiple of 64."""
-        if ops.gemm_dw_tn_any(dy, x, g):
-            return
-        rp = (dy.shape[0] + 63) // 64 * 64
-        ops.gemm_dw(ops.transpose_to_bf16(dy, ldo=rp), ops.transpose_to_bf16(x, ldo=rp), g, cfg=self.cfg)
+        ops.weight_grad(dy, x, g, cfg=self.cfg)
 
     def _dw(self, name, dy, x, cols=None):
         """grads[name] += dy^T x (both bf16 [rows, *])."""

@@ -208,19 +208,11 @@ class TowerTrainer:
                                      folds(l), folds(l + 1), cls_only=cls_only, write_out=write_out, mm=mm)
 
     # ------------------------------------------------------------------------------------------ backward
-    def _dw(self, name, dy, x, rows, bias_name=None):
-        """grads[name] += dy^T x  (dy [rows, N], x [rows, K] -> [N, K]); operands transposed to bf16.  The bias gradient
-        (column sums of dy) is produced by the transpose of dy, which reads all of dy anyway."""
+    def _dw(self, name, dy, x, bias_name=None):
+        """grads[name] += dy^T x  (dy [rows, N], x [rows, K] -> [N, K]), grads[bias_name] += the column sums of dy."""
         g = self.grad_buffer(name, torch.empty(dy.shape[1], x.shape[1]))
-        rp = (rows + 63) // 64 * 64
         gb = self.grad_buffer(bias_name, torch.empty(dy.shape[1])) if bias_name else None
-        if rows == dy.shape[0] == x.shape[0] and ops.gemm_dw_tn(dy, x, g):      # token-major operands: no transposed copies
-            if gb is not None:
-                ops.colsum(dy, gb)
-            return
-        dyt = ops.transpose_colsum(dy, rp, colsum_out=gb)
-        xt = ops.transpose_colsum(x, rp)
-        ops.gemm_dw(dyt, xt, g, cfg=self.eng.gemm_cfg)
+        ops.weight_grad(dy, x, g, bias_grad=gb, narrow=False, cfg=self.eng.gemm_cfg)
 
     def backward(self, dfeat: torch.Tensor, on_block_done=None) -> torch.Tensor:
         """dfeat f32 [B, E] -> gradient w.r.t. the input tokens, f32 [B*T, D]; fills self.grads.  After a forward that dropped
@@ -322,8 +314,8 @@ class TowerTrainer:
             # ---- MLP branch: x2 = x1 + proj(gelu(fc(ln2(x1)))) ----
             ops.gemm(S.dxb, wT["proj_w"], None, out=S.du, res=S.u[l], epi=ops.EPI_DGELU, act=self.act_dsave, cfg=cfg)   # du = (dx W_proj) * act'(u)
             if trainable:
-                self._dw(bp + "mlp.c_proj.weight", S.dx, S.hidk[l], rows, bp + "mlp.c_proj.bias")
-                self._dw(bp + "mlp.c_fc.weight", S.du, S.h2[l], rows, bp + "mlp.c_fc.bias")
+                self._dw(bp + "mlp.c_proj.weight", S.dx, S.hidk[l], bp + "mlp.c_proj.bias")
+                self._dw(bp + "mlp.c_fc.weight", S.du, S.h2[l], bp + "mlp.c_fc.bias")
             ops.gemm(S.du, wT["fc_w"], None, out=S.dh, epi=ops.EPI_BF16, cfg=cfg)                           # dh2
             if trainable:
                 ops.layernorm_bwd_params(S.dh, S.X[2 * l + 1], m2, r2, self.grad_buffer(bp + "ln_2.weight", w["ln2_w"]),
@@ -331,12 +323,12 @@ class TowerTrainer:
             ops.layernorm_bwd(S.dh, S.X[2 * l + 1], m2, r2, w["ln2_w"], rows, D, dres=S.dx, dx=S.dx, dx_bf16=dxb_out)
             # ---- attention branch: x1 = x0 + out(attn(qkv(ln1(x0)))) ----
             if trainable:
-                self._dw(bp + "attn.out_proj.weight", S.dx, S.a[l], rows, bp + "attn.out_proj.bias")
+                self._dw(bp + "attn.out_proj.weight", S.dx, S.a[l], bp + "attn.out_proj.bias")
             ops.gemm(S.dxb, wT["out_w"], None, out=S.dOm, epi=ops.EPI_BF16, cfg=cfg)                        # dO
             ops.attn_bwd(S.q[l], S.k[l], S.v[l], S.dO, S.av[l], S.lse[l], S.delta,
                          S.dqkv, S.dqkv[:, D:], S.dqkv[:, 2 * D:], 3 * D, 3 * D, causal=self.causal)
             if trainable:
-                self._dw(bp + "attn.in_proj_weight", S.dqkv, S.h1[l], rows, bp + "attn.in_proj_bias")
+                self._dw(bp + "attn.in_proj_weight", S.dqkv, S.h1[l], bp + "attn.in_proj_bias")
             ops.gemm(S.dqkv, wT["in_w"], None, out=S.dh, epi=ops.EPI_BF16, cfg=cfg)                         # dh1
             if trainable:
                 ops.layernorm_bwd_params(S.dh, S.X[2 * l], m1, r1, self.grad_buffer(bp + "ln_1.weight", w["ln1_w"]),
@@ -351,10 +343,7 @@ def conv_weight_grad(dtok: torch.Tensor, cols: torch.Tensor, g: torch.Tensor, ge
     gradient of its output tokens, cols bf16 [R, Kp] = the im2col rows the forward kept).  Token-major operands for the dW
     kernel (the fp32 gradient cast to bf16 - the values a transposed copy would hold too); the transposing NT path where the
     shape does not fit."""
-    if ops.gemm_dw_tn_any(ops.cast_bf16(dtok.contiguous()), cols, g):
-        return
-    rp = (dtok.shape[0] + 63) // 64 * 64
-    ops.gemm_dw(ops.transpose_to_bf16(dtok, ldo=rp), ops.transpose_to_bf16(cols, ldo=rp), g, cfg=gemm_cfg)
+    ops.weight_grad(ops.cast_bf16(dtok.contiguous()), cols, g, cfg=gemm_cfg)
 
 
 class DepthLensTrainer:
@@ -713,13 +702,8 @@ class PerceiverTrainer:
         return st["X"][-1]
 
     # ---- backward ---------------------------------------------------------------------------------
-    def _dw(self, name, dy, x, rows):
-        g = self.grad_buffer(name, (dy.shape[1], x.shape[1]))
-        rp = (rows + 63) // 64 * 64
-        # token-major operands, no transposed copies (narrow projections: the small operand zero-padded to whole tiles)
-        if rows == dy.shape[0] == x.shape[0] and ops.gemm_dw_tn_any(dy, x, g):
-            return
-        ops.gemm_dw(ops.transpose_to_bf16(dy, ldo=rp), ops.transpose_to_bf16(x, ldo=rp), g, cfg=self.pe.gemm_cfg)
+    def _dw(self, name, dy, x):
+        ops.weight_grad(dy, x, self.grad_buffer(name, (dy.shape[1], x.shape[1])), cfg=self.pe.gemm_cfg)
 
     def _ln_params(self, name, dy, x, stats, rows, D):
         ops.layernorm_bwd_params(dy, x, stats[0], stats[1], self.grad_buffer(name + ".weight", (D,)),
@@ -739,13 +723,13 @@ class PerceiverTrainer:
             # the fp32 residual gradient there, not a bf16 copy)
             n = self.pe.cfg.num_latents
             ops.ff_drop_bwd(st["dx"], st["dxb"], rows // n, n, drop.pf, drop.seed, drop.sample0, sub, dy_f32=s.y)
-            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
+            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid)
             ops.colsum(s.y, self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
         else:
-            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid, rows)
+            self._dw(pname + "1.fn.net.2.weight", st["dxb"], s.hid)
             ops.colsum(st["dx"], self.grad_buffer(pname + "1.fn.net.2.bias", (D,)))
         ops.gemm(st["dxb"], wT["w2"], None, out=st["dh8"], res=s.h, epi=ops.EPI_DGEGLU, cfg=cfg)     # d(pre-activation), interleaved
-        self._dw(pname + "1.fn.net.0.weight_il", st["dh8"], s.hn, rows)
+        self._dw(pname + "1.fn.net.0.weight_il", st["dh8"], s.hn)
         ops.colsum(st["dh8"], self.grad_buffer(pname + "1.fn.net.0.bias_il", (8 * D,)))
         ops.gemm(st["dh8"], wT["w0"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
         self._ln_params(pname + "1.norm", st["dhn"], s.x0, s.stats, rows, D)
@@ -758,7 +742,7 @@ class PerceiverTrainer:
         input gradient is ADDED to st['ddata'] (every cross layer reads the same data)."""
         cfg, (rows, D), inner = self.pe.gemm_cfg, s.x0.shape, s.a.shape[1]
         packed = dkv is None
-        self._dw(pname + "0.fn.to_out.weight", st["dxb"], s.a, rows)
+        self._dw(pname + "0.fn.to_out.weight", st["dxb"], s.a)
         ops.colsum(st["dx"], self.grad_buffer(pname + "0.fn.to_out.bias", (D,)))
         ops.gemm(st["dxb"], wT["out"], None, out=s.dOm, epi=ops.EPI_BF16, cfg=cfg)
         dk, dv, lds = (dq[:, inner:], dq[:, 2 * inner:], (3 * inner, 3 * inner)) if packed else (dkv, dkv[:, inner:], (inner, 2 * inner))
@@ -769,14 +753,14 @@ class PerceiverTrainer:
         else:
             ops.attn_bwd(s.q, s.k, s.v, s.dO, s.av, s.lse, s.delta, dq, dk, dv, *lds)
         # query side: LN(x0) -> to_q (packed: -> [to_q ; to_kv])
-        self._dw(pname + ("0.fn.to_qkv.weight" if packed else "0.fn.to_q.weight"), dq, s.hn, rows)
+        self._dw(pname + ("0.fn.to_qkv.weight" if packed else "0.fn.to_q.weight"), dq, s.hn)
         ops.gemm(dq, wT["qkv" if packed else "q"], None, out=st["dhn"], epi=ops.EPI_BF16, cfg=cfg)
         self._ln_params(pname + "0.norm", st["dhn"], s.x0, s.stats, rows, D)
         ops.layernorm_bwd(st["dhn"], s.x0, s.stats[0], s.stats[1], norm[0], rows, D, dres=st["dx"], dx=st["dx"], dx_bf16=st["dxb"])
         if packed:
             return
         crows, C = data.shape
-        self._dw(pname + "0.fn.to_kv.weight", dkv, s.cn, crows)
+        self._dw(pname + "0.fn.to_kv.weight", dkv, s.cn)
         ops.gemm(dkv, wT["kv"], None, out=st["dctx"], epi=ops.EPI_BF16, cfg=cfg)
         self._ln_params(pname + "0.norm_context", st["dctx"], data, s.cstats, crows, C)
         ops.layernorm_bwd(st["dctx"], data, s.cstats[0], s.cstats[1], norm_ctx[0], crows, C, dres=st["ddata"], dx=st["ddata"])
