@@ -251,7 +251,11 @@ int vl_ln_row_stats(const float* row_part, int P, const void* x_bf16, long x_row
 /* LayerNorm over the last dim (eps inside sqrt, biased variance): y = (x-mean)*rstd*w + b.
  * Source row for output row r is  r*row_mul + row_index[r]  when row_index != NULL (EOT gather,
  * model.py:539; cls pooling uses row_index == NULL with x_row_stride = (T+1)*D), else r.
- * Replaces LayerNorm/LayerNormFp32 (transformer.py:17-34) and PreNorm (perceiver.py:67-82). */
+ * Replaces LayerNorm/LayerNormFp32 (transformer.py:17-34) and PreNorm (perceiver.py:67-82).
+ * Dtype pairs (x -> y): f32 -> f32 | bf16 | f16, bf16 -> f32 | bf16; any other pair is refused with a status, and so is one of
+ * mean / rstd without the other (this holds for vl_assemble_ln_pre and vl_assemble_ln_pre_keep too).  D % 256 == 0 rows whose
+ * strides and base addresses (x, y, w, b; cls, pos, pos2, xpre) are multiples of 4 elements are held in registers and moved 8 /
+ * 16 bytes at a time; everything else takes the any-D form, one element at a time. */
 int vl_layernorm_fwd(const void* x, int x_dtype, long x_row_stride, const int64_t* row_index, long row_mul,
                      const float* w, const float* b, void* y, int y_dtype, long y_row_stride,
                      float* mean, float* rstd, int rows, int D, float eps, hipStream_t stream);
@@ -297,12 +301,14 @@ int vl_l2_normalize_bwd(const float* f, const float* df, const float* norms, flo
 int vl_im2col_bf16(const float* x, void* patches, int N, int C, int H, int W, int kh, int kw, int sh, int sw,
                    int Kp, int transpose_hw, hipStream_t stream);
 
-/* out[b,l,:] = token_embedding[ids[b,l]] + positional_embedding[l]   (model.py:531-533) */
+/* out[b,l,:] = token_embedding[ids[b,l]] + positional_embedding[l]   (model.py:531-533); ids are clamped into [0, vocab).
+ * out_dtype VL_F32 | VL_BF16, anything else is refused with a status. */
 int vl_text_embed(const int64_t* ids, const float* tok_emb, const float* pos, void* out, int out_dtype,
                   int B, int L, int D, int vocab, hipStream_t stream);
 
 int vl_cast_f32_bf16(const float* x, void* y, long n, hipStream_t stream);
-/* y[r,:] = x[r,:] + table[r % T,:]   (x_vada["x"] + x_vada["pos"], transformer.py:743-745) */
+/* y[r,:] = x[r,:] + table[r % T,:]   (x_vada["x"] + x_vada["pos"], transformer.py:743-745).  x_dtype, y_dtype VL_F32 |
+ * VL_BF16, anything else is refused with a status. */
 int vl_add_rows(const void* x, int x_dtype, const float* table, void* y, int y_dtype, long rows, int T, int D,
                 hipStream_t stream);
 /* out[c,r] bf16 = in[r,c]; columns r in [R, ldo) zero-filled (operand prep for gradient GEMMs) */
@@ -347,7 +353,10 @@ int vl_layernorm_bwd(const void* dy, int dy_dtype, long dy_stride, const void* x
                      const float* mean, const float* rstd, const float* w, const float* dres, float* dx,
                      void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream);
 /* The same with the residual-gradient stream (dres in, dx out) in dtype g_dtype (VL_F32 | VL_BF16): bf16 is what the
- * reference's amp_bf16 autocast carries for the gradients of its bf16 residual stream. */
+ * reference's amp_bf16 autocast carries for the gradients of its bf16 residual stream.  dy_dtype, x_dtype and g_dtype other
+ * than VL_F32 | VL_BF16 are refused with a status (vl_layernorm_bwd_sres too).  D in {256, 512, 768, 1024} with every row
+ * stride (the sparse form's dres_stride included) and every base address (dy, x, w, dres, dx, dx_bf16) a multiple of 4
+ * elements: one read of the row into registers, 8 / 16-byte accesses; everything else: the any-D form. */
 int vl_layernorm_bwd_g(const void* dy, int dy_dtype, long dy_stride, const void* x, int x_dtype, long x_stride,
                        const float* mean, const float* rstd, const float* w, const void* dres, void* dx, int g_dtype,
                        void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream);

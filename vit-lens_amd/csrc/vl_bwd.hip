@@ -288,7 +288,8 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* s
   }
 }
 
-__global__ void clamp_scalar_kernel(float* p, float lo, float hi) { *p = fminf(fmaxf(*p, lo), hi); }
+// (fminf / fmaxf return the other operand for a NaN: a diverged logit_scale would come out as lo.  torch.clamp_ keeps the NaN)
+__global__ void clamp_scalar_kernel(float* p, float lo, float hi) { const float v = *p; *p = v != v ? v : fminf(fmaxf(v, lo), hi); }
 
 // out[i] = a[i] + b[i] (f32), used to merge gradient contributions of shared tensors
 __global__ void __launch_bounds__(256) axpy_kernel(float* y, const float* x, float alpha, long n) {
@@ -322,7 +323,12 @@ static int grid_for(long n) { long g = (n + 255) / 256; return (int)(g > 4096 ? 
 template <typename TDY, typename TX, typename TG>
 static void ln_bwd_launch(const LnBwdP& p, hipStream_t stream) {
   const dim3 g((p.rows + 3) / 4), b(256);
-  const bool vec = (p.D % 256 == 0) && (p.dys % 4 == 0) && (p.xs % 4 == 0) && (p.dxs % 4 == 0);
+  // the register forms read and write every operand four elements (8 or 16 bytes) at a time: the strides AND the bases must be
+  // multiples of that (the column reductions' rule, vl_colreduce.hip), the sparse residual's own stride included
+  auto al4 = [](const void* q, size_t elem) { return (uintptr_t)q % (4 * elem) == 0; };      // a null (absent) operand passes
+  const bool vec = (p.D % 256 == 0) && (p.dys % 4 == 0) && (p.xs % 4 == 0) && (p.dxs % 4 == 0) &&
+                   (!(p.dres && p.dres_every > 1) || p.dres_s % 4 == 0) && al4(p.dy, sizeof(TDY)) && al4(p.x, sizeof(TX)) &&
+                   al4(p.w, 4) && al4(p.dres, sizeof(TG)) && al4(p.dx, sizeof(TG)) && al4(p.dxb, 2);
   if (vec && p.D == 1024) hipLaunchKernelGGL((ln_bwd_kernel<4, TDY, TX, TG>), g, b, 0, stream, p);
   else if (vec && p.D == 768) hipLaunchKernelGGL((ln_bwd_kernel<3, TDY, TX, TG>), g, b, 0, stream, p);
   else if (vec && p.D == 512) hipLaunchKernelGGL((ln_bwd_kernel<2, TDY, TX, TG>), g, b, 0, stream, p);
@@ -334,6 +340,8 @@ static int ln_bwd_run(const void* dy, int dy_dtype, long dy_stride, const void* 
                       const float* mean, const float* rstd, const float* w, const void* dres, int dres_every, long dres_stride,
                       void* dx, int g_dtype, void* dx_bf16, long dx_stride, int rows, int D, hipStream_t stream) {
   if (rows <= 0 || D <= 0) return vl_set_error("vl_layernorm_bwd: empty problem");
+  for (const int dt : {dy_dtype, x_dtype, g_dtype})
+    if (dt != VL_F32 && dt != VL_BF16) return vl_set_error("vl_layernorm_bwd: dy_dtype, x_dtype and g_dtype must be VL_F32 or VL_BF16");
   LnBwdP p{dy, x, mean, rstd, w, dres, dx, (bf16_t*)dx_bf16, dy_stride, x_stride, dx_stride, rows, D, dres_every, dres_stride};
   const int key = (dy_dtype == VL_BF16 ? 4 : 0) | (x_dtype == VL_BF16 ? 2 : 0) | (g_dtype == VL_BF16 ? 1 : 0);
   switch (key) {

@@ -9,6 +9,7 @@
 // token_embedding + positional_embedding (model.py:531-533).
 #include "vl_common.h"
 #include "vitlens_hip.h"
+#include <string>
 
 namespace {
 
@@ -149,10 +150,17 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const LnP p) {
   }
 }
 
+// a pointer the register forms read or write four elements (8 or 16 bytes) at a time; a null (absent) operand passes
+template <typename T> bool aligned4(const void* p) { return (uintptr_t)p % (4 * sizeof(T)) == 0; }
+
 template <typename TIN, typename TOUT, int MODE>
 hipError_t ln_launch(const LnP& p, hipStream_t s) {
   const dim3 grid((p.rows + 3) / 4), block(256);
-  const bool vec = (p.D % 256 == 0) && (p.xs % 4 == 0) && (p.ys % 4 == 0);
+  // the register forms need every row of every operand on a 4-element boundary: the strides AND the bases (the column
+  // reductions' rule, vl_colreduce.hip); anything else takes the generic form
+  const bool vec = (p.D % 256 == 0) && (p.xs % 4 == 0) && (p.ys % 4 == 0) && aligned4<TIN>(p.x) && aligned4<TOUT>(p.y) &&
+                   aligned4<float>(p.w) && aligned4<float>(p.b) &&
+                   (MODE == 0 || (aligned4<float>(p.cls) && aligned4<float>(p.pos) && aligned4<float>(p.pos2) && aligned4<float>(p.y2)));
   const int nch = vec ? p.D / 256 : 0;
   switch (nch) {
     case 1: hipLaunchKernelGGL((ln_rows_kernel<1, TIN, TOUT, MODE>), grid, block, 0, s, p); break;
@@ -172,7 +180,18 @@ hipError_t ln_dispatch(const LnP& p, int in_dt, int out_dt, hipStream_t s) {
   if (in_dt == VL_F32 && out_dt == VL_BF16) return ln_launch<float, bf16_t, MODE>(p, s);
   if (in_dt == VL_BF16 && out_dt == VL_BF16) return ln_launch<bf16_t, bf16_t, MODE>(p, s);
   if (in_dt == VL_F32 && out_dt == VL_F32) return ln_launch<float, float, MODE>(p, s);
-  return ln_launch<bf16_t, float, MODE>(p, s);
+  if (in_dt == VL_BF16 && out_dt == VL_F32) return ln_launch<bf16_t, float, MODE>(p, s);
+  return hipErrorInvalidValue;      // (the entries refuse such a pair with a message first: ln_args_error)
+}
+
+// What the three LayerNorm-forward entries refuse before any launch: a dtype pair without a kernel (a 4-byte store into a
+// 2-byte buffer otherwise) and one of mean / rstd without the other (the kernel writes both when it writes one).
+const char* ln_args_error(int in_dt, int out_dt, const float* mean, const float* rstd) {
+  const bool pair = (in_dt == VL_F32 && (out_dt == VL_F32 || out_dt == VL_BF16 || out_dt == VL_F16)) ||
+                    (in_dt == VL_BF16 && (out_dt == VL_F32 || out_dt == VL_BF16));
+  if (!pair) return "unsupported dtype pair (f32 -> f32 | bf16 | f16, bf16 -> f32 | bf16)";
+  if ((mean == nullptr) != (rstd == nullptr)) return "mean and rstd are written together: give both or neither";
+  return nullptr;
 }
 
 // ---- L2 normalise rows (F.normalize, eps 1e-12) -> f32 and optional bf16 copy -------------------
@@ -262,6 +281,7 @@ extern "C" int vl_layernorm_fwd(const void* x, int x_dtype, long x_row_stride, c
                                 const float* w, const float* b, void* y, int y_dtype, long y_row_stride,
                                 float* mean, float* rstd, int rows, int D, float eps, hipStream_t stream) {
   if (rows <= 0 || D <= 0) return vl_set_error("vl_layernorm_fwd: empty problem");
+  if (const char* e = ln_args_error(x_dtype, y_dtype, mean, rstd)) return vl_set_error((std::string("vl_layernorm_fwd: ") + e).c_str());
   LnP p{}; p.x = x; p.ridx = row_index; p.xs = x_row_stride; p.rmul = row_mul; p.w = w; p.b = b; p.y = y; p.ys = y_row_stride;
   p.mean = mean; p.rstd = rstd; p.rows = rows; p.D = D; p.eps = eps;
   VL_HIP_OK(ln_dispatch<0>(p, x_dtype, y_dtype, stream));
@@ -383,6 +403,7 @@ extern "C" int vl_assemble_ln_pre(const void* tokens, int tok_dtype, const float
                                   const float* w, const float* b, void* y, int y_dtype, float* xpre, float* mean, float* rstd,
                                   int B, int T, int D, float eps, hipStream_t stream) {
   if (B <= 0 || T <= 0 || D <= 0) return vl_set_error("vl_assemble_ln_pre: empty problem");
+  if (const char* e = ln_args_error(tok_dtype, y_dtype, mean, rstd)) return vl_set_error((std::string("vl_assemble_ln_pre: ") + e).c_str());
   LnP p{}; p.x = tokens; p.xs = D; p.w = w; p.b = b; p.y = y; p.ys = D; p.rows = B * (T + 1); p.D = D; p.eps = eps;
   p.cls = cls; p.pos = pos; p.pos2 = pos2; p.T = T; p.y2 = xpre; p.mean = mean; p.rstd = rstd;
   VL_HIP_OK(ln_dispatch<1>(p, tok_dtype, y_dtype, stream));
@@ -394,6 +415,7 @@ extern "C" int vl_assemble_ln_pre_keep(const void* tokens, int tok_dtype, const 
                                        float* mean, float* rstd, int B, int T, int K, int D, float eps, hipStream_t stream) {
   if (B <= 0 || T <= 0 || D <= 0 || K < 1 || K > T) return vl_set_error("vl_assemble_ln_pre_keep: bad shape (B, D >= 1, 1 <= K <= T)");
   if (!keep) return vl_set_error("vl_assemble_ln_pre_keep: keep missing (vl_assemble_ln_pre is the dense form)");
+  if (const char* e = ln_args_error(tok_dtype, y_dtype, mean, rstd)) return vl_set_error((std::string("vl_assemble_ln_pre_keep: ") + e).c_str());
   LnP p{}; p.x = tokens; p.xs = D; p.w = w; p.b = b; p.y = y; p.ys = D; p.rows = B * (K + 1); p.D = D; p.eps = eps;
   p.cls = cls; p.pos = pos; p.pos2 = pos2; p.T = T; p.y2 = xpre; p.mean = mean; p.rstd = rstd; p.keep = keep; p.K = K;
   VL_HIP_OK(ln_dispatch<1>(p, tok_dtype, y_dtype, stream));
@@ -431,6 +453,7 @@ extern "C" int vl_im2col_f32(const float* x, float* patches, int N, int C, int H
 extern "C" int vl_text_embed(const int64_t* ids, const float* tok_emb, const float* pos, void* out, int out_dtype,
                              int B, int L, int D, int vocab, hipStream_t stream) {
   if (B <= 0 || L <= 0) return vl_set_error("vl_text_embed: empty problem");
+  if (out_dtype != VL_F32 && out_dtype != VL_BF16) return vl_set_error("vl_text_embed: out_dtype must be VL_F32 or VL_BF16");
   const int rows = B * L;
   if (out_dtype == VL_F32)
     hipLaunchKernelGGL(text_embed_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, stream, ids, tok_emb, pos, (float*)out, rows, L, D, vocab);
@@ -450,6 +473,8 @@ extern "C" int vl_cast_f32_bf16(const float* x, void* y, long n, hipStream_t str
 extern "C" int vl_add_rows(const void* x, int x_dtype, const float* table, void* y, int y_dtype, long rows, int T, int D,
                            hipStream_t stream) {
   if (rows <= 0) return 0;
+  if ((x_dtype != VL_F32 && x_dtype != VL_BF16) || (y_dtype != VL_F32 && y_dtype != VL_BF16))
+    return vl_set_error("vl_add_rows: x_dtype and y_dtype must be VL_F32 or VL_BF16");
   const dim3 g(grid_for(rows * D)), b(256);
   if (x_dtype == VL_F32 && y_dtype == VL_F32) hipLaunchKernelGGL((add_rows_kernel<float, float>), g, b, 0, stream, (const float*)x, table, (float*)y, rows, T, D);
   else if (x_dtype == VL_F32) hipLaunchKernelGGL((add_rows_kernel<float, bf16_t>), g, b, 0, stream, (const float*)x, table, (bf16_t*)y, rows, T, D);

@@ -406,12 +406,19 @@ def weight_grad(dy, x, g, bias_grad=None, narrow=True, cfg=-1):
     bias_grad is given, bias_grad += the column sums of dy.  Token-major operands where the shape fits the dW kernel (narrow:
     column counts that are not whole 256-column tiles too, through gemm_dw_tn_any's zero-padded copies; otherwise gemm_dw_tn
     alone), the bias gradient from colsum; else both operands transposed to bf16 with the token axis padded to whole 64-token
-    steps - the transpose of dy reads all of dy anyway and produces the bias gradient - and gemm_dw (kernel configuration cfg)."""
+    steps - the transpose of a bf16 dy reads all of dy anyway and produces the bias gradient - and gemm_dw (kernel
+    configuration cfg).
+    The bias gradient is the column sums of dy AS GIVEN on every route, whatever the row count: the fused transpose sums the
+    bf16 values it writes, which for an fp32 dy are rounded ones, so an fp32 dy gets its sums from colsum on the fp32 values
+    (the product itself is bf16 x bf16 on every route)."""
     if (gemm_dw_tn_any if narrow else gemm_dw_tn)(dy, x, g):
         if bias_grad is not None:
             colsum(dy, bias_grad)
         return g
     rp = (dy.shape[0] + 63) // 64 * 64
+    if bias_grad is not None and dy.dtype != torch.bfloat16:
+        colsum(dy, bias_grad)
+        bias_grad = None
     return gemm_dw(transpose_colsum(dy, rp, colsum_out=bias_grad), transpose_to_bf16(x, ldo=rp), g, cfg=cfg)
 
 
@@ -523,8 +530,14 @@ def attn_fwd_q1(q, k, v, out, lse=None, qrow=0, qscale=1.0):
     return out
 
 
+def _chk_mean_rstd(mean, rstd, who):
+    if (mean is None) != (rstd is None):
+        raise ValueError(f"{who}: mean and rstd are written together: give both or neither")
+
+
 def layernorm(x, w, b, out, rows, D, x_row_stride=None, row_index=None, row_mul=0, mean=None, rstd=None,
               eps=1e-5):
+    _chk_mean_rstd(mean, rstd, "layernorm")
     xs = D if x_row_stride is None else x_row_stride
     check(_lib.vl_layernorm_fwd(_p(x), _dt(x), xs, _p(row_index), row_mul, _p(w), _p(b), _p(out), _dt(out),
                                 out.stride(-2) if out.dim() >= 2 else D, _p(mean), _p(rstd), rows, D,
@@ -533,6 +546,7 @@ def layernorm(x, w, b, out, rows, D, x_row_stride=None, row_index=None, row_mul=
 
 
 def assemble_ln_pre(tokens, cls, pos, pos2, w, b, out, B, T, D, eps=1e-5, xpre=None, mean=None, rstd=None):
+    _chk_mean_rstd(mean, rstd, "assemble_ln_pre")
     check(_lib.vl_assemble_ln_pre(_p(tokens), _dt(tokens), _p(cls), _p(pos), _p(pos2), _p(w), _p(b), _p(out),
                                   _dt(out), _p(xpre), _p(mean), _p(rstd), B, T, D, float(eps), _stream()))
     return out
@@ -580,6 +594,7 @@ def _chk_keep(keep, B, who):
 def assemble_ln_pre_keep(tokens, keep, cls, pos, pos2, w, b, out, B, T, D, eps=1e-5, xpre=None, mean=None, rstd=None):
     """assemble_ln_pre on the class token + the kept tokens only: out [B*(K+1), D] (keep int32 [B,K] from patch_keep)."""
     _chk_keep(keep, B, "assemble_ln_pre_keep")
+    _chk_mean_rstd(mean, rstd, "assemble_ln_pre_keep")
     K = keep.shape[1]
     check(_lib.vl_assemble_ln_pre_keep(_p(tokens), _dt(tokens), _p(keep), _p(cls), _p(pos), _p(pos2), _p(w), _p(b), _p(out),
                                        _dt(out), _p(xpre), _p(mean), _p(rstd), B, T, K, D, float(eps), _stream()))
