@@ -718,6 +718,43 @@ int vl_lars_multi_step(const vl_lars_slot* slots, int nslots, float lr, float mo
 int vl_topk_hits(const float* logits, long ld, const int64_t* target, int B, int C, int k0, int k1, int* hits,
                  uint8_t* correct, hipStream_t stream);
 
+/* ---- evaluation metrics on the device (training/zero_shot.py's drivers, open_clip/metrics/map.py; csrc/vl_eval.hip) ----
+ * vl_eval_hits: vl_topk_hits with a class map, per-class counters and the arg-max.  logits f32 [B, ld >= C], target int64 [B],
+ * class_map int32 [C] or NULL (identity).  Per sample b, with t = target[b]:
+ *   g = map[t];  m = the best member of group g: the largest logit among {c: map[c] == g}, the lowest index on a tie;
+ *   rank_b = #{c: logits[b,c] > logits[b,m]} + #{c < m: logits[b,c] == logits[b,m]}
+ * All outputs are int32 and ACCUMULATE (the caller zeroes them once per evaluation; integer atomics, any order gives the same
+ * counts): hits[0] += #{b: rank_b < k0}, hits[1] += #{b: rank_b < k1}; optional cls_count[C], cls_hit0[C], cls_hit1[C] indexed
+ * by t; optional pred[B] = the row's arg-max, lowest index on ties (written, not accumulated).  The group-best rank is the
+ * reference's cond_acc (top-k of the raw logits, predictions and target mapped, a hit if any is equal: the best member of the
+ * target's group is within the top k exactly when any member is); with the identity map it is vl_topk_hits, whose conventions
+ * hold: a NaN logit counts as not greater (and, where the best member and the arg-max are chosen, orders as -inf); a target
+ * outside [0, C) is a miss - the index is clamped before any read and no per-class counter changes.  Any C >= 1, also C < k1.
+ *
+ * vl_average_precision: scores f32 [N, ld >= C], targets f32 [N, ldt >= C] (positive: > 0) -> ap f64 [C], scikit-learn's
+ * average_precision_score(average=None) with tied scores grouped, from its integer form: for class c with P positives
+ *   AP_c = (1 / P) sum_{positive i} #{positive j: s_j >= s_i} / #{j: s_j >= s_i}
+ * Each ratio is formed in fp64 and the sum runs in a fixed order (no floating-point atomics): two calls agree bit for bit.
+ * P = 0 gives AP_c = 0.0, which scikit-learn 1.7 returns with a warning (older releases gave NaN).  The entry takes RAW scores:
+ * the sigmoid of open_clip/metrics/map.py is strictly monotone and is never formed; the one difference from that path is that
+ * two distinct scores which float32 sigmoid collapses into a tie stay distinct here.  NaN scores are unsupported (scikit-learn
+ * raises): nothing faults, the result is unspecified; +-inf order as IEEE numbers.  ws: vl_average_precision_ws_bytes(N, C)
+ * bytes, 8-byte aligned (the row tiles' partial sums and counts).  Cost: O(P N) comparisons per class, no sort - O(N^2) for a
+ * class where a fixed share of the samples is positive (N = 20 000, every one of 527 classes half positive: 1e11).
+ *
+ * vl_clip_mean_normalize: x f32 [B * n_clip, ldx >= D], the clips of a sample in consecutive rows -> out f32 [B, D] (contiguous,
+ * not x) = F.normalize(x.view(B, n_clip, D).mean(1), dim=-1, eps): the clips are added in order in fp32 and divided by n_clip,
+ * then vl_l2_normalize's arithmetic.  n_clip = 1 is vl_l2_normalize.  The audio evaluation's multi-clip mean.
+ * NOTE on the version: like vl_pc_augment, these entries were added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before them reports the same number and lacks the symbols, and a client must look them up when it
+ * loads the library (vitlens_hip/_lib.py does, and names such a library as stale). */
+int vl_eval_hits(const float* logits, long ld, const int64_t* target, const int* class_map, int B, int C, int k0, int k1,
+                 int* hits, int* cls_count, int* cls_hit0, int* cls_hit1, int* pred, hipStream_t stream);
+long vl_average_precision_ws_bytes(int N, int C);
+int vl_average_precision(const float* scores, long ld, const float* targets, long ldt, int N, int C, double* ap, void* ws,
+                         hipStream_t stream);
+int vl_clip_mean_normalize(const float* x, long ldx, int B, int n_clip, int D, float eps, float* out, hipStream_t stream);
+
 /* ---- the contrastive exchange over RCCL (csrc/vl_comm.cpp) ----
  * One process per GPU, one communicator per process; RCCL (librccl.so.1) is resolved at run time.  These are the three
  * collectives of a training step of the hot path, for a host that is not Python (the Python host makes the same calls

@@ -122,6 +122,11 @@ SIGNATURES = {
     "vl_lars_ws_floats": [L, I],
     "vl_lars_multi_step": [P, I, F, F, F, F, F, P, P, L, P],
     "vl_topk_hits": [P, L, P, I, I, I, I, P, P, P],
+    # evaluation metrics (csrc/vl_eval.hip)
+    "vl_eval_hits": [P, L, P, P, I, I, I, I, P, P, P, P, P, P],
+    "vl_average_precision_ws_bytes": [I, I],
+    "vl_average_precision": [P, L, P, L, I, I, P, P, P],
+    "vl_clip_mean_normalize": [P, L, I, I, I, F, P, P],
     # RCCL exchange (csrc/vl_comm.cpp): comm handles are opaque pointers
     "vl_comm_unique_id": [P],
     "vl_comm_create": [C.POINTER(P), P, I, I],
@@ -134,7 +139,7 @@ SIGNATURES = {
 
 # functions that do not return a status code
 _RET = {"vl_colreduce_ws_floats": L, "vl_ce_grad_ws_floats": L, "vl_sumsq_ws_floats": L, "vl_ce_label_ws_floats": L,
-        "vl_lars_ws_floats": L}
+        "vl_lars_ws_floats": L, "vl_average_precision_ws_bytes": L}
 
 
 def load_library():

@@ -1488,3 +1488,79 @@ def topk_hits(logits, target, ks=(1, 5), hits=None, correct=None, need_correct=F
         raise ValueError(f"topk_hits: correct must be a contiguous u8 [{B}, 2] tensor")
     check(_lib.vl_topk_hits(_p(logits), logits.stride(0), _p(target), B, Cc, int(ks[0]), int(ks[1]), _p(hits), _p(correct), _stream()))
     return hits, correct
+
+
+def _i32(t, n, name, device):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous int32 tensor of {n} elements on the logits' device")
+    return t
+
+
+def eval_hits(logits, target, ks=(1, 5), class_map=None, hits=None, per_class=None, pred=None, need_pred=False):
+    """`topk_hits` with a class map, per-class counters and the arg-max (vl_eval_hits): logits f32 [B, C], target int64 [B] ->
+    (hits, pred).  class_map: int32 [C] (None: identity) - a sample hits at k when the best-scoring member of its target's group
+    ranks below k, the reference's cond_acc.  hits int32 [2] and per_class int32 [3, C] (rows: samples, hits at ks[0], hits at
+    ks[1], indexed by the target) ACCUMULATE; hits is a new zeroed tensor when None.  pred int32 [B] (need_pred: allocated here):
+    the row's arg-max, lowest index on ties.  A target outside [0, C) is a miss and changes no per-class counter."""
+    _chk2d(logits, "eval_hits: logits", torch.float32)
+    B, Cc = logits.shape
+    if B < 1 or Cc < 1:
+        raise ValueError("eval_hits: empty problem")
+    dev = logits.device
+    if target.dtype != torch.int64 or tuple(target.shape) != (B,) or not target.is_contiguous() or target.device != dev:
+        raise ValueError(f"eval_hits: target must be a contiguous int64 [{B}] tensor on the logits' device")
+    if len(ks) != 2 or min(int(k) for k in ks) < 1:
+        raise ValueError("eval_hits: two values of k, each >= 1")
+    if class_map is not None:
+        _i32(class_map, Cc, "eval_hits: class_map", dev)
+    hits = torch.zeros(2, device=dev, dtype=torch.int32) if hits is None else _i32(hits, 2, "eval_hits: hits", dev)
+    if per_class is not None and (per_class.dim() != 2 or per_class.shape[0] != 3):
+        raise ValueError(f"eval_hits: per_class must be int32 [3, {Cc}]")
+    pc = [None] * 3 if per_class is None else list(_i32(per_class, 3 * Cc, "eval_hits: per_class", dev))
+    if pred is None and need_pred:
+        pred = torch.empty(B, device=dev, dtype=torch.int32)
+    if pred is not None:
+        _i32(pred, B, "eval_hits: pred", dev)
+    check(_lib.vl_eval_hits(_p(logits), logits.stride(0), _p(target), _p(class_map), B, Cc, int(ks[0]), int(ks[1]), _p(hits),
+                            _p(pc[0]), _p(pc[1]), _p(pc[2]), _p(pred), _stream()))
+    return hits, pred
+
+
+def class_map_from_merge(num_classes, idx_mapping, merge_idx, device):
+    """The class map of `eval_hits` for the reference's cond_acc(idx_mapping, merge_idx): the listed classes become merge_idx."""
+    m = list(range(int(num_classes)))
+    for i in idx_mapping:
+        if 0 <= int(i) < len(m):
+            m[int(i)] = int(merge_idx)
+    return torch.tensor(m, dtype=torch.int32, device=device)
+
+
+def average_precision(scores, targets, out=None):
+    """Per-class average precision (vl_average_precision; scikit-learn's average_precision_score(average=None) on RAW scores):
+    scores f32 [N, C], targets f32 [N, C] (positive: > 0) -> f64 [C].  A class without positives scores 0.0."""
+    _chk2d(scores, "average_precision: scores", torch.float32)
+    _chk2d(targets, "average_precision: targets", torch.float32)
+    N, Cc = scores.shape
+    if N < 1 or Cc < 1 or tuple(targets.shape) != (N, Cc) or targets.device != scores.device:
+        raise ValueError(f"average_precision: scores and targets must be non-empty [N, C] tensors of one shape on one device, got "
+                         f"{tuple(scores.shape)} and {tuple(targets.shape)}")
+    if out is None:
+        out = torch.empty(Cc, device=scores.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.numel() != Cc or not out.is_contiguous():
+        raise ValueError(f"average_precision: out must be a contiguous f64 [{Cc}] tensor")
+    ws = torch.empty(int(_lib.vl_average_precision_ws_bytes(N, Cc)) // 8 + 1, device=scores.device, dtype=torch.float64)
+    check(_lib.vl_average_precision(_p(scores), scores.stride(0), _p(targets), targets.stride(0), N, Cc, _p(out), _p(ws), _stream()))
+    return out
+
+
+def clip_mean_normalize(x, n_clip, eps=1e-12):
+    """x f32 [B * n_clip, D], a sample's clips in consecutive rows -> F.normalize(x.view(B, n_clip, D).mean(1), dim=-1) f32 [B, D]
+    (vl_clip_mean_normalize: the audio evaluation's mean over clips and the normalisation in one launch)."""
+    _chk2d(x, "clip_mean_normalize: x", torch.float32)
+    n_clip = int(n_clip)
+    if n_clip < 1 or x.shape[0] < n_clip or x.shape[0] % n_clip or x.shape[1] < 1:
+        raise ValueError(f"clip_mean_normalize: {x.shape[0]} rows are no positive multiple of n_clip = {n_clip}")
+    B, D = x.shape[0] // n_clip, x.shape[1]
+    out = torch.empty(B, D, device=x.device, dtype=torch.float32)
+    check(_lib.vl_clip_mean_normalize(_p(x), x.stride(0), B, n_clip, D, float(eps), _p(out), _stream()))
+    return out
