@@ -551,6 +551,58 @@ int vl_pc_augment(const float* pts, const int64_t* idx, float* out, int B, int N
 int vl_rgbd_augment(const void* records, int n, int S, int max_nrows, const void* tables, float* tmp, const float* mean,
                     const float* stdv, float depth_lo, float depth_hi, float depth_div, float* out_rgb, float* out_depth,
                     hipStream_t stream);
+/* The plain-image training transform of the tactile and EEG recipes (csrc/vl_image_augment.hip), one call per batch of n RGB
+ * images of any sizes: RandomResizedCrop(S, bilinear) + RandomHorizontalFlip + RandAugment on the 8-bit image, every stage
+ * byte for byte the Pillow call it ends in, then ToTensor + ColorJitter + Normalize (modal_eeg/processors/eeg_processor.py:
+ * 93-139).  out [n,3,S,S] f32; out_u8 (may be NULL) [n,S,S,3]: the 8-bit image after RandAugment.  Every random scalar is
+ * drawn by the host and arrives in the sample's record.
+ * records: DEVICE array of one 368-byte record per sample, 92 little-endian 32-bit words:
+ *     words  0 ..  1   uint64 src          device pointer, uint8 [H,W,3]
+ *     word   2         int32 stride        bytes per row of src
+ *     words  3 ..  4   int32 H, W
+ *     words  5 ..  8   int32 top, left, bh, bw     the crop box, inside the image
+ *     words  9 .. 10   int32 row0, nrows   the rows of the box, counted from top, that the vertical taps touch
+ *     words 11 .. 13   int32 hb, hk, hks   horizontal table (bw -> S): offsets of its bounds [S,2] int32 and coefficients
+ *                                          [S,hks] int32 (22-bit fixed point) in `tables`, in 32-bit words; taps per row
+ *     words 14 .. 16   int32 vb, vk, vks   the same for the vertical table (bh -> S)
+ *     word  17         int32 flags         1 flip, 2 brightness, 4 contrast, 8 saturation, 16 hue (the jitter term is applied);
+ *                                          bits 8 .. 15: the order of the four terms, two bits per position, first position
+ *                                          lowest (0 brightness, 1 contrast, 2 saturation, 3 hue)
+ *     words 18 .. 19   int64 tmp           offset of the sample's [nrows,S,3] intermediate in `tmp`, in bytes
+ *     words 20 .. 25   float b, 1-b, c, 1-c, s, 1-s        the jitter factors; 1 - f is formed in double on the host
+ *     word  26         float hue           the hue shift
+ *     word  27         int32 num_ops       RandAugment ops of this sample, 0 .. 4
+ *     words 28 .. 91   four 64-byte op slots, applied in order:
+ *         word  0      int32 code          0 Identity, 1 ShearX, 2 ShearY, 3 TranslateX, 4 TranslateY, 5 Rotate, 6 Brightness,
+ *                                          7 Color, 8 Contrast, 9 Sharpness, 10 Posterize, 11 Solarize, 12 AutoContrast, 13 Equalize
+ *         word  1      int32 ipay          Posterize: the mask a byte is and-ed with; Solarize: bytes >= it become 255 - byte
+ *         word  2      float fpay          6 .. 9: the factor of ImageEnhance.*.enhance
+ *         word  3      unused
+ *         words 4 .. 15  double m[6]       1 .. 5: the matrix of Image.transform(AFFINE, BILINEAR), output pixel centre to source
+ * tables: the packed per-axis tables of the distinct (edge -> S) pairs; tmp: sum of nrows * S * 3 bytes; max_nrows: the largest
+ * nrows; work: 2 * n * S * S * 3 bytes (each sample's two images); max_ops: the largest num_ops of the batch, which the
+ * kernels do not read (each sample runs its record's num_ops, clamped to [0, 4]): it is a parameter only so that a batch with
+ * more than 4 ops per sample is refused here, on the host, where the records cannot be read; mean / stdv:
+ * HOST arrays of 3 floats.  Per sample, in this order: Pillow's two-pass 8-bit resampler over the box (a flipped sample's
+ * column x reads column S-1-x), the ops (the affine position and blend in doubles, the enhance blends and the SMOOTH filter in
+ * float32, nothing contracted, Pillow's truncation; Contrast blends with int(mean(L) + 0.5); AutoContrast and Equalize build
+ * their LUTs from the per-channel histograms), byte / 255, the enabled jitter terms in the record's order (contrast blends
+ * with the mean of 0.2989 R + 0.587 G + 0.114 B, summed in a fixed order), (x - mean[c]) / stdv[c].  A sample's result does
+ * not depend on its place in the batch.
+ * Refused with a status, nothing launched: n outside [1, 65535], S outside [1, 4096], max_nrows < 1, max_ops outside [0, 4], a
+ * null operand (out_u8 may be null), records not 8-byte aligned, a zero stdv.  The records live in device memory: their
+ * contents (op codes, finite matrices, the box, the order field, the table and intermediate offsets against the sizes of
+ * `tables` and `tmp`) are checked where they are packed on the host (vitlens_hip.ops.image_augment_pack); in the kernels an index outside the box or the image is clamped into it and an unknown
+ * op code is skipped.  Stream-ordered, three launches, no global state, no host synchronisation.
+ * vl_image_crop_resize_u8 is the first two launches alone: out_u8 [n,S,S,3] = img.crop(box).resize((S, S), BILINEAR), flipped
+ * where the record says so.
+ * NOTE on the version: like vl_pc_augment, these entries were added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before them reports the same number and lacks the symbols, and a client must look them up when it
+ * loads the library (vitlens_hip/_lib.py does, and names such a library as stale). */
+int vl_image_crop_resize_u8(const void* records, int n, int S, int max_nrows, const void* tables, uint8_t* tmp, uint8_t* out_u8,
+                            hipStream_t stream);
+int vl_image_augment(const void* records, int n, int S, int max_nrows, int max_ops, const void* tables, uint8_t* tmp,
+                     uint8_t* work, const float* mean, const float* stdv, float* out, uint8_t* out_u8, hipStream_t stream);
 /* ---- evaluation-time image / depth preprocessing (csrc/vl_preproc.hip) ----
  * Separable bicubic resampling restricted to a crop window, tables built by the host (vitlens_hip/preproc.py):
  * bounds [n_out,2] int32 = (first tap, tap count) and coefficients [n_out,ksize] per OUTPUT index of the full resized

@@ -6,7 +6,9 @@ workers run): Pillow bicubic resize + crop + torch ToTensor/Normalize for images
 one thread.  Prints one JSON object; `python tools/preproc_bench.py > gpurun_out/preproc_bench.json`."""
 # `--pc-train-only` prints the row of the 3D training transform alone (PCProcessorTrain against the numpy restatement of the
 # reference's five passes on the host's cores); `--rgbd-train-only` the row of the depth training transform alone
-# (RGBD_Processor_Train against the torch restatement of the reference's pipeline on the host's cores)
+# (RGBD_Processor_Train against the torch restatement of the reference's pipeline on the host's cores); `--image-train-only`
+# the row of the plain-image training transform alone (Image_Processor_Train against the same draws applied with Pillow on one
+# host thread)
 import json
 import os
 import sys
@@ -123,7 +125,55 @@ def rgbd_train_row(B=1024, H=480, W=640, threads=16, distinct=64):
     return row
 
 
+def image_train_row(B=1024, H=480, W=640, distinct=64):
+    """Image_Processor_Train.batch at B samples of H x W (`distinct` different sources, each used B / distinct times): the
+    three launches alone, `batch` as a whole with resident and with host sources, the host's share (draws, planning), and
+    the same draws applied with Pillow and torch on one host thread (tests/image_augment_ref.py), the yardstick."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import image_augment_ref as A
+    from open_clip.modal_tactile.processors.tact_processor import Image_Processor_Train
+    src = [torch.from_numpy(A.source(H, W, "random", seed=200 + i)) for i in range(distinct)]
+    images = [src[i % distinct] for i in range(B)]
+    dev = [a.cuda() for a in src]
+    images_d = [dev[i % distinct] for i in range(B)]
+    proc = Image_Processor_Train.from_config()
+    row = {"n": B, "in": [H, W], "size": proc.size, "num_ops": proc.num_ops, "magnitude": proc.magnitude,
+           "source_mb_per_batch": round(B * H * W * 3 / 1e6, 1)}
+    torch.manual_seed(0)
+    t0 = time.perf_counter(); draws = [proc.draw(H, W) for _ in range(B)]
+    row["host_draws_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3, 2)
+    plan_of = lambda ims: preproc.plan_image_train(ims, draws, proc.size, proc.mean, proc.std)
+    plan = plan_of(images_d)
+    row["intermediate_mb"] = round(plan.tmp.numel() / 1e6, 1)
+    out = torch.empty(B, 3, proc.size, proc.size, device="cuda")
+    s = min(gpu_time(lambda: plan.launch(out=out), n_warm=2) for _ in range(5))
+    row["gpu_kernels_ms_per_batch"] = round(s * 1e3, 3)                              # the three launches, sources resident
+    s = min(gpu_time(plan.crop_resize, n_warm=2) for _ in range(5))
+    row["gpu_crop_resize_ms_per_batch"] = round(s * 1e3, 3)                          # the first two of them
+
+    def timed(fn):
+        fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3, 2)
+    row["host_plan_ms_resident_sources"] = timed(lambda: plan_of(images_d))          # records, tables, one upload
+    row["host_plan_ms_host_sources"] = timed(lambda: plan_of(images))                # + packing and upload of the image bytes
+    row["gpu_batch_ms_resident_sources"] = timed(lambda: proc.batch(images_d))       # draws, planning, launches
+    row["gpu_batch_ms_host_sources"] = timed(lambda: proc.batch(images))
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    n_cpu = min(B, 128)
+    t0 = time.perf_counter()
+    for b in range(n_cpu):
+        A.float_tail(A.eight_bit(images[b].numpy(), draws[b], proc.size), draws[b], proc.mean, proc.std)
+    row["pillow_1thread_ms_per_batch"] = round((time.perf_counter() - t0) / n_cpu * B * 1e3, 1)
+    torch.set_num_threads(nt)
+    return row
+
+
 def main():
+    if "--image-train-only" in sys.argv[1:]:
+        print(json.dumps({"image_train": image_train_row()}))
+        return
     if "--pc-train-only" in sys.argv[1:]:
         print(json.dumps({"pc_train": pc_train_row()}))
         return
@@ -208,6 +258,7 @@ def main():
     res["pc"] = {"n": B, "in": [10000, 3], "npoint": 8192, "gpu_resident_clouds_per_s": round(B / s, 1)}
     res["pc_train"] = pc_train_row()
     res["rgbd_train"] = rgbd_train_row()
+    res["image_train"] = image_train_row()
     print(json.dumps(res))
 
 

@@ -31,6 +31,8 @@ import re
 import numpy as np
 import torch
 
+from open_clip.transform import image_u8, jitter_range
+
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
@@ -143,20 +145,6 @@ class BlipCaptionProcessor(BaseProcessor):
         return " ".join(words[:self.max_words]) if len(words) > self.max_words else caption
 
 
-def _image_u8(img):
-    """A path, a PIL image, a uint8 array or a uint8 tensor -> uint8 [H, W, 3] tensor (host data stays on the host)."""
-    if isinstance(img, str) or hasattr(img, "__fspath__"):
-        from PIL import Image
-        img = Image.open(img)
-    if hasattr(img, "mode") and hasattr(img, "convert"):
-        img = np.array(img.convert("RGB"))
-    if isinstance(img, np.ndarray):
-        img = torch.from_numpy(np.ascontiguousarray(img))
-    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-        raise ValueError(f"expected a uint8 [H, W, 3] image, got {tuple(img.shape)} {img.dtype}")
-    return img
-
-
 def _depth_f32(depth):
     """A path (torch.load), a tensor or an array, [H, W] or [1, H, W] -> float32 [H, W] tensor."""
     if isinstance(depth, str) or hasattr(depth, "__fspath__"):
@@ -168,17 +156,6 @@ def _depth_f32(depth):
     if depth.dim() != 2:
         raise ValueError(f"expected an [H, W] or [1, H, W] disparity map, got {tuple(depth.shape)}")
     return depth.to(torch.float32)
-
-
-def _jitter_range(value, center, floor=None):
-    """torchvision ColorJitter._check_input for a number: [center - value, center + value], the lower end not below `floor`;
-    None where the term is off (value None or 0)."""
-    if value is None or value == 0:
-        return None
-    if value < 0:
-        raise ValueError(f"a jitter strength must be non-negative, got {value}")
-    lo, hi = center - float(value), center + float(value)
-    return (lo if floor is None else max(lo, floor)), hi
 
 
 class _RGBDProcessor(BaseProcessor):
@@ -224,7 +201,7 @@ class RGBD_Processor_Train(_RGBDProcessor):
         b, c, s, h = color_jitter
         if h is not None and not 0 <= h <= 0.5:
             raise ValueError(f"the hue strength must be in [0, 0.5], got {h}")
-        self.jitter = (_jitter_range(b, 1.0, 0.0), _jitter_range(c, 1.0, 0.0), _jitter_range(s, 1.0, 0.0), _jitter_range(h, 0.0))
+        self.jitter = (jitter_range(b, 1.0, 0.0), jitter_range(c, 1.0, 0.0), jitter_range(s, 1.0, 0.0), jitter_range(h, 0.0))
         self.color_jitter, self.erase_p = tuple(color_jitter), float(erase_p)
 
     def draw(self, H, W):
@@ -263,7 +240,7 @@ class RGBD_Processor_Train(_RGBDProcessor):
         draws are made sample by sample in order (or given: `draws`, one `draw()` result per sample, to replay a batch);
         host data goes up as one packed copy and the kernels are launched once for the batch."""
         from vitlens_hip import preproc
-        ims, dps = [_image_u8(im) for im in images], [_depth_f32(d) for d in depths]
+        ims, dps = [image_u8(im) for im in images], [_depth_f32(d) for d in depths]
         if draws is None:
             draws = [self.draw(im.shape[0], im.shape[1]) for im in ims]
         return preproc.plan_rgbd(ims, dps, draws, self.size, self.mean, self.std, self.depth_clamp, antialias=self.antialias,
@@ -290,7 +267,7 @@ class RGBD_Processor_Eval(_RGBDProcessor):
 
     def __call__(self, img_path, depth_path):
         from vitlens_hip import preproc
-        img = _image_u8(img_path).to(self.device, non_blocking=True)
+        img = image_u8(img_path).to(self.device, non_blocking=True)
         depth = _depth_f32(depth_path).to(self.device, non_blocking=True)
         if tuple(depth.shape) != tuple(img.shape[:2]):
             raise ValueError(f"image {tuple(img.shape[:2])} and depth {tuple(depth.shape)} differ in size")

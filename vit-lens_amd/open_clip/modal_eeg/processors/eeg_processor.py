@@ -2,9 +2,13 @@
 [channels, time] recording is cut to the window [time_low, time_high) and linearly resampled to `data_len` points per
 channel (scipy `interp1d` over a [0, 1] grid in the reference).  128 x 512 values per sample: host-side data plumbing,
 done here with the same two-point formula in numpy (pinned against scipy in tests/test_preproc_host.py); the result is
-the [channels, data_len] float32 tensor the EEG tokenizer (PatchEmbed1D) takes."""
+the [channels, data_len] float32 tensor the EEG tokenizer (PatchEmbed1D) takes.  `EEG_Processor` is the training-side name of the
+same arithmetic; the paired image of a training sample goes through `Image_Processor_Train` (on the GPU, shared with the
+tactile recipe: modal_tactile/processors/tact_processor.py)."""
 import numpy as np
 import torch
+
+from open_clip.modal_tactile.processors.tact_processor import Image_Processor_Train  # noqa: F401  (the EEG recipe's paired image)
 
 
 class BaseProcessor:
@@ -43,3 +47,24 @@ class EEGProcessorEval(BaseProcessor):
         eeg = np.asarray(eeg.float().cpu() if isinstance(eeg, torch.Tensor) else eeg, dtype=np.float32)
         eeg = eeg[:, self.time_low:self.time_high]
         return torch.from_numpy(linear_resample(eeg, self.data_len)).float()
+
+
+eeg_conf = {"time_low": 20, "time_high": 460, "data_len": 512}
+
+
+class EEG_Processor(EEGProcessorEval):
+    """The training-side processor (reference :196-226): the same window and resampling as `EEGProcessorEval`, configured by
+    an argument object or mapping with `time_low`, `time_high`, `data_len`.  As in the reference the three values are read
+    from `args` BEFORE `update_conf` is merged into it, so `update_conf` does not reach them."""
+
+    def __init__(self, args=None, update_conf=None):
+        conf = dict(eeg_conf)
+        if args is not None:
+            conf.update(args if hasattr(args, "keys") else {k: getattr(args, k) for k in conf if hasattr(args, k)})
+        super().__init__(conf["time_low"], conf["time_high"], conf["data_len"])
+
+    @classmethod
+    def from_config(cls, cfg=None):
+        cfg = dict(cfg or {})
+        update_conf = cfg.pop("update_conf", None)
+        return cls(args=cfg.get("params", eeg_conf), update_conf=update_conf)

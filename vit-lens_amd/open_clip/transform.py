@@ -34,6 +34,31 @@ class AugmentationCfg:
     use_timm: bool = False
 
 
+def image_u8(img):
+    """A path, a PIL image, a uint8 array or a uint8 tensor -> uint8 [H, W, 3] tensor (host data stays on the host)."""
+    if isinstance(img, str) or hasattr(img, "__fspath__"):
+        from PIL import Image
+        img = Image.open(img)
+    if hasattr(img, "mode") and hasattr(img, "convert"):
+        img = np.array(img.convert("RGB"))
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"expected a uint8 [H, W, 3] image, got {tuple(img.shape)} {img.dtype}")
+    return img
+
+
+def jitter_range(value, center, floor=None):
+    """torchvision ColorJitter._check_input for a number: [center - value, center + value], the lower end not below `floor`;
+    None where the term is off (value None or 0)."""
+    if value is None or value == 0:
+        return None
+    if value < 0:
+        raise ValueError(f"a jitter strength must be non-negative, got {value}")
+    lo, hi = center - float(value), center + float(value)
+    return (lo if floor is None else max(lo, floor)), hi
+
+
 def random_resized_crop_params(height, width, scale, ratio=(3.0 / 4.0, 4.0 / 3.0)):
     """RandomResizedCrop.get_params: (top, left, h, w), ten attempts with the global torch RNG, then the central
     crop at the nearest admissible aspect ratio."""

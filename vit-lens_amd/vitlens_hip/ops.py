@@ -1144,6 +1144,102 @@ def rgbd_augment(records, tables, tmp, S, max_nrows, mean, std, depth_clamp, out
     return out_rgb, out_depth
 
 
+# one record per sample, as csrc/vl_image_augment.hip reads it (368 bytes; include/vitlens_hip.h spells the layout out)
+IMAGE_OP_DTYPE = np.dtype([("code", "<i4"), ("ipay", "<i4"), ("fpay", "<f4"), ("pad", "<i4"), ("m", "<f8", (6,))])
+IMAGE_AUGMENT_DTYPE = np.dtype(
+    [("src", "<u8"), ("stride", "<i4"), ("H", "<i4"), ("W", "<i4"), ("top", "<i4"), ("left", "<i4"), ("bh", "<i4"), ("bw", "<i4"),
+     ("row0", "<i4"), ("nrows", "<i4"), ("hb", "<i4"), ("hk", "<i4"), ("hks", "<i4"), ("vb", "<i4"), ("vk", "<i4"), ("vks", "<i4"),
+     ("flags", "<i4"), ("tmp", "<i8"), ("b", "<f4"), ("b1", "<f4"), ("c", "<f4"), ("c1", "<f4"), ("s", "<f4"), ("s1", "<f4"),
+     ("hue", "<f4"), ("num_ops", "<i4"), ("ops", IMAGE_OP_DTYPE, (4,))])
+IMAGE_MAX_OPS = 4
+IMAGE_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness",
+             "Posterize", "Solarize", "AutoContrast", "Equalize")         # the op codes, in RandAugment's own order
+
+
+def image_augment_pack(rows, S, table_words, tmp_bytes) -> np.ndarray:
+    """rows: an IMAGE_AUGMENT_DTYPE array for an S x S output, `table_words` int32 words of tables and `tmp_bytes` of
+    intermediate -> int32 [n, 92], the words of the records.  The records are read on the device, where the entry cannot look
+    at them, so their contents are checked here: the box inside the image, the touched rows inside the box, the stride, the
+    tables ([S,2] bounds, [S,ks] coefficients) and the [nrows,S,3] intermediate inside their buffers, the op count and codes,
+    finite matrices and factors, the order field a permutation of the four terms."""
+    a = np.ascontiguousarray(np.asarray(rows, dtype=IMAGE_AUGMENT_DTYPE).reshape(-1))
+
+    def need(ok, what):
+        if not np.all(ok):
+            raise ValueError(f"image_augment_pack: {what} (sample {int(np.argmin(np.asarray(ok).reshape(len(a), -1).all(axis=1)))})")
+    need(a["src"] != 0, "null source pointer")
+    need((a["H"] >= 1) & (a["W"] >= 1) & (a["stride"] >= 3 * a["W"]), "bad source size or stride")
+    need((a["top"] >= 0) & (a["bh"] >= 1) & (a["top"] + a["bh"] <= a["H"]) & (a["left"] >= 0) & (a["bw"] >= 1)
+         & (a["left"] + a["bw"] <= a["W"]), "the crop box must lie inside the image")
+    need((a["row0"] >= 0) & (a["nrows"] >= 1) & (a["row0"] + a["nrows"] <= a["bh"]), "the touched rows must lie inside the box")
+    S, i8 = int(S), lambda name: a[name].astype(np.int64)
+    need((a["hks"] >= 1) & (a["vks"] >= 1) & (a["hb"] >= 0) & (a["hk"] >= 0) & (a["vb"] >= 0) & (a["vk"] >= 0) & (a["tmp"] >= 0)
+         & (i8("hb") + 2 * S <= table_words) & (i8("vb") + 2 * S <= table_words) & (i8("hk") + S * i8("hks") <= table_words)
+         & (i8("vk") + S * i8("vks") <= table_words) & (a["tmp"] + i8("nrows") * S * 3 <= tmp_bytes), "bad table or intermediate offset")
+    order = (a["flags"] >> RGBD_ORDER_SHIFT) & 0xFF
+    need(sum(1 << ((order >> (2 * k)) & 3) for k in range(4)) == 15, "the order field must hold each of the four terms once")
+    need(((a["flags"] >> (RGBD_ORDER_SHIFT + 8)) == 0) & ((a["flags"] & (RGBD_ERASE | 0xC0)) == 0), "unknown flag bits")
+    need(np.isfinite(np.stack([a[k] for k in ("b", "b1", "c", "c1", "s", "s1", "hue")], axis=1)), "a jitter factor is not finite")
+    need((a["num_ops"] >= 0) & (a["num_ops"] <= IMAGE_MAX_OPS), f"num_ops must be in [0, {IMAGE_MAX_OPS}]")
+    used = np.arange(IMAGE_MAX_OPS)[None, :] < a["num_ops"][:, None]
+    code = a["ops"]["code"]
+    need(~used | ((code >= 0) & (code < len(IMAGE_OPS))), "unknown op code")
+    need(~(used & (code >= 1) & (code <= 5))[..., None] | np.isfinite(a["ops"]["m"]), "the matrix of a geometric op is not finite")
+    need(~(used & (code >= 6) & (code <= 9)) | np.isfinite(a["ops"]["fpay"]), "the factor of an enhance op is not finite")
+    need(~(used & (code == 10)) | ((a["ops"]["ipay"] >= 0) & (a["ops"]["ipay"] <= 255)), "the Posterize mask must be a byte")
+    need(~(used & (code == 11)) | ((a["ops"]["ipay"] >= 0) & (a["ops"]["ipay"] <= 256)), "the Solarize threshold must be in [0, 256]")
+    return a.view(np.int32).reshape(len(a), IMAGE_AUGMENT_DTYPE.itemsize // 4)
+
+
+def _image_augment_operands(name, records, tables, tmp):
+    words = IMAGE_AUGMENT_DTYPE.itemsize // 4
+    if records.dim() != 2 or records.shape[1] != words or records.dtype != torch.int32 or not records.is_cuda:
+        raise ValueError(f"{name}: records must be int32 [n, {words}] on the GPU, got {tuple(records.shape)} {records.dtype} {records.device}")
+    dev = records.device
+    if tables.dtype != torch.int32 or tables.device != dev or tmp.dtype != torch.uint8 or tmp.device != dev:
+        raise ValueError(f"{name}: tables must be int32 and tmp uint8 on the device of the records")
+    return records.shape[0], dev
+
+
+def image_crop_resize_u8(records, tables, tmp, S, max_nrows, out_u8=None):
+    """img.crop(box).resize((S, S), BILINEAR) and the flip for a batch (vl_image_crop_resize_u8, two launches): records int32
+    [n, 92] (the words of `image_augment_pack`), tables int32 [*] and tmp uint8 [*] on the device -> uint8 [n, S, S, 3]."""
+    n, dev = _image_augment_operands("image_crop_resize_u8", records, tables, tmp)
+    if n < 1 or S < 1:                   # (the entry refuses these too; nothing of size 0 is allocated first)
+        raise RuntimeError(f"libvitlens_hip: vl_image_crop_resize_u8: bad shape: n={n} S={S}")
+    if out_u8 is None:
+        out_u8 = torch.empty(n, S, S, 3, device=dev, dtype=torch.uint8)
+    if out_u8.dtype != torch.uint8 or not out_u8.is_contiguous() or tuple(out_u8.shape) != (n, S, S, 3) or out_u8.device != dev:
+        raise ValueError("image_crop_resize_u8: out_u8 must be contiguous uint8 [n, S, S, 3] on the device of the records")
+    check(_lib.vl_image_crop_resize_u8(_p(records.contiguous()), n, int(S), int(max_nrows), _p(tables), _p(tmp), _p(out_u8), _stream()))
+    return out_u8
+
+
+def image_augment(records, tables, tmp, S, max_nrows, max_ops, mean, std, out=None, out_u8=None, want_u8=False):
+    """The plain-image training transform for a batch (vl_image_augment, three launches): records int32 [n, 92] (the words of
+    `image_augment_pack`), tables int32 [*] and tmp uint8 [*] on the device; mean / std: 3 numbers -> out [n,3,S,S] f32, and
+    with `want_u8` (or a given `out_u8`) also the 8-bit image after RandAugment, uint8 [n,S,S,3]."""
+    n, dev = _image_augment_operands("image_augment", records, tables, tmp)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("image_augment: mean and std hold three numbers")
+    if n < 1 or S < 1:                   # (the entry refuses these too; nothing of size 0 is allocated first)
+        raise RuntimeError(f"libvitlens_hip: vl_image_augment: bad shape: n={n} S={S}")
+    if out is None:
+        out = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
+    if out_u8 is None and want_u8:
+        out_u8 = torch.empty(n, S, S, 3, device=dev, dtype=torch.uint8)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, 3, S, S) or out.device != dev:
+        raise ValueError("image_augment: out must be contiguous f32 [n, 3, S, S] on the device of the records")
+    if out_u8 is not None and (out_u8.dtype != torch.uint8 or not out_u8.is_contiguous() or tuple(out_u8.shape) != (n, S, S, 3)
+                               or out_u8.device != dev):
+        raise ValueError("image_augment: out_u8 must be contiguous uint8 [n, S, S, 3] on the device of the records")
+    work = torch.empty(2, n, S, S, 3, device=dev, dtype=torch.uint8)
+    fl = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    check(_lib.vl_image_augment(_p(records.contiguous()), n, int(S), int(max_nrows), int(max_ops), _p(tables), _p(tmp), _p(work),
+                                fl(mean), fl(std), _p(out), _p(out_u8), _stream()))
+    return (out, out_u8) if out_u8 is not None else out
+
+
 def knn_group(xyz, center_idx, k, Kp=64, want_idx=False):
     B, N, _ = xyz.shape
     G = center_idx.shape[1]

@@ -5,7 +5,9 @@ The tables depend only on (input size, output size), so they are built once on t
 ATen build theirs - cached, and kept on the device.
 
   * `pil_bicubic_tables`  = Pillow `Resample.c:precompute_coeffs` + `normalize_coeffs_8bpc` (double precision, Keys
-    kernel a = -0.5, support scaled when shrinking, 22-bit fixed point rounded half away from zero);
+    kernel a = -0.5, support scaled when shrinking, 22-bit fixed point rounded half away from zero); `pil_bilinear_tables`
+    is the same with the triangle filter, for the crop boxes of the plain-image training transform (`plan_image_train`,
+    csrc/vl_image_augment.hip);
   * `aten_bicubic_tables` = ATen `UpSampleKernel.cpp` weights: antialiased (`_compute_indices_min_size_weights_aa`,
     float32, a = -0.5, normalised) or plain (`get_cubic_upsample_coefficients`, a = -0.75, 4 taps from floor(src) - 1,
     border-clamped in the kernel);
@@ -17,6 +19,7 @@ window (torchvision `_compute_resized_output_size`, `center_crop`); see open_cli
 open_clip/modal_depth/processors/vt_processor.py for the reference-facing classes."""
 import collections
 import ctypes
+import fractions
 import functools
 import math
 
@@ -44,21 +47,20 @@ def _keys(x, a):
     return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
 
 
-@functools.lru_cache(maxsize=256)
-def pil_bicubic_tables(in_size, out_size, in0=0.0, in1=None):
-    """-> (bounds [out,2] int32, kk [out,ksize] int32, ksize); operation order as in Resample.c so that every double
-    is the one Pillow computes (the row sum is a left-to-right running sum)."""
+def _pil_tables(in_size, out_size, in0, in1, filt, filter_support):
+    """Pillow `Resample.c:precompute_coeffs` + `normalize_coeffs_8bpc` for one filter: operation order as in Resample.c so
+    that every double is the one Pillow computes (the row sum is a left-to-right running sum)."""
     in1 = float(in_size) if in1 is None else float(in1)
     scale = (in1 - in0) / out_size
     filterscale = scale if scale >= 1.0 else 1.0
-    support = 2.0 * filterscale
+    support = filter_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / filterscale
     center = in0 + (np.arange(out_size, dtype=np.float64) + 0.5) * scale
     xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)               # C cast: truncation (values >= -1.5 -> ok)
     xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
     j = np.arange(ksize, dtype=np.int64)[None, :]
-    w = _keys(((j + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss, -0.5)
+    w = filt(((j + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
     w = np.where(j < xmax[:, None], w, 0.0)
     ww = np.cumsum(w, axis=1)[:, -1:]                                             # sequential, as the C loop
     w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
@@ -67,6 +69,19 @@ def pil_bicubic_tables(in_size, out_size, in0=0.0, in1=None):
     kk = np.where(j < xmax[:, None], kk, 0).astype(np.int32)
     bounds = np.stack([xmin, xmax], 1).astype(np.int32)
     return bounds, kk, ksize
+
+
+@functools.lru_cache(maxsize=256)
+def pil_bicubic_tables(in_size, out_size, in0=0.0, in1=None):
+    """-> (bounds [out,2] int32, kk [out,ksize] int32, ksize) of Image.resize(BICUBIC): Keys kernel a = -0.5, support 2."""
+    return _pil_tables(in_size, out_size, in0, in1, lambda x: _keys(x, -0.5), 2.0)
+
+
+@functools.lru_cache(maxsize=1024)
+def pil_bilinear_tables(in_size, out_size, in0=0.0, in1=None):
+    """-> (bounds [out,2] int32, kk [out,ksize] int32, ksize) of Image.resize(BILINEAR): the triangle filter max(0, 1 - |x|),
+    support 1 (times the scale when shrinking), the same 22-bit fixed point as `pil_bicubic_tables`."""
+    return _pil_tables(in_size, out_size, in0, in1, lambda x: np.maximum(1.0 - np.abs(x), 0.0), 1.0)
 
 
 @functools.lru_cache(maxsize=256)
@@ -343,14 +358,10 @@ def images_to_tensor(images, size, mean, std, out=None, boxes=None):
     return plan_images(images, size, mean, std, out=out, boxes=boxes).launch()
 
 
-def rgbd_record_scalars(rec, draw):
-    """Write a draw's scalars into one RGBD_AUGMENT_DTYPE row: the box, the flip, the jitter order, the enabled terms with
-    factor and 1 - factor (the difference formed in double, as torchvision's _blend forms it, then rounded to float32),
-    the erase rectangle.  draw: {"box": (top, left, h, w), "flip": bool, "order": 4 ids (0 brightness, 1 contrast,
-    2 saturation, 3 hue), "brightness" / "contrast" / "saturation" / "hue": a float or None (term off),
-    "erase": (i, j, h, w) or None}."""
+def _jitter_flags(rec, draw):
+    """The flip, the jitter order and the enabled terms of a draw -> the record's flag bits; writes factor and 1 - factor (the
+    difference formed in double, as torchvision's _blend forms it, then rounded to float32) and the hue shift into `rec`."""
     from . import ops
-    rec["top"], rec["left"], rec["bh"], rec["bw"] = draw["box"]
     order = [int(k) for k in draw["order"]]
     if sorted(order) != [0, 1, 2, 3]:
         raise ValueError(f"the jitter order must be a permutation of 0..3, got {order}")
@@ -364,6 +375,17 @@ def rgbd_record_scalars(rec, draw):
     if draw.get("hue") is not None:
         flags |= ops.RGBD_HUE
         rec["hue"] = float(draw["hue"])
+    return flags
+
+
+def rgbd_record_scalars(rec, draw):
+    """Write a draw's scalars into one RGBD_AUGMENT_DTYPE row: the box, the flip, the jitter order, the enabled terms with
+    factor and 1 - factor (`_jitter_flags`), the erase rectangle.  draw: {"box": (top, left, h, w), "flip": bool, "order": 4 ids
+    (0 brightness, 1 contrast, 2 saturation, 3 hue), "brightness" / "contrast" / "saturation" / "hue": a float or None (term
+    off), "erase": (i, j, h, w) or None}."""
+    from . import ops
+    rec["top"], rec["left"], rec["bh"], rec["bw"] = draw["box"]
+    flags = _jitter_flags(rec, draw)
     if draw.get("erase") is not None:
         flags |= ops.RGBD_ERASE
         rec["ei"], rec["ej"], rec["eh"], rec["ew"] = draw["erase"]
@@ -455,3 +477,193 @@ def plan_rgbd(images, depths, draws, size, mean, std, depth_clamp, antialias=Tru
     tmp = torch.empty(tmp_vec, 4, device=dev, dtype=torch.float32)
     keep.append(packed)
     return RgbdPlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), list(mean), list(std), tuple(depth_clamp), keep)
+
+
+# ---------------------------------------------------------------------------------------------- the plain-image training transform
+RANDAUGMENT_SIGNED = (False,) + (True,) * 9 + (False,) * 4          # per op code (ops.IMAGE_OPS): the op draws a sign
+
+
+@functools.lru_cache(maxsize=64)
+def randaugment_magnitudes(num_bins, S, solarize_from=256.0):
+    """RandAugment's magnitude table for an S x S image -> one tuple of `num_bins` Python floats per op code (float32 values,
+    as torch.linspace gives them).  `solarize_from`: 256 (the reference's copy of the table) or 255 (later torchvision)."""
+    lin = lambda lo, hi: tuple(float(v) for v in torch.linspace(lo, hi, num_bins))
+    zero = (0.0,) * num_bins
+    shear, move, enhance = lin(0.0, 0.3), lin(0.0, 150.0 / 331.0 * S), lin(0.0, 0.9)
+    # Posterize keeps 8 bits at bin 0 and 4 at the last bin, in steps of one bit: 8 - round-half-even(4 i / (bins - 1)), exact
+    bits = tuple(float(8 - round(fractions.Fraction(4 * i, num_bins - 1))) for i in range(num_bins))
+    return (zero, shear, shear, move, move, lin(0.0, 30.0), enhance, enhance, enhance, enhance, bits, lin(float(solarize_from), 0.0),
+            zero, zero)
+
+
+def affine_inverse_matrix(center, angle, translate, shear):
+    """The six doubles (a, b, c, d, e, f) that take an output pixel centre to its source position, x' = a x + b y + c,
+    y' = d x + e y + f, for: rotate by `angle` and shear by `shear` = (sx, sy) (degrees) about `center`, then move by
+    `translate`.  The forward matrix is T(translate) C R Sh C^-1 with R Sh = [[cos(r - sy) / cos sy, -cos(r - sy) tan sx / cos sy
+    - sin r], [sin(r - sy) / cos sy, -sin(r - sy) tan sx / cos sy + cos r]] of determinant 1, so its inverse is the adjugate."""
+    r, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    (cx, cy), (tx, ty) = center, translate
+    a = math.cos(r - sy) / math.cos(sy)
+    b = -math.cos(r - sy) * math.tan(sx) / math.cos(sy) - math.sin(r)
+    c = math.sin(r - sy) / math.cos(sy)
+    d = -math.sin(r - sy) * math.tan(sx) / math.cos(sy) + math.cos(r)
+    m = [d, -b, 0.0, -c, a, 0.0]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def pil_rotate_matrix(angle, w, h):
+    """The matrix Image.rotate(angle) hands to Image.transform for a w x h image (rotation about the centre, entries rounded
+    to 15 places as Pillow rounds them); None where Pillow returns a copy (a multiple of 360 degrees)."""
+    angle = angle % 360.0
+    if angle == 0:
+        return None
+    cx, cy = w / 2, h / 2
+    t = -math.radians(angle)
+    m = [round(math.cos(t), 15), round(math.sin(t), 15), 0.0, round(-math.sin(t), 15), round(math.cos(t), 15), 0.0]
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def randaugment_slot(slot, code, magnitude, S, shear_atan=False):
+    """Write one op at the signed `magnitude` (a Python float) on an S x S image into a record's op slot (ops.IMAGE_OP_DTYPE):
+    the geometric ops as the matrix of the Pillow call (ShearX/Y about the centre with shear = degrees(m), or with
+    `shear_atan` about (0, 0) with degrees(atan(m)); TranslateX/Y by int(m); Rotate as Image.rotate), the enhance ops as the
+    factor 1 + m, Posterize as the mask of int(m) kept bits, Solarize as the first inverted byte."""
+    code = int(code)
+    slot["code"], slot["ipay"], slot["fpay"], slot["pad"], slot["m"] = code, 0, 0.0, 0, 0.0
+    centre = [S * 0.5, S * 0.5]
+    m = None
+    if code in (1, 2):
+        deg = math.degrees(math.atan(magnitude)) if shear_atan else math.degrees(magnitude)
+        m = affine_inverse_matrix([0, 0] if shear_atan else centre, 0.0, [0, 0], [deg, 0.0] if code == 1 else [0.0, deg])
+    elif code in (3, 4):
+        m = affine_inverse_matrix(centre, 0.0, [int(magnitude), 0] if code == 3 else [0, int(magnitude)], [0.0, 0.0])
+    elif code == 5:
+        m = pil_rotate_matrix(magnitude, S, S)
+        if m is None:
+            slot["code"] = 0                                                # Pillow's copy
+    elif 6 <= code <= 9:
+        slot["fpay"] = 1.0 + magnitude
+    elif code == 10:
+        bits = int(magnitude)
+        if not 0 <= bits <= 8:
+            raise ValueError(f"Posterize keeps 0 to 8 bits, got {bits}")
+        slot["ipay"] = ~(2 ** (8 - bits) - 1) & 0xFF
+    elif code == 11:
+        slot["ipay"] = min(max(int(math.ceil(magnitude)), 0), 256)          # byte < m  <=>  byte < ceil(m)
+    elif code not in (0, 12, 13):
+        raise ValueError(f"unknown RandAugment op code {code}")
+    if m is not None:
+        slot["m"] = m
+
+
+def image_record_scalars(rec, draw, S, num_bins=31, shear_atan=False, solarize_from=256.0):
+    """Write a draw's scalars into one IMAGE_AUGMENT_DTYPE row: the box, the flip, the op slots, the jitter order and the
+    enabled terms with factor and 1 - factor (`_jitter_flags`).  draw: {"box": (top, left, h, w), "flip": bool,
+    "ops": [(code, negative, bin), ...] (at most 4), "order": 4 ids, "brightness" / "contrast" / "saturation" / "hue": a
+    float or None (term off)}."""
+    from . import ops
+    rec["top"], rec["left"], rec["bh"], rec["bw"] = draw["box"]
+    rec["flags"] = _jitter_flags(rec, draw)
+    chosen = list(draw["ops"])
+    if len(chosen) > ops.IMAGE_MAX_OPS:
+        raise ValueError(f"at most {ops.IMAGE_MAX_OPS} RandAugment ops per sample, got {len(chosen)}")
+    table = randaugment_magnitudes(num_bins, S, solarize_from)
+    rec["num_ops"] = len(chosen)
+    for k, (code, negative, mag_bin) in enumerate(chosen):
+        if not (0 <= int(code) < len(table) and 0 <= int(mag_bin) < num_bins):
+            raise ValueError(f"op {k}: code {code} or magnitude bin {mag_bin} out of range")
+        mag = table[int(code)][int(mag_bin)]
+        randaugment_slot(rec["ops"][k], code, -mag if (negative and RANDAUGMENT_SIGNED[int(code)]) else mag, S, shear_atan)
+
+
+class ImagePlan:
+    """Device-side description of one batch of the plain-image training transform: the packed buffer (records, tables, host
+    sources), the intermediate and the tensors that keep device sources alive.  `launch()` enqueues vl_image_augment; it can
+    be repeated (same inputs, same outputs)."""
+
+    def __init__(self, records, tables, tmp, n, S, max_nrows, max_ops, mean, std, keep):
+        self.records, self.tables, self.tmp, self.keep = records, tables, tmp, keep
+        self.n, self.S, self.max_nrows, self.max_ops, self.mean, self.std = n, S, max_nrows, max_ops, mean, std
+
+    def launch(self, out=None, out_u8=None, want_u8=False):
+        from . import ops
+        return ops.image_augment(self.records, self.tables, self.tmp, self.S, self.max_nrows, self.max_ops, self.mean, self.std,
+                                 out=out, out_u8=out_u8, want_u8=want_u8)
+
+    def crop_resize(self):
+        from . import ops
+        return ops.image_crop_resize_u8(self.records, self.tables, self.tmp, self.S, self.max_nrows)
+
+
+def plan_image_train(images, draws, size, mean, std, num_bins=31, shear_atan=False, solarize_from=256.0, device="cuda"):
+    """Host side of the plain-image training transform.  images[i]: uint8 [H, W, 3] tensor (host or device; sizes differ
+    between samples), draws[i]: the sample's scalars (`image_record_scalars`).  Everything the host provides - records, the
+    packed Pillow bilinear tables of the distinct (box edge -> size) pairs, host image bytes - is laid out in ONE pinned
+    buffer and travels in ONE copy; device sources are read where they are."""
+    from . import ops
+    n, S, dev = len(images), int(size), torch.device(device)
+    if n < 1 or len(draws) != n:
+        raise ValueError(f"plan_image_train: {n} images, {len(draws)} draws")
+    rec = np.zeros(n, dtype=ops.IMAGE_AUGMENT_DTYPE)
+    parts, offsets, cursor = [], {}, 0
+
+    def table(in_size):
+        nonlocal cursor
+        if in_size not in offsets:
+            b, kk, ks = pil_bilinear_tables(in_size, S)
+            offsets[in_size] = (cursor, cursor + b.size, ks, b)
+            parts.extend((b.reshape(-1), kk.reshape(-1)))
+            cursor += b.size + kk.size
+        return offsets[in_size]
+    tmp_bytes, keep, host = 0, [], []
+    for i, (im, draw) in enumerate(zip(images, draws)):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f"plan_image_train: image {i} must be uint8 [H, W, 3], got {tuple(im.shape)} {im.dtype}")
+        H, W = im.shape[:2]
+        r = rec[i]
+        r["H"], r["W"], r["stride"] = H, W, 3 * W
+        if im.is_cuda:
+            im = im.contiguous()
+            keep.append(im)
+            r["src"] = im.data_ptr()
+        else:
+            host.append((i, im))
+        image_record_scalars(r, draw, S, num_bins, shear_atan, solarize_from)
+        top, left, bh, bw = (int(v) for v in draw["box"])
+        if not (0 <= top and 1 <= bh and top + bh <= H and 0 <= left and 1 <= bw and left + bw <= W):
+            raise ValueError(f"plan_image_train: box {draw['box']} of sample {i} is not inside its {H} x {W} image")
+        r["hb"], r["hk"], r["hks"], _ = table(bw)
+        r["vb"], r["vk"], r["vks"], vb_host = table(bh)
+        r["row0"], r["nrows"] = _window(vb_host, 0, S, bh)
+        r["tmp"] = tmp_bytes
+        tmp_bytes += int(r["nrows"]) * S * 3
+    tables = np.concatenate(parts)
+    # layout: records | tables | host image bytes
+    off_tables = (rec.nbytes + 15) & ~15
+    cursor = off_tables + tables.nbytes
+    place = {}
+    for i, t in host:
+        place[i] = cursor
+        cursor += t.numel()
+    packed = torch.empty(max(cursor, 1), device=dev, dtype=torch.uint8)
+    for i, off in place.items():
+        rec[i]["src"] = packed.data_ptr() + off
+    stage = torch.empty(cursor, dtype=torch.uint8, pin_memory=dev.type == "cuda")
+    buf = stage.numpy()
+    buf[:rec.nbytes] = ops.image_augment_pack(rec, S, tables.size, tmp_bytes).view(np.uint8).reshape(-1)
+    buf[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
+    for i, t in host:
+        stage[place[i]:place[i] + t.numel()].copy_(t.contiguous().reshape(-1))
+    packed.copy_(stage, non_blocking=True)
+    records = packed[:rec.nbytes].view(torch.int32).view(n, -1)
+    tables_d = packed[off_tables:off_tables + tables.nbytes].view(torch.int32)
+    tmp = torch.empty(tmp_bytes, device=dev, dtype=torch.uint8)
+    keep.append(packed)
+    return ImagePlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), int(rec["num_ops"].max()), list(mean), list(std), keep)
