@@ -13,9 +13,13 @@
 //   4 GELU with gelu'(pre-activation) written to out2 (EPI_DGELU: the aux operand IS the saved derivative, of either activation),
 //   5 QuickGELU, 6 QuickGELU with qgelu'(pre-activation) written to out2.
 //   vl_gemm_park.hip only: 10 + code = the code with LayerNorm folded into the epilogue, 20 = EPI_RES_BF16 + partial row statistics.
-// 1, 2 and 5 act on the fp32 values BEFORE they are packed (epi_act2 / epi_prepack); 3, 4, 6 and the epilogues with a second operand of
-// the output's shape act on the bf16-ROUNDED values (epi_post8 after a transpose, epi_direct4 without one) - the rounding
-// points of the reference's autocast (bf16 linear output, then the add / activation).
+// 1, 2 and 5 act on the fp32 values BEFORE they are packed (epi_act2 / epi_prepack).  Behind a 16-byte transpose (epi_post8:
+// store_tile_lds16, vl_gemm_pp.hip, vl_gemm_park.hip) 3, 4, 6 and the epilogues with a second operand of the output's shape act on
+// the bf16-ROUNDED values - the rounding points of the reference's autocast (bf16 linear output, then the add / activation).
+// Without one (epi_direct4: store_tile and the fp32 transpose) only 4 and 6 do: 3 stores bf16(v) to out2 and applies GELU to the
+// fp32 v, and the residual add, ReLU after it, the dGELU product, GEGLU and DGEGLU act on the fp32 v, with ONE rounding at the
+// store (at most one bf16 ulp from the other form; the _DSAVE codes the trainers use are the same either way).  The table, and
+// the tests that tell the two forms apart: tests/test_hip_gemm_families.py.
 //
 // A new activation: its arithmetic in vl_common.h (scalar and pair form, a host test that the two agree), its VL_ACT_* code in
 // epi_act_code and epi_bf16_family_ok, its branch in epi_act2 and / or epi_post8, in epi_direct4 and in store_tile_lds16's
