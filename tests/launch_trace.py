@@ -1,5 +1,6 @@
 """Records the library launches of a forward / backward that runs on CPU tensors instead of executing them: which kernels a
-host-side plan (engine.run_blocks, TowerTrainer.forward / backward, TextEngine.encode_text ...) enqueues, in which order and
+host-side plan (engine.run_blocks / block_forward in any arithmetic, engine.text_features, VitEngine.trunk, TowerTrainer.forward /
+backward, TextEngine.encode_text, perceiver_forward ...) enqueues, in which order and
 with which arguments - without a GPU.
 
     with recording() as trace:

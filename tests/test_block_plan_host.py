@@ -1,5 +1,6 @@
-"""CPU: which kernels one transformer block enqueues (engine.block_forward through VitEngine.trunk and TowerTrainer.forward),
-recorded instead of executed (launch_trace.py).  The host-side branch selection of the LayerNorm folding depends on how many
+"""CPU: which kernels one transformer block enqueues on a bf16 stream (engine.block_forward in engine.Bf16Arith, LayerNorm-folded
+and pruned, through VitEngine.trunk and TowerTrainer.forward), recorded instead of executed (launch_trace.py; the block with its
+LayerNorm passes in each of the four arithmetics: test_tower_plan_host.py).  The host-side branch selection of the LayerNorm folding depends on how many
 rows the persistent GEMM takes of each problem (vl_gemm_main_rows), so the plan differs with the batch; the three plans of a
 ViT-L-width tower at L = 257 are written out below.  No GPU test reaches the B = 50 one."""
 import pytest

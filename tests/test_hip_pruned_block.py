@@ -1,5 +1,6 @@
-"""The pruned last block of a class-token-pooled tower (engine.PRUNE_LAST_BLOCK; engine.run_blocks(pooled_only=True),
-train.TowerTrainer): everything behind the last block's in-projection runs on the B class rows only.
+"""The pruned last block of a class-token-pooled tower (engine.PRUNE_LAST_BLOCK; engine.run_blocks(..., pooled_only=True) ->
+block_forward(cls_only=True) -> _cls_tail_forward in engine.Bf16Arith, from VitEngine.trunk and train.TowerTrainer): everything
+behind the last block's in-projection runs on the B class rows only.
 
 Same tree, switch on and off: features, dxpre and every gradient of the trainable block 0, each path measured against a float64
 torch autograd evaluation (the oracle's vit_trunk) of the same bf16-rounded parameters.  Bounds: the ones test_hip_train.py

@@ -8,6 +8,7 @@ pre-allocated workspaces (no allocation inside the block loop -> hipGraph-captur
 Precision contract (= the reference under torch autocast): GEMM operands bf16, accumulation fp32,
 LayerNorm / softmax statistics / residual stream / final features fp32 (residual dtype selectable).
 """
+from copy import copy
 from dataclasses import dataclass, replace
 from typing import Dict, Optional
 
@@ -51,13 +52,13 @@ def _dev(t, device, dtype=torch.float32):
     return out.clone() if out.data_ptr() == t.data_ptr() else out
 
 
-def prep_block(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
-    """Device copies of one ResidualAttentionBlock: GEMM weights bf16, the rest f32; with the LayerNorm folding switched on
-    also the operands of the two LayerNorm -> Linear pairs with the LayerNorm folded in (ops.fold_ln_linear; used for frozen
-    blocks on a bf16 stream)."""
+def prep_block(sd: Dict[str, torch.Tensor], p: str, device, wdtype=torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """Device copies of one ResidualAttentionBlock: GEMM weights in `wdtype`, the rest f32; bf16 with the LayerNorm folding
+    switched on: also the operands of the two LayerNorm -> Linear pairs with the LayerNorm folded in (ops.fold_ln_linear; used
+    for frozen blocks on a bf16 stream)."""
     dv = lambda k: sd[p + k].detach().to(device)
-    blk = block_operands(sd, p, device)
-    if LN_FOLD:          # (read at call time: engines built while the switch is on carry the folded operands)
+    blk = block_operands(sd, p, device, wdtype)
+    if LN_FOLD and wdtype == torch.bfloat16:      # (read at call time: engines built while the switch is on carry the folded operands)
         blk["in_f"] = ops.fold_ln_linear(dv("attn.in_proj_weight"), dv("attn.in_proj_bias"), dv("ln_1.weight"), dv("ln_1.bias"))
         blk["fc_f"] = ops.fold_ln_linear(dv("mlp.c_fc.weight"), dv("mlp.c_fc.bias"), dv("ln_2.weight"), dv("ln_2.bias"))
     return blk
@@ -99,6 +100,79 @@ def copy_tree(dst, src):
             copy_tree(d, s_)
 
 
+class Bf16Arith:
+    """The matrix products of a tower or a Perceiver on bf16 operands with fp32 accumulation.  block_forward, text_features,
+    VitEngine.trunk and perceiver_forward call one of these objects and never ask which: F16Arith and Bf16x2Arith below,
+    f32.F32Arith."""
+    dtype = torch.bfloat16
+    ln = staticmethod(ops.layernorm)           # LayerNorm into a GEMM operand (the two-term arithmetic writes it twice)
+
+    def __init__(self, gemm_cfg=-1):
+        self.cfg = gemm_cfg
+
+    def linear(self, a, w, b, out, res=None, act=ops.ACT_NONE, out2=None):
+        epi = ops.EPI_BF16 if res is None else ops.EPI_RES_F32 if res.dtype == torch.float32 else ops.EPI_RES_BF16
+        ops.gemm(a, w, b, out=out, res=res, epi=epi, act=act, cfg=self.cfg, out2=out2)
+
+    def geglu(self, a, w, b, out, out2=None):
+        ops.gemm(a, w, b, out=out, epi=ops.EPI_GEGLU, cfg=self.cfg, out2=out2)
+
+    def attn(self, q, k, v, out, lse, dh, causal=False):
+        ops.attn_fwd(q, k, v, out, lse=lse, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
+
+    # train mode with dropout (LensDrop): the attention with the mask on its probabilities, and a down-projection that leaves
+    # its fp32 output apart from the residual for ops.ff_drop_fwd (also: a tower's output projection)
+    def attn_drop(self, q, k, v, out, lse, dh, drop, sublayer):
+        ops.attn_fwd_drop(q, k, v, out, drop.pa, drop.seed, drop.sample0, sublayer, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
+
+    def linear_f32(self, a, w, b, out=None):
+        return ops.gemm(a, w, b, out=out, epi=ops.EPI_F32, cfg=self.cfg)
+
+
+class Bf16x2Arith(Bf16Arith):
+    """Weights as the sum of TWO bf16 terms (prep_block_wsplit) on an fp32 stream.  A projection that writes an activation takes
+    the pair K-concatenated, [N, 2K] against an operand row [a, a]: the LayerNorm in front of it writes its output into both
+    halves of a [rows, 2D] buffer.  A residual projection takes the pair (hi, lo) and runs as two launches that accumulate
+    into the stream: hi with the bias, then lo without."""
+
+    def ln(self, x, w, b, out, rows, D, **kw):
+        for half in (out[:, :D], out[:, D:]):
+            ops.layernorm(x, w, b, half, rows, D, **kw)
+
+    def linear(self, a, w, b, out, res=None, act=ops.ACT_NONE, out2=None):
+        if res is None:
+            return super().linear(a, w, b, out, act=act, out2=out2)
+        super().linear(a, w[0], b, out, res=res)
+        super().linear(a, w[1], None, out, res=out)
+
+
+class F16Arith:
+    """IEEE-half operands (the frozen text tower): vl_gemm_f16, which is the persistent kernel only - whole 256-row tiles - and
+    the fp16 attention.  plan (a TextPlan): the rows are captions packed one behind the other - q is then the packed
+    in-projection output [rows, 3D] itself and the attention runs caption by caption."""
+    dtype = torch.float16
+    ln = staticmethod(ops.layernorm)
+
+    def __init__(self, plan=None):
+        self.plan = plan
+
+    def linear(self, a, w, b, out, res=None, act=ops.ACT_NONE, out2=None):
+        ops.gemm_f16(a, w, b, out=out, res=res, epi=ops.EPI_BF16 if res is None else ops.EPI_RES_F32, act=act)
+
+    def attn(self, q, k, v, out, lse, dh, causal=False):
+        p, qscale = self.plan, dh ** -0.5 * ops.LOG2E
+        if p is None:
+            ops.attn_fwd(q, k, v, out, lse=lse, causal=causal, qscale=qscale)
+        else:
+            ops.attn_fwd_varlen(q, p.start, p.lens, out, q.shape[1] // (3 * dh), p.max_len, lse=lse, qscale=qscale)
+
+    def linear_f32(self, a, w, b, out=None):
+        """vl_gemm_f16 has no fp32-output epilogue: the product accumulates into a ZEROED fp32 buffer through EPI_RES_F32."""
+        out = torch.zeros(a.shape[0], w.shape[0], device=a.device, dtype=torch.float32) if out is None else out.zero_()
+        ops.gemm_f16(a, w, b, out=out, res=out, epi=ops.EPI_RES_F32)
+        return out
+
+
 @dataclass
 class BlockSlots:
     """Where block_forward reads and writes one ResidualAttentionBlock: built once with the buffers (one for an engine's
@@ -106,19 +180,19 @@ class BlockSlots:
     x0: torch.Tensor                  # residual stream: block input, after the attention branch, block output (an engine
     x1: torch.Tensor                  # passes one tensor three times: in place)
     x2: torch.Tensor
-    h1: torch.Tensor                  # ln_1 / ln_2 output of a block that runs the LayerNorm passes
+    h1: torch.Tensor                  # ln_1 / ln_2 output of a block that runs the LayerNorm passes ([rows, 2D]: two-term)
     h2: torch.Tensor
     h_left: torch.Tensor              # LayerNorm output of a folded GEMM's leftover rows
     qkv: torch.Tensor                 # packed in-projection output and its q / k / v views by heads (ops.heads_view)
-    q: torch.Tensor
+    q: torch.Tensor                   # (a packed text batch has no such views: all three are qkv itself, _Workspace.packed)
     k: torch.Tensor
     v: torch.Tensor
     a: torch.Tensor                   # attention output
     hid: torch.Tensor                 # MLP hidden
     part: Optional[torch.Tensor]      # partial row sums between a gemm_res_rowstats and the ln_row_stats behind it
-    a1: torch.Tensor                  # the class rows of a pruned last block: attention output, ln_2 output, MLP hidden
-    h2c: torch.Tensor
-    hid1: torch.Tensor
+    a1: Optional[torch.Tensor]        # the class rows of a pruned last block: attention output, ln_2 output, MLP hidden
+    h2c: Optional[torch.Tensor]       # (bf16 operands only)
+    hid1: Optional[torch.Tensor]
     stats: Optional[tuple] = None     # (mean1, rstd1, mean2, rstd2); a folded block needs them
     lse: Optional[torch.Tensor] = None
     u: Optional[torch.Tensor] = None  # the second output of c_fc (the activation's derivative, with a *_DSAVE act)
@@ -128,30 +202,53 @@ class BlockSlots:
 
 
 class _Workspace:
-    def __init__(self, B, L, D, H, hidden, device, res_dtype):
-        dh = D // H
-        bf = torch.bfloat16
-        self.Lp = (L + 7) // 8 * 8
-        self.x = torch.empty(B * L, D, device=device, dtype=res_dtype)
-        self.h = torch.empty(B * L, D, device=device, dtype=bf)
-        self.qkv = torch.empty(B * L, 3 * D, device=device, dtype=bf)     # packed in-projection output, read in place
-        hv = lambda i: ops.heads_view(self.qkv, B, L, H, dh, i * D)
-        self.q, self.k, self.v = hv(0), hv(1), hv(2)
-        self.a = torch.empty(B * L, D, device=device, dtype=bf)
-        self.hid = torch.empty(B * L, hidden, device=device, dtype=bf)
-        # LayerNorm folding: row statistics of the residual rows and the producing GEMMs' partial sums
-        self.mean = torch.empty(B * L, device=device, dtype=torch.float32)
-        self.rstd = torch.empty(B * L, device=device, dtype=torch.float32)
-        self.part = torch.empty(B * L * (D // 64) * 2, device=device, dtype=torch.float32) if D % 64 == 0 else None
-        # the pruned last block (PRUNE_LAST_BLOCK): attention output, LayerNorm output and MLP hidden of the class rows only
-        self.a1 = torch.empty(B, D, device=device, dtype=bf)
-        self.h1 = torch.empty(B, D, device=device, dtype=bf)
-        self.hid1 = torch.empty(B, hidden, device=device, dtype=bf)
+    """The activations of one tower at (B, L), one in-place stream x (res_dtype) and one set of buffers in the operand `dtype`:
+    LayerNorm output h (`h_width` columns: 2D for the two-term arithmetic), packed in-projection output, attention output, MLP
+    hidden.  bf16 operands also get what LayerNorm folding and the pruned last block need.
+
+    row_tile (256 for the fp16 text tower, vl_gemm_f16 being the persistent kernel only): B*L rows padded to whole row tiles,
+    sized for the dense run, plus the pooled rows and the packed path's feature accumulator f.  Rows beyond the ones a call
+    owns - [B*L, Mp) of a dense call, [rows, roundup(rows, 256)) of a packed one - are GEMM padding: never normalised, never read
+    by the attention or the pooling, and their CONTENT is unspecified.  They start as zeros, a dense call only ever feeds zeros
+    of h and a into them, but a packed call writes x, qkv and hid there from whatever h and a hold in those rows (stale rows of
+    an earlier, larger call), and with roundup(rows, 256) > B*L that reaches the dense run's padding too.  Nothing depends on
+    it: GEMM rows are independent of each other, and tests/test_hip_text_pack.py runs both paths on NaN-filled workspaces."""
+
+    def __init__(self, B, L, D, H, hidden, device, res_dtype, dtype=torch.bfloat16, h_width=None, row_tile=None):
+        f32 = torch.float32
+        pad = (lambda n: n) if row_tile is None else (lambda n: (n + row_tile - 1) // row_tile * row_tile)
+        alloc = torch.empty if row_tile is None else torch.zeros
+        new = lambda *shape, dt=dtype: alloc(*shape, device=device, dtype=dt)
+        self.rows, self.Mp, self.Bp = B * L, pad(B * L), pad(B)
+        self.x = new(self.Mp, D, dt=res_dtype)
+        self.h = new(self.Mp, h_width or D)
+        self.qkv = new(self.Mp, 3 * D)                                    # packed in-projection output, read in place
+        self.q, self.k, self.v = (ops.heads_view(self.qkv, B, L, H, D // H, i * D) for i in range(3))
+        self.a = new(self.Mp, D)
+        self.hid = new(self.Mp, hidden)
+        self.pooled = new(self.Bp, D) if row_tile else None
+        self.f = None                     # [Bp, E] f32, the packed path's feature accumulator (allocated at first use)
+        self.mean = self.rstd = self.part = self.a1 = self.h1 = self.hid1 = None
+        if dtype == torch.bfloat16:
+            # LayerNorm folding: row statistics of the residual rows and the producing GEMMs' partial sums
+            self.mean, self.rstd = new(B * L, dt=f32), new(B * L, dt=f32)
+            self.part = new(B * L * (D // 64) * 2, dt=f32) if D % 64 == 0 else None
+            # the pruned last block (PRUNE_LAST_BLOCK): attention output, LayerNorm output and MLP hidden of the class rows only
+            self.a1, self.h1, self.hid1 = new(B, D), new(B, D), new(B, hidden)
         # one in-place stream, one LayerNorm buffer.  A block that runs its LayerNorm passes keeps no statistics (slots); a
         # folded one leaves both LayerNorms' in the one (mean, rstd) pair (slots_folded)
         self.slots = BlockSlots(x0=self.x, x1=self.x, x2=self.x, h1=self.h, h2=self.h, h_left=self.h, qkv=self.qkv, q=self.q,
                                 k=self.k, v=self.v, a=self.a, hid=self.hid, part=self.part, a1=self.a1, h2c=self.h1, hid1=self.hid1)
         self.slots_folded = replace(self.slots, stats=(self.mean, self.rstd, self.mean, self.rstd))
+
+    def packed(self, Mr):
+        """The first Mr rows as ONE packed sequence (a TextPlan's rows in whole row tiles): row views for the GEMMs, and in place
+        of the q / k / v views by heads the packed in-projection output itself (F16Arith.attn)."""
+        v = copy(self)
+        v.x, v.h, v.qkv, v.a, v.hid = (t[:Mr] for t in (self.x, self.h, self.qkv, self.a, self.hid))
+        v.slots = replace(self.slots, x0=v.x, x1=v.x, x2=v.x, h1=v.h, h2=v.h, h_left=v.h, qkv=v.qkv, q=v.qkv, k=v.qkv, v=v.qkv,
+                          a=v.a, hid=v.hid)
+        return v
 
 
 # LayerNorm folding is ON by default since round 5 (the whole GPU suite is green with it: profiles/r05_pytest_gpu_lnfold_on_*.log;
@@ -185,63 +282,64 @@ def cls_rows(x2d, B, L):
     return x2d.as_strided((B, D), (L * D, 1), x2d.storage_offset())
 
 
-def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, cfg):
-    """The pruned last block behind its in-projection (see PRUNE_LAST_BLOCK): single-query attention, out_proj + residual,
-    ln_2, c_fc + activation and c_proj + residual on the B class rows b*L of x0 / x1 / x2 (row-strided views, no copy); the
-    other rows of x1 and x2 and the full-size a / hid / u are neither written nor read."""
+def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, ar):
+    """The pruned last block behind its in-projection (see PRUNE_LAST_BLOCK; bf16 stream): single-query attention, out_proj +
+    residual, ln_2, c_fc + activation and c_proj + residual on the B class rows b*L of x0 / x1 / x2 (row-strided views, no
+    copy); the other rows of x1 and x2 and the full-size a / hid / u are neither written nor read."""
     x0c, x1c, x2c = (cls_rows(x, B, L) for x in (s.x0, s.x1, s.x2))
     m2, r2 = s.stats2c or (None, None)
     ops.attn_fwd_q1(s.q, s.k, s.v, s.a1, lse=s.lse1, qrow=0, qscale=(D // H) ** -0.5 * ops.LOG2E)
-    ops.gemm(s.a1, w["out_w"], w["out_b"], out=x1c, res=x0c, epi=ops.EPI_RES_BF16, cfg=cfg)
-    ops.layernorm(x1c, w["ln2_w"], w["ln2_b"], s.h2c, B, D, x_row_stride=L * D, mean=m2, rstd=r2)
-    ops.gemm(s.h2c, w["fc_w"], w["fc_b"], out=s.hid1, epi=ops.EPI_BF16, act=act, cfg=cfg, out2=s.u1)
-    ops.gemm(s.hid1, w["proj_w"], w["proj_b"], out=x2c, res=x1c, epi=ops.EPI_RES_BF16, cfg=cfg)
+    ar.linear(s.a1, w["out_w"], w["out_b"], x1c, res=x0c)
+    ar.ln(x1c, w["ln2_w"], w["ln2_b"], s.h2c, B, D, x_row_stride=L * D, mean=m2, rstd=r2)
+    ar.linear(s.h2c, w["fc_w"], w["fc_b"], s.hid1, act=act, out2=s.u1)
+    ar.linear(s.hid1, w["proj_w"], w["proj_b"], x2c, res=x1c)
 
 
-def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, cfg, folded, next_folded, cls_only=False, write_out=True, mm=0):
-    """One pre-LN ResidualAttentionBlock (transformer.py:254-272) with the operands `w` on the buffers `s`:
+def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_folded, cls_only=False, write_out=True, mm=0):
+    """One pre-LN ResidualAttentionBlock (transformer.py:254-272) with the operands `w` on the buffers `s` in the arithmetic
+    `ar` (Bf16Arith, Bf16x2Arith, F16Arith, f32.F32Arith: ln / linear / attn):
     x1 = x0 + out_proj(attn(in_proj(ln_1(x0)))), x2 = x1 + c_proj(act(c_fc(ln_2(x1)))).  The one forward of the engines and
-    the trainers: it branches on what it is given, never on who calls.
-    folded: the LayerNorms are folded into the GEMMs either side of them (w carries "in_f" / "fc_f", bf16 stream, s.stats and
-    s.part given) - ln_1 / ln_2 are never materialised, the in-projection and c_fc read the residual rows and apply
-    (mean, rstd) in their epilogues, the out-projection leaves the partial row sums of what it stores (ops.gemm_lnfold /
-    gemm_res_rowstats).  Otherwise the LayerNorm passes run, and leave their statistics where s.stats is given.
+    the trainers: it branches on what it is given, never on who calls or which arithmetic.  B*L is the number of rows the
+    LayerNorms run on (a packed text batch is one sequence: B = 1, L = its rows); the GEMMs take every row of their buffers.
+    folded (Bf16Arith only): the LayerNorms are folded into the GEMMs either side of them (w carries "in_f" / "fc_f", bf16
+    stream, s.stats and s.part given) - ln_1 / ln_2 are never materialised, the in-projection and c_fc read the residual rows
+    and apply (mean, rstd) in their epilogues, the out-projection leaves the partial row sums of what it stores
+    (ops.gemm_lnfold / gemm_res_rowstats).  Otherwise the LayerNorm passes run, and leave their statistics where s.stats is given.
     next_folded: the consumer of x2 is a folded block - c_proj leaves the partial row sums too.
     cls_only: the caller reads only the class-token rows b*L of x2 - dense up to the in-projection, then _cls_tail_forward.
     write_out=False (the recompute in front of a block's backward, which does not need x2): c_proj is skipped.
     mm: the rows of x0 whose partial sums are in s.part (what the block before returned; 0: the statistics come from the rows).
     Returns the rows of x2 whose partial sums it left in s.part."""
     rows = B * L
-    res_epi = ops.EPI_RES_F32 if s.x0.dtype == torch.float32 else ops.EPI_RES_BF16
     m1, r1, m2, r2 = s.stats or (None,) * 4
 
     def ln_linear(x, mm, mean, rstd, ln, lin, h, out, act=ops.ACT_NONE, out2=None):
         """out = act(Linear(LayerNorm(x))) for the pair (ln, lin) of w; mm rows of x have their partial sums in s.part."""
         ln_w, ln_b, lin_w, lin_b = w[ln + "_w"], w[ln + "_b"], w[lin + "_w"], w[lin + "_b"]
         if not folded:
-            ops.layernorm(x, ln_w, ln_b, h, rows, D, mean=mean, rstd=rstd)
-            ops.gemm(h, lin_w, lin_b, out=out, epi=ops.EPI_BF16, act=act, cfg=cfg, out2=out2)
+            ar.ln(x, ln_w, ln_b, h, rows, D, mean=mean, rstd=rstd)
+            ar.linear(h, lin_w, lin_b, out, act=act, out2=out2)
             return
         # (the row-statistics launch also writes the LayerNorm output of the GEMM's leftover rows into s.h_left - where all of
         # them are rows whose statistics it computes from the rows themselves)
         r = ops.fold_rows(x, out, out.shape[1])
         k = dict(ln_w=ln_w, ln_b=ln_b, h_left=s.h_left, h_row0=r) if mm <= r else {}
         ops.ln_row_stats(s.part, x, mm, mean, rstd, **k)
-        ops.gemm_lnfold(x, w[lin + "_f"], mean, rstd, out, lin_w, lin_b, ln_w, ln_b, s.h_left, act=act, out2=out2, cfg=cfg,
+        ops.gemm_lnfold(x, w[lin + "_f"], mean, rstd, out, lin_w, lin_b, ln_w, ln_b, s.h_left, act=act, out2=out2, cfg=ar.cfg,
                         h_ready=bool(k))
 
     def linear_res(a, lin, out, res, leave_sums):
         """out = res + Linear(a); returns the rows of out whose partial sums it left in s.part."""
         if leave_sums:
-            return ops.gemm_res_rowstats(a, w[lin + "_w"], w[lin + "_b"], out, res, s.part, cfg=cfg)
-        ops.gemm(a, w[lin + "_w"], w[lin + "_b"], out=out, res=res, epi=res_epi, cfg=cfg)
+            return ops.gemm_res_rowstats(a, w[lin + "_w"], w[lin + "_b"], out, res, s.part, cfg=ar.cfg)
+        ar.linear(a, w[lin + "_w"], w[lin + "_b"], out, res=res)
         return 0
 
     ln_linear(s.x0, mm, m1, r1, "ln1", "in", s.h1, s.qkv)
     if cls_only:
-        _cls_tail_forward(w, s, B, L, D, H, act, cfg)
+        _cls_tail_forward(w, s, B, L, D, H, act, ar)
         return 0
-    ops.attn_fwd(s.q, s.k, s.v, s.a, lse=s.lse, causal=causal, qscale=(D // H) ** -0.5 * ops.LOG2E)
+    ar.attn(s.q, s.k, s.v, s.a, s.lse, D // H, causal)
     mm = linear_res(s.a, "out", s.x1, s.x0, folded)
     # s.u = act'(fc output) under a *_DSAVE act: all the backward needs of the pre-activation, evaluated next to the activation
     # from the same exp / rational pieces (+3 VALU per element here) - the dX GEMM's epilogue is then one multiplication,
@@ -252,10 +350,11 @@ def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, cfg, folded, next_f
     return linear_res(s.hid, "proj", s.x2, s.x1, next_folded)
 
 
-def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=None, quick_gelu=False, pooled_only=False):
-    """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:364-371), each one block_forward in place.
+def run_blocks(blocks, ws: _Workspace, B, L, D, H, ar, causal=False, fold=None, quick_gelu=False, pooled_only=False):
+    """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:364-371), each one block_forward in place in
+    the arithmetic `ar`.
     quick_gelu: the tower's MLP activation (TowerCfg / TextCfg.quick_gelu; `act_layer`, transformer.py:217-231).
-    fold (default: engine.LN_FOLD, bf16 stream only): the LayerNorms folded into the GEMMs either side of them.
+    fold (default: engine.LN_FOLD; bf16 stream and operands only): the LayerNorms folded into the GEMMs either side of them.
     pooled_only: the caller reads only the class-token rows b*L of the result (VitEngine.trunk) - the last block then runs on
     those rows alone where prune_last_ok() allows, and the other rows of ws.x are left as the block before it wrote them."""
     prune = prune_last_ok(D, H, ws.x.dtype, L, pooled_only, causal)
@@ -268,7 +367,7 @@ def run_blocks(blocks, ws: _Workspace, B, L, D, H, causal=False, cfg=-1, fold=No
     folded = [can_fold and "in_f" in w for w in blocks] + [False]
     mm = 0                                            # rows of ws.x whose partial sums are in ws.part
     for i, w in enumerate(blocks):
-        mm = block_forward(w, ws.slots_folded if folded[i] else ws.slots, B, L, D, H, causal, act, cfg, folded[i], folded[i + 1],
+        mm = block_forward(w, ws.slots_folded if folded[i] else ws.slots, B, L, D, H, causal, act, ar, folded[i], folded[i + 1],
                            cls_only=prune and i + 1 == len(blocks), mm=mm)
 
 
@@ -281,44 +380,26 @@ def _hi_lo(w: torch.Tensor, device):
 
 
 def prep_block_wsplit(sd: Dict[str, torch.Tensor], p: str, device) -> Dict[str, torch.Tensor]:
-    """One ResidualAttentionBlock with TWO-TERM bf16 weights (`TextEngine(wsplit=True)`): the projections that write a
-    bf16 activation take the pair K-concatenated ([N, 2K] against an activation row [a, a]); the two residual projections
-    run as two launches (hi, then lo) that accumulate into the fp32 residual stream."""
-    blk = prep_block(sd, p, device)
-    for key, name in (("in_w", "attn.in_proj_weight"), ("fc_w", "mlp.c_fc.weight")):
-        hi, lo = _hi_lo(sd[p + name], device)
-        blk[key + "2"] = torch.cat([hi, lo], dim=1).contiguous()
-    for key, name in (("out_w", "attn.out_proj.weight"), ("proj_w", "mlp.c_proj.weight")):
-        blk[key], blk[key + "_lo"] = _hi_lo(sd[p + name], device)
+    """One ResidualAttentionBlock with TWO-TERM bf16 weights (`TextEngine(arith="bf16x2")`), as Bf16x2Arith takes them: in_w and
+    fc_w K-concatenated [N, 2K], out_w and proj_w the pair (hi, lo)."""
+    blk = block_operands(sd, p, device)
+    for key in ("in_w", "fc_w"):
+        blk[key] = torch.cat(_hi_lo(sd[p + _BLOCK_OPERANDS[key]], device), dim=1).contiguous()
+    for key in ("out_w", "proj_w"):
+        blk[key] = _hi_lo(sd[p + _BLOCK_OPERANDS[key]], device)
     return blk
 
 
-def run_blocks_wsplit(blocks, ws: "_Workspace", B, L, D, H, causal=False, cfg=-1, quick_gelu=False):
-    """run_blocks with two-term weights (prep_block_wsplit); the residual stream must be fp32."""
-    dh = D // H
-    act = ops.mlp_act(quick_gelu)
-    h2 = ws.h2
-    for w in blocks:
-        ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], h2[:, :D], B * L, D)
-        ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], h2[:, D:], B * L, D)
-        ops.gemm(h2, w["in_w2"], w["in_b"], out=ws.qkv, epi=ops.EPI_BF16, cfg=cfg)
-        ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=causal, qscale=dh ** -0.5 * ops.LOG2E)
-        ops.gemm(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
-        ops.gemm(ws.a, w["out_w_lo"], None, out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
-        ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], h2[:, :D], B * L, D)
-        ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], h2[:, D:], B * L, D)
-        ops.gemm(h2, w["fc_w2"], w["fc_b"], out=ws.hid, epi=ops.EPI_BF16, act=act, cfg=cfg)
-        ops.gemm(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
-        ops.gemm(ws.hid, w["proj_w_lo"], None, out=ws.x, res=ws.x, epi=ops.EPI_RES_F32, cfg=cfg)
-
-
 class VitEngine:
-    """One ViT tower (`image.` or `visual.` prefix of the TriCLIP state_dict) on the GPU."""
+    """One ViT tower (`image.` or `visual.` prefix of the TriCLIP state_dict) on the GPU, in the arithmetic `arith` (default:
+    Bf16Arith(gemm_cfg); f32.VitEngineF32 passes F32Arith): the operands are built in its dtype."""
 
     def __init__(self, sd, prefix: str, cfg: TowerCfg, device, res_dtype=torch.float32, gemm_cfg: int = -1,
-                 n_tokens: Optional[int] = None):
+                 n_tokens: Optional[int] = None, arith=None):
         self.cfg, self.device, self.res_dtype, self.gemm_cfg = cfg, torch.device(device), res_dtype, gemm_cfg
         self.prefix = prefix
+        self.math = Bf16Arith(gemm_cfg) if arith is None else arith
+        wd = self.math.dtype
         D = cfg.width
         self.cls = _dev(sd[prefix + "class_embedding"], device)
         self.pos = _dev(sd[prefix + "positional_embedding"], device)
@@ -327,11 +408,11 @@ class VitEngine:
         self.ln_post = (_dev(sd[prefix + "ln_post.weight"], device), _dev(sd[prefix + "ln_post.bias"], device))
         # [E, D]; None = the tower has no output projection (`if self.proj is not None`, transformer.py:783-784;
         # CLIPBindWrap drops it when the feature width differs, VitLens-OpenShape/src/models/clip_bind.py:35-47)
-        self.projT = _dev(sd[prefix + "proj"].t(), device, torch.bfloat16) if prefix + "proj" in sd else None
-        self.blocks = [prep_block(sd, f"{prefix}transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+        self.projT = _dev(sd[prefix + "proj"].t(), device, wd) if prefix + "proj" in sd else None
+        self.blocks = [prep_block(sd, f"{prefix}transformer.resblocks.{i}.", device, wd) for i in range(cfg.layers)]
         self.conv_w = None
         if prefix + "conv1.weight" in sd:
-            self.conv_w = conv_weight_as_gemm(sd[prefix + "conv1.weight"], device)
+            self.conv_w = conv_weight_as_gemm(sd[prefix + "conv1.weight"], device, wd)
         self._ws = {}
 
     def update_params(self, sd, names):
@@ -348,15 +429,15 @@ class VitEngine:
         if "proj" in top and self.projT is not None:
             self.projT.copy_(sd[p + "proj"].t())
         if "conv1.weight" in top and self.conv_w is not None:
-            self.conv_w.copy_(conv_weight_as_gemm(sd[p + "conv1.weight"], dev))
+            self.conv_w.copy_(conv_weight_as_gemm(sd[p + "conv1.weight"], dev, self.math.dtype))
         for l in sorted({int(n.split(".")[2]) for n in names if n.startswith("transformer.resblocks.")}):
-            copy_tree(self.blocks[l], prep_block(sd, f"{p}transformer.resblocks.{l}.", dev))
+            copy_tree(self.blocks[l], prep_block(sd, f"{p}transformer.resblocks.{l}.", dev, self.math.dtype))
 
     def workspace(self, B, L):
         key = (B, L)
         if key not in self._ws:
             self._ws[key] = _Workspace(B, L, self.cfg.width, self.cfg.heads, int(self.cfg.width * self.cfg.mlp_ratio),
-                                       self.device, self.res_dtype)
+                                       self.device, self.res_dtype, self.math.dtype)
         return self._ws[key]
 
     # -- stages ---------------------------------------------------------------------------------
@@ -368,10 +449,13 @@ class VitEngine:
 
     def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos=True,
               keep: Optional[torch.Tensor] = None):
-        """tokens [B*T, D] (bf16|f32) -> un-normalised features f32 [B, E].
+        """tokens [B*T, D] (bf16|f32; f32 for the fp32 arithmetic) -> un-normalised features f32 [B, E]: [cls; tokens] + pos
+        (+ pos2) -> ln_pre -> blocks -> ln_post(cls) @ proj (transformer.py:756-787).
         keep int32 [B,K] (ops.patch_keep): patch dropout of a tower in train mode (PatchDropout, transformer.py:53-90) - the
-        trunk runs on the class token + the kept tokens, L = K + 1."""
-        cfg = self.cfg
+        trunk runs on the class token + the kept tokens, L = K + 1.  bf16 operands only: the fp32 engines are eval-only."""
+        cfg, ar = self.cfg, self.math
+        if keep is not None and ar.dtype != torch.bfloat16:
+            raise NotImplementedError("trunk: patch dropout (keep=) is a train-mode forward; the fp32 engines are eval-only")
         D, T = cfg.width, tokens.shape[0] // B
         L = T + 1 if keep is None else keep.shape[1] + 1
         ws = self.workspace(B, L)
@@ -381,14 +465,11 @@ class VitEngine:
         else:
             ops.assemble_ln_pre_keep(tokens, keep, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
         # (only the class-token rows are read below: the last block may run on them alone)
-        run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=False, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu, pooled_only=True)
-        pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
-        if self.projT is None:
-            pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
-        ops.layernorm(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
-        if self.projT is None:
-            return pooled
-        return ops.gemm(pooled, self.projT, None, epi=ops.EPI_F32, cfg=self.gemm_cfg)
+        run_blocks(self.blocks, ws, B, L, D, cfg.heads, ar, quick_gelu=cfg.quick_gelu, pooled_only=True)
+        # (a tower without output projection: ln_post of the class rows IS the feature, fp32)
+        pooled = torch.empty(B, D, device=self.device, dtype=torch.float32 if self.projT is None else ar.dtype)
+        ar.ln(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
+        return pooled if self.projT is None else ar.linear_f32(pooled, self.projT, None)
 
     def encode_image(self, image: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         B = image.shape[0]
@@ -441,28 +522,31 @@ class TextPlan:
     last_row: torch.Tensor    # int64 [B]: the pooled row of every caption
 
 
-class _WorkspaceF16:
-    """Activations of the fp16 text tower, sized for the dense run: B*L rows padded to whole 256-row tiles (vl_gemm_f16 is the
-    persistent kernel only).  Rows beyond the ones a call owns - [B*L, Mp) of a dense call, [rows, roundup(rows, 256)) of a packed
-    one - are GEMM padding: never normalised, never read by the attention or the pooling, and their CONTENT is unspecified.
-    They start as zeros, a dense call only ever feeds zeros of h and a into them, but a packed call writes x, qkv and hid there
-    from whatever h and a hold in those rows (stale rows of an earlier, larger call), and with roundup(rows, 256) > B*L that
-    reaches the dense run's padding too.  Nothing depends on it: GEMM rows are independent of each other, and
-    tests/test_hip_text_pack.py runs both paths on NaN-filled workspaces."""
-
-    def __init__(self, B, L, D, H, device):
-        hf = torch.float16
-        self.rows = B * L
-        self.Mp = (self.rows + 255) // 256 * 256
-        self.Bp = (B + 255) // 256 * 256
-        z = lambda *shape, dt=hf: torch.zeros(*shape, device=device, dtype=dt)
-        self.x = z(self.Mp, D, dt=torch.float32)
-        self.h, self.qkv, self.a, self.hid = z(self.Mp, D), z(self.Mp, 3 * D), z(self.Mp, D), z(self.Mp, 4 * D)
-        dh = D // H
-        hv = lambda i: ops.heads_view(self.qkv, B, L, H, dh, i * D)
-        self.q, self.k, self.v = hv(0), hv(1), hv(2)
-        self.pooled = z(self.Bp, D)
-        self.f = None             # [Bp, E] f32, the packed path's feature accumulator (allocated at first use)
+def text_features(e, ar, ws: _Workspace, text: torch.Tensor, plan: Optional[TextPlan] = None) -> torch.Tensor:
+    """TriCLIP.encode_text behind the token tensor (model.py:528-540) for the engine `e` (tok, pos, blocks, ln_final, projT) in
+    the arithmetic `ar` on the workspace `ws`: embed, blocks, ln_final at every caption's pooled row, projection -> the
+    un-normalised features f32 [B, E].  The one text head of TextEngine and f32.TextEngineF32, in two row layouts:
+    dense (plan None)  every caption at the full context, row b*L + t; the pooled row is b*L + argmax(text[b]);
+    packed (a TextPlan; F16Arith(plan)) only the rows up to each caption's pooled one, one caption behind the other in whole
+                       256-row tiles; the pooled rows are plan.last_row and the result is a view of ws.f."""
+    cfg, (B, L), D = e.cfg, text.shape, e.cfg.width
+    if plan is None:
+        ops.text_embed(text, e.tok, e.pos, ws.x)
+        index, mul = text.argmax(dim=-1).contiguous(), L                   # index-exact EOT position (model.py:539)
+        layout, out = (ws, B, L), None
+    else:
+        if ws.f is None:
+            ws.f = torch.empty(ws.Bp, e.projT.shape[0], device=e.device, dtype=torch.float32)
+        Mr = (plan.rows + 255) // 256 * 256                                # whole row tiles of the persistent GEMM
+        # (rows [rows, Mr) of x are zeroed here; of h and a they hold whatever an earlier call left: GEMM rows are independent)
+        ops.text_embed_packed(text, plan.start, plan.lens, e.tok, e.pos, ws.x, plan.rows, Mr)
+        index, mul = plan.last_row, 0                                      # src = r * 0 + last_row[r]
+        layout, out = (ws.packed(Mr), 1, plan.rows), ws.f                  # (one sequence of plan.rows rows)
+    run_blocks(e.blocks, *layout, D, cfg.heads, ar, causal=True, fold=False, quick_gelu=cfg.quick_gelu)
+    # the pooled rows: two-term [B, 2D]; fp16 in the workspace, padded to whole row tiles of zeros
+    pooled = ws.pooled if ws.pooled is not None else torch.empty(B, ws.h.shape[1], device=e.device, dtype=ar.dtype)
+    ar.ln(ws.x, e.ln_final[0], e.ln_final[1], pooled, B, D, x_row_stride=D, row_index=index, row_mul=mul)
+    return ar.linear_f32(pooled, e.projT, None, out)[:B]
 
 
 class TextEngine:
@@ -500,51 +584,24 @@ class TextEngine:
         self.tok = _dev(sd["token_embedding.weight"], device)
         self.pos = _dev(sd["positional_embedding"], device)
         self.ln_final = (_dev(sd["ln_final.weight"], device), _dev(sd["ln_final.bias"], device))
-        if arith == "f16":
-            self.projT = _dev(sd["text_projection"].t(), device, torch.float16)       # [E, D]
-            self.blocks = [block_operands(sd, f"transformer.resblocks.{i}.", device, torch.float16) for i in range(cfg.layers)]
-        elif self.wsplit:
-            hi, lo = _hi_lo(sd["text_projection"].t(), device)
-            self.projT = torch.cat([hi, lo], dim=1).contiguous()                      # [E, 2D]
-            self.blocks = [prep_block_wsplit(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+        # the arithmetic object (self.arith stays the name: text_pack_mode and the callers read it)
+        self.math = F16Arith() if arith == "f16" else Bf16x2Arith(gemm_cfg) if self.wsplit else Bf16Arith(gemm_cfg)
+        blocks = lambda prep, *a: [prep(sd, f"transformer.resblocks.{i}.", device, *a) for i in range(cfg.layers)]
+        if self.wsplit:
+            self.projT = torch.cat(_hi_lo(sd["text_projection"].t(), device), dim=1).contiguous()         # [E, 2D]
+            self.blocks = blocks(prep_block_wsplit)
         else:
-            self.projT = _dev(sd["text_projection"].t(), device, torch.bfloat16)
-            self.blocks = [block_operands(sd, f"transformer.resblocks.{i}.", device) for i in range(cfg.layers)]
+            self.projT = _dev(sd["text_projection"].t(), device, self.math.dtype)                         # [E, D]
+            self.blocks = blocks(block_operands, self.math.dtype)
         self._ws = {}
 
-    def _workspace_f16(self, B, L) -> _WorkspaceF16:
-        key = ("f16", B, L)
-        if key not in self._ws:
-            self._ws[key] = _WorkspaceF16(B, L, self.cfg.width, self.cfg.heads, self.device)      # worst-case size: no allocation depends on the data
-        return self._ws[key]
-
-    def _blocks_f16(self, x, h, qkv, a, hid, rows, attn):
-        """x <- the blocks of the fp16 tower, on row views of a _WorkspaceF16 (whole 256-row tiles for the GEMMs): the
-        LayerNorms run on the first `rows` rows, attn() is the attention launch from qkv into a."""
-        D = self.cfg.width
-        act = ops.mlp_act(self.cfg.quick_gelu)
-        for w in self.blocks:
-            ops.layernorm(x, w["ln1_w"], w["ln1_b"], h, rows, D)
-            ops.gemm_f16(h, w["in_w"], w["in_b"], out=qkv)
-            attn()
-            ops.gemm_f16(a, w["out_w"], w["out_b"], out=x, res=x, epi=ops.EPI_RES_F32)
-            ops.layernorm(x, w["ln2_w"], w["ln2_b"], h, rows, D)
-            ops.gemm_f16(h, w["fc_w"], w["fc_b"], out=hid, act=act)
-            ops.gemm_f16(hid, w["proj_w"], w["proj_b"], out=x, res=x, epi=ops.EPI_RES_F32)
-
-    def _encode_f16(self, text: torch.Tensor) -> torch.Tensor:
-        B, L = text.shape
-        D, H = self.cfg.width, self.cfg.heads
-        ws = self._workspace_f16(B, L)
-        ops.text_embed(text, self.tok, self.pos, ws.x[:ws.rows])
-        eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
-        qs = (D // H) ** -0.5 * ops.LOG2E
-        self._blocks_f16(ws.x, ws.h, ws.qkv, ws.a, ws.hid, ws.rows,
-                         lambda: ops.attn_fwd(ws.q, ws.k, ws.v, ws.a, causal=True, qscale=qs))
-        ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
-        f = torch.zeros(ws.Bp, self.projT.shape[0], device=self.device, dtype=torch.float32)
-        ops.gemm_f16(ws.pooled, self.projT, None, out=f, res=f, epi=ops.EPI_RES_F32)
-        return f[:B]
+    def workspace(self, B, L) -> _Workspace:
+        """Sized for the dense run: no allocation depends on the data."""
+        if (B, L) not in self._ws:
+            D, f16 = self.cfg.width, self.arith == "f16"
+            self._ws[B, L] = _Workspace(B, L, D, self.cfg.heads, 4 * D, self.device, self.res_dtype, self.math.dtype,
+                                        h_width=2 * D if self.wsplit else D, row_tile=256 if f16 else None)
+        return self._ws[B, L]
 
     def plan_text(self, text: torch.Tensor) -> Optional[TextPlan]:
         """The packing plan of a token batch, or None where the batch runs dense (text_pack_mode).  For a token tensor on the
@@ -588,71 +645,28 @@ class TextEngine:
             rows, max_len = int(self._plan_pin[0]), int(self._plan_pin[1])
         return TextPlan(B, L, rows, max_len, lens, start, last_row)
 
-    def _encode_f16_packed(self, text: torch.Tensor, plan: TextPlan) -> torch.Tensor:
-        cfg = self.cfg
-        B, L = text.shape
-        D, H = cfg.width, cfg.heads
-        if (plan.B, plan.L) != (B, L) or not (B <= plan.rows <= B * L) or not (1 <= plan.max_len <= L):
-            raise ValueError(f"encode_text: the plan was made for another batch ({plan.B} x {plan.L}, {plan.rows} rows, "
-                             f"longest {plan.max_len}; text {B} x {L})")
-        ws = self._workspace_f16(B, L)
-        E = self.projT.shape[0]
-        if ws.f is None:
-            ws.f = torch.empty(ws.Bp, E, device=self.device, dtype=torch.float32)
-        cur = torch.cuda.current_stream(self.device)
-        for t in (plan.lens, plan.start, plan.last_row):                 # (made on the stream the plan was requested on)
-            t.record_stream(cur)
-        rows = plan.rows
-        Mr = (rows + 255) // 256 * 256                                   # whole row tiles of the persistent GEMM
-        x, h, qkv, a, hid = ws.x[:Mr], ws.h[:Mr], ws.qkv[:Mr], ws.a[:Mr], ws.hid[:Mr]
-        # (rows [rows, Mr) of x are zeroed here; of h and a they hold whatever an earlier call left: GEMM rows are independent)
-        ops.text_embed_packed(text, plan.start, plan.lens, self.tok, self.pos, ws.x, rows, Mr)
-        qs = (D // H) ** -0.5 * ops.LOG2E
-        self._blocks_f16(x, h, qkv, a, hid, rows,
-                         lambda: ops.attn_fwd_varlen(qkv, plan.start, plan.lens, a, H, plan.max_len, qscale=qs))
-        # the pooled rows: src = r * 0 + last_row[r]
-        ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], ws.pooled, B, D, x_row_stride=D, row_index=plan.last_row, row_mul=0)
-        ws.f.zero_()
-        ops.gemm_f16(ws.pooled, self.projT, None, out=ws.f, res=ws.f, epi=ops.EPI_RES_F32)
-        return ws.f[:B]
-
     def encode_text(self, text: torch.Tensor, normalize: bool = False, plan=None) -> torch.Tensor:
         """plan: what plan_text(text) returned for THIS token tensor; None: made here where the batch runs packed; False: run
         every caption at the full context length (no plan is made, the host never waits)."""
-        cfg = self.cfg
         B, L = text.shape
-        D = cfg.width
         if plan is False:
             plan = None
         elif self.arith == "f16" and plan is None:
             plan = self.plan_text(text)                    # (before the copy below: a CPU tensor gives its lengths on the host)
         text = text.to(self.device).contiguous()
-        if self.arith == "f16":
-            # (not under a capture even with a plan in hand; the packed path's result lives in the workspace: hand out a copy)
-            if plan is not None and text_pack_mode(self.arith, text, self.device) != "dense":
-                f = self._encode_f16_packed(text if text.dtype == torch.int64 else text.long(), plan)
-                return ops.l2_normalize(f) if normalize else f.clone()
-            f = self._encode_f16(text)
-            return ops.l2_normalize(f) if normalize else f.contiguous()
-        key = (B, L)
-        if key not in self._ws:
-            self._ws[key] = _Workspace(B, L, D, cfg.heads, 4 * D, self.device, self.res_dtype)
-        ws = self._ws[key]
-        ops.text_embed(text, self.tok, self.pos, ws.x)
-        eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
-        if self.wsplit:
-            if not hasattr(ws, "h2"):
-                ws.h2 = torch.empty(B * L, 2 * D, device=self.device, dtype=torch.bfloat16)
-            run_blocks_wsplit(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg, quick_gelu=cfg.quick_gelu)
-            pooled = torch.empty(B, 2 * D, device=self.device, dtype=torch.bfloat16)
-            for half in (pooled[:, :D], pooled[:, D:]):
-                ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], half, B, D, x_row_stride=D, row_index=eot, row_mul=L)
-        else:
-            run_blocks(self.blocks, ws, B, L, D, cfg.heads, causal=True, cfg=self.gemm_cfg, fold=False, quick_gelu=cfg.quick_gelu)
-            pooled = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
-            ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
-        f = ops.gemm(pooled, self.projT, None, epi=ops.EPI_F32, cfg=self.gemm_cfg)
-        return ops.l2_normalize(f) if normalize else f
+        if plan is not None and text_pack_mode(self.arith, text, self.device) == "dense":
+            plan = None                                    # (not under a capture even with a plan in hand)
+        if plan is not None:
+            if (plan.B, plan.L) != (B, L) or not (B <= plan.rows <= B * L) or not (1 <= plan.max_len <= L):
+                raise ValueError(f"encode_text: the plan was made for another batch ({plan.B} x {plan.L}, {plan.rows} rows, "
+                                 f"longest {plan.max_len}; text {B} x {L})")
+            cur = torch.cuda.current_stream(self.device)
+            for t in (plan.lens, plan.start, plan.last_row):                 # (made on the stream the plan was requested on)
+                t.record_stream(cur)
+            text = text.long()
+        f = text_features(self, self.math if plan is None else F16Arith(plan), self.workspace(B, L), text, plan)
+        # (the packed path's result lives in the workspace: hand out a copy)
+        return ops.l2_normalize(f) if normalize else f.clone() if plan is not None else f
 
 
 # ------------------------------------------------------------------------------------------------
@@ -712,7 +726,7 @@ def lens_sublayer(c: "LensCfg", li: int, sj: int = -1, ff: bool = False) -> int:
     return li * (2 + 2 * c.self_per_cross) + 2 * (sj + 1) + (1 if ff else 0)
 
 
-def _interleave_geglu(w: torch.Tensor, b: torch.Tensor):
+def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     """Linear(D, 8D) rows [a(0..4D) ; gate(4D..8D)] -> interleaved (a_j, gate_j) so the GEGLU epilogue
     finds both halves of a pair in one lane (perceiver.py:85-89 `x, gates = x.chunk(2, dim=-1)`)."""
     half = w.shape[0] // 2
@@ -721,10 +735,17 @@ def _interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     return wi, bi
 
 
+def deinterleave_geglu(g: torch.Tensor, *more):
+    """Inverse of interleave_geglu for a weight, a bias or a gradient in the kernels' interleaved (a_j, gate_j) row order ->
+    the reference's [a ; gate] order; several tensors -> a tuple."""
+    out = tuple(torch.cat([t[0::2], t[1::2]], dim=0) for t in (g,) + more)
+    return out if more else out[0]
+
+
 def perceiver_operands(sd: Dict[str, torch.Tensor], prefix: str, cfg: LensCfg, device, wdtype=torch.bfloat16) -> list:
     """Device copies of the Perceiver's layers: one dict per layer (cross attention "x_*", its FeedForward "x_ff*", the latent
     "selfs"), GEMM weights in `wdtype` (bf16; f32 for the fp32 engine), LayerNorm parameters and biases f32.  to_q / to_kv of a
-    latent self-attention are one packed "qkv_w"; the GEGLU's first Linear is row-interleaved (_interleave_geglu)."""
+    latent self-attention are one packed "qkv_w"; the GEGLU's first Linear is row-interleaved (interleave_geglu)."""
     dv = lambda k, dt=torch.float32: _dev(sd[k], device, dt)
     ln = lambda q: (dv(q + ".weight"), dv(q + ".bias"))
 
@@ -737,7 +758,7 @@ def perceiver_operands(sd: Dict[str, torch.Tensor], prefix: str, cfg: LensCfg, d
         return d
 
     def ff(p):
-        w0, b0 = _interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
+        w0, b0 = interleave_geglu(sd[p + "net.0.weight"].detach().float(), sd[p + "net.0.bias"].detach().float())
         return {"w0": _dev(w0, device, wdtype), "b0": _dev(b0, device), "w2": dv(p + "net.2.weight", wdtype), "b2": dv(p + "net.2.bias")}
     layers = []
     for i in range(cfg.depth):
@@ -755,32 +776,6 @@ def perceiver_operands(sd: Dict[str, torch.Tensor], prefix: str, cfg: LensCfg, d
                                  "ff": ff(r + "1.fn.")})
         layers.append(lay)
     return layers
-
-
-class Bf16Arith:
-    """The Perceiver's matrix products on bf16 operands with fp32 accumulation, on an fp32 residual stream (f32.F32Arith: the
-    same three in fp32)."""
-    dtype = torch.bfloat16
-
-    def __init__(self, gemm_cfg=-1):
-        self.cfg = gemm_cfg
-
-    def linear(self, a, w, b, out, res=None):
-        ops.gemm(a, w, b, out=out, res=res, epi=ops.EPI_BF16 if res is None else ops.EPI_RES_F32, cfg=self.cfg)
-
-    def geglu(self, a, w, b, out, out2=None):
-        ops.gemm(a, w, b, out=out, epi=ops.EPI_GEGLU, cfg=self.cfg, out2=out2)
-
-    def attn(self, q, k, v, out, lse, dh):
-        ops.attn_fwd(q, k, v, out, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
-
-    # train mode with dropout (LensDrop): the attention with the mask on its probabilities, and a down-projection that leaves
-    # its fp32 output apart from the residual for ops.ff_drop_fwd
-    def attn_drop(self, q, k, v, out, lse, dh, drop, sublayer):
-        ops.attn_fwd_drop(q, k, v, out, drop.pa, drop.seed, drop.sample0, sublayer, lse=lse, qscale=dh ** -0.5 * ops.LOG2E)
-
-    def linear_f32(self, a, w, b, out):
-        ops.gemm(a, w, b, out=out, epi=ops.EPI_F32, cfg=self.cfg)
 
 
 @dataclass

@@ -18,7 +18,8 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import LensCfg, PerceiverEngine, TextCfg, TowerCfg, _dev, _interleave_geglu, _pad64, block_operands, lens_cols
+from .engine import (LensCfg, PerceiverEngine, TextCfg, TowerCfg, VitEngine, _dev, _Workspace, block_operands, conv_weight_as_gemm,
+                     deinterleave_geglu, interleave_geglu, lens_cols, text_features)  # noqa: F401  (the two GEGLU helpers: re-exported)
 
 
 def f32_head_dim_ok(dh: int) -> bool:
@@ -30,37 +31,29 @@ def f32_supported(width: int, heads: int) -> bool:
     return width % heads == 0 and f32_head_dim_ok(width // heads) and width % 4 == 0
 
 
-class _Ws:
-    def __init__(self, B, L, D, H, hidden, device):
-        z = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)
-        self.x, self.h, self.qkv, self.a, self.hid = z(B * L, D), z(B * L, D), z(B * L, 3 * D), z(B * L, D), z(B * L, hidden)
-        dh = D // H
-        hv = lambda i: ops.heads_view(self.qkv, B, L, H, dh, i * D)
-        self.q, self.k, self.v = hv(0), hv(1), hv(2)
+class F32Arith:
+    """engine.Bf16Arith in fp32: every matrix product on the fp32-input MFMA (the GEGLU FeedForward's first Linear as ONE GEMM
+    with the GEGLU epilogue, vl_gemm_f32_ex), attention on vl_attn_fwd_f32.  Inference only: no second outputs, no dropout."""
+    dtype = torch.float32
+    ln = staticmethod(ops.layernorm)
 
+    def linear(self, a, w, b, out, res=None, act=ops.ACT_NONE, out2=None):
+        ops.gemm_f32(a, w, b, out=out, res=res, act=act)
 
-def run_blocks_f32(blocks, ws: _Ws, B, L, D, H, causal=False, quick_gelu=False):
-    """x <- N pre-LN transformer blocks, fp32 throughout (transformer.py:254-272, 364-371); quick_gelu: the tower's MLP
-    activation (TowerCfg / TextCfg.quick_gelu)."""
-    scale = (D // H) ** -0.5
-    act = ops.mlp_act(quick_gelu)
-    for w in blocks:
-        ops.layernorm(ws.x, w["ln1_w"], w["ln1_b"], ws.h, B * L, D)
-        ops.gemm_f32(ws.h, w["in_w"], w["in_b"], out=ws.qkv)
-        ops.attn_fwd_f32(ws.q, ws.k, ws.v, ws.a, causal=causal, scale=scale)
-        ops.gemm_f32(ws.a, w["out_w"], w["out_b"], out=ws.x, res=ws.x)
-        ops.layernorm(ws.x, w["ln2_w"], w["ln2_b"], ws.h, B * L, D)
-        ops.gemm_f32(ws.h, w["fc_w"], w["fc_b"], out=ws.hid, act=act)
-        ops.gemm_f32(ws.hid, w["proj_w"], w["proj_b"], out=ws.x, res=ws.x)
+    def geglu(self, a, w, b, out, out2=None):
+        ops.gemm_f32_ex(a, w, b, out=out, geglu=True)
+
+    def attn(self, q, k, v, out, lse, dh, causal=False):
+        ops.attn_fwd_f32(q, k, v, out, causal=causal, scale=dh ** -0.5)
+
+    def linear_f32(self, a, w, b, out=None):
+        return ops.gemm_f32(a, w, b, out=out)
 
 
 def conv_as_gemm_f32(w: torch.Tensor, device="cpu") -> torch.Tensor:
     """Conv weight [O, C, *kernel] -> f32 [O, Kp] (K = C * prod(kernel) zero-padded to a multiple of 64, as the 16-bit stem
     lays it out; column order (c, i, j) = im2col's)."""
-    O, K = w.shape[0], w[0].numel()
-    out = torch.zeros(O, _pad64(K), dtype=torch.float32, device=device)
-    out[:, :K] = w.detach().reshape(O, K).float().to(device)
-    return out
+    return conv_weight_as_gemm(w, device, torch.float32)
 
 
 def fold_bn_f32(w, b, gamma, beta, running_mean, running_var, eps=1e-5):
@@ -77,16 +70,6 @@ def pad_k4(w: torch.Tensor) -> torch.Tensor:
     out = torch.zeros(w.shape[0], (K + 3) // 4 * 4, dtype=torch.float32, device=w.device)
     out[:, :K] = w.float()
     return out
-
-
-def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
-    """Linear(D, 8D) rows [a ; gate] -> interleaved (a_j, gate_j) (the GEGLU epilogue's layout; engine._interleave_geglu)."""
-    return _interleave_geglu(w, b)
-
-
-def deinterleave_geglu(wi: torch.Tensor, bi: torch.Tensor):
-    """Inverse of interleave_geglu: rows (a_j, gate_j) -> [a ; gate]."""
-    return torch.cat([wi[0::2], wi[1::2]], 0), torch.cat([bi[0::2], bi[1::2]], 0)
 
 
 def f32_lens_supported(tower: TowerCfg, lens: Optional[LensCfg]) -> bool:
@@ -107,49 +90,22 @@ def f32_lens_supported(tower: TowerCfg, lens: Optional[LensCfg]) -> bool:
     return True
 
 
-class VitEngineF32:
-    """One ViT tower in fp32: `image.` / `visual.` of TriCLIP for the image and tactile modalities, and - with `depth=True` - the
-    depth Lens with an identity Perceiver (visual_adapter.conv1 + pos_emb in front of the same trunk).  A `visual.` tower of the
-    other Lenses has no stem of its own: LensEngineF32 feeds `trunk` the Perceiver's latents."""
+class VitEngineF32(VitEngine):
+    """One ViT tower in fp32 - engine.VitEngine on fp32 operands, an fp32 stream and F32Arith: `image.` / `visual.` of TriCLIP for
+    the image and tactile modalities, and - with `depth=True` - the depth Lens with an identity Perceiver (visual_adapter.conv1 +
+    pos_emb in front of the same trunk).  A `visual.` tower of the other Lenses has no stem of its own: LensEngineF32 feeds
+    `trunk` the Perceiver's latents."""
 
     def __init__(self, sd, prefix: str, cfg: TowerCfg, device, depth: bool = False, use_orig_pos: bool = True,
                  disable_adapter_pos: bool = False):
         if not f32_supported(cfg.width, cfg.heads):
             raise NotImplementedError("fp32 inference: head dim must be 32, 64 or a multiple of 8 in (64, 128]")
-        self.cfg, self.device, self.depth, self.use_orig_pos = cfg, torch.device(device), depth, use_orig_pos
-        self.cls = _dev(sd[prefix + "class_embedding"], device)
-        self.pos = _dev(sd[prefix + "positional_embedding"], device)
-        ln = lambda n: (_dev(sd[prefix + n + ".weight"], device), _dev(sd[prefix + n + ".bias"], device))
-        self.ln_pre, self.ln_post = ln("ln_pre"), ln("ln_post")
-        self.projT = _dev(sd[prefix + "proj"].t(), device) if prefix + "proj" in sd else None       # [E, D]
-        self.blocks = [block_operands(sd, f"{prefix}transformer.resblocks.{i}.", device, torch.float32) for i in range(cfg.layers)]
-        self.pos2 = None
-        self.conv_w = None
+        super().__init__(sd, prefix, cfg, device, res_dtype=torch.float32, arith=F32Arith())
+        self.depth, self.use_orig_pos, self.pos2 = depth, use_orig_pos, None
         if depth:
             a = prefix + "visual_adapter."
             self.conv_w = conv_as_gemm_f32(sd[a + "conv1.weight"], device)
             self.pos2 = _dev(sd[a + "pos_emb"].detach().float() * (0.0 if disable_adapter_pos else 1.0), device)
-        elif prefix + "conv1.weight" in sd:
-            self.conv_w = conv_as_gemm_f32(sd[prefix + "conv1.weight"], device)
-        self._ws = {}
-
-    def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos: bool = True) -> torch.Tensor:
-        """tokens f32 [B*T, D] -> un-normalised features f32 [B, E]: [cls; tokens] + pos (+ pos2) -> ln_pre -> blocks ->
-        ln_post(cls) @ proj (VitEngine.trunk in fp32; transformer.py:756-787)."""
-        cfg = self.cfg
-        D = cfg.width
-        T = tokens.shape[0] // B
-        L = T + 1
-        key = (B, L)
-        if key not in self._ws:
-            self._ws[key] = _Ws(B, L, D, cfg.heads, int(D * cfg.mlp_ratio), self.device)
-        ws = self._ws[key]
-        pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
-        ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
-        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads, quick_gelu=cfg.quick_gelu)
-        pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
-        ops.layernorm(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
-        return pooled if self.projT is None else ops.gemm_f32(pooled, self.projT)
 
     def encode(self, x: torch.Tensor, normalize: bool = False, **kw) -> torch.Tensor:
         if self.conv_w is None:
@@ -164,7 +120,8 @@ class VitEngineF32:
 
 
 class TextEngineF32:
-    """TriCLIP.encode_text in fp32 (model.py:528-540): embedding, causal transformer, ln_final at the EOT token, projection."""
+    """TriCLIP.encode_text in fp32 (model.py:528-540): embedding, causal transformer, ln_final at the EOT token, projection -
+    engine.text_features on fp32 operands in F32Arith."""
 
     def __init__(self, sd, cfg: TextCfg, device):
         if not f32_supported(cfg.width, cfg.heads):
@@ -179,41 +136,17 @@ class TextEngineF32:
         self._ws = {}
 
     def encode_text(self, text: torch.Tensor, normalize: bool = False) -> torch.Tensor:
-        cfg = self.cfg
         B, L = text.shape
-        D = cfg.width
-        key = (B, L)
-        if key not in self._ws:
-            self._ws[key] = _Ws(B, L, D, cfg.heads, 4 * D, self.device)
-        ws = self._ws[key]
-        text = text.to(self.device).contiguous()
-        ops.text_embed(text, self.tok, self.pos, ws.x)
-        eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
-        run_blocks_f32(self.blocks, ws, B, L, D, cfg.heads, causal=True, quick_gelu=cfg.quick_gelu)
-        pooled = torch.empty(B, D, device=self.device, dtype=torch.float32)
-        ops.layernorm(ws.x, self.ln_final[0], self.ln_final[1], pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L)
-        f = ops.gemm_f32(pooled, self.projT)
+        D, f32 = self.cfg.width, torch.float32
+        if (B, L) not in self._ws:
+            self._ws[B, L] = _Workspace(B, L, D, self.cfg.heads, 4 * D, self.device, f32, f32)
+        f = text_features(self, F32Arith(), self._ws[B, L], text.to(self.device).contiguous())
         return ops.l2_normalize(f) if normalize else f
 
 
 # ------------------------------------------------------------------------------------------------
 # The Lenses with a Perceiver (audio, EEG, point cloud, depth): tokenizer -> (+pos) -> Perceiver -> trunk, all in fp32
 # ------------------------------------------------------------------------------------------------
-class F32Arith:
-    """engine.Bf16Arith in fp32: the Perceiver's matrix products on the fp32-input MFMA (the GEGLU FeedForward's first Linear as
-    ONE GEMM with the GEGLU epilogue, vl_gemm_f32_ex), attention on vl_attn_fwd_f32.  Inference only: no second outputs."""
-    dtype = torch.float32
-
-    def linear(self, a, w, b, out, res=None):
-        ops.gemm_f32(a, w, b, out=out, res=res)
-
-    def geglu(self, a, w, b, out, out2=None):
-        ops.gemm_f32_ex(a, w, b, out=out, geglu=True)
-
-    def attn(self, q, k, v, out, lse, dh):
-        ops.attn_fwd_f32(q, k, v, out, scale=dh ** -0.5)
-
-
 class PerceiverEngineF32(PerceiverEngine):
     """Perceiver.forward(return_embeddings=True) (open_clip/perceiver.py:289-328) in fp32: engine.perceiver_forward on fp32
     operands and an fp32 workspace in F32Arith.  data f32 [B*Tc, C] -> latents f32 [B*n, D]."""

@@ -151,14 +151,14 @@ class AbiComm:
 # ------------------------------------------------------------------------------------------------ checkpointing
 def _master_from_sd(name: str, sd, like: torch.Tensor) -> torch.Tensor:
     """Value of master `name` (kernel layout) from a reference-layout state_dict."""
-    from .engine import _interleave_geglu, conv_weight_as_gemm
+    from .engine import conv_weight_as_gemm, interleave_geglu
     dev = like.device
     f32 = lambda k: sd[k].detach().float().to(dev).clone()
     if name.endswith("conv1.weight_gemm"):                       # conv-as-GEMM, K zero-padded to 64
         return conv_weight_as_gemm(sd[name[:-5]], dev, torch.float32)
     if name.endswith("net.0.weight_il") or name.endswith("net.0.bias_il"):      # GEGLU rows interleaved (a_j, gate_j)
         base = name[:name.rindex("net.0.")] + "net.0."
-        w, b = _interleave_geglu(f32(base + "weight"), f32(base + "bias"))
+        w, b = interleave_geglu(f32(base + "weight"), f32(base + "bias"))
         return (w if name.endswith("weight_il") else b).contiguous()
     if name.endswith("fn.to_qkv.weight"):                        # self-attention: [to_q ; to_kv]
         return torch.cat([f32(name.replace("to_qkv", "to_q")), f32(name.replace("to_qkv", "to_kv"))], 0).contiguous()
@@ -968,9 +968,9 @@ class _PerceiverLensStep(_StepState):
         self.masters[p + "fn.to_out.bias"] = a["to_out_b"]
 
     def _ff(self, p, ff, norm, path, sd, f32):
-        from .engine import _interleave_geglu
+        from .engine import interleave_geglu
         self.masters[p + "norm.weight"], self.masters[p + "norm.bias"] = norm
-        w0, _ = _interleave_geglu(f32(p + "fn.net.0.weight"), f32(p + "fn.net.0.bias"))
+        w0, _ = interleave_geglu(f32(p + "fn.net.0.weight"), f32(p + "fn.net.0.bias"))
         self.masters[p + "fn.net.0.weight_il"] = w0.contiguous(); self.refresh.append((p + "fn.net.0.weight_il", ff["w0"], path + ("w0",)))
         self.masters[p + "fn.net.0.bias_il"] = ff["b0"]
         self.masters[p + "fn.net.2.weight"] = f32(p + "fn.net.2.weight"); self.refresh.append((p + "fn.net.2.weight", ff["w2"], path + ("w2",)))

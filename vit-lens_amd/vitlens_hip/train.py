@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from . import engine as _engine
-from .engine import VitEngine
+from .engine import VitEngine, deinterleave_geglu  # noqa: F401  (re-exported: the inverse of engine.interleave_geglu)
 
 BF = torch.bfloat16
 
@@ -204,7 +204,7 @@ class TowerTrainer:
         def folds(k):
             return bool(_engine.LN_FOLD and S.part is not None and k < self.layers and "in_f" in e.blocks[k]
                         and k not in self.train_blocks)
-        return _engine.block_forward(e.blocks[l], S.slots[l], B, L, self.D, self.H, self.causal, self.act_dsave, e.gemm_cfg,
+        return _engine.block_forward(e.blocks[l], S.slots[l], B, L, self.D, self.H, self.causal, self.act_dsave, e.math,
                                      folds(l), folds(l + 1), cls_only=cls_only, write_out=write_out, mm=mm)
 
     # ------------------------------------------------------------------------------------------ backward
@@ -418,7 +418,7 @@ class _TextAsTower:
         from types import SimpleNamespace
         c = te.cfg
         self.cfg = SimpleNamespace(width=c.width, heads=c.heads, mlp_ratio=4.0, layers=c.layers, quick_gelu=c.quick_gelu)
-        self.device, self.res_dtype, self.gemm_cfg = te.device, torch.float32, te.gemm_cfg
+        self.device, self.res_dtype, self.gemm_cfg, self.math = te.device, torch.float32, te.gemm_cfg, te.math
         self.blocks, self.projT, self.ln_post = te.blocks, te.projT, te.ln_final
         self.tok, self.pos = te.tok, te.pos
 
@@ -607,11 +607,6 @@ class AdamW:
 # ------------------------------------------------------------------------------------------------
 # Perceiver ("Lens") training: autograd of Perceiver.forward (open_clip/perceiver.py:289-328)
 # ------------------------------------------------------------------------------------------------
-def deinterleave_geglu(g: torch.Tensor) -> torch.Tensor:
-    """gradient / weight in the kernels' interleaved (a_j, gate_j) row order -> the reference's [a ; gate] order."""
-    return torch.cat([g[0::2], g[1::2]], dim=0)
-
-
 def at_path(node, path):
     """node[path[0]][path[1]]... of a nest of dicts and lists."""
     for k in path:
