@@ -84,6 +84,7 @@ int vl_version(void);
  *    5 (4 = alias)      round-1 persistent kernel (any shape) | 6: the same on 256x128 tiles
  *    0 / 1              one 256x256 / 128x128 LDS-DMA tile per workgroup | 2 / 3: the same with register staging
  *    9                  split-K tail kernel (32x32 tile per workgroup) | 11 / 12: 64x64 / 128x64 tiles
+ * (inside the library every number has a name: enum GemmCfg of csrc/vl_gemm_plan.h, which also holds the row split of -1)
  * Replaces nn.Linear / out_proj / mlp.c_fc(+GELU) / mlp.c_proj(+residual)
  * (open_clip/transformer.py:226-234,268-271), Perceiver to_q/to_kv/to_out/FeedForward
  * (open_clip/perceiver.py:85-123), pooled @ proj (transformer.py:786-787) and
@@ -223,6 +224,8 @@ int vl_attn_fwd_bf16(const void* q, const void* k, const void* v, const long* st
  * produced those rows can leave their partial sums behind: the normalised activations are never written or read.
  *   vl_gemm_main_rows          rows of an [M, K] x [N, K]^T problem that vl_gemm_bf16 (cfg -1) gives to the persistent
  *                              256x256-tile kernel; the entries below take exactly such row ranges (0: none)
+ *   vl_gemm_rest_cfg           the cfg (1, 11 or 9) vl_gemm_bf16 (cfg -1) runs `rows` rows behind that range on: what a caller
+ *                              that splits the rows itself passes for them (a standalone call of that size would get 128x128 tiles)
  *   vl_gemm_lnfold_bf16        out bf16[M,N] = act(rstd_m * (A Wg^T - mean_m * ln_c) + bias_f); A = raw rows bf16 [M,K],
  *                              Wg = bf16(W * gamma) [N,K], bias_f = b + W beta f32 [N], ln_c f32 [N] (sums of the ROUNDED
  *                              Wg rows), ln_mean / ln_rstd f32 [M]; act = VL_ACT_NONE / VL_ACT_GELU / VL_ACT_GELU_DSAVE /
@@ -239,6 +242,7 @@ int vl_attn_fwd_bf16(const void* q, const void* k, const void* v, const long* st
  * Whole 256x256 tiles, K >= 512, 16-byte aligned operands; anything else is refused (the caller keeps vl_layernorm_fwd +
  * vl_gemm_bf16 for it). */
 int vl_gemm_main_rows(int M, int N);
+int vl_gemm_rest_cfg(int rows, int N);
 int vl_gemm_lnfold_bf16(const void* A, const void* Wg, const float* bias_f, const float* ln_c, const float* ln_mean,
                         const float* ln_rstd, void* out, void* out2, int M, int N, int K, int lda, int ldw, int ldo, int act,
                         hipStream_t stream);

@@ -17,7 +17,7 @@ import ctypes
 
 import torch
 
-HOST_FUNCTIONS = ("vl_version", "vl_last_error", "vl_gemm_main_rows", "vl_attn_bwd_fused_supported")
+HOST_FUNCTIONS = ("vl_version", "vl_last_error", "vl_gemm_main_rows", "vl_gemm_rest_cfg", "vl_attn_bwd_fused_supported")
 
 
 class Ptr:

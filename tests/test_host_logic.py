@@ -43,6 +43,10 @@ def test_row_split_of_the_folded_gemms_follows_the_dispatcher():
     assert ops._leftover_cfg(256, 3072, -1) == 11 and ops._leftover_cfg(256, 4096, -1) == 11      # 4 x 48 / 4 x 64 tiles of 64 x 64
     assert ops._leftover_cfg(256, 1024, -1) == 9                                                  # 64 tiles: split-K tail kernel
     assert ops._leftover_cfg(256, 1024, 5) == 5 and ops._leftover_cfg(4096, 1024, -1) == -1       # explicit cfg / many rows: untouched
+    # the library's own statement of the dispatcher's choice (csrc/vl_gemm_plan.h), which _leftover_cfg asks up to 512 rows
+    assert lib.vl_gemm_rest_cfg(256, 3072) == 11 and lib.vl_gemm_rest_cfg(256, 4096) == 11 and lib.vl_gemm_rest_cfg(256, 1024) == 9
+    # ... and above 512 rows the two differ: run_gemm launches 128x128 tiles, the Python split re-enters cfg -1
+    assert lib.vl_gemm_rest_cfg(4096, 1024) == 1
 
 
 def test_folding_entries_refuse_bad_arguments_without_touching_the_gpu():

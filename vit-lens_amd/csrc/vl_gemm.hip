@@ -16,6 +16,7 @@
 //     vl_gemm_park.hip; this file keeps the three ways of getting values to memory: direct (store_tile), fp32 LDS transpose
 //     (store_tile_lds) and bf16 LDS transpose with 16-byte stores (store_tile_lds16).
 #include "vl_gemm_epi.h"
+#include "vl_gemm_plan.h"
 
 namespace {
 
@@ -612,26 +613,28 @@ hipError_t launch_best_persist(const GemmP& p0, hipStream_t s) {
   return launch_persist<EPI>(p, s);
 }
 
+static_assert(GEMM_CFG_PARK == VL_GEMM_PERSIST && GEMM_CFG_PINGPONG == VL_GEMM_PINGPONG, "vl_gemm_plan.h and vitlens_hip.h name the same numbers");
+
 template <int EPI>
 hipError_t dispatch(const GemmP& p, int cfg, hipStream_t s) {
-  if (cfg == 8) {
-    if (!vl_gemm_park_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
-    return (hipError_t)vl_gemm_park_launch(epi_base(EPI), &p, num_cus(), s);
+  switch (cfg) {
+    case GEMM_CFG_PARK:
+      if (!vl_gemm_park_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
+      return (hipError_t)vl_gemm_park_launch(epi_base(EPI), &p, num_cus(), s);
+    case GEMM_CFG_PINGPONG:
+      if (!vl_gemm_pp_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
+      return (hipError_t)vl_gemm_pp_launch(epi_base(EPI), &p, num_cus(), s);
+    case GEMM_CFG_PERSIST1_OLD:
+    case GEMM_CFG_PERSIST1: return launch_persist<EPI>(p, s);
+    case GEMM_CFG_PERSIST1_N128: return launch_persist<EPI, 128>(p, s);
+    case GEMM_CFG_TAIL: return launch_tail<EPI>(p, s);
+    case GEMM_CFG_T64: return launch<64, 64, 2, 2, EPI, true>(p, s);      // few-row problems
+    case GEMM_CFG_T128X64: return launch<128, 64, 2, 2, EPI, true>(p, s);
   }
-  if (cfg == 10) {
-    if (!vl_gemm_pp_supported(epi_base(EPI), &p)) return hipErrorInvalidValue;
-    return (hipError_t)vl_gemm_pp_launch(epi_base(EPI), &p, num_cus(), s);
-  }
-  // cfg bit0: 0 = 256x256 tile (8 waves), 1 = 128x128 tile (4 waves); bit1: 1 = register staging
-  if (cfg == 4 || cfg == 5) return launch_persist<EPI>(p, s);       // 4: historical alias
-  if (cfg == 6) return launch_persist<EPI, 128>(p, s);              // 256x128 tiles (experiment)
-  if (cfg == 9) return launch_tail<EPI>(p, s);
-  if (cfg == 11) return launch<64, 64, 2, 2, EPI, true>(p, s);      // few-row problems: one 64x64 tile per workgroup
-  if (cfg == 12) return launch<128, 64, 2, 2, EPI, true>(p, s);
-  switch (cfg & 3) {
-    case 0: return launch<256, 256, 2, 4, EPI, true>(p, s);
-    case 1: return launch<128, 128, 2, 2, EPI, true>(p, s);
-    case 2: return launch<256, 256, 2, 4, EPI, false>(p, s);
+  switch (cfg & 3) {      // bit0: 0 = 256x256 tile (8 waves), 1 = 128x128 tile (4 waves); bit1: 1 = register staging
+    case GEMM_CFG_T256: return launch<256, 256, 2, 4, EPI, true>(p, s);
+    case GEMM_CFG_T128: return launch<128, 128, 2, 2, EPI, true>(p, s);
+    case GEMM_CFG_T256_REG: return launch<256, 256, 2, 4, EPI, false>(p, s);
     default: return launch<128, 128, 2, 2, EPI, false>(p, s);
   }
 }
@@ -640,32 +643,13 @@ hipError_t dispatch(const GemmP& p, int cfg, hipStream_t s) {
 
 extern "C" int vl_set_error(const char* msg);
 
-static int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
-
 // cfg >= 0: run exactly that kernel configuration.
-// cfg == -1 (auto): problems smaller than one wave of 256x256 tiles use 128x128 tiles; larger ones run
-// the persistent 256x256 kernel on the largest row range whose tile count is a multiple of the CU count
-// (every CU gets the same number of tiles -> no tail round) and the few remaining rows on 128x128 tiles.
+// cfg == -1 (auto): the row split of vl_gemm_plan.h - the main rows on the persistent kernels, the rest on gemm_rest_cfg's kernel.
 template <int EPI>
 static hipError_t run_gemm(const GemmP& p, int cfg, hipStream_t s) {
   if (cfg >= 0) return dispatch<EPI>(p, cfg, s);
-  const int G = num_cus() & ~7;
-  const int tiles_n = (p.N + 255) / 256, full_m = p.M / 256;
-  // fewer 256x256 tiles than 3/4 of the CUs: 128x128 tiles.  (Between 3/4 and one full round the persistent kernel's single
-  // uneven round wins: text tower out_proj / c_proj, 77 x 3 = 231 tiles, 30 / 86 us against 89 us on 128x128 tiles.)
-  if ((long)full_m * tiles_n < (G * 3) / 4) return dispatch<EPI>(p, 1, s);
-  int step = G / gcd_i(G, tiles_n);
-  int main_m = (full_m / step) * step;
-  if ((p.N & 255) == 128) {       // 256x128 tiles on the ping-pong kernel (two workgroups per CU): whole rounds where the row
-    step = 2 * G / gcd_i(2 * G, p.N >> 7);      // count allows, otherwise every full row tile (an uneven last round beats 128x128 tiles)
-    main_m = (full_m / step) * step;
-    if (main_m == 0) main_m = full_m;
-  }
-  // no whole round fits (e.g. the text tower's 77 row tiles x 9 or 12 column tiles): every full row tile on the persistent
-  // kernel with an uneven last round (launch_best_persist falls back to the round-1 kernel where the round-2 one does not apply)
-  if (main_m == 0) main_m = full_m;
-  if (main_m == 0) return launch_persist<EPI>(p, s);
-  const int rows_main = main_m * 256;
+  const int rows_main = gemm_main_rows(p.M, p.N, num_cus() & ~7);
+  if (rows_main == 0) return dispatch<EPI>(p, GEMM_CFG_T128, s);
   GemmP pm = p; pm.M = rows_main;
   hipError_t e = launch_best_persist<EPI>(pm, s);
   if (e != hipSuccess || rows_main == p.M) return e;
@@ -679,14 +663,26 @@ static hipError_t run_gemm(const GemmP& p, int cfg, hipStream_t s) {
   // every other epilogue indexes res with the local row.
   if (p.res && EPI != EPI_RES_BF16) pr.res = (const unsigned char*)p.res + (size_t)rows_main * p.ldo * osz;
   if (p.out2) pr.out2 = (bf16_t*)p.out2 + (size_t)rows_main * p.ldo * (EPI == EPI_GEGLU ? 2 : 1);
-  if (pr.M > 512) return dispatch<EPI>(pr, 1, s);
-  // leftover rows: 64x64 LDS-DMA tiles when they fill most of the chip (N >= 3072 at 256 rows: 10-12 us against 15-20 us,
-  // profiles/r03b_tail_probe.log), otherwise the split-K 32x32 tail kernel (long K, few columns: 17 us against 28-32 us)
-  const long t64 = (long)((pr.M + 63) / 64) * ((pr.N + 63) / 64);
-  return t64 >= 192 ? dispatch<EPI>(pr, 11, s) : launch_tail<EPI>(pr, s);
+  return dispatch<EPI>(pr, gemm_rest_cfg(pr.M, pr.N), s);
 }
 
 #define VL_CHECK_ARG(c, msg) do { if (!(c)) return vl_set_error(msg); } while (0)
+
+static int status(hipError_t e) { return e == hipSuccess ? 0 : vl_set_error(hipGetErrorString(e)); }
+
+// the fields every entry fills; what only one entry needs (f16, ln_*, row_part, the split-K fields) it sets afterwards
+static GemmP gemm_params(const void* A, const void* W, const float* bias, void* out, const void* res, void* out2, int M, int N, int K,
+                         int lda, int ldw, int ldo, float alpha, int act, int res_div) {
+  GemmP p{};
+  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res; p.out2 = out2;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = alpha; p.act = act; p.res_div = res_div;
+  return p;
+}
+
+static hipError_t launch_splitk_reduce(const float* ws, int splits, int M, int N, float* out, long ldo, hipStream_t stream) {
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)M * (N >> 2) + 255) / 256)), dim3(256), 0, stream, ws, splits, M, N, out, ldo);
+  return hipGetLastError();
+}
 
 // ---- LayerNorm folded into the GEMMs either side of it (round 4; frozen pre-LN blocks on a bf16 residual stream) ----
 // LN(x) W^T + b = rstd (x (W gamma)^T - mean c) + (b + W beta),  c_n = sum_k (W gamma)[n, k]: the consuming GEMM reads the raw
@@ -696,15 +692,11 @@ static hipError_t run_gemm(const GemmP& p, int cfg, hipStream_t s) {
 // 256x256 tiles): the host code runs the rows vl_gemm_main_rows() reports through these entries and the leftover rows
 // through vl_layernorm_fwd + vl_gemm_bf16.
 extern "C" int vl_gemm_main_rows(int M, int N) {
-  const int G = num_cus() & ~7;
-  if (M <= 0 || N <= 0 || (N & 255)) return 0;
-  const int tiles_n = N / 256, full_m = M / 256;
-  if ((long)full_m * tiles_n < (G * 3) / 4) return 0;
-  const int step = G / gcd_i(G, tiles_n);
-  int main_m = (full_m / step) * step;
-  if (main_m == 0) main_m = full_m;
-  return main_m * 256;
+  if (M <= 0 || N <= 0) return 0;
+  return (N & 255) ? 0 : gemm_main_rows(M, N, num_cus() & ~7);
 }
+// the kernel run_gemm gives `rows` leftover rows of width N: what a caller that splits the rows itself passes as cfg
+extern "C" int vl_gemm_rest_cfg(int rows, int N) { return gemm_rest_cfg(rows, N); }
 
 extern "C" int vl_gemm_lnfold_bf16(const void* A, const void* Wg, const float* bias_f, const float* ln_c, const float* ln_mean,
                                    const float* ln_rstd, void* out, void* out2, int M, int N, int K, int lda, int ldw, int ldo,
@@ -715,30 +707,20 @@ extern "C" int vl_gemm_lnfold_bf16(const void* A, const void* Wg, const float* b
   VL_CHECK_ARG((act == VL_ACT_GELU_DSAVE || act == VL_ACT_QGELU_DSAVE) == (out2 != nullptr),
                "vl_gemm_lnfold_bf16: out2 goes with VL_ACT_GELU_DSAVE / VL_ACT_QGELU_DSAVE");
   VL_CHECK_ARG((((uintptr_t)ln_c | (uintptr_t)bias_f) & 15) == 0, "vl_gemm_lnfold_bf16: column vectors must be 16-byte aligned");
-  GemmP p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)Wg; p.bias = bias_f; p.out = out; p.out2 = out2;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = 1.0f; p.act = act; p.res_div = 1;
+  GemmP p = gemm_params(A, Wg, bias_f, out, nullptr, out2, M, N, K, lda, ldw, ldo, 1.0f, act, 1);
   p.ln_mean = ln_mean; p.ln_rstd = ln_rstd; p.ln_c = ln_c;
-  const GemmP& q = p;
-  VL_CHECK_ARG(vl_gemm_park_supported(EPI_BF16, &q), "vl_gemm_lnfold_bf16: whole 256x256 tiles, K >= 512, 16-byte aligned operands required");
-  const hipError_t e = (hipError_t)vl_gemm_park_launch(EPI_BF16, &q, num_cus(), stream);
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  VL_CHECK_ARG(vl_gemm_park_supported(EPI_BF16, &p), "vl_gemm_lnfold_bf16: whole 256x256 tiles, K >= 512, 16-byte aligned operands required");
+  return status((hipError_t)vl_gemm_park_launch(EPI_BF16, &p, num_cus(), stream));
 }
 
 extern "C" int vl_gemm_res_rowstats_bf16(const void* A, const void* W, const float* bias, void* out, const void* res,
                                          float* row_part, int M, int N, int K, int lda, int ldw, int ldo, hipStream_t stream) {
   VL_CHECK_ARG(A && W && out && res && row_part, "vl_gemm_res_rowstats_bf16: null operand");
   VL_CHECK_ARG((((uintptr_t)row_part) & 7) == 0, "vl_gemm_res_rowstats_bf16: row_part must be 8-byte aligned");
-  GemmP p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = 1.0f; p.res_div = 1;
+  GemmP p = gemm_params(A, W, bias, out, res, nullptr, M, N, K, lda, ldw, ldo, 1.0f, VL_ACT_NONE, 1);
   p.row_part = row_part;
-  const GemmP& q = p;
-  VL_CHECK_ARG(vl_gemm_park_supported(EPI_RES_BF16, &q), "vl_gemm_res_rowstats_bf16: whole 256x256 tiles, K >= 512, 16-byte aligned operands required");
-  const hipError_t e = (hipError_t)vl_gemm_park_launch(EPI_RES_BF16, &q, num_cus(), stream);
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  VL_CHECK_ARG(vl_gemm_park_supported(EPI_RES_BF16, &p), "vl_gemm_res_rowstats_bf16: whole 256x256 tiles, K >= 512, 16-byte aligned operands required");
+  return status((hipError_t)vl_gemm_park_launch(EPI_RES_BF16, &p, num_cus(), stream));
 }
 
 extern "C" int vl_gemm_bf16_ex(const void* A, const void* W, const float* bias, void* out, const void* res, void* out2,
@@ -760,9 +742,7 @@ extern "C" int vl_gemm_bf16_ex(const void* A, const void* W, const float* bias, 
   VL_CHECK_ARG((N & 3) == 0, "vl_gemm_bf16: N must be a multiple of 4");
   VL_CHECK_ARG((lda & 7) == 0 && (ldw & 7) == 0, "vl_gemm_bf16: lda/ldw must be multiples of 8");
   VL_CHECK_ARG((ldo & 3) == 0, "vl_gemm_bf16: ldo must be a multiple of 4");
-  GemmP p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res; p.out2 = out2;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = alpha; p.act = act; p.res_div = res_div;
+  GemmP p = gemm_params(A, W, bias, out, res, out2, M, N, K, lda, ldw, ldo, alpha, act, res_div);
   // QuickGELU (VL_ACT_QGELU, VL_ACT_QGELU_DSAVE): the activation of a VL_EPI_BF16 output, or - the _DSAVE code - the saved
   // derivative of VL_EPI_DGELU.  Every other epilogue, the recompute form of VL_EPI_DGELU and the store-the-pre-activation
   // form (VL_ACT_GELU + out2) are exact-erf only.
@@ -787,8 +767,7 @@ extern "C" int vl_gemm_bf16_ex(const void* A, const void* W, const float* bias, 
     case VL_EPI_DGEGLU: VL_CHECK_ARG(res, "vl_gemm_bf16: pre-activation tensor missing"); VL_CHECK_ARG((ldo & 7) == 0, "vl_gemm_bf16: DGEGLU needs ldo % 8 == 0"); e = run_gemm<EPI_DGEGLU>(p, cfg, stream); break;
     default: return vl_set_error("vl_gemm_bf16: unknown epilogue");
   }
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  return status(e);
 }
 
 // IEEE-half operands on the persistent 256x256 kernel (frozen text tower).  No other kernel family carries the type: the caller
@@ -799,14 +778,11 @@ extern "C" int vl_gemm_f16(const void* A, const void* W, const float* bias, void
   VL_CHECK_ARG(epi == VL_EPI_BF16 || epi == VL_EPI_RES_F32, "vl_gemm_f16: VL_EPI_BF16 (16-bit output, here fp16) or VL_EPI_RES_F32");
   VL_CHECK_ARG(epi != VL_EPI_RES_F32 || (res && act == VL_ACT_NONE), "vl_gemm_f16: VL_EPI_RES_F32 needs res and takes no activation");
   VL_CHECK_ARG(act == VL_ACT_NONE || act == VL_ACT_GELU || act == VL_ACT_QGELU, "vl_gemm_f16: act must be none, GELU or QGELU");
-  GemmP p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = bias; p.out = out; p.res = res;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = ldo; p.alpha = alpha; p.act = act; p.res_div = 1; p.f16 = 1;
+  GemmP p = gemm_params(A, W, bias, out, res, nullptr, M, N, K, lda, ldw, ldo, alpha, act, 1);
+  p.f16 = 1;
   const int e_ = epi == VL_EPI_BF16 ? (int)EPI_BF16 : (int)EPI_RES_F32;
   VL_CHECK_ARG(vl_gemm_park_supported(e_, &p), "vl_gemm_f16: whole 256x256 tiles (M % 256 == N % 256 == 0), K % 64 == 0, K >= 512, 16-byte aligned operands required");
-  const hipError_t e = (hipError_t)vl_gemm_park_launch(e_, &p, num_cus(), stream);
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  return status((hipError_t)vl_gemm_park_launch(e_, &p, num_cus(), stream));
 }
 
 // vl_gemm_tn.hip: token-major operands (At [K, M], Bt [K, N]) through the LDS transpose read
@@ -825,16 +801,11 @@ extern "C" int vl_gemm_tn_splitk_accum_f32(const void* At, const void* Bt, float
   const int nk = K >> 6;
   const int len = (nk + splits - 1) / splits, eff = (nk + len - 1) / len;      // slices of `len` 64-token steps; the last one may be shorter
   VL_CHECK_ARG(len >= 4 && nk - (eff - 1) * len >= 4, "vl_gemm_tn_splitk: every K slice needs >= 4 steps of 64");
-  GemmP p{};
-  p.A = (const bf16_t*)At; p.W = (const bf16_t*)Bt; p.out = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldb; p.ldo = N;
-  p.alpha = alpha; p.res_div = 1; p.split_stride = (long)M * N; p.ksplit_len = len;
+  GemmP p = gemm_params(At, Bt, nullptr, ws, nullptr, nullptr, M, N, K, lda, ldb, N, alpha, VL_ACT_NONE, 1);
+  p.split_stride = (long)M * N; p.ksplit_len = len;
   VL_CHECK_ARG(vl_gemm_tn_supported(&p), "vl_gemm_tn_splitk: operands must be 16-byte aligned and a slice below 2 GB");
-  hipError_t e = (hipError_t)vl_gemm_tn_launch(&p, num_cus(), stream);
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)M * (N >> 2) + 255) / 256)), dim3(256), 0, stream, ws, eff, M, N, out, ldo);
-  e = hipGetLastError();
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  const hipError_t e = (hipError_t)vl_gemm_tn_launch(&p, num_cus(), stream);
+  return status(e != hipSuccess ? e : launch_splitk_reduce(ws, eff, M, N, out, ldo, stream));
 }
 
 // out[M,N] (f32, row stride ldo) += alpha * A[M,K] . W[N,K]^T with the K range cut into `splits` slices computed by
@@ -846,34 +817,24 @@ extern "C" int vl_gemm_splitk_accum_f32(const void* A, const void* W, float* out
                "vl_gemm_splitk: K % 64, N % 4, lda/ldw % 8, ldo % 4 required");
   VL_CHECK_ARG(splits >= 1 && splits <= 1024 && ws, "vl_gemm_splitk: 1 <= splits <= 1024 and a workspace of splits*M*N floats");
   const int nk = K >> 6;
-  GemmP p{};
-  p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.out = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldo = N;
-  p.alpha = alpha; p.res_div = 1;
+  GemmP p = gemm_params(A, W, nullptr, ws, nullptr, nullptr, M, N, K, lda, ldw, N, alpha, VL_ACT_NONE, 1);
   p.split_stride = (long)M * N;
   if (nk % splits == 0) {       // whole 256x256 tiles and equal slices: the persistent kernels write the partials
     p.ksplit_len = nk / splits;
     if (vl_gemm_park_supported(EPI_F32, &p)) {
-      hipError_t e = (hipError_t)vl_gemm_park_launch(EPI_F32, &p, num_cus(), stream);
-      if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)M * (N >> 2) + 255) / 256)), dim3(256), 0, stream, ws, splits, M, N, out, ldo);
-      e = hipGetLastError();
-      if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-      return 0;
+      const hipError_t e = (hipError_t)vl_gemm_park_launch(EPI_F32, &p, num_cus(), stream);
+      return status(e != hipSuccess ? e : launch_splitk_reduce(ws, splits, M, N, out, ldo, stream));
     }
   }
   p.ksplit_len = (nk + splits - 1) / splits;
   const int eff = (nk + p.ksplit_len - 1) / p.ksplit_len;
-  p.split_stride = (long)M * N;
   using S = Smem<128, 128>;
   auto kern = gemm_nt_kernel<128, 128, 2, 2, EPI_F32, true>;
   constexpr int smem = 2 * S::STAGE;
   static const hipError_t attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if (attr != hipSuccess) return vl_set_error(hipGetErrorString(attr));
+  if (attr != hipSuccess) return status(attr);
   const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
   hipLaunchKernelGGL(kern, dim3(tiles, eff), dim3(256), smem, stream, p);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)M * (N >> 2) + 255) / 256)), dim3(256), 0, stream, ws, eff, M, N, out, ldo);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vl_set_error(hipGetErrorString(e));
-  return 0;
+  return status(launch_splitk_reduce(ws, eff, M, N, out, ldo, stream));
 }
 

@@ -41,6 +41,7 @@ SIGNATURES = {
     "vl_attn_fwd_varlen_f16": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
     "vl_layernorm_fwd": [P, I, L, P, L, P, P, P, I, L, P, P, I, I, F, P],
     "vl_gemm_main_rows": [I, I],
+    "vl_gemm_rest_cfg": [I, I],
     "vl_gemm_lnfold_bf16": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "vl_gemm_res_rowstats_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "vl_ln_row_stats": [P, I, P, L, I, I, I, F, P, P, P, P, P, L, I, P],

@@ -55,36 +55,45 @@ def _chk2d(t, name, dtype=None):
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
+def _gemm_operands(who, a, w, in_dtype, out, out_dtype, res, bias, out_cols=(1, 1), res_div=None, strict=True):
+    """The one operand check of gemm, gemm_f16, gemm_f32 and gemm_f32_ex: a [M,K] and w [N,K] row-major of in_dtype; out row-major
+    (None: allocated here, [M, N * out_cols[0] // out_cols[1]] of out_dtype); res row-major with out's row stride and, where res_div
+    is given, a row for every res_div rows of out; bias f32 [N].  strict: out has to be of out_dtype and res f32 (TypeError);
+    otherwise - gemm, whose epilogue decides both - res has to be of out's dtype.  Returns (M, N, K, out)."""
+    _chk2d(a, f"{who}: a", in_dtype); _chk2d(w, f"{who}: w", in_dtype)
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"{who}: K mismatch {a.shape} vs {w.shape}")
+    if out is None:
+        out = torch.empty(M, N * out_cols[0] // out_cols[1], device=a.device, dtype=out_dtype)
+    _chk2d(out, f"{who}: out", out_dtype if strict else None)
+    if res is not None:
+        _chk2d(res, f"{who}: res", torch.float32 if strict else None)
+        if res.stride(0) != out.stride(0) or (not strict and res.dtype != out.dtype):
+            raise ValueError(f"{who}: residual must share out's row stride" + ("" if strict else " and dtype"))
+        if res_div is not None and res.shape[0] * res_div < M:
+            raise ValueError(f"{who}: residual has too few rows (one for every {res_div} rows of out)")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
+        raise ValueError(f"{who}: bias must be f32 [N]")
+    return M, N, K, out
+
+
 def gemm(a, w, bias=None, out=None, res=None, epi=EPI_BF16, act=ACT_NONE, alpha=1.0, cfg=-1, out2=None, res_div=1):
     """out = epilogue(a @ w.T).  a [M,K] bf16, w [N,K] bf16.  out2: optional pre-activation copy (bf16; with
     act=ACT_GELU_DSAVE / ACT_QGELU_DSAVE: the activation's derivative at pre instead, the operand of the backward's EPI_DGELU
     launched with the same act)."""
     if act in (ACT_GELU_DSAVE, ACT_QGELU_DSAVE) and epi == EPI_BF16 and out2 is None:
         raise ValueError("gemm: ACT_GELU_DSAVE / ACT_QGELU_DSAVE need out2")
-    _chk2d(a, "a", torch.bfloat16); _chk2d(w, "w", torch.bfloat16)
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K:
-        raise ValueError(f"gemm: K mismatch {a.shape} vs {w.shape}")
+    M, N, K, out = _gemm_operands("gemm", a, w, torch.bfloat16, out, torch.float32 if epi in (EPI_F32, EPI_RES_F32) else torch.bfloat16,
+                                  res, bias, out_cols=(1, 2) if epi == EPI_GEGLU else ((2, 1) if epi == EPI_DGEGLU else (1, 1)),
+                                  res_div=res_div if res_div > 1 else None, strict=False)
+    if out2 is not None and (out2.stride(0) != out.stride(0) * (2 if epi == EPI_GEGLU else 1) or out2.dtype != torch.bfloat16):
+        raise ValueError("gemm: out2 must be bf16 with out's row stride (twice that for GEGLU)")
     if K % 64:   # kernels stream 64-wide K slabs: zero-pad odd reduction lengths (toy configs only)
         Kp = (K + 63) // 64 * 64
         a = torch.nn.functional.pad(a, (0, Kp - K)); w = torch.nn.functional.pad(w, (0, Kp - K))
         K = Kp
-    if out is None:
-        n_out = N // 2 if epi == EPI_GEGLU else (2 * N if epi == EPI_DGEGLU else N)
-        odt = torch.float32 if epi in (EPI_F32, EPI_RES_F32) else torch.bfloat16
-        out = torch.empty(M, n_out, device=a.device, dtype=odt)
-    _chk2d(out, "out")
-    if res is not None:
-        _chk2d(res, "res")
-        if res.stride(0) != out.stride(0) or res.dtype != out.dtype:
-            raise ValueError("gemm: residual must share out's row stride and dtype")
-        if res_div > 1 and res.shape[0] * res_div < M:
-            raise ValueError("gemm: broadcast residual has too few rows")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
-        raise ValueError("gemm: bias must be f32 [N]")
-    if out2 is not None and (out2.stride(0) != out.stride(0) * (2 if epi == EPI_GEGLU else 1) or out2.dtype != torch.bfloat16):
-        raise ValueError("gemm: out2 must be bf16 with out's row stride (twice that for GEGLU)")
     check(_lib.vl_gemm_bf16_ex(_p(a), _p(w), _p(bias), _p(out), _p(res), _p(out2), M, N, K, a.stride(0), w.stride(0),
                                out.stride(0), float(alpha), epi, act, res_div, cfg, _stream()))
     return out
@@ -94,20 +103,7 @@ def gemm_f16(a, w, bias=None, out=None, res=None, epi=EPI_BF16, act=ACT_NONE, al
     """The persistent 256x256 GEMM on IEEE-half operands (vl_gemm_f16; the frozen text tower): a [M,K], w [N,K] fp16;
     epi = EPI_BF16 -> out fp16 [M,N] = act(a @ w.T + bias), epi = EPI_RES_F32 -> out f32 = res + a @ w.T + bias (in place
     allowed).  M, N multiples of 256, K a multiple of 64 and >= 512: the caller pads (TextEngine keeps whole row tiles)."""
-    _chk2d(a, "a", torch.float16); _chk2d(w, "w", torch.float16)
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K:
-        raise ValueError(f"gemm_f16: K mismatch {a.shape} vs {w.shape}")
-    if out is None:
-        out = torch.empty(M, N, device=a.device, dtype=torch.float32 if epi == EPI_RES_F32 else torch.float16)
-    _chk2d(out, "out", torch.float32 if epi == EPI_RES_F32 else torch.float16)
-    if res is not None:
-        _chk2d(res, "res", torch.float32)
-        if res.stride(0) != out.stride(0):
-            raise ValueError("gemm_f16: residual must share out's row stride")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
-        raise ValueError("gemm_f16: bias must be f32 [N]")
+    M, N, K, out = _gemm_operands("gemm_f16", a, w, torch.float16, out, torch.float32 if epi == EPI_RES_F32 else torch.float16, res, bias)
     check(_lib.vl_gemm_f16(_p(a), _p(w), _p(bias), _p(out), _p(res), M, N, K, a.stride(0), w.stride(0), out.stride(0),
                            float(alpha), epi, act, _stream()))
     return out
@@ -116,20 +112,7 @@ def gemm_f16(a, w, bias=None, out=None, res=None, epi=EPI_BF16, act=ACT_NONE, al
 # ---- true fp32 arithmetic (inference under precision="fp32": vitlens_hip/f32.py) ----
 def gemm_f32(a, w, bias=None, out=None, res=None, act=ACT_NONE, alpha=1.0):
     """out f32 = act(alpha * a @ w.T + bias) (+ res), a [M,K], w [N,K] f32, any M and N, K % 4 == 0 (vl_gemm_f32: fp32-input MFMA)."""
-    _chk2d(a, "a", torch.float32); _chk2d(w, "w", torch.float32)
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K:
-        raise ValueError(f"gemm_f32: K mismatch {a.shape} vs {w.shape}")
-    if out is None:
-        out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    _chk2d(out, "out", torch.float32)
-    if res is not None:
-        _chk2d(res, "res", torch.float32)
-        if res.stride(0) != out.stride(0):
-            raise ValueError("gemm_f32: residual must share out's row stride")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
-        raise ValueError("gemm_f32: bias must be f32 [N]")
+    M, N, K, out = _gemm_operands("gemm_f32", a, w, torch.float32, out, torch.float32, res, bias)
     check(_lib.vl_gemm_f32(_p(a), _p(w), _p(bias), _p(out), _p(res), M, N, K, a.stride(0), w.stride(0), out.stride(0),
                            float(alpha), act, _stream()))
     return out
@@ -157,22 +140,8 @@ def gemm_f32_ex(a, w, bias=None, out=None, res=None, act=ACT_NONE, alpha=1.0, re
     """vl_gemm_f32_ex: gemm_f32 with the epilogues of the fp32 Lenses.  res_pre: out = act(alpha a @ w.T + bias + res[m // res_div])
     (res [ceil(M / res_div), N] with out's row stride).  geglu: w rows interleaved (a_j, gate_j) -> out f32 [M, N/2] =
     a * gelu(gate); no residual.  With the defaults this is gemm_f32 (the library routes it to the same kernel)."""
-    _chk2d(a, "a", torch.float32); _chk2d(w, "w", torch.float32)
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K:
-        raise ValueError(f"gemm_f32_ex: K mismatch {a.shape} vs {w.shape}")
-    if out is None:
-        out = torch.empty(M, N // 2 if geglu else N, device=a.device, dtype=torch.float32)
-    _chk2d(out, "out", torch.float32)
-    if res is not None:
-        _chk2d(res, "res", torch.float32)
-        if res.stride(0) != out.stride(0):
-            raise ValueError("gemm_f32_ex: residual must share out's row stride")
-        if res.shape[0] * res_div < M:
-            raise ValueError("gemm_f32_ex: residual has too few rows")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N):
-        raise ValueError("gemm_f32_ex: bias must be f32 [N]")
+    M, N, K, out = _gemm_operands("gemm_f32_ex", a, w, torch.float32, out, torch.float32, res, bias,
+                                  out_cols=(1, 2) if geglu else (1, 1), res_div=res_div)
     check(_lib.vl_gemm_f32_ex(_p(a), _p(w), _p(bias), _p(out), _p(res), M, N, K, a.stride(0), w.stride(0), out.stride(0),
                               float(alpha), act, int(res_div), 1 if res_pre else 0, 1 if geglu else 0, _stream()))
     return out
@@ -212,11 +181,15 @@ def _fold_rows(x, out, N, K):
 
 
 def _leftover_cfg(rows, N, cfg):
-    """Kernel of the leftover rows of a row-split GEMM, as vl_gemm.hip's run_gemm picks it (64x64 LDS-DMA tiles when they fill
-    most of the chip, else the split-K tail kernel); a standalone call of that size would get 128x128 tiles and a serial K."""
+    """cfg of the leftover rows of a GEMM whose rows the caller split: the kernel run_gemm (csrc/vl_gemm.hip) gives such rows, from
+    the library itself (vl_gemm_rest_cfg; a standalone call of that size would get 128x128 tiles and a serial K)."""
+    # THE ONE DIFFERENCE from run_gemm: above 512 leftover rows run_gemm launches 128x128 tiles (vl_gemm_rest_cfg says 1), while this
+    # split passes cfg -1 on, so the leftover rows re-enter the auto dispatch as a problem of their own - which can pick the persistent
+    # kernel again with an uneven round (N = 1024: 56 leftover row tiles x 4 = 224 tiles >= 192).  Neither choice has been measured
+    # against the other; both are kept as they were (DESIGN.md 7.13).
     if cfg >= 0 or rows > 512:
         return cfg
-    return 11 if ((rows + 63) // 64) * ((N + 63) // 64) >= 192 else 9
+    return int(load_library().vl_gemm_rest_cfg(rows, N))      # a pure host function: the library's own, also where `_lib` is a recorder
 
 
 def gemm_lnfold(x, fold, mean, rstd, out, w, b, ln_w, ln_b, h_ws, act=ACT_NONE, out2=None, eps=1e-5, cfg=-1, h_ready=False):
