@@ -607,6 +607,40 @@ int vl_image_crop_resize_u8(const void* records, int n, int S, int max_nrows, co
                             hipStream_t stream);
 int vl_image_augment(const void* records, int n, int S, int max_nrows, int max_ops, const void* tables, uint8_t* tmp,
                      uint8_t* work, const float* mean, const float* stdv, float* out, uint8_t* out_u8, hipStream_t stream);
+/* The training transform of the tactile recipe (csrc/vl_tactile_augment.hip), one call per batch of n RGB images of any sizes:
+ * ToTensor + RandomResizedCrop(S, bilinear) + RandomHorizontalFlip + RandomVerticalFlip + RandomRotation(nearest, fill 0) +
+ * Normalize, all on the float tensor (modal_tactile/processors/tact_processor.py:189-233).  out [n,3,S,S] f32.  Every random
+ * scalar is drawn by the host and arrives in the sample's record.
+ * records: DEVICE array of one 96-byte record per sample, 24 little-endian 32-bit words:
+ *     words  0 ..  1   uint64 src          device pointer, uint8 [H,W,3]
+ *     word   2         int32 stride        bytes per row of src
+ *     words  3 ..  4   int32 H, W
+ *     words  5 ..  8   int32 top, left, bh, bw     the crop box, inside the image
+ *     words  9 .. 10   int32 row0, nrows   the rows of the box, counted from top, that the vertical taps touch
+ *     words 11 .. 13   int32 hb, hw, hks   horizontal table (bw -> S): offsets of its bounds [S,2] int32 and weights [S,hks]
+ *                                          f32 in `tables`, counted in 32-bit words, and the taps per row
+ *     words 14 .. 16   int32 vb, vw, vks   the same for the vertical table (bh -> S)
+ *     word  17         int32 flags         bit 0 horizontal flip, bit 1 vertical flip
+ *     words 18 .. 19   int64 tmp           offset of the sample's [nrows,S] intermediate in `tmp`, counted in float4
+ *     words 20 .. 23   float t00, t01, t10, t11    the rotation: entries 0, 1, 3, 4 of torchvision's inverse affine matrix for
+ *                                          -angle about the centre, rounded to float32 and divided in float32 by
+ *                                          float32(0.5 S) (its rescaled theta; entries 2 and 5 are 0)
+ * Taps are relative to the box and clamped into it; tables: the packed per-axis tables of the distinct (edge -> S) pairs;
+ * tmp: sum of nrows * S float4, 16-byte aligned; max_nrows: the largest nrows; mean / stdv: HOST arrays of 3 floats.  Per
+ * output pixel (x, y), in float32 with every operation rounded on its own: xb = x - S/2 + 0.5, yb likewise, gx = xb t00 +
+ * yb t01, gy = xb t10 + yb t11, ix = ((gx + 1) S - 1) / 2, iy likewise, sx = rint(ix), sy = rint(iy) (half to even).  With sx
+ * or sy outside [0, S) the pixel is (0 - mean[c]) / stdv[c].  Otherwise it is pixel (row sy or, vertically flipped, S-1-sy;
+ * column sx or, horizontally flipped, S-1-sx) of the box resized to S x S, (v - mean[c]) / stdv[c]; that value has the same
+ * bits whichever output pixel takes it.  A sample's result does not depend on its place in the batch.
+ * Refused with a status, nothing launched: n outside [1, 65535], S outside [1, 4096], max_nrows < 1, a null operand, records
+ * not 8-byte or tmp not 16-byte aligned, a zero stdv.  The records live in device memory: their contents are checked where
+ * they are packed on the host (vitlens_hip.ops.tactile_augment_pack); in the kernels a row or column outside the image is
+ * clamped into it.  Stream-ordered, two launches, no global state, no host synchronisation.
+ * NOTE on the version: like vl_pc_augment, this entry was added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before it reports the same number and lacks the symbol, and a client must look it up when it loads
+ * the library (vitlens_hip/_lib.py does, and names such a library as stale).  No existing entry changes. */
+int vl_tactile_augment(const void* records, int n, int S, int max_nrows, const void* tables, float* tmp, const float* mean,
+                       const float* stdv, float* out, hipStream_t stream);
 /* ---- evaluation-time image / depth preprocessing (csrc/vl_preproc.hip) ----
  * Separable bicubic resampling restricted to a crop window, tables built by the host (vitlens_hip/preproc.py):
  * bounds [n_out,2] int32 = (first tap, tap count) and coefficients [n_out,ksize] per OUTPUT index of the full resized

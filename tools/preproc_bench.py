@@ -8,7 +8,8 @@ one thread.  Prints one JSON object; `python tools/preproc_bench.py > gpurun_out
 # reference's five passes on the host's cores); `--rgbd-train-only` the row of the depth training transform alone
 # (RGBD_Processor_Train against the torch restatement of the reference's pipeline on the host's cores); `--image-train-only`
 # the row of the plain-image training transform alone (Image_Processor_Train against the same draws applied with Pillow on one
-# host thread)
+# host thread); `--tactile-train-only` the row of the tactile training transform alone (Tactile_Processor_Train against the torch
+# restatement of the same draws on one host thread)
 import json
 import os
 import sys
@@ -170,7 +171,63 @@ def image_train_row(B=1024, H=480, W=640, distinct=64):
     return row
 
 
+def tactile_train_row(B=1024, H=480, W=640, distinct=64):
+    """Tactile_Processor_Train.batch at B samples of H x W (`distinct` different sources, each used B / distinct times): the
+    two launches alone, `batch` as a whole with resident and with host sources, the host's share (draws, planning), and the
+    same draws through the torch restatement on one host thread (tests/tactile_augment_ref.py), the yardstick.
+    The gather of the second launch is priced by running the same boxes with angle 0 and no flips (every load coalesced, every
+    pixel computed: the work of a vertical pass that materialises the resized image) and by a plain device copy of the output
+    (read + write of [B,3,S,S] f32: the least a separate gather launch could cost)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tactile_augment_ref as T
+    from open_clip.modal_tactile.processors.tact_processor import Tactile_Processor_Train
+    src = [T.source(H, W, 300 + i) for i in range(distinct)]
+    images = [src[i % distinct] for i in range(B)]
+    dev = [a.cuda() for a in src]
+    images_d = [dev[i % distinct] for i in range(B)]
+    proc = Tactile_Processor_Train.from_config()
+    row = {"n": B, "in": [H, W], "size": proc.size, "source_mb_per_batch": round(B * H * W * 3 / 1e6, 1)}
+    torch.manual_seed(0)
+    t0 = time.perf_counter(); draws = [proc.draw(H, W) for _ in range(B)]
+    row["host_draws_ms_per_batch"] = round((time.perf_counter() - t0) * 1e3, 2)
+    plan_of = lambda ims, dr=draws: preproc.plan_tactile_train(ims, dr, proc.size, proc.mean, proc.std, antialias=proc.antialias)
+    plan = plan_of(images_d)
+    row["intermediate_mb"] = round(plan.tmp.numel() * 4 / 1e6, 1)
+    row["fill_share"] = round(float(np.mean([(T.index_map(proc.size, d["angle"]) < 0).mean() for d in draws[:64]])), 4)
+    out = torch.empty(B, 3, proc.size, proc.size, device="cuda")
+    s = min(gpu_time(lambda: plan.launch(out=out), n_warm=2) for _ in range(5))
+    row["gpu_kernels_ms_per_batch"] = round(s * 1e3, 3)                              # the two launches, sources resident
+    still = plan_of(images_d, [dict(d, flip_h=False, flip_v=False, angle=0.0) for d in draws])
+    s = min(gpu_time(lambda: still.launch(out=out), n_warm=2) for _ in range(5))
+    row["gpu_kernels_ms_per_batch_angle0_no_flips"] = round(s * 1e3, 3)              # same boxes, the gather is the identity
+    other = torch.empty_like(out)
+    s = min(gpu_time(lambda: other.copy_(out), n_warm=2) for _ in range(5))
+    row["device_copy_of_output_ms"] = round(s * 1e3, 3)                              # floor of a third (gather) launch
+    del still, other
+
+    def timed(fn):
+        fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) * 1e3, 2)
+    row["host_plan_ms_resident_sources"] = timed(lambda: plan_of(images_d))          # records, tables, one upload
+    row["host_plan_ms_host_sources"] = timed(lambda: plan_of(images))                # + packing and upload of the image bytes
+    row["gpu_batch_ms_resident_sources"] = timed(lambda: proc.batch(images_d))       # draws, planning, launches
+    row["gpu_batch_ms_host_sources"] = timed(lambda: proc.batch(images))
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    n_cpu = min(B, 64)
+    t0 = time.perf_counter()
+    for b in range(n_cpu):
+        T.apply(images[b], draws[b], proc.size, proc.mean, proc.std, proc.antialias, torch.float32)
+    row["cpu_1thread_ms_per_batch"] = round((time.perf_counter() - t0) / n_cpu * B * 1e3, 1)
+    torch.set_num_threads(nt)
+    return row
+
+
 def main():
+    if "--tactile-train-only" in sys.argv[1:]:
+        print(json.dumps({"tactile_train": tactile_train_row()}))
+        return
     if "--image-train-only" in sys.argv[1:]:
         print(json.dumps({"image_train": image_train_row()}))
         return
@@ -259,6 +316,7 @@ def main():
     res["pc_train"] = pc_train_row()
     res["rgbd_train"] = rgbd_train_row()
     res["image_train"] = image_train_row()
+    res["tactile_train"] = tactile_train_row()
     print(json.dumps(res))
 
 

@@ -5,7 +5,9 @@ modal_depth/processors/vt_processor.py for the `antialias` default), so the thre
 resampler of csrc/vl_preproc.hip with ToTensor's /255 fused into the read.  Same class name and call convention as the
 reference (a file path; a PIL image or an [H, W, 3] uint8 array is accepted too); result [3, 224, 224] float32 on the GPU.
 `Image_Processor_Train` (reference :92-138) is the training transform of the paired image: its RandAugment runs on the 8-bit
-image, one Pillow call per op, and is reproduced byte for byte by csrc/vl_image_augment.hip."""
+image, one Pillow call per op, and is reproduced byte for byte by csrc/vl_image_augment.hip.  `Tactile_Processor_Train`
+(reference :189-233) is the training transform of the tactile image itself, all of it on the float tensor
+(csrc/vl_tactile_augment.hip), and `Tactile_Processor_Eval` (:236-278) the reference's other name for the evaluation transform."""
 import numpy as np
 import torch
 
@@ -51,6 +53,87 @@ class TactileRGBProcessorEval(BaseProcessor):
                                              antialias=self.antialias, out=out)
 
 
+tactile_transform_conf = {}
+
+
+def _processor_config(cls, cfg, default_args):
+    """The reference's from_config: `update_conf` is taken out of a copy of the mapping, `params` are the args."""
+    cfg = dict(cfg or {})
+    update_conf = cfg.pop("update_conf", None)
+    return cls(args=cfg.get("params", default_args), img_mean=cfg.get("img_mean", OPENAI_CLIP_MEAN),
+               img_std=cfg.get("img_std", OPENAI_CLIP_STD), update_conf=update_conf)
+
+
+class Tactile_Processor_Eval(TactileRGBProcessorEval):
+    """The reference's other name for the evaluation transform (:236-278): the arithmetic of `TactileRGBProcessorEval` behind
+    the `(args, img_mean, img_std, update_conf)` signature of the reference's training-recipe classes.  The reference's
+    `args` hold nothing this transform reads (`tactile_transform_conf` is empty)."""
+
+    def __init__(self, args=None, img_mean=None, img_std=None, update_conf=None, device="cuda", *, resize=256, size=224,
+                 antialias=True):
+        super().__init__(img_mean=img_mean, img_std=img_std, resize=resize, size=size, antialias=antialias, device=device)
+        self.conf = dict(args or {}, **(update_conf or {}))
+
+    @classmethod
+    def from_config(cls, cfg=None):
+        return _processor_config(cls, cfg, tactile_transform_conf)
+
+
+class Tactile_Processor_Train(BaseProcessor):
+    """The tactile image of a training sample ON THE GPU (reference :189-233): ToTensor -> RandomResizedCrop(224, bilinear) ->
+    RandomHorizontalFlip -> RandomVerticalFlip -> RandomRotation((0, 360), nearest, fill 0) -> Normalize, every stage on the
+    float tensor (csrc/vl_tactile_augment.hip).
+
+    proc(img) -> [3, size, size] f32 on the GPU for a path, a PIL image or an [H, W, 3] uint8 array; `batch` for a list.  Every
+    random scalar is drawn on the host from torch's global CPU generator (`draw`), in the order of the reference's pipeline.
+    `antialias`: F.interpolate's flag for the crop's resize (see modal_depth/processors/vt_processor.py for the default).
+    The reference's `args` hold nothing this transform reads; they are kept as `conf`."""
+
+    SCALE, RATIO = (0.08, 1.0), (3.0 / 4.0, 4.0 / 3.0)                       # RandomResizedCrop's defaults
+
+    def __init__(self, args=None, img_mean=None, img_std=None, update_conf=None, device="cuda", *, size=224, antialias=True,
+                 degrees=(0.0, 360.0)):
+        self.mean = list(img_mean if img_mean is not None else OPENAI_CLIP_MEAN)
+        self.std = list(img_std if img_std is not None else OPENAI_CLIP_STD)
+        self.conf = dict(args or {}, **(update_conf or {}))
+        self.degrees = (float(degrees[0]), float(degrees[1]))
+        if not self.degrees[0] <= self.degrees[1]:
+            raise ValueError(f"degrees must be (min, max), got {degrees}")
+        self.size, self.antialias, self.device = int(size), bool(antialias), torch.device(device)
+
+    @classmethod
+    def from_config(cls, cfg=None):
+        return _processor_config(cls, cfg, tactile_transform_conf)
+
+    def draw(self, H, W):
+        """One sample's scalars for an H x W source, from torch's global CPU generator in the order of the reference's
+        pipeline: the crop box (ten attempts, then the central fallback), the horizontal flip, the vertical flip, the angle."""
+        from open_clip.transform import random_resized_crop_params
+        return {"box": random_resized_crop_params(H, W, self.SCALE, self.RATIO), "flip_h": bool(torch.rand(1) < 0.5),
+                "flip_v": bool(torch.rand(1) < 0.5), "angle": float(torch.empty(1).uniform_(self.degrees[0], self.degrees[1]))}
+
+    def batch(self, images, draws=None):
+        """images: a list of paths / PIL images / uint8 [H, W, 3] arrays or tensors, sizes free per sample -> [B, 3, size, size]
+        f32 on the GPU.  The draws are made sample by sample in order (or given: `draws`, one `draw()` result per sample, so
+        that a loader worker can draw ahead); host data goes up as one packed copy and the two kernels are launched once for
+        the batch."""
+        from vitlens_hip import preproc
+        ims = [image_u8(im) for im in images]
+        if draws is None:
+            draws = [self.draw(im.shape[0], im.shape[1]) for im in ims]
+        return preproc.plan_tactile_train(ims, draws, self.size, self.mean, self.std, antialias=self.antialias,
+                                          device=self.device).launch()
+
+    def __call__(self, img):
+        return self.batch([img])[0]
+
+    def __repr__(self):
+        return ("(DataAugmentationForRGBD,\ntransform = [ToTensor(), RandomResizedCrop(size=%d, scale=%s, ratio=%s, "
+                "interpolation=bilinear, antialias=%s), RandomHorizontalFlip(p=0.5), RandomVerticalFlip(p=0.5), "
+                "RandomRotation(degrees=%s, interpolation=nearest, expand=False, fill=0), Normalize(mean=%s, std=%s)],\n)"
+                % (self.size, self.SCALE, self.RATIO, self.antialias, list(self.degrees), self.mean, self.std))
+
+
 image_transform_conf = {"num_ops": 2, "magnitude": 9}
 
 
@@ -94,10 +177,7 @@ class Image_Processor_Train(BaseProcessor):
 
     @classmethod
     def from_config(cls, cfg=None):
-        cfg = dict(cfg or {})
-        update_conf = cfg.pop("update_conf", None)
-        return cls(args=cfg.get("params", image_transform_conf), img_mean=cfg.get("img_mean", OPENAI_CLIP_MEAN),
-                   img_std=cfg.get("img_std", OPENAI_CLIP_STD), update_conf=update_conf)
+        return _processor_config(cls, cfg, image_transform_conf)
 
     def draw(self, H, W):
         """One sample's scalars for an H x W source, from torch's global CPU generator in the order of the reference's

@@ -74,6 +74,7 @@ SIGNATURES = {
     "vl_rgbd_augment": [P, I, I, I, P, P, P, P, F, F, F, P, P, P],
     "vl_image_crop_resize_u8": [P, I, I, I, P, P, P, P],
     "vl_image_augment": [P, I, I, I, I, P, P, P, P, P, P, P, P],
+    "vl_tactile_augment": [P, I, I, I, P, P, P, P, P, P],
     "vl_resample_h_u8": [P, L, I, I, I, I, P, P, I, I, I, P, P],
     "vl_resample_v_u8_norm": [P, I, I, I, I, P, P, I, I, I, P, P, P, P, P],
     "vl_resample_batch_u8_norm": [P, I, I, I, I, I, P, P, P, P, P, P],

@@ -1213,6 +1213,62 @@ def image_augment(records, tables, tmp, S, max_nrows, max_ops, mean, std, out=No
     return (out, out_u8) if out_u8 is not None else out
 
 
+# one record per sample, as csrc/vl_tactile_augment.hip reads it (96 bytes; include/vitlens_hip.h spells the layout out)
+TACTILE_AUGMENT_DTYPE = np.dtype(
+    [("src", "<u8"), ("stride", "<i4"), ("H", "<i4"), ("W", "<i4"), ("top", "<i4"), ("left", "<i4"), ("bh", "<i4"), ("bw", "<i4"),
+     ("row0", "<i4"), ("nrows", "<i4"), ("hb", "<i4"), ("hw", "<i4"), ("hks", "<i4"), ("vb", "<i4"), ("vw", "<i4"), ("vks", "<i4"),
+     ("flags", "<i4"), ("tmp", "<i8"), ("t00", "<f4"), ("t01", "<f4"), ("t10", "<f4"), ("t11", "<f4")])
+TACTILE_HFLIP, TACTILE_VFLIP = 1, 2
+
+
+def tactile_augment_pack(rows, S, table_words, tmp_vec) -> np.ndarray:
+    """rows: a TACTILE_AUGMENT_DTYPE array for an S x S output, `table_words` int32 words of tables and `tmp_vec` float4 of
+    intermediate -> int32 [n, 24], the words of the records.  The records are read on the device, where the entry cannot look
+    at them, so their contents are checked here: the box inside the image, the touched rows inside the box, the stride, the
+    tables ([S,2] bounds, [S,ks] weights) and the [nrows,S] intermediate inside their buffers, the rotation's four floats
+    finite, no flag bit beyond the two flips."""
+    a = np.ascontiguousarray(np.asarray(rows, dtype=TACTILE_AUGMENT_DTYPE).reshape(-1))
+
+    def need(ok, what):
+        if not np.all(ok):
+            raise ValueError(f"tactile_augment_pack: {what} (sample {int(np.argmin(np.asarray(ok).reshape(len(a), -1).all(axis=1)))})")
+    need(a["src"] != 0, "null source pointer")
+    need((a["H"] >= 1) & (a["W"] >= 1) & (a["stride"] >= 3 * a["W"]), "bad source size or stride")
+    need((a["top"] >= 0) & (a["bh"] >= 1) & (a["top"] + a["bh"] <= a["H"]) & (a["left"] >= 0) & (a["bw"] >= 1)
+         & (a["left"] + a["bw"] <= a["W"]), "the crop box must lie inside the image")
+    need((a["row0"] >= 0) & (a["nrows"] >= 1) & (a["row0"] + a["nrows"] <= a["bh"]), "the touched rows must lie inside the box")
+    S, i8 = int(S), lambda name: a[name].astype(np.int64)
+    need((a["hks"] >= 1) & (a["vks"] >= 1) & (a["hb"] >= 0) & (a["hw"] >= 0) & (a["vb"] >= 0) & (a["vw"] >= 0) & (a["tmp"] >= 0)
+         & (i8("hb") + 2 * S <= table_words) & (i8("vb") + 2 * S <= table_words) & (i8("hw") + S * i8("hks") <= table_words)
+         & (i8("vw") + S * i8("vks") <= table_words) & (a["tmp"] + i8("nrows") * S <= tmp_vec), "bad table or intermediate offset")
+    need((a["flags"] & ~(TACTILE_HFLIP | TACTILE_VFLIP)) == 0, "unknown flag bits")
+    need(np.isfinite(np.stack([a[k] for k in ("t00", "t01", "t10", "t11")], axis=1)), "the rotation matrix is not finite")
+    return a.view(np.int32).reshape(len(a), TACTILE_AUGMENT_DTYPE.itemsize // 4)
+
+
+def tactile_augment(records, tables, tmp, S, max_nrows, mean, std, out=None):
+    """The tactile recipe's training transform for a batch (vl_tactile_augment, two launches): records int32 [n, 24] (the words
+    of `tactile_augment_pack`), tables int32 [*] and tmp f32 [*, 4] on the device; mean / std: 3 numbers -> out [n,3,S,S] f32."""
+    words = TACTILE_AUGMENT_DTYPE.itemsize // 4
+    if records.dim() != 2 or records.shape[1] != words or records.dtype != torch.int32 or not records.is_cuda:
+        raise ValueError(f"tactile_augment: records must be int32 [n, {words}] on the GPU, got {tuple(records.shape)} {records.dtype} {records.device}")
+    n, dev = records.shape[0], records.device
+    if tables.dtype != torch.int32 or tables.device != dev or tmp.dtype != torch.float32 or tmp.device != dev:
+        raise ValueError("tactile_augment: tables must be int32 and tmp float32 on the device of the records")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("tactile_augment: mean and std hold three numbers")
+    if n < 1 or S < 1:                   # (the entry refuses these too; nothing of size 0 is allocated first)
+        raise RuntimeError(f"libvitlens_hip: vl_tactile_augment: bad shape: n={n} S={S}")
+    if out is None:
+        out = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, 3, S, S) or out.device != dev:
+        raise ValueError("tactile_augment: out must be contiguous f32 [n, 3, S, S] on the device of the records")
+    fl = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    check(_lib.vl_tactile_augment(_p(records.contiguous()), n, int(S), int(max_nrows), _p(tables), _p(tmp), fl(mean), fl(std), _p(out),
+                                  _stream()))
+    return out
+
+
 def knn_group(xyz, center_idx, k, Kp=64, want_idx=False):
     B, N, _ = xyz.shape
     G = center_idx.shape[1]

@@ -392,6 +392,61 @@ def rgbd_record_scalars(rec, draw):
     rec["flags"] = flags
 
 
+def _table_packer(build):
+    """-> (table, parts): table(in_size) -> (offset of the bounds, offset of the coefficients, taps per row, host bounds) of
+    `build(in_size)` = (bounds, coefficients, ksize) inside the concatenation of `parts`, counted in 32-bit words; each distinct
+    size is packed once."""
+    parts, offsets, cursor = [], {}, 0
+
+    def table(in_size):
+        nonlocal cursor
+        if in_size not in offsets:
+            b, coef, ks = build(in_size)
+            offsets[in_size] = (cursor, cursor + b.size, ks, b)
+            parts.extend((b.reshape(-1), coef.reshape(-1).view(np.int32)))
+            cursor += b.size + coef.size
+        return offsets[in_size]
+    return table, parts
+
+
+def _box_fields(r, box, H, W, S, table, who, i, coef="w"):
+    """The crop box of sample i of plan `who` against its H x W image -> its record fields: the two tables' offsets and tap
+    counts (`hb`, `h<coef>`, `hks` for the box width -> S, `v..` for the height) and the rows of the box that the vertical taps
+    of the S output rows touch (`row0`, `nrows`).  -> nrows"""
+    top, left, bh, bw = (int(v) for v in box)
+    if not (0 <= top and 1 <= bh and top + bh <= H and 0 <= left and 1 <= bw and left + bw <= W):
+        raise ValueError(f"{who}: box {box} of sample {i} is not inside its {H} x {W} image")
+    r["hb"], r["h" + coef], r["hks"], _ = table(bw)
+    r["vb"], r["v" + coef], r["vks"], vb_host = table(bh)
+    r["row0"], r["nrows"] = _window(vb_host, 0, S, bh)
+    return int(r["nrows"])
+
+
+def _upload_packed(rec, pack, tables, host, dev):
+    """Everything the host provides for a batch in ONE pinned buffer and ONE copy, laid out as records | tables (16-byte
+    aligned) | host sources in the order given.  rec: the record array; host: (sample, pointer field, source tensor) - the
+    field receives the source's device address before `pack(rec)` checks the records and gives their words.
+    -> (records int32 [n, words], tables int32 [*], the device buffer that holds both and the sources)."""
+    off_tables = (rec.nbytes + 15) & ~15
+    cursor = off_tables + tables.nbytes
+    place = []
+    for i, field, t in host:
+        place.append(cursor)
+        cursor += t.numel() * t.element_size()
+    packed = torch.empty(max(cursor, 1), device=dev, dtype=torch.uint8)
+    for (i, field, _), off in zip(host, place):
+        rec[i][field] = packed.data_ptr() + off
+    stage = torch.empty(cursor, dtype=torch.uint8, pin_memory=dev.type == "cuda")
+    buf = stage.numpy()
+    buf[:rec.nbytes] = pack(rec).view(np.uint8).reshape(-1)
+    buf[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
+    for (_, _, t), off in zip(host, place):
+        stage[off:off + t.numel() * t.element_size()].copy_(t.contiguous().view(torch.uint8).reshape(-1))
+    packed.copy_(stage, non_blocking=True)
+    records = packed[:rec.nbytes].view(torch.int32).view(len(rec), -1)
+    return records, packed[off_tables:off_tables + tables.nbytes].view(torch.int32), packed
+
+
 class RgbdPlan:
     """Device-side description of one batch of the depth training transform: the packed buffer (records, tables, host
     sources), the intermediate and the tensors that keep device sources alive.  `launch()` enqueues vl_rgbd_augment; it can
@@ -418,17 +473,8 @@ def plan_rgbd(images, depths, draws, size, mean, std, depth_clamp, antialias=Tru
     if n < 1 or len(depths) != n or len(draws) != n:
         raise ValueError(f"plan_rgbd: {n} images, {len(depths)} depth maps, {len(draws)} draws")
     rec = np.zeros(n, dtype=ops.RGBD_AUGMENT_DTYPE)
-    parts, offsets, cursor = [], {}, 0
-
-    def table(in_size):
-        nonlocal cursor
-        if in_size not in offsets:
-            b, w, ks = aten_bilinear_tables(in_size, S, antialias)
-            offsets[in_size] = (cursor, cursor + b.size, ks, b)
-            parts.extend((b.reshape(-1), w.reshape(-1).view(np.int32)))
-            cursor += b.size + w.size
-        return offsets[in_size]
-    tmp_vec, keep, host = 0, [], []                    # host: (record field, source tensor) to be packed
+    table, parts = _table_packer(lambda in_size: aten_bilinear_tables(in_size, S, antialias))
+    tmp_vec, keep, host = 0, [], []                    # host: (sample, record field, source tensor) to be packed
     for i, (im, dp, draw) in enumerate(zip(images, depths, draws)):
         if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
             raise ValueError(f"plan_rgbd: image {i} must be uint8 [H, W, 3], got {tuple(im.shape)} {im.dtype}")
@@ -445,38 +491,75 @@ def plan_rgbd(images, depths, draws, size, mean, std, depth_clamp, antialias=Tru
             else:
                 host.append((i, field, t))
         rgbd_record_scalars(r, draw)
-        top, left, bh, bw = (int(v) for v in draw["box"])
-        if not (0 <= top and 1 <= bh and top + bh <= H and 0 <= left and 1 <= bw and left + bw <= W):
-            raise ValueError(f"plan_rgbd: box {draw['box']} of sample {i} is not inside its {H} x {W} image")
-        r["hb"], r["hw"], r["hks"], _ = table(bw)
-        r["vb"], r["vw"], r["vks"], vb_host = table(bh)
-        r["row0"], r["nrows"] = _window(vb_host, 0, S, bh)
         r["tmp"] = tmp_vec
-        tmp_vec += int(r["nrows"]) * S
-    tables = np.concatenate(parts)
-    # layout: records | tables | host depth maps (4-byte aligned) | host image bytes
-    off_tables = (rec.nbytes + 15) & ~15
-    cursor = off_tables + tables.nbytes
-    place = {}
-    for i, field, t in sorted(host, key=lambda h: h[1] != "depth"):
-        place[(i, field)] = cursor
-        cursor += t.numel() * t.element_size()
-    packed = torch.empty(max(cursor, 1), device=dev, dtype=torch.uint8)
-    for (i, field), off in place.items():
-        rec[i][field] = packed.data_ptr() + off
-    stage = torch.empty(cursor, dtype=torch.uint8, pin_memory=dev.type == "cuda")
-    buf = stage.numpy()
-    buf[:rec.nbytes] = ops.rgbd_augment_pack(rec, S).view(np.uint8).reshape(-1)
-    buf[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
-    for i, field, t in host:
-        off = place[(i, field)]
-        stage[off:off + t.numel() * t.element_size()].copy_(t.contiguous().view(torch.uint8).reshape(-1))
-    packed.copy_(stage, non_blocking=True)
-    records = packed[:rec.nbytes].view(torch.int32).view(n, -1)
-    tables_d = packed[off_tables:off_tables + tables.nbytes].view(torch.int32)
+        tmp_vec += _box_fields(r, draw["box"], H, W, S, table, "plan_rgbd", i) * S
+    # host depth maps (4-byte aligned) go in front of host image bytes
+    records, tables_d, packed = _upload_packed(rec, lambda r: ops.rgbd_augment_pack(r, S), np.concatenate(parts),
+                                               sorted(host, key=lambda h: h[1] != "depth"), dev)
     tmp = torch.empty(tmp_vec, 4, device=dev, dtype=torch.float32)
     keep.append(packed)
     return RgbdPlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), list(mean), list(std), tuple(depth_clamp), keep)
+
+
+# ---------------------------------------------------------------------------------------------- the tactile training transform
+def tactile_record_scalars(rec, draw, S):
+    """Write a draw's scalars into one TACTILE_AUGMENT_DTYPE row for an S x S output: the box, the two flips, the rotation.
+    draw: {"box": (top, left, h, w), "flip_h": bool, "flip_v": bool, "angle": degrees}.  The rotation is F.rotate's of a
+    tensor: `affine_inverse_matrix` for -angle about the centre in doubles, rounded to float32, its four rotation entries
+    divided in float32 by float32(0.5 S) (torchvision's rescaled theta; the two translations are 0)."""
+    from . import ops
+    rec["top"], rec["left"], rec["bh"], rec["bw"] = draw["box"]
+    rec["flags"] = (ops.TACTILE_HFLIP if draw["flip_h"] else 0) | (ops.TACTILE_VFLIP if draw["flip_v"] else 0)
+    m = np.array(affine_inverse_matrix([0.0, 0.0], -float(draw["angle"]), [0.0, 0.0], [0.0, 0.0]), dtype=np.float64).astype(np.float32)
+    rec["t00"], rec["t01"], rec["t10"], rec["t11"] = m[[0, 1, 3, 4]] / np.float32(0.5 * S)
+
+
+class TactilePlan:
+    """Device-side description of one batch of the tactile training transform: the packed buffer (records, tables, host
+    sources), the intermediate and the tensors that keep device sources alive.  `launch()` enqueues vl_tactile_augment; it
+    can be repeated (same inputs, same output)."""
+
+    def __init__(self, records, tables, tmp, n, S, max_nrows, mean, std, keep):
+        self.records, self.tables, self.tmp, self.keep = records, tables, tmp, keep
+        self.n, self.S, self.max_nrows, self.mean, self.std = n, S, max_nrows, mean, std
+
+    def launch(self, out=None):
+        from . import ops
+        return ops.tactile_augment(self.records, self.tables, self.tmp, self.S, self.max_nrows, self.mean, self.std, out=out)
+
+
+def plan_tactile_train(images, draws, size, mean, std, antialias=True, device="cuda"):
+    """Host side of the tactile training transform.  images[i]: uint8 [H, W, 3] tensor (host or device; sizes differ between
+    samples), draws[i]: the sample's scalars (`tactile_record_scalars`).  Everything the host provides - records, the packed
+    bilinear tables of the distinct (box edge -> size) pairs, host image bytes - is laid out in ONE pinned buffer and travels
+    in ONE copy; device sources are read where they are."""
+    from . import ops
+    n, S, dev = len(images), int(size), torch.device(device)
+    if n < 1 or len(draws) != n:
+        raise ValueError(f"plan_tactile_train: {n} images, {len(draws)} draws")
+    rec = np.zeros(n, dtype=ops.TACTILE_AUGMENT_DTYPE)
+    table, parts = _table_packer(lambda in_size: aten_bilinear_tables(in_size, S, antialias))
+    tmp_vec, keep, host = 0, [], []
+    for i, (im, draw) in enumerate(zip(images, draws)):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+            raise ValueError(f"plan_tactile_train: image {i} must be uint8 [H, W, 3], got {tuple(im.shape)} {im.dtype}")
+        H, W = im.shape[:2]
+        r = rec[i]
+        r["H"], r["W"], r["stride"] = H, W, 3 * W
+        if im.is_cuda:
+            im = im.contiguous()
+            keep.append(im)
+            r["src"] = im.data_ptr()
+        else:
+            host.append((i, "src", im))
+        tactile_record_scalars(r, draw, S)
+        r["tmp"] = tmp_vec
+        tmp_vec += _box_fields(r, draw["box"], H, W, S, table, "plan_tactile_train", i) * S
+    tables = np.concatenate(parts)
+    records, tables_d, packed = _upload_packed(rec, lambda r: ops.tactile_augment_pack(r, S, tables.size, tmp_vec), tables, host, dev)
+    tmp = torch.empty(tmp_vec, 4, device=dev, dtype=torch.float32)
+    keep.append(packed)
+    return TactilePlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), list(mean), list(std), keep)
 
 
 # ---------------------------------------------------------------------------------------------- the plain-image training transform
@@ -612,16 +695,7 @@ def plan_image_train(images, draws, size, mean, std, num_bins=31, shear_atan=Fal
     if n < 1 or len(draws) != n:
         raise ValueError(f"plan_image_train: {n} images, {len(draws)} draws")
     rec = np.zeros(n, dtype=ops.IMAGE_AUGMENT_DTYPE)
-    parts, offsets, cursor = [], {}, 0
-
-    def table(in_size):
-        nonlocal cursor
-        if in_size not in offsets:
-            b, kk, ks = pil_bilinear_tables(in_size, S)
-            offsets[in_size] = (cursor, cursor + b.size, ks, b)
-            parts.extend((b.reshape(-1), kk.reshape(-1)))
-            cursor += b.size + kk.size
-        return offsets[in_size]
+    table, parts = _table_packer(lambda in_size: pil_bilinear_tables(in_size, S))
     tmp_bytes, keep, host = 0, [], []
     for i, (im, draw) in enumerate(zip(images, draws)):
         if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
@@ -634,36 +708,12 @@ def plan_image_train(images, draws, size, mean, std, num_bins=31, shear_atan=Fal
             keep.append(im)
             r["src"] = im.data_ptr()
         else:
-            host.append((i, im))
+            host.append((i, "src", im))
         image_record_scalars(r, draw, S, num_bins, shear_atan, solarize_from)
-        top, left, bh, bw = (int(v) for v in draw["box"])
-        if not (0 <= top and 1 <= bh and top + bh <= H and 0 <= left and 1 <= bw and left + bw <= W):
-            raise ValueError(f"plan_image_train: box {draw['box']} of sample {i} is not inside its {H} x {W} image")
-        r["hb"], r["hk"], r["hks"], _ = table(bw)
-        r["vb"], r["vk"], r["vks"], vb_host = table(bh)
-        r["row0"], r["nrows"] = _window(vb_host, 0, S, bh)
         r["tmp"] = tmp_bytes
-        tmp_bytes += int(r["nrows"]) * S * 3
+        tmp_bytes += _box_fields(r, draw["box"], H, W, S, table, "plan_image_train", i, coef="k") * S * 3
     tables = np.concatenate(parts)
-    # layout: records | tables | host image bytes
-    off_tables = (rec.nbytes + 15) & ~15
-    cursor = off_tables + tables.nbytes
-    place = {}
-    for i, t in host:
-        place[i] = cursor
-        cursor += t.numel()
-    packed = torch.empty(max(cursor, 1), device=dev, dtype=torch.uint8)
-    for i, off in place.items():
-        rec[i]["src"] = packed.data_ptr() + off
-    stage = torch.empty(cursor, dtype=torch.uint8, pin_memory=dev.type == "cuda")
-    buf = stage.numpy()
-    buf[:rec.nbytes] = ops.image_augment_pack(rec, S, tables.size, tmp_bytes).view(np.uint8).reshape(-1)
-    buf[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
-    for i, t in host:
-        stage[place[i]:place[i] + t.numel()].copy_(t.contiguous().reshape(-1))
-    packed.copy_(stage, non_blocking=True)
-    records = packed[:rec.nbytes].view(torch.int32).view(n, -1)
-    tables_d = packed[off_tables:off_tables + tables.nbytes].view(torch.int32)
+    records, tables_d, packed = _upload_packed(rec, lambda r: ops.image_augment_pack(r, S, tables.size, tmp_bytes), tables, host, dev)
     tmp = torch.empty(tmp_bytes, device=dev, dtype=torch.uint8)
     keep.append(packed)
     return ImagePlan(records, tables_d, tmp, n, S, int(rec["nrows"].max()), int(rec["num_ops"].max()), list(mean), list(std), keep)
