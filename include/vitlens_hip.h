@@ -482,6 +482,39 @@ int vl_resample_sinc(const float* in, long in_stride, int batch, long n_in, cons
  * by seed, counter = (t F + f) / 4, word (t F + f) % 4. */
 int vl_fbank_augment(const float* in, float* out, int batch, int T, int F, const void* params, float mean, float std,
                      hipStream_t stream);
+/* The training clips of a batch, with audio mix-up, in one launch from recordings on the device (csrc/vl_audio_mix.hip):
+ * audio_get_clip (at_processor.py:193-224) and `mix = lam * wf + (1 - lam) * sec_wf; mix -= mix.mean()`
+ * (open_clip/modal_audio/datasets.py:279-326).  src: packed f32 [src_floats]; source i is C_i rows of L_i samples at float
+ * offset off_i, any offset (no alignment is asked for; a row that sits on a 16-byte boundary is read 16 bytes at a time).
+ * out [batch, n] f32; means (may be NULL: the same out) [batch, 3] f32 = mA, mB, mM (0 where there is no partner).
+ * recs: DEVICE array of one 40-byte record per output row, 10 little-endian 32-bit words:
+ *     words 0 .. 3   int32 off_a, ch_a, len_a, start_a     clip A: ch_a rows of len_a samples at src + off_a
+ *     words 4 .. 7   int32 off_b, ch_b, len_b, start_b     the partner; ch_b = 0: none
+ *     words 8 .. 9   float lam, mu                         float32 roundings of lambda and of the double 1 - lambda
+ * Clip A is a[c][t] = src[off_a + c len_a + (start_a + t) mod len_a], t < n (the repeated doubling of a short cut is a
+ * periodic extension, the crop a shift), clip B likewise.  Every step below is one float32 operation, nothing contracted:
+ *   mA = mean over the ch_a n elements of a,  a' = a - mA;            no partner: out[t] = a'[0][t]
+ *   mB, b' likewise;  m[c][t] = (lam a'[ca][t]) + (mu b'[cb][t]) with torch's broadcast over channels (ch_a == ch_b, or
+ *   one of them 1);  mM = mean over the max(ch_a, ch_b) n elements of m;  out[t] = m[0][t] - mM     (channel 0 only: the
+ *   filterbank reads channel 0).
+ * A mean is a sum in the fixed order csrc/vl_audio_mix.hip states (at most ceil(ceil(N / 4) / 256) + 10 additions on any
+ * element's way, N the element count), divided by float(N): two calls give the same bits.
+ * Refused with a status, nothing launched: a null src / recs / out, batch < 1, n or src_floats outside [1, 2^31 - 1].  The
+ * records live in device memory, where the entry cannot look at them: a row whose record has len < 1, ch < 1, start
+ * outside [0, len), an offset with [off, off + ch len) outside [0, src_floats), ch n > 2^31 - 1 or channel counts that do
+ * not broadcast is refused by the kernel - nothing of that row of out and means is written, and no address outside src is
+ * read - and where the records are packed on the host (vitlens_hip.audio.wave_clip_mix: ValueError, no launch).
+ * NOTE on the version: like vl_pc_augment, these entries were added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before them reports the same number and lacks the symbols, and a client must look them up when it
+ * loads the library (vitlens_hip/_lib.py does, and names such a library as stale). */
+int vl_wave_clip_mix(const float* src, long src_floats, const void* recs, float* out, float* means, int batch, long n,
+                     hipStream_t stream);
+/* The same mix of two samples' frames (datasets.py:318-321), rows f32 [rows, n]: out[r] = a[r] bit for bit where
+ * partner[r] < 0, else out[r][i] = (lam_r a[r][i]) + (mu_r b[partner[r]][i]), three float32 roundings, nothing contracted.
+ * partner int32 [rows] (DEVICE; an index >= rows leaves the row of out unwritten - the host wrapper refuses it), lam_mu f32
+ * [rows, 2].  out may alias a, not b.  Refused: a null operand, rows or n < 1, n > 65535 * 1024, out == b. */
+int vl_mix_rows(const float* a, const float* b, const int* partner, const float* lam_mu, float* out, int rows, long n,
+                hipStream_t stream);
 /* ---- point-cloud tokenizer (PointBERT grouping) ---- */
 /* farthest point sampling: xyz [B,N,3] f32, start [B] (the reference draws it with torch.randint, misc.py:60);
  * idx [B,G] int64 (bit-exact vs misc.fps), centers [B,G,3] optional. */

@@ -2,7 +2,13 @@
 bytes per second next to a device-to-device hipMemcpyAsync that moves the same number of bytes in the same run; (b)
 `AudioASTProcessorTrain.batch` on 256 five-second 16 kHz clips already on the device, in clips per second, with the
 filterbank launch and the augment launch timed alone.  Device events around repeated calls, the median reported.
-Writes one JSON object: `python tools/audio_frontend_bench.py profiles/audio_frontend.json`."""
+Writes one JSON object: `python tools/audio_frontend_bench.py profiles/audio_frontend.json`.
+
+`python tools/audio_frontend_bench.py --mixup profiles/audio_mixup.log`: the mix-up mode.  B = 32 and 256 ten-second 16 kHz
+mono recordings on the host; `batch(items)` (clips assembled on the host, one copy per clip), `batch(items, seconds=[None] * B)`
+(the same clips assembled by one vl_wave_clip_mix launch from one packed copy) and `batch(items, seconds=...)` with every
+second row mixed with another recording, alternated in one process; wall time of each call up to the device's last kernel,
+median / min / max over 20 batches after 3 warm-up rounds, one line per variant."""
 import ctypes
 import json
 import os
@@ -31,6 +37,36 @@ def event_times(fn, reps, warm=2):
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1) * 1e-3)
     return out
+
+
+def mixup(path=None, rounds=20, warm=3):
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    g = torch.Generator().manual_seed(0)
+    lines = [f"# {torch.cuda.get_device_name(0)}: AudioASTProcessorTrain.batch, 10 s 16 kHz mono recordings on the host, 5 s clips; "
+             f"wall ms per batch incl. the device, median [min, max] over {rounds} alternated batches after {warm} warm-up rounds"]
+    for B in (32, 256):
+        items = [torch.randn(160000, generator=g) * 0.1 for _ in range(B)]
+        seconds = [items[(i + 7) % B] if i % 2 == 0 else None for i in range(B)]
+        lambdas = [0.5 if s is not None else None for s in seconds]
+        proc = AudioASTProcessorTrain(seed=0, mix_up=True)
+        variants = {"host clips, no mix-up (batch(items))": lambda: proc.batch(items),
+                    "device clips, no row mixed (seconds=[None] * B)": lambda: proc.batch(items, seconds=[None] * B),
+                    "device clips, half the rows mixed": lambda: proc.batch(items, seconds=seconds, lambdas=lambdas)}
+        times = {k: [] for k in variants}
+        for r in range(warm + rounds):
+            for k, fn in variants.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+                if r >= warm:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+        for k, ts in times.items():
+            med = statistics.median(ts)
+            lines.append(f"B={B:<4d}{k:<50s}{med:9.3f} ms [{min(ts):.3f}, {max(ts):.3f}]  {B / med * 1e3:9.1f} clips/s")
+    text = "\n".join(lines)
+    print(text)
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
 
 
 def main():
@@ -91,4 +127,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "--mixup":
+        mixup(sys.argv[2] if len(sys.argv) > 2 else None)
+    else:
+        main()

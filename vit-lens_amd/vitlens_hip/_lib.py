@@ -68,6 +68,8 @@ SIGNATURES = {
     "vl_kaldi_fbank": [P, L, I, L, P, P, P, I, I, I, I, I, F, F, F, P],
     "vl_resample_sinc": [P, L, I, L, P, P, I, I, I, P, L, L, L, P],
     "vl_fbank_augment": [P, P, I, I, I, P, F, F, P],
+    "vl_wave_clip_mix": [P, L, P, P, P, I, L, P],
+    "vl_mix_rows": [P, P, P, P, P, I, L, P],
     "vl_fps": [P, P, P, P, I, I, I, P],
     "vl_pc_gather_normalize": [P, P, P, I, I, I, I, P],
     "vl_pc_augment": [P, P, P, I, I, I, I, P, F, P],

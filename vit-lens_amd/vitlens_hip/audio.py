@@ -166,3 +166,93 @@ def fbank_augment(fbank: torch.Tensor, params: torch.Tensor, mean: float, std: f
     out = torch.empty_like(x)
     check(_lib.vl_fbank_augment(_p(x), _p(out), x.shape[0], x.shape[1], x.shape[2], _p(params.contiguous()), float(mean), float(std), _stream()))
     return out
+
+
+# ---- clip assembly and audio mix-up (csrc/vl_audio_mix.hip) ----
+# one record per output row, as vl_wave_clip_mix reads it (40 bytes; include/vitlens_hip.h)
+MIX_DTYPE = np.dtype([("off_a", "<i4"), ("ch_a", "<i4"), ("len_a", "<i4"), ("start_a", "<i4"),
+                      ("off_b", "<i4"), ("ch_b", "<i4"), ("len_b", "<i4"), ("start_b", "<i4"), ("lam", "<f4"), ("mu", "<f4")])
+
+
+def mix_mean_chain(n_elems: int) -> int:
+    """K: the most float32 additions any element passes through in a mean of vl_wave_clip_mix over n_elems elements - its
+    thread's chunks (four accumulators, 256 threads), 2 to join the accumulators, 6 across the wave, 2 across the waves."""
+    chunks = -(-int(n_elems) // 4)
+    return -(-chunks // 256) + 10
+
+
+def mix_record(a, b=None, lam=None):
+    """One MIX_DTYPE row from clip A = (off, ch, len, start), its partner b (the same four, or None) and lambda: `lam` and
+    `mu` are the float32 roundings of lambda and of the double 1 - lambda, as torch rounds the two Python scalars."""
+    if b is None:
+        return tuple(a) + (0, 0, 1, 0, 1.0, 0.0)
+    if lam is None:
+        raise ValueError("a row with a partner needs its lambda")
+    return tuple(a) + tuple(b) + (np.float32(lam), np.float32(1.0 - float(lam)))
+
+
+def check_mix_records(recs: np.ndarray, n: int, src_floats: int):
+    """ValueError for what vl_wave_clip_mix's kernel would leave unwritten (include/vitlens_hip.h)."""
+    if recs.dtype != MIX_DTYPE or recs.ndim != 1 or len(recs) < 1:
+        raise ValueError("expected a non-empty 1-d array of MIX_DTYPE records")
+    if not 1 <= int(n) <= 2 ** 31 - 1 or not 1 <= int(src_floats) <= 2 ** 31 - 1:
+        raise ValueError(f"n and the source buffer's length must be in [1, 2^31 - 1], got {n} and {src_floats}")
+    for i, r in enumerate(recs):
+        for s in ("a", "b") if r["ch_b"] != 0 else ("a",):
+            off, ch, ln, st = (int(r[k + "_" + s]) for k in ("off", "ch", "len", "start"))
+            if ch < 1 or ln < 1 or not 0 <= st < ln or off < 0 or off + ch * ln > src_floats or ch * int(n) > 2 ** 31 - 1:
+                raise ValueError(f"row {i}, clip {s}: off {off}, ch {ch}, len {ln}, start {st} is no clip inside {src_floats} floats "
+                                 "(ch, len >= 1, 0 <= start < len, off >= 0, off + ch * len inside the buffer)")
+        if r["ch_b"] != 0 and not (r["ch_a"] == r["ch_b"] or r["ch_a"] == 1 or r["ch_b"] == 1):
+            raise ValueError(f"row {i}: {int(r['ch_a'])} and {int(r['ch_b'])} channels do not broadcast")
+
+
+def wave_clip_mix(src: torch.Tensor, recs: np.ndarray, n: int, means: bool = False, recs_dev: torch.Tensor = None):
+    """src: packed f32 recordings on the GPU, recs: MIX_DTYPE rows (host; checked here) -> out [B, n] f32, channel 0 of every
+    mean-free clip / mix, in one vl_wave_clip_mix launch; with `means` also [B, 3] = mA, mB, mM.  recs_dev: the same records
+    already on src's device as int32 [B, 10] (the processor sends them in the copy that brings the recordings)."""
+    if src.device.type != "cuda":
+        raise RuntimeError("wave_clip_mix runs on the MI355X kernels only")
+    if src.dtype != torch.float32 or src.dim() != 1 or not src.is_contiguous():
+        raise ValueError(f"expected a packed 1-d float32 buffer, got {src.dtype} {tuple(src.shape)}")
+    check_mix_records(recs, n, src.numel())
+    B = len(recs)
+    if recs_dev is None:
+        recs_dev = torch.from_numpy(recs.view(np.int32).reshape(B, 10)).to(src.device)
+    elif recs_dev.shape != (B, 10) or recs_dev.dtype != torch.int32 or recs_dev.device != src.device or not recs_dev.is_contiguous():
+        raise ValueError("recs_dev must be the records as contiguous int32 [B, 10] on src's device")
+    out = torch.empty(B, int(n), device=src.device, dtype=torch.float32)
+    m = torch.zeros(B, 3, device=src.device, dtype=torch.float32) if means else None
+    check(ops._lib.vl_wave_clip_mix(ops._p(src), src.numel(), ops._p(recs_dev), ops._p(out), ops._p(m), B, int(n), ops._stream()))
+    return (out, m) if means else out
+
+
+def mix_rows(a: torch.Tensor, b: torch.Tensor, partner, lambdas, out: torch.Tensor = None) -> torch.Tensor:
+    """a, b [rows, ...] f32 on the GPU, flattened per row; partner: per row an index into b or None / negative (the row of a
+    is copied); lambdas: per mixed row its lambda -> out[r] = lam_r * a[r] + (1 - lam_r) * b[partner[r]] as torch rounds it,
+    in one vl_mix_rows launch.  `out` may be `a`."""
+    if a.device.type != "cuda":
+        raise RuntimeError("mix_rows runs on the MI355X kernels only")
+    rows = a.shape[0]
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape or b.device != a.device or rows < 1 or a.numel() == 0:
+        raise ValueError(f"expected two float32 tensors of one shape on one device, got {tuple(a.shape)} / {tuple(b.shape)}")
+    if len(partner) != rows or len(lambdas) != rows:
+        raise ValueError(f"partner and lambdas need one entry per row ({rows})")
+    host = np.zeros((rows, 3), dtype=np.float32)
+    idx = host[:, 0].view(np.int32)
+    for r, (p, lam) in enumerate(zip(partner, lambdas)):
+        if p is None or int(p) < 0:
+            idx[r] = -1
+            continue
+        if int(p) >= rows or lam is None:
+            raise ValueError(f"row {r}: partner {p} is no row of b, or its lambda is missing")
+        idx[r], host[r, 1], host[r, 2] = int(p), np.float32(lam), np.float32(1.0 - float(lam))
+    dev = torch.from_numpy(host).to(a.device)
+    part, lam_mu = dev[:, 0].contiguous().view(torch.int32), dev[:, 1:].contiguous()
+    a, b = a.contiguous(), b.contiguous()
+    if out is None:
+        out = torch.empty_like(a)
+    elif out.shape != a.shape or out.dtype != torch.float32 or out.device != a.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of a's shape on its device")
+    check(ops._lib.vl_mix_rows(ops._p(a), ops._p(b), ops._p(part), ops._p(lam_mu), ops._p(out), rows, a.numel() // rows, ops._stream()))
+    return out

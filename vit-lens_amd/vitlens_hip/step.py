@@ -1060,6 +1060,38 @@ class DualAudioStep(_PerceiverLensStep):
         return loss, dv, (ds,)
 
 
+class TriModalAudioStep(DualAudioStep):
+    """Audio tri-modal step (reference `tri_train_one_epoch` + TriClipLoss; the published AudioSet recipe,
+    TRAIN_INFERENCE.md:283-299: --n_tower 3 --audio_load_vision --lock-visual --unlock-cls): image and text towers frozen,
+    visual tower = `DualAudioStep`'s - AST tokenizer + Perceiver + class token trainable in front of the locked ViT.  The
+    loss is the base class's (image <-> audio and text <-> audio).  `images`: the video frame that goes with each clip, after
+    `AudioASTProcessorTrain.mix_frames` where mix-up is on."""
+
+    def __init__(self, sd, tower: TowerCfg, text: TextCfg, lens: LensCfg, device, micro_batch: int = 256, lr: float = 2e-4,
+                 betas=(0.9, 0.98), eps: float = 1e-6, weight_decay: float = 0.2, rank: int = 0, world_size: int = 1,
+                 gemm_cfg: int = -1, comm=None, frozen_res_dtype=torch.float32, local_loss: bool = False,
+                 gather_with_grad: bool = False, train_res_dtype=torch.float32, force_comm: bool = False, text_wsplit: Optional[bool] = None, text_arith: str = "f16",
+                 overlap_frozen: bool = True, overlap_backward: bool = True,
+                 grad_clip_norm: Optional[float] = None, patch_dropout: float = 0.0, drop_seed: int = 0,
+                 perceiver_attn_dropout: float = 0.0, perceiver_ff_dropout: float = 0.0):
+        self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, overlap_frozen,
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed, perceiver_attn_dropout, perceiver_ff_dropout),
+                        (lr, betas, eps, weight_decay),
+                        sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
+                        text_wsplit=text_wsplit, text_arith=text_arith)
+
+    def _build(self, sd, tower, text, lens, gemm_cfg=-1, frozen_res_dtype=torch.float32, train_res_dtype=torch.float32,
+               text_wsplit=None, text_arith="f16"):
+        self.image = VitEngine(sd, "image.", tower, self.dev, gemm_cfg=gemm_cfg, res_dtype=frozen_res_dtype)
+        super()._build(sd, tower, text, lens, gemm_cfg=gemm_cfg, frozen_res_dtype=frozen_res_dtype, train_res_dtype=train_res_dtype,
+                       text_wsplit=text_wsplit, text_arith=text_arith)
+
+    def forward_backward(self, images: torch.Tensor, texts: torch.Tensor, audio: torch.Tensor) -> torch.Tensor:
+        return self._forward_backward(texts, images, audio)
+
+    _loss = _StepState._loss
+
+
 class TriModalPCStep(_PerceiverLensStep):
     """Point-cloud tri-modal step (reference pc_tri_main.py -> `tri_train_one_epoch` + TriClipLoss; model
     mm_vit_lens/model_cfg.py:85-110): image and text towers frozen, visual tower = PointBERT tokenizer (FPS -> kNN ->
