@@ -271,6 +271,23 @@ int vl_assemble_ln_pre(const void* tokens, int tok_dtype, const float* cls, cons
                        const float* w, const float* b, void* y, int y_dtype, float* xpre, float* mean, float* rstd,
                        int B, int T, int D, float eps, hipStream_t stream);
 
+/* [cls ; tokens] + positional_embedding (+ adapter pos on rows 1..T) with NO LayerNorm behind it: the token assembly of a tower
+ * without ln_pre (the BLIP-2 EVA ViT-g adds pos_embed and enters block 0).  vl_assemble_ln_pre's arguments minus w, b, eps,
+ * mean, rstd: tokens [B,T,D] f32 | bf16; cls [D], pos [T+1,D], pos2 [T,D] or NULL, f32; y [B,T+1,D] f32 | bf16 (the residual-
+ * stream dtype); xpre optional f32 [B,T+1,D] copy of the same rows.  Dense form only.  One wave per row; rows whose operands'
+ * base addresses are multiples of 4 elements, with D % 4 == 0, move 8 / 16 bytes at a time, everything else one element at a
+ * time (vl_layernorm_fwd's rule).  Refused with a status: an empty problem, a missing operand, any other dtype code.
+ *
+ * With this entry, vl_layernorm_fwd (row_index == NULL or not) and the three vl_layernorm_bwd* entries hold a D = 1408 row
+ * (5 * 256 + 128) in registers too: five 256-element chunks and a half chunk in lanes 0-31, the other lanes entering the wave
+ * reductions with zeros - under the same alignment conditions as the D % 256 == 0 forms, the any-D form otherwise.  No other
+ * width changes its path.
+ * NOTE on the version: like vl_pc_augment, this entry was added under VL_ABI_VERSION 610, which tests/test_linprobe_host.py
+ * pins: a library built before it reports the same number and lacks the symbol, and a client must look it up when it loads the
+ * library (vitlens_hip/_lib.py does, and names such a library as stale).  No existing entry changes. */
+int vl_assemble_tokens(const void* tokens, int tok_dtype, const float* cls, const float* pos, const float* pos2,
+                       void* y, int y_dtype, float* xpre, int B, int T, int D, hipStream_t stream);
+
 /* ---- patch dropout (PatchDropout, open_clip/transformer.py:53-90: train mode keeps the class token + K of the T tokens) ----
  * The selection.  keep int32 [B,K]: keep[b,j] = the index of the j-th largest key of sample b, ties to the lower index (with
  * distinct keys: torch.topk(keys, K).indices exactly); inv int32 [B,T]: inv[b,t] = j + 1 if keep[b,j] == t, else 0.

@@ -43,7 +43,9 @@ struct LnBwdP {
 
 // One wave per row.  NCH > 0: the row (D = NCH*256 elements) is read ONCE into registers with 8/16-byte accesses;
 // NCH == 0: any D, two passes over global memory.  TG = dtype of the residual-gradient stream (dres / dx).
-template <int NCH, typename TDY, typename TX, typename TG>
+// HALF: D = NCH*256 + 128 (1408 = 5*256 + 128, the EVA ViT-g width): lanes 0-31 hold four more elements each, lanes 32-63 hold
+// zeros there, which add nothing to either wave sum, and store nothing.
+template <int NCH, typename TDY, typename TX, typename TG, bool HALF = false>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdP p) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -60,11 +62,18 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdP p) {
   const float mu = p.mean[row], rs = p.rstd[row];
   const int D = p.D;
   if constexpr (NCH > 0) {
-    float g[NCH][4], xh[NCH][4];
+    constexpr int NV = NCH + (HALF ? 1 : 0);
+    const bool tail = lane < 32;      // HALF: this lane owns four elements of the half chunk
+    float g[NV][4], xh[NV][4];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
+    for (int c = 0; c < NV; ++c) {
       const int e = c * 256 + lane * 4;
+      if (HALF && c == NCH && !tail) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { g[c][k] = 0.f; xh[c][k] = 0.f; }
+        continue;
+      }
       float ww[4];
       ld4(dy + e, g[c]); ld4(x + e, xh[c]); ld4(p.w + e, ww);
 #pragma unroll
@@ -75,7 +84,8 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const LnBwdP p) {
     }
     s1 = wave_sum(s1) / (float)D; s2 = wave_sum(s2) / (float)D;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
+    for (int c = 0; c < NV; ++c) {
+      if (HALF && c == NCH && !tail) break;
       const int e = c * 256 + lane * 4;
       float v[4];
 #pragma unroll
@@ -326,10 +336,12 @@ static void ln_bwd_launch(const LnBwdP& p, hipStream_t stream) {
   // the register forms read and write every operand four elements (8 or 16 bytes) at a time: the strides AND the bases must be
   // multiples of that (the column reductions' rule, vl_colreduce.hip), the sparse residual's own stride included
   auto al4 = [](const void* q, size_t elem) { return (uintptr_t)q % (4 * elem) == 0; };      // a null (absent) operand passes
-  const bool vec = (p.D % 256 == 0) && (p.dys % 4 == 0) && (p.xs % 4 == 0) && (p.dxs % 4 == 0) &&
+  const bool al = (p.dys % 4 == 0) && (p.xs % 4 == 0) && (p.dxs % 4 == 0) &&
                    (!(p.dres && p.dres_every > 1) || p.dres_s % 4 == 0) && al4(p.dy, sizeof(TDY)) && al4(p.x, sizeof(TX)) &&
                    al4(p.w, 4) && al4(p.dres, sizeof(TG)) && al4(p.dx, sizeof(TG)) && al4(p.dxb, 2);
-  if (vec && p.D == 1024) hipLaunchKernelGGL((ln_bwd_kernel<4, TDY, TX, TG>), g, b, 0, stream, p);
+  const bool vec = al && (p.D % 256 == 0);
+  if (al && p.D == 1408) hipLaunchKernelGGL((ln_bwd_kernel<5, TDY, TX, TG, true>), g, b, 0, stream, p);    // 5*256 + 128: EVA ViT-g
+  else if (vec && p.D == 1024) hipLaunchKernelGGL((ln_bwd_kernel<4, TDY, TX, TG>), g, b, 0, stream, p);
   else if (vec && p.D == 768) hipLaunchKernelGGL((ln_bwd_kernel<3, TDY, TX, TG>), g, b, 0, stream, p);
   else if (vec && p.D == 512) hipLaunchKernelGGL((ln_bwd_kernel<2, TDY, TX, TG>), g, b, 0, stream, p);
   else if (vec && p.D == 256) hipLaunchKernelGGL((ln_bwd_kernel<1, TDY, TX, TG>), g, b, 0, stream, p);

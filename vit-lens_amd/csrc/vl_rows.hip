@@ -53,8 +53,10 @@ struct LnP {
   const int* keep; int K;
 };
 
-// NCH = number of 256-element chunks held in registers (0 = generic any-D path)
-template <int NCH, typename TIN, typename TOUT, int MODE>
+// NCH = number of 256-element chunks held in registers (0 = generic any-D path).  HALF: one more chunk of 128 elements behind
+// them (D = NCH*256 + 128; the EVA ViT-g width 1408 = 5*256 + 128): lanes 0-31 hold four elements each, lanes 32-63 hold zeros
+// there - they add 0 to the row sum, are left out of the sum of squared deviations (0 - mean is not 0) and store nothing.
+template <int NCH, typename TIN, typename TOUT, int MODE, bool HALF = false>
 __global__ void __launch_bounds__(256) ln_rows_kernel(const LnP p) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -79,7 +81,55 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const LnP p) {
   TOUT* y = (TOUT*)p.y + (long)row * p.ys;
   const float invD = 1.0f / (float)D;
 
-  if constexpr (NCH > 0) {
+  if constexpr (HALF) {
+    static_assert(MODE == 0 && NCH > 0, "the half-chunk form is the plain LayerNorm's");
+    float v[NCH + 1][4];
+    const bool tail = lane < 32;                 // this lane owns four elements of the half chunk
+    const int et = NCH * 256 + lane * 4;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) load4(x + c * 256 + lane * 4, v[c]);
+    if (tail) load4(x + et, v[NCH]);
+    else { v[NCH][0] = 0.f; v[NCH][1] = 0.f; v[NCH][2] = 0.f; v[NCH][3] = 0.f; }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c <= NCH; ++c) s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
+    // An fp32 mean is off by up to half an ulp of ITSELF, and that error shifts every x - mean of the row: relative to the row's
+    // spread it is 2^-24 |mean| / sigma, 2.5e-7 already at |mean| = 4 sigma and 1e-5 for a stream that sits at 1000 +- 4.  So the
+    // deviations d = x - mu0 are taken from the rounded mean mu0 (exactly, where it matters: x within a factor 2 of mu0), their
+    // own mean `corr` - a small number, known to its own 2^-24 - is taken off again, and the variance is E[d^2] - corr^2.
+    // 1 / 1408 is no power of two: s * fl(1/D) rounds twice, s / D once; per row, not per element, so the divisions are free.
+    const float fD = (float)D;
+    const float mu0 = wave_sum(s) / fD;
+    float sd = 0.f, q = 0.f;
+#pragma unroll
+    for (int c = 0; c <= NCH; ++c) {
+      if (c == NCH && !tail) break;               // (the zeros of lanes 32-63 are no elements of the row: 0 - mu0 is not 0)
+      float dd = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { v[c][k] -= mu0; dd += v[c][k]; q = fmaf(v[c][k], v[c][k], q); }
+      sd += dd;
+    }
+    const float corr = wave_sum(sd) / fD;
+    const float mu = mu0 + corr;
+    // rstd scales every element of the row, so its error is the row's: the hardware reciprocal root (1 ulp) gets one Newton
+    // step whose residual 1 - a r0^2 is formed exactly (two fma's recover the rounding of a * r0); the result is within half an
+    // ulp of a^-1/2 plus the last rounding
+    const float a = fmaxf(fmaf(-corr, corr, wave_sum(q) / fD), 0.f) + p.eps;
+    const float r0 = rsqrtf(a);
+    const float t = a * r0, tl = fmaf(a, r0, -t);
+    const float rs = fmaf(0.5f * r0, fmaf(-t, r0, 1.0f) - tl * r0, r0);
+    if (p.mean && lane == 0) { p.mean[row] = mu; p.rstd[row] = rs; }
+#pragma unroll
+    for (int c = 0; c <= NCH; ++c) {
+      if (c == NCH && !tail) break;
+      const int e = c * 256 + lane * 4;
+      float ww[4], bb[4], o[4];
+      load4(p.w + e, ww); load4(p.b + e, bb);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = fmaf((v[c][k] - corr) * rs, ww[k], bb[k]);
+      store4(y + e, o);
+    }
+  } else if constexpr (NCH > 0) {
     float v[NCH][4];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -158,9 +208,16 @@ hipError_t ln_launch(const LnP& p, hipStream_t s) {
   const dim3 grid((p.rows + 3) / 4), block(256);
   // the register forms need every row of every operand on a 4-element boundary: the strides AND the bases (the column
   // reductions' rule, vl_colreduce.hip); anything else takes the generic form
-  const bool vec = (p.D % 256 == 0) && (p.xs % 4 == 0) && (p.ys % 4 == 0) && aligned4<TIN>(p.x) && aligned4<TOUT>(p.y) &&
+  const bool al = (p.xs % 4 == 0) && (p.ys % 4 == 0) && aligned4<TIN>(p.x) && aligned4<TOUT>(p.y) &&
                    aligned4<float>(p.w) && aligned4<float>(p.b) &&
                    (MODE == 0 || (aligned4<float>(p.cls) && aligned4<float>(p.pos) && aligned4<float>(p.pos2) && aligned4<float>(p.y2)));
+  if constexpr (MODE == 0) {       // D = 1408 = 5*256 + 128 (EVA ViT-g): five chunks and a half; no other width takes this form
+    if (al && p.D == 1408) {
+      hipLaunchKernelGGL((ln_rows_kernel<5, TIN, TOUT, 0, true>), grid, block, 0, s, p);
+      return hipGetLastError();
+    }
+  }
+  const bool vec = al && (p.D % 256 == 0);
   const int nch = vec ? p.D / 256 : 0;
   switch (nch) {
     case 1: hipLaunchKernelGGL((ln_rows_kernel<1, TIN, TOUT, MODE>), grid, block, 0, s, p); break;
@@ -268,6 +325,60 @@ __global__ void __launch_bounds__(256) add_rows_kernel(const TIN* x, const float
     const long r = i / D; const int d = (int)(i - r * D);
     store1(y + i, load1(x + i) + t[(r % T) * D + d]);
   }
+}
+
+
+// ---- [cls ; tokens] + pos (+ pos2), no LayerNorm (a tower without ln_pre: the EVA ViT) ------------------------------------
+// One wave per output row (b, l), l in [0, T]: l == 0 -> cls + pos[0], else tokens[b][l-1] + pos[l] (+ pos2[l-1]).
+// VEC: four elements (8 / 16 bytes) per access, any D % 4 == 0; otherwise one element at a time.
+struct AsmP { const void* tok; const float* cls; const float* pos; const float* pos2; void* y; float* y2; int rows, T, D; };
+template <bool VEC, typename TIN, typename TOUT>
+__global__ void __launch_bounds__(256) assemble_rows_kernel(const AsmP p) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= p.rows) return;
+  const int D = p.D;
+  const int bb = row / (p.T + 1), l = row - bb * (p.T + 1);
+  const TIN* x = (const TIN*)p.tok + ((long)bb * p.T + (l > 0 ? l - 1 : 0)) * D;
+  const float* ps = p.pos + (long)l * D;
+  const float* ps2 = (p.pos2 && l > 0) ? p.pos2 + (long)(l - 1) * D : nullptr;
+  TOUT* y = (TOUT*)p.y + (long)row * D;
+  float* y2 = p.y2 ? p.y2 + (long)row * D : nullptr;
+  if constexpr (VEC) {
+    for (int e = lane * 4; e < D; e += 256) {
+      float t[4], a[4];
+      if (l == 0) load4(p.cls + e, t); else load4(x + e, t);
+      load4(ps + e, a);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t[k] += a[k];
+      if (ps2) {
+        load4(ps2 + e, a);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] += a[k];
+      }
+      store4(y + e, t);
+      if (y2) store4(y2 + e, t);
+    }
+  } else {
+    for (int e = lane; e < D; e += 64) {
+      float t = (l == 0) ? p.cls[e] : load1(x + e);
+      t += ps[e];
+      if (ps2) t += ps2[e];
+      store1(y + e, t);
+      if (y2) y2[e] = t;
+    }
+  }
+}
+
+template <typename TIN, typename TOUT>
+hipError_t assemble_launch(const AsmP& p, hipStream_t s) {
+  const dim3 grid((p.rows + 3) / 4), block(256);
+  // ln_launch's rule: every row of every operand on a 4-element boundary (rows are D apart here), else the generic form
+  const bool vec = (p.D % 4 == 0) && aligned4<TIN>(p.tok) && aligned4<TOUT>(p.y) && aligned4<float>(p.cls) &&
+                   aligned4<float>(p.pos) && aligned4<float>(p.pos2) && aligned4<float>(p.y2);
+  if (vec) hipLaunchKernelGGL((assemble_rows_kernel<true, TIN, TOUT>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((assemble_rows_kernel<false, TIN, TOUT>), grid, block, 0, s, p);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -419,6 +530,23 @@ extern "C" int vl_assemble_ln_pre_keep(const void* tokens, int tok_dtype, const 
   LnP p{}; p.x = tokens; p.xs = D; p.w = w; p.b = b; p.y = y; p.ys = D; p.rows = B * (K + 1); p.D = D; p.eps = eps;
   p.cls = cls; p.pos = pos; p.pos2 = pos2; p.T = T; p.y2 = xpre; p.mean = mean; p.rstd = rstd; p.keep = keep; p.K = K;
   VL_HIP_OK(ln_dispatch<1>(p, tok_dtype, y_dtype, stream));
+  return 0;
+}
+
+extern "C" int vl_assemble_tokens(const void* tokens, int tok_dtype, const float* cls, const float* pos, const float* pos2,
+                                  void* y, int y_dtype, float* xpre, int B, int T, int D, hipStream_t stream) {
+  if (B <= 0 || T <= 0 || D <= 0) return vl_set_error("vl_assemble_tokens: empty problem");
+  if (!tokens || !cls || !pos || !y) return vl_set_error("vl_assemble_tokens: tokens, cls, pos and y are required");
+  if ((tok_dtype != VL_F32 && tok_dtype != VL_BF16) || (y_dtype != VL_F32 && y_dtype != VL_BF16))
+    return vl_set_error("vl_assemble_tokens: tok_dtype and y_dtype must be VL_F32 or VL_BF16");
+  if ((long)B * (T + 1) > 0x7fffffffL) return vl_set_error("vl_assemble_tokens: B * (T + 1) must fit 31 bits");
+  const AsmP p{tokens, cls, pos, pos2, y, xpre, B * (T + 1), T, D};
+  hipError_t e;
+  if (tok_dtype == VL_F32 && y_dtype == VL_F32) e = assemble_launch<float, float>(p, stream);
+  else if (tok_dtype == VL_F32) e = assemble_launch<float, bf16_t>(p, stream);
+  else if (y_dtype == VL_F32) e = assemble_launch<bf16_t, float>(p, stream);
+  else e = assemble_launch<bf16_t, bf16_t>(p, stream);
+  VL_HIP_OK(e);
   return 0;
 }
 

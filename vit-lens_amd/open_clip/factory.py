@@ -136,7 +136,7 @@ def tri_create_model(model_name: str, pretrained: Optional[str] = None, precisio
     if output_dict:
         model.output_dict = True
     skip = getattr(args, "skip_trans_first_n_layers", None) if args is not None else None
-    if skip is not None:
+    if skip is not None and model.visual_arch == "perceiver_vit":       # (the EVA tower drops its first layers in its constructor)
         # "Add skip-first-n-layers here to drop layers" (factory.py:347-360): after the weights are in place
         n_layers = model.visual.cfg.layers
         assert skip < n_layers

@@ -169,13 +169,7 @@ class VisionTransformer(nn.Module):
         self._check_lens_dropout()
         n_tok = _g(a, "perceiver_num_latents", grid) if self.use_perceiver else grid
         scale = D ** -0.5
-        prm = {"class_embedding": scale * torch.randn(D), "positional_embedding": scale * torch.randn(n_tok + 1, D),
-               "proj": scale * torch.randn(D, embed_dim)}
-        for n in ("ln_pre", "ln_post"):
-            prm[n + ".weight"] = torch.ones(D); prm[n + ".bias"] = torch.zeros(D)
-        hidden = int(D * cfg.mlp_ratio)
-        for i in range(cfg.layers):
-            prm.update(_block_params(f"transformer.resblocks.{i}.", D, hidden))
+        prm = self._tower_params(D, n_tok, embed_dim)
         bufs = {}
         if self.modality in ("image", "tactile"):
             prm["conv1.weight"] = _uni((D, 3, P, P), (3 * P * P) ** -0.5)
@@ -263,6 +257,26 @@ class VisionTransformer(nn.Module):
         self._trainer_obj, self._trainer_key, self._gen = None, None, 0
         self._freeze_bn = False
         self._bn_sync = None          # (communicator, world size) once set_bn_sync(True) was called in a multi-rank job
+
+    def _tower_params(self, D, n_tok, embed_dim):
+        """name -> initial tensor of the transformer behind the Lens (the CLIP ViT; third_vit/blip_eva_vit.py has the EVA one)."""
+        cfg, scale = self.cfg, D ** -0.5
+        prm = {"class_embedding": scale * torch.randn(D), "positional_embedding": scale * torch.randn(n_tok + 1, D),
+               "proj": scale * torch.randn(D, embed_dim)}
+        for n in ("ln_pre", "ln_post"):
+            prm[n + ".weight"] = torch.ones(D); prm[n + ".bias"] = torch.zeros(D)
+        hidden = int(D * cfg.mlp_ratio)
+        for i in range(cfg.layers):
+            prm.update(_block_params(f"transformer.resblocks.{i}.", D, hidden))
+        return prm
+
+    def _engine_names(self, names):
+        """This module's parameter names -> the names the engines and trainers use (the same, for the CLIP ViT)."""
+        return list(names)
+
+    def _module_grads(self, raw):
+        """A trainer's gradients -> under this module's parameter names (the same, for the CLIP ViT)."""
+        return raw
 
     def set_bn_sync(self, enabled=True, comm=None, world_size=None):
         """Counterpart of `torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)` (--use-bn-sync, e.g.
@@ -408,13 +422,13 @@ class VisionTransformer(nn.Module):
                 self._engine.update_params(sd, "t.", changed)
             if self._trainer_obj is not None and self._trainer_key is not None and self._trainer_key[0] == id(self._engine):
                 from vitlens_hip.train import refresh_trainer
-                refresh_trainer(self._trainer_obj, sd, changed)
+                refresh_trainer(self._trainer_obj, sd, self._engine_names(changed))
             self._engine_vers = vers
         return self._engine
 
     # -------------------------------------------------------------------------------------- training (autograd)
     def _train_flags(self):
-        req = {n for n, p in self.named_parameters() if p.requires_grad}
+        req = set(self._engine_names(n for n, p in self.named_parameters() if p.requires_grad))
         blocks = tuple(sorted({int(n.split(".")[2]) for n in req if n.startswith("transformer.resblocks.")}))
         return (blocks, "class_embedding" in req, "positional_embedding" in req, any(n.startswith("ln_pre.") for n in req),
                 any(n.startswith("ln_post.") for n in req), "proj" in req, "conv1.weight" in req,
@@ -455,7 +469,7 @@ class VisionTransformer(nn.Module):
 
     def _named_grads(self, tr):
         """Gradients of the last backward under THIS module's parameter names and shapes."""
-        raw = tr.perc.reference_named_grads() if hasattr(tr, "perc") else dict(tr.grads)
+        raw = self._module_grads(tr.perc.reference_named_grads() if hasattr(tr, "perc") else dict(tr.grads))
         params = dict(self.named_parameters())
         out = {}
         for k, g in raw.items():
@@ -700,6 +714,17 @@ def _normalize(x):
     return ops.l2_normalize(x.contiguous().float())
 
 
+def _build_visual_arch(visual_arch, args, embed_dim, vision_cfg=None, depth=40, n_tokens=None):
+    """The `visual` tower of a visual_arch other than 'perceiver_vit' (the reference's _build_visual_arch): the Lens at width
+    1408 in front of the BLIP-2 EVA ViT-g with 40 blocks (`--use_eva_pt_lin`: its nn.Linear(1408, 1024) head is the output
+    projection)."""
+    if visual_arch != "perceiver_blip_eva_g_vit":
+        raise NotImplementedError(f"visual_arch {visual_arch!r}")
+    from .third_vit.blip_eva_vit import Perceiver_Blip_EVA_ViT, create_eva_vit_g
+    eva_vit = create_eva_vit_g(depth=depth, use_nnlinear=bool(_g(args, "use_eva_pt_lin", False)))
+    return Perceiver_Blip_EVA_ViT(None, None, eva_vit, args, embed_dim=embed_dim, vision_cfg=vision_cfg)
+
+
 class TriCLIP(nn.Module):
     def __init__(self, embed_dim: int, vision_cfg, text_cfg, quick_gelu: bool = False, cast_dtype=None,
                  output_dict: bool = False):
@@ -712,14 +737,18 @@ class TriCLIP(nn.Module):
         self.exp_args = vision_cfg.exp_args
         self.output_dict = output_dict
         self.visual_arch = vision_cfg.visual_arch
-        if self.visual_arch != "perceiver_vit":
-            raise NotImplementedError("only visual_arch='perceiver_vit' (Lens -> frozen ViT) is on the hot path")
+        if self.visual_arch not in ("perceiver_vit", "perceiver_blip_eva_g_vit"):
+            raise NotImplementedError(f"visual_arch {self.visual_arch!r}: 'perceiver_vit' (Lens -> frozen CLIP ViT) and "
+                                      "'perceiver_blip_eva_g_vit' (Lens -> frozen BLIP-2 EVA ViT-g) are on the hot path")
         img_cfg = CLIPVisionCfg(layers=vision_cfg.layers, width=vision_cfg.width, head_width=vision_cfg.head_width,
                                 mlp_ratio=vision_cfg.mlp_ratio, patch_size=vision_cfg.patch_size,
                                 image_size=vision_cfg.image_size, exp_args=vision_cfg.exp_args,
                                 patch_dropout=vision_cfg.patch_dropout)     # (both towers are built from one vision cfg)
         self.image = VisionTransformer(embed_dim, img_cfg, quick_gelu=self.quick_gelu)      # module_cfg.set_default_image_cfg
-        self.visual = VisionTransformer(embed_dim, vision_cfg, quick_gelu=self.quick_gelu)
+        if self.visual_arch == "perceiver_vit":
+            self.visual = VisionTransformer(embed_dim, vision_cfg, quick_gelu=self.quick_gelu)
+        else:
+            self.visual = _build_visual_arch(self.visual_arch, vision_cfg.exp_args, embed_dim=embed_dim, vision_cfg=vision_cfg)
         # text tower flattened into the root (model.py:435-443)
         self.text_cfg = text_cfg
         self.context_length, self.vocab_size = text_cfg.context_length, text_cfg.vocab_size
@@ -849,6 +878,14 @@ class TriCLIP(nn.Module):
     def encode_visual(self, visual_x, normalize: bool = False, **kwargs):
         features = self.visual(visual_x, **kwargs)
         return _normalize(features) if normalize else features
+
+    def encode_visual_tokens(self, visual_x, **kwargs):
+        """The [B, 257, 1408] token stream of a 'perceiver_blip_eva_g_vit' visual tower behind its last block and in front of
+        `norm` (eva_vit.forward_features): what an MLLM's ln_vision reads.  No graph is kept."""
+        if not hasattr(self.visual, "forward_tokens"):
+            raise NotImplementedError("encode_visual_tokens: the token stream is the EVA tower's output (visual_arch "
+                                      "'perceiver_blip_eva_g_vit'); the CLIP towers are pooled")
+        return self.visual.forward_tokens(visual_x, **kwargs)
 
     def _text_trainer(self):
         """The trainable text tower (bf16 operands, saved activations), rebuilt when a text parameter changed."""

@@ -46,6 +46,7 @@ SIGNATURES = {
     "vl_gemm_res_rowstats_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "vl_ln_row_stats": [P, I, P, L, I, I, I, F, P, P, P, P, P, L, I, P],
     "vl_assemble_ln_pre": [P, I, P, P, P, P, P, P, I, P, P, P, I, I, I, F, P],
+    "vl_assemble_tokens": [P, I, P, P, P, P, I, P, I, I, I, P],
     "vl_patch_keep": [P, C.c_uint64, C.c_int64, I, I, I, P, P, P],
     "vl_assemble_ln_pre_keep": [P, I, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, F, P],
     "vl_scatter_rows_keep": [P, P, P, I, I, I, I, P],

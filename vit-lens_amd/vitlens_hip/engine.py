@@ -28,6 +28,8 @@ class TowerCfg:
     embed_dim: int = 768
     in_chans: int = 3
     quick_gelu: bool = False     # the blocks' MLP activation: QuickGELU x * sigmoid(1.702 x) (OpenAI-pretrained CLIP) instead of erf-GELU
+    ln_eps: float = 1e-5         # eps of every LayerNorm of the tower (the EVA ViT: 1e-6)
+    pre_norm: bool = True        # the tower has ln_pre behind [cls; tokens] + pos (the EVA ViT has none: pos_embed, then block 0)
 
 
 @dataclass
@@ -39,6 +41,7 @@ class TextCfg:
     layers: int = 12
     embed_dim: int = 768
     quick_gelu: bool = False     # as TowerCfg.quick_gelu
+    ln_eps: float = 1e-5         # as TowerCfg.ln_eps (every CLIP text tower: 1e-5)
 
 
 def _pad64(n):
@@ -282,7 +285,7 @@ def cls_rows(x2d, B, L):
     return x2d.as_strided((B, D), (L * D, 1), x2d.storage_offset())
 
 
-def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, ar):
+def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, ar, eps=1e-5):
     """The pruned last block behind its in-projection (see PRUNE_LAST_BLOCK; bf16 stream): single-query attention, out_proj +
     residual, ln_2, c_fc + activation and c_proj + residual on the B class rows b*L of x0 / x1 / x2 (row-strided views, no
     copy); the other rows of x1 and x2 and the full-size a / hid / u are neither written nor read."""
@@ -290,12 +293,13 @@ def _cls_tail_forward(w, s: BlockSlots, B, L, D, H, act, ar):
     m2, r2 = s.stats2c or (None, None)
     ops.attn_fwd_q1(s.q, s.k, s.v, s.a1, lse=s.lse1, qrow=0, qscale=(D // H) ** -0.5 * ops.LOG2E)
     ar.linear(s.a1, w["out_w"], w["out_b"], x1c, res=x0c)
-    ar.ln(x1c, w["ln2_w"], w["ln2_b"], s.h2c, B, D, x_row_stride=L * D, mean=m2, rstd=r2)
+    ar.ln(x1c, w["ln2_w"], w["ln2_b"], s.h2c, B, D, x_row_stride=L * D, mean=m2, rstd=r2, eps=eps)
     ar.linear(s.h2c, w["fc_w"], w["fc_b"], s.hid1, act=act, out2=s.u1)
     ar.linear(s.hid1, w["proj_w"], w["proj_b"], x2c, res=x1c)
 
 
-def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_folded, cls_only=False, write_out=True, mm=0):
+def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_folded, cls_only=False, write_out=True, mm=0,
+                  eps=1e-5):
     """One pre-LN ResidualAttentionBlock (transformer.py:254-272) with the operands `w` on the buffers `s` in the arithmetic
     `ar` (Bf16Arith, Bf16x2Arith, F16Arith, f32.F32Arith: ln / linear / attn):
     x1 = x0 + out_proj(attn(in_proj(ln_1(x0)))), x2 = x1 + c_proj(act(c_fc(ln_2(x1)))).  The one forward of the engines and
@@ -309,6 +313,7 @@ def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_fo
     cls_only: the caller reads only the class-token rows b*L of x2 - dense up to the in-projection, then _cls_tail_forward.
     write_out=False (the recompute in front of a block's backward, which does not need x2): c_proj is skipped.
     mm: the rows of x0 whose partial sums are in s.part (what the block before returned; 0: the statistics come from the rows).
+    eps: of ln_1 and ln_2 (TowerCfg / TextCfg: 1e-5; the EVA ViT's 1e-6), the folded form's row statistics included.
     Returns the rows of x2 whose partial sums it left in s.part."""
     rows = B * L
     m1, r1, m2, r2 = s.stats or (None,) * 4
@@ -317,16 +322,16 @@ def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_fo
         """out = act(Linear(LayerNorm(x))) for the pair (ln, lin) of w; mm rows of x have their partial sums in s.part."""
         ln_w, ln_b, lin_w, lin_b = w[ln + "_w"], w[ln + "_b"], w[lin + "_w"], w[lin + "_b"]
         if not folded:
-            ar.ln(x, ln_w, ln_b, h, rows, D, mean=mean, rstd=rstd)
+            ar.ln(x, ln_w, ln_b, h, rows, D, mean=mean, rstd=rstd, eps=eps)
             ar.linear(h, lin_w, lin_b, out, act=act, out2=out2)
             return
         # (the row-statistics launch also writes the LayerNorm output of the GEMM's leftover rows into s.h_left - where all of
         # them are rows whose statistics it computes from the rows themselves)
         r = ops.fold_rows(x, out, out.shape[1])
         k = dict(ln_w=ln_w, ln_b=ln_b, h_left=s.h_left, h_row0=r) if mm <= r else {}
-        ops.ln_row_stats(s.part, x, mm, mean, rstd, **k)
-        ops.gemm_lnfold(x, w[lin + "_f"], mean, rstd, out, lin_w, lin_b, ln_w, ln_b, s.h_left, act=act, out2=out2, cfg=ar.cfg,
-                        h_ready=bool(k))
+        ops.ln_row_stats(s.part, x, mm, mean, rstd, eps=eps, **k)
+        ops.gemm_lnfold(x, w[lin + "_f"], mean, rstd, out, lin_w, lin_b, ln_w, ln_b, s.h_left, act=act, out2=out2, eps=eps,
+                        cfg=ar.cfg, h_ready=bool(k))
 
     def linear_res(a, lin, out, res, leave_sums):
         """out = res + Linear(a); returns the rows of out whose partial sums it left in s.part."""
@@ -337,7 +342,7 @@ def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_fo
 
     ln_linear(s.x0, mm, m1, r1, "ln1", "in", s.h1, s.qkv)
     if cls_only:
-        _cls_tail_forward(w, s, B, L, D, H, act, ar)
+        _cls_tail_forward(w, s, B, L, D, H, act, ar, eps)
         return 0
     ar.attn(s.q, s.k, s.v, s.a, s.lse, D // H, causal)
     mm = linear_res(s.a, "out", s.x1, s.x0, folded)
@@ -350,13 +355,14 @@ def block_forward(w, s: BlockSlots, B, L, D, H, causal, act, ar, folded, next_fo
     return linear_res(s.hid, "proj", s.x2, s.x1, next_folded)
 
 
-def run_blocks(blocks, ws: _Workspace, B, L, D, H, ar, causal=False, fold=None, quick_gelu=False, pooled_only=False):
+def run_blocks(blocks, ws: _Workspace, B, L, D, H, ar, causal=False, fold=None, quick_gelu=False, pooled_only=False, eps=1e-5):
     """x (ws.x, residual stream) <- N pre-LN transformer blocks (transformer.py:364-371), each one block_forward in place in
     the arithmetic `ar`.
     quick_gelu: the tower's MLP activation (TowerCfg / TextCfg.quick_gelu; `act_layer`, transformer.py:217-231).
     fold (default: engine.LN_FOLD; bf16 stream and operands only): the LayerNorms folded into the GEMMs either side of them.
     pooled_only: the caller reads only the class-token rows b*L of the result (VitEngine.trunk) - the last block then runs on
-    those rows alone where prune_last_ok() allows, and the other rows of ws.x are left as the block before it wrote them."""
+    those rows alone where prune_last_ok() allows, and the other rows of ws.x are left as the block before it wrote them.
+    eps: the blocks' LayerNorm eps (TowerCfg.ln_eps)."""
     prune = prune_last_ok(D, H, ws.x.dtype, L, pooled_only, causal)
     act = ops.mlp_act(quick_gelu)
     if fold is None:
@@ -368,7 +374,7 @@ def run_blocks(blocks, ws: _Workspace, B, L, D, H, ar, causal=False, fold=None, 
     mm = 0                                            # rows of ws.x whose partial sums are in ws.part
     for i, w in enumerate(blocks):
         mm = block_forward(w, ws.slots_folded if folded[i] else ws.slots, B, L, D, H, causal, act, ar, folded[i], folded[i + 1],
-                           cls_only=prune and i + 1 == len(blocks), mm=mm)
+                           cls_only=prune and i + 1 == len(blocks), mm=mm, eps=eps)
 
 
 def _hi_lo(w: torch.Tensor, device):
@@ -404,11 +410,13 @@ class VitEngine:
         self.cls = _dev(sd[prefix + "class_embedding"], device)
         self.pos = _dev(sd[prefix + "positional_embedding"], device)
         self.T = self.pos.shape[0] - 1
-        self.ln_pre = (_dev(sd[prefix + "ln_pre.weight"], device), _dev(sd[prefix + "ln_pre.bias"], device))
+        self.ln_pre = (_dev(sd[prefix + "ln_pre.weight"], device), _dev(sd[prefix + "ln_pre.bias"], device)) if cfg.pre_norm else None
         self.ln_post = (_dev(sd[prefix + "ln_post.weight"], device), _dev(sd[prefix + "ln_post.bias"], device))
         # [E, D]; None = the tower has no output projection (`if self.proj is not None`, transformer.py:783-784;
         # CLIPBindWrap drops it when the feature width differs, VitLens-OpenShape/src/models/clip_bind.py:35-47)
         self.projT = _dev(sd[prefix + "proj"].t(), device, wd) if prefix + "proj" in sd else None
+        # the bias of an output projection that is an nn.Linear (the EVA ViT's `head`, eva_tower_state); CLIP's `proj` has none
+        self.proj_b = _dev(sd[prefix + "proj_bias"], device) if prefix + "proj_bias" in sd else None
         self.blocks = [prep_block(sd, f"{prefix}transformer.resblocks.{i}.", device, wd) for i in range(cfg.layers)]
         self.conv_w = None
         if prefix + "conv1.weight" in sd:
@@ -424,10 +432,12 @@ class VitEngine:
         if "positional_embedding" in top:
             self.pos.copy_(sd[p + "positional_embedding"])
         for nm, pair in (("ln_pre", self.ln_pre), ("ln_post", self.ln_post)):
-            if nm + ".weight" in top or nm + ".bias" in top:
+            if pair is not None and (nm + ".weight" in top or nm + ".bias" in top):
                 pair[0].copy_(sd[p + nm + ".weight"]); pair[1].copy_(sd[p + nm + ".bias"])
         if "proj" in top and self.projT is not None:
             self.projT.copy_(sd[p + "proj"].t())
+        if "proj_bias" in top and self.proj_b is not None:
+            self.proj_b.copy_(sd[p + "proj_bias"])
         if "conv1.weight" in top and self.conv_w is not None:
             self.conv_w.copy_(conv_weight_as_gemm(sd[p + "conv1.weight"], dev, self.math.dtype))
         for l in sorted({int(n.split(".")[2]) for n in names if n.startswith("transformer.resblocks.")}):
@@ -448,11 +458,14 @@ class VitEngine:
         return ops.gemm(cols, self.conv_w, None, epi=ops.EPI_BF16, cfg=self.gemm_cfg)
 
     def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos=True,
-              keep: Optional[torch.Tensor] = None):
+              keep: Optional[torch.Tensor] = None, tokens_out: bool = False):
         """tokens [B*T, D] (bf16|f32; f32 for the fp32 arithmetic) -> un-normalised features f32 [B, E]: [cls; tokens] + pos
         (+ pos2) -> ln_pre -> blocks -> ln_post(cls) @ proj (transformer.py:756-787).
         keep int32 [B,K] (ops.patch_keep): patch dropout of a tower in train mode (PatchDropout, transformer.py:53-90) - the
-        trunk runs on the class token + the kept tokens, L = K + 1.  bf16 operands only: the fp32 engines are eval-only."""
+        trunk runs on the class token + the kept tokens, L = K + 1.  bf16 operands only: the fp32 engines are eval-only.
+        A tower without ln_pre (cfg.pre_norm False: the EVA ViT) enters block 0 with [cls; tokens] + pos (+ pos2) itself.
+        tokens_out: return the [B, L, D] stream behind the last block and in front of ln_post instead (a copy, in the residual
+        dtype) - what the EVA ViT's forward_features returns and an MLLM's ln_vision reads; the last block then runs on all rows."""
         cfg, ar = self.cfg, self.math
         if keep is not None and ar.dtype != torch.bfloat16:
             raise NotImplementedError("trunk: patch dropout (keep=) is a train-mode forward; the fp32 engines are eval-only")
@@ -460,21 +473,142 @@ class VitEngine:
         L = T + 1 if keep is None else keep.shape[1] + 1
         ws = self.workspace(B, L)
         pos = self.pos if use_orig_pos else torch.zeros_like(self.pos)
-        if keep is None:
-            ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
+        if not cfg.pre_norm:
+            if keep is not None:
+                raise NotImplementedError("trunk: patch dropout on a tower without ln_pre (vl_assemble_tokens is the dense form only)")
+            ops.assemble_tokens(tokens, self.cls, pos, pos2, ws.x[:B * L], B, T, D)
+        elif keep is None:
+            ops.assemble_ln_pre(tokens, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D, eps=cfg.ln_eps)
         else:
-            ops.assemble_ln_pre_keep(tokens, keep, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D)
+            ops.assemble_ln_pre_keep(tokens, keep, self.cls, pos, pos2, self.ln_pre[0], self.ln_pre[1], ws.x, B, T, D, eps=cfg.ln_eps)
         # (only the class-token rows are read below: the last block may run on them alone)
-        run_blocks(self.blocks, ws, B, L, D, cfg.heads, ar, quick_gelu=cfg.quick_gelu, pooled_only=True)
+        run_blocks(self.blocks, ws, B, L, D, cfg.heads, ar, quick_gelu=cfg.quick_gelu, pooled_only=not tokens_out, eps=cfg.ln_eps)
+        if tokens_out:
+            return ws.x[:B * L].view(B, L, D).clone()
         # (a tower without output projection: ln_post of the class rows IS the feature, fp32)
         pooled = torch.empty(B, D, device=self.device, dtype=torch.float32 if self.projT is None else ar.dtype)
-        ar.ln(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D)
-        return pooled if self.projT is None else ar.linear_f32(pooled, self.projT, None)
+        ar.ln(ws.x, self.ln_post[0], self.ln_post[1], pooled, B, D, x_row_stride=L * D, eps=cfg.ln_eps)
+        return pooled if self.projT is None else ar.linear_f32(pooled, self.projT, self.proj_b)
 
     def encode_image(self, image: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None) -> torch.Tensor:
         B = image.shape[0]
         f = self.trunk(self.patch_tokens(image), B, keep=keep)
         return ops.l2_normalize(f) if normalize else f
+
+
+# ------------------------------------------------------------------------------------------------
+# The BLIP-2 / InstructBLIP EVA ViT-g as a tower (visual_arch "perceiver_blip_eva_g_vit"): width 1408 = 16 heads x 88, MLP hidden
+# int(1408 * 4.3637) = 6144, 40 blocks, LayerNorm eps 1e-6, no ln_pre, a qkv bias on q and v only.  Its blocks are pre-LN
+# residual blocks with an erf-GELU MLP, so they run on block_forward as they are: only the NAMES differ.
+# ------------------------------------------------------------------------------------------------
+_EVA_BLOCK = {"norm1.weight": "ln_1.weight", "norm1.bias": "ln_1.bias", "attn.qkv.weight": "attn.in_proj_weight",
+              "attn.proj.weight": "attn.out_proj.weight", "attn.proj.bias": "attn.out_proj.bias",
+              "norm2.weight": "ln_2.weight", "norm2.bias": "ln_2.bias", "mlp.fc1.weight": "mlp.c_fc.weight",
+              "mlp.fc1.bias": "mlp.c_fc.bias", "mlp.fc2.weight": "mlp.c_proj.weight", "mlp.fc2.bias": "mlp.c_proj.bias"}
+
+
+def eva_tower_cfg(width=1408, layers=40, heads=16, embed_dim=768, mlp_ratio=4.3637, **kw) -> TowerCfg:
+    """TowerCfg of an EVA ViT: eps 1e-6, no ln_pre (defaults: ViT-g as BLIP-2 ships it, 40 blocks)."""
+    return TowerCfg(width=width, layers=layers, heads=heads, mlp_ratio=mlp_ratio, embed_dim=embed_dim, ln_eps=1e-6, pre_norm=False, **kw)
+
+
+def eva_tower_state(sd: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
+    """The operands VitEngine and prep_block take, under VitEngine's names and the same `prefix`, out of a
+    Perceiver_Blip_EVA_ViT state_dict (`prefix`eva_vit.* and `prefix`eva_vit_proj):
+    cls_token [1,1,D] -> class_embedding [D]; pos_embed [1,L,D] -> positional_embedding [L,D] (absent under disable_orig_pos:
+    zeros would be wrong silently, so the caller passes use_orig_pos=False and the table is sized from cls_token - see below);
+    blocks.N.{norm1,norm2} -> ln_1 / ln_2; attn.qkv.weight -> in_proj_weight; cat(q_bias, 0, v_bias) -> in_proj_bias (zeros
+    where the block has no qkv bias); attn.proj -> out_proj; mlp.fc1 / fc2 -> c_fc / c_proj; norm -> ln_post; the output
+    projection: eva_vit_proj [D,E] -> proj, or eva_vit.head (nn.Linear(D, E), `--use_eva_pt_lin`) -> proj = weight^T and
+    proj_bias.  Views where a view does (no copy of a 1408 x 6144 weight); everything else of `sd` under `prefix` (the Lens:
+    visual_adapter.*, perceiver.*) is passed through."""
+    e = prefix + "eva_vit."
+    if e + "cls_token" not in sd:
+        raise KeyError(f"eva_tower_state: no {e}cls_token in the state_dict (is the prefix right?)")
+    out = {k: v for k, v in sd.items() if k.startswith(prefix) and not k.startswith((e, prefix + "eva_vit_proj"))}
+    D = sd[e + "cls_token"].shape[-1]
+    out[prefix + "class_embedding"] = sd[e + "cls_token"].reshape(D)
+    if e + "pos_embed" in sd:
+        out[prefix + "positional_embedding"] = sd[e + "pos_embed"].reshape(-1, D)
+    out[prefix + "ln_post.weight"], out[prefix + "ln_post.bias"] = sd[e + "norm.weight"], sd[e + "norm.bias"]
+    if prefix + "eva_vit_proj" in sd:                      # a Parameter [D, E], no bias
+        out[prefix + "proj"] = sd[prefix + "eva_vit_proj"]
+    elif e + "head.weight" in sd:                          # nn.Linear(D, E): y = x W^T + b
+        out[prefix + "proj"] = sd[e + "head.weight"].t()
+        out[prefix + "proj_bias"] = sd[e + "head.bias"]
+    n = 0
+    while f"{e}blocks.{n}.norm1.weight" in sd:
+        src, dst = f"{e}blocks.{n}.", f"{prefix}transformer.resblocks.{n}."
+        for a, b in _EVA_BLOCK.items():
+            out[dst + b] = sd[src + a]
+        w = sd[src + "attn.qkv.weight"]
+        if src + "attn.q_bias" in sd:
+            q, v = sd[src + "attn.q_bias"], sd[src + "attn.v_bias"]
+            out[dst + "attn.in_proj_bias"] = torch.cat([q.detach(), torch.zeros_like(v), v.detach()])
+        else:
+            out[dst + "attn.in_proj_bias"] = torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
+        n += 1
+    return out
+
+
+def eva_param_names(names) -> list:
+    """Parameter names of a Perceiver_Blip_EVA_ViT (relative to its prefix) -> the names VitEngine.update_params and the
+    trainers use (eva_tower_state's); Lens names pass through."""
+    top = {"eva_vit.cls_token": "class_embedding", "eva_vit.pos_embed": "positional_embedding", "eva_vit.norm.weight": "ln_post.weight",
+           "eva_vit.norm.bias": "ln_post.bias", "eva_vit_proj": "proj", "eva_vit.head.weight": "proj", "eva_vit.head.bias": "proj_bias",
+           "eva_vit_proj.weight": "proj", "eva_vit_proj.bias": "proj_bias"}
+    out = []
+    for n in names:
+        if n in top:
+            out.append(top[n])
+        elif n.startswith("eva_vit.blocks."):
+            _, _, l, rest = n.split(".", 3)
+            out.append(f"transformer.resblocks.{l}." + ("attn.in_proj_bias" if rest in ("attn.q_bias", "attn.v_bias") else _EVA_BLOCK[rest]))
+        else:
+            out.append(n)
+    return sorted(set(out))
+
+
+def eva_grads(grads: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
+    """A trainer's gradients under VitEngine's names -> under the module's (the inverse of eva_tower_state on the names):
+    the packed in_proj_bias gradient splits into q_bias and v_bias (the k third belongs to no parameter)."""
+    inv = {v: k for k, v in _EVA_BLOCK.items()}
+    top = {"class_embedding": "eva_vit.cls_token", "positional_embedding": "eva_vit.pos_embed", "ln_post.weight": "eva_vit.norm.weight",
+           "ln_post.bias": "eva_vit.norm.bias", "proj": "eva_vit_proj"}
+    out = {}
+    for k, g in grads.items():
+        n = k[len(prefix):]
+        if not k.startswith(prefix):
+            out[k] = g
+        elif n in top:
+            out[prefix + top[n]] = g.view(1, 1, -1) if n == "class_embedding" else g.unsqueeze(0) if n == "positional_embedding" else g
+        elif n.startswith("transformer.resblocks."):
+            _, _, l, rest = n.split(".", 3)
+            b = f"{prefix}eva_vit.blocks.{l}."
+            if rest == "attn.in_proj_bias":
+                Dm = g.numel() // 3
+                out[b + "attn.q_bias"], out[b + "attn.v_bias"] = g[:Dm], g[2 * Dm:]
+            else:
+                out[b + inv[rest]] = g
+        else:
+            out[k] = g
+    return out
+
+
+class EvaVitEngine(VitEngine):
+    """VitEngine over the EVA ViT of a Perceiver_Blip_EVA_ViT state_dict: the same trunk on the same run_blocks, operands and
+    updates through eva_tower_state.  cfg: eva_tower_cfg(...) - pre_norm False, ln_eps 1e-6."""
+
+    def __init__(self, sd, prefix: str, cfg: TowerCfg, device, **kw):
+        if cfg.pre_norm:
+            raise ValueError("EvaVitEngine: the EVA ViT has no ln_pre - build the TowerCfg with pre_norm=False (eva_tower_cfg)")
+        m = eva_tower_state(sd, prefix)
+        if prefix + "positional_embedding" not in m:       # disable_orig_pos deleted the table: the trunk is then run without it
+            m[prefix + "positional_embedding"] = torch.zeros(kw.get("n_tokens") or 257, cfg.width)
+        super().__init__(m, prefix, cfg, device, **kw)
+
+    def update_params(self, sd, names):
+        super().update_params(eva_tower_state(sd, self.prefix), eva_param_names(names))
 
 
 # The text feature is ln_final(x[b, argmax(text[b])]) @ text_projection (model.py:528-540) out of a CAUSAL tower: row t depends on
@@ -542,10 +676,10 @@ def text_features(e, ar, ws: _Workspace, text: torch.Tensor, plan: Optional[Text
         ops.text_embed_packed(text, plan.start, plan.lens, e.tok, e.pos, ws.x, plan.rows, Mr)
         index, mul = plan.last_row, 0                                      # src = r * 0 + last_row[r]
         layout, out = (ws.packed(Mr), 1, plan.rows), ws.f                  # (one sequence of plan.rows rows)
-    run_blocks(e.blocks, *layout, D, cfg.heads, ar, causal=True, fold=False, quick_gelu=cfg.quick_gelu)
+    run_blocks(e.blocks, *layout, D, cfg.heads, ar, causal=True, fold=False, quick_gelu=cfg.quick_gelu, eps=cfg.ln_eps)
     # the pooled rows: two-term [B, 2D]; fp16 in the workspace, padded to whole row tiles of zeros
     pooled = ws.pooled if ws.pooled is not None else torch.empty(B, ws.h.shape[1], device=e.device, dtype=ar.dtype)
-    ar.ln(ws.x, e.ln_final[0], e.ln_final[1], pooled, B, D, x_row_stride=D, row_index=index, row_mul=mul)
+    ar.ln(ws.x, e.ln_final[0], e.ln_final[1], pooled, B, D, x_row_stride=D, row_index=index, row_mul=mul, eps=cfg.ln_eps)
     return ar.linear_f32(pooled, e.projT, None, out)[:B]
 
 
@@ -989,7 +1123,9 @@ class LensEngine:
 
     def __init__(self, sd, prefix: str, tower: TowerCfg, lens: LensCfg, device, res_dtype=torch.float32, gemm_cfg=-1):
         self.tower, self.lens, self.device, self.gemm_cfg = tower, lens, torch.device(device), gemm_cfg
-        self.vit = VitEngine(sd, prefix, tower, device, res_dtype=res_dtype, gemm_cfg=gemm_cfg)
+        # a tower without ln_pre is the EVA ViT of a Perceiver_Blip_EVA_ViT (its state_dict names, eva_tower_state)
+        eva = {} if tower.pre_norm else {"n_tokens": lens.num_latents + 1}
+        self.vit = (EvaVitEngine if eva else VitEngine)(sd, prefix, tower, device, res_dtype=res_dtype, gemm_cfg=gemm_cfg, **eva)
         a = prefix + "visual_adapter."
         self.prefix_adapter = a
         self.adapter_pos = None
@@ -1016,7 +1152,7 @@ class LensEngine:
     def update_params(self, sd, prefix: str, names):
         """In-place refresh after the parameters `names` (relative to `prefix`) changed, e.g. by an optimizer step."""
         L, a = self.lens, prefix + "visual_adapter."
-        self.vit.update_params(sd, [n for n in names if not n.startswith(("visual_adapter.", "perceiver."))])
+        self.vit.update_params(sd, [n for n in names if not n.startswith(("visual_adapter.", "perceiver."))])    # (EVA names: EvaVitEngine maps them)
         if any(n.startswith("visual_adapter.") for n in names):
             scale = 0.0 if L.disable_adapter_pos else 1.0
             if L.modality in ("depth", "audio"):
@@ -1046,10 +1182,17 @@ class LensEngine:
         return ops.gemm(self.cols(x), self.conv_w, self.conv_b, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
 
     def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None,
-               drop: Optional[LensDrop] = None, **kw) -> torch.Tensor:
+               drop: Optional[LensDrop] = None, tokens_out: bool = False, **kw) -> torch.Tensor:
         """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk).
-        drop (PerceiverEngine.draw): the Perceiver's dropout of a train-mode forward without autograd."""
+        drop (PerceiverEngine.draw): the Perceiver's dropout of a train-mode forward without autograd.
+        tokens_out: the trunk's [B, L, D] token stream instead of the pooled feature (VitEngine.trunk)."""
         B = x.shape[0]
+        if tokens_out:
+            if normalize:
+                raise ValueError("LensEngine.encode: tokens_out returns the un-pooled stream, there is nothing to normalise")
+            trunk = lambda *a, **k: self.vit.trunk(*a, tokens_out=True, **k)
+        else:
+            trunk = self.vit.trunk
         if self.lens.modality == "pc":
             pend = getattr(self, "_points_pending", None)
             if pend is not None:
@@ -1058,15 +1201,15 @@ class LensEngine:
                 self._points_pending = None
             tok = self.points.forward(x, **kw)                 # already x + pos, [B*G, C] bf16
             lat = self.perceiver.forward(tok, B, drop)
-            f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
+            f = trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         else:
             tok, pos = self.tokens(x)
             if self.perceiver is None:
-                f = self.vit.trunk(tok, B, pos2=pos, use_orig_pos=self.lens.use_orig_pos, keep=keep)
+                f = trunk(tok, B, pos2=pos, use_orig_pos=self.lens.use_orig_pos, keep=keep)
             else:
                 T = tok.shape[0] // B
                 xin = torch.empty_like(tok)
                 ops.add_rows(tok, pos, xin, tok.shape[0], T, tok.shape[1])
                 lat = self.perceiver.forward(xin, B, drop)
-                f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
+                f = trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         return ops.l2_normalize(f) if normalize else f

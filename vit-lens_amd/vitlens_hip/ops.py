@@ -525,6 +525,24 @@ def assemble_ln_pre(tokens, cls, pos, pos2, w, b, out, B, T, D, eps=1e-5, xpre=N
     return out
 
 
+def assemble_tokens(tokens, cls, pos, pos2, out, B, T, D, xpre=None):
+    """out [B*(T+1), D] (f32 | bf16) = [cls ; tokens] + pos (+ pos2 on rows 1..T): assemble_ln_pre without the LayerNorm, for a
+    tower that has no ln_pre (the EVA ViT).  xpre: optional f32 copy of the rows."""
+    for name, t in (("tokens", tokens), ("out", out)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"assemble_tokens: {name} must be f32 or bf16, got {t.dtype}")
+    for name, t in (("cls", cls), ("pos", pos), ("pos2", pos2), ("xpre", xpre)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"assemble_tokens: {name} must be f32, got {t.dtype}")
+    if tokens.numel() != B * T * D or out.numel() != B * (T + 1) * D or cls.numel() != D or pos.numel() != (T + 1) * D:
+        raise ValueError("assemble_tokens: tokens [B,T,D], cls [D], pos [T+1,D] and out [B*(T+1),D] do not fit B, T, D")
+    if (pos2 is not None and pos2.numel() != T * D) or (xpre is not None and xpre.numel() != out.numel()):
+        raise ValueError("assemble_tokens: pos2 is [T,D] and xpre [B*(T+1),D]")
+    check(_lib.vl_assemble_tokens(_p(tokens), _dt(tokens), _p(cls), _p(pos), _p(pos2), _p(out), _dt(out), _p(xpre), B, T, D,
+                                  _stream()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ patch dropout
 PATCH_KEEP_MAX_T = 4096
 

@@ -169,12 +169,16 @@ class TowerTrainer:
             raise ValueError(f"TowerTrainer.forward: keep [B,K] / inv [B,T] do not fit B={B}, T={T}: {tuple(keep.shape)}, {tuple(inv.shape)}")
         L = T + 1 if keep is None else keep.shape[1] + 1
         S = self.saved(B, L)
-        cfg = e.gemm_cfg
-        if keep is None:
-            ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
+        cfg, eps = e.gemm_cfg, e.cfg.ln_eps
+        if not e.cfg.pre_norm:          # a tower without ln_pre (the EVA ViT): block 0 reads [cls; tokens] + pos (+ pos2) itself
+            if keep is not None:
+                raise NotImplementedError("TowerTrainer.forward: patch dropout on a tower without ln_pre (vl_assemble_tokens is dense only)")
+            ops.assemble_tokens(tokens, e.cls, e.pos, pos2, S.X[0], B, T, D)
+        elif keep is None:
+            ops.assemble_ln_pre(tokens, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D, eps=eps,
                                 xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
         else:
-            ops.assemble_ln_pre_keep(tokens, keep, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D,
+            ops.assemble_ln_pre_keep(tokens, keep, e.cls, e.pos, pos2, e.ln_pre[0], e.ln_pre[1], S.X[0], B, T, D, eps=eps,
                                      xpre=S.xpre, mean=S.pre_stats[0], rstd=S.pre_stats[1])
         self._drop = None if keep is None else (T, inv)
         # only the class rows of the last block's output are read (ln_post below, and its backward)
@@ -184,11 +188,11 @@ class TowerTrainer:
             mm = self._block_forward(S, l, B, L, cls_only=self._pruned and l == self.layers - 1, mm=mm)
         xl = S.X[2 * self.layers]
         ops.layernorm(xl, e.ln_post[0], e.ln_post[1], S.pooled, B, D, x_row_stride=L * D,
-                      mean=S.post_stats[0], rstd=S.post_stats[1])
+                      mean=S.post_stats[0], rstd=S.post_stats[1], eps=eps)
         if e.projT is None:          # features = ln_post(cls) itself (bf16 activation, returned as f32)
             feat = S.pooled.float()
-        else:
-            feat = ops.gemm(S.pooled, e.projT, None, epi=ops.EPI_F32, cfg=cfg)
+        else:                        # (proj_b: the bias of an nn.Linear head - frozen in every recipe, it only enters the forward)
+            feat = ops.gemm(S.pooled, e.projT, getattr(e, "proj_b", None), epi=ops.EPI_F32, cfg=cfg)
         self.ctx = (B, L, tokens, pos2 is not None)
         return feat
 
@@ -205,7 +209,7 @@ class TowerTrainer:
             return bool(_engine.LN_FOLD and S.part is not None and k < self.layers and "in_f" in e.blocks[k]
                         and k not in self.train_blocks)
         return _engine.block_forward(e.blocks[l], S.slots[l], B, L, self.D, self.H, self.causal, self.act_dsave, e.math,
-                                     folds(l), folds(l + 1), cls_only=cls_only, write_out=write_out, mm=mm)
+                                     folds(l), folds(l + 1), cls_only=cls_only, write_out=write_out, mm=mm, eps=e.cfg.ln_eps)
 
     # ------------------------------------------------------------------------------------------ backward
     def _dw(self, name, dy, x, bias_name=None):
@@ -250,11 +254,15 @@ class TowerTrainer:
                               dx=S.dx, x_row_stride=L * D, dx_row_stride=L * D)
         self._blocks_backward(S, B, L, on_block_done, cls_only=self._pruned)
         # ---- ln_pre and the [cls; tokens] + pos assembly ----
-        dxpre = torch.empty(S.dx.shape, device=S.dx.device, dtype=torch.float32)
-        if self.train_ln_pre:
-            ops.layernorm_bwd_params(S.dx, S.xpre, S.pre_stats[0], S.pre_stats[1], self.grad_buffer(P + "ln_pre.weight", e.ln_pre[0]),
-                                     self.grad_buffer(P + "ln_pre.bias", e.ln_pre[1]), rows, D)
-        ops.layernorm_bwd(S.dx, S.xpre, S.pre_stats[0], S.pre_stats[1], e.ln_pre[0], rows, D, dx=dxpre)
+        if not e.cfg.pre_norm:
+            # no ln_pre: the gradient of block 0's input IS the gradient of the assembled rows (fp32 for the reductions below)
+            dxpre = S.dx.float() if S.dx.dtype != torch.float32 else S.dx.clone()
+        else:
+            dxpre = torch.empty(S.dx.shape, device=S.dx.device, dtype=torch.float32)
+            if self.train_ln_pre:
+                ops.layernorm_bwd_params(S.dx, S.xpre, S.pre_stats[0], S.pre_stats[1], self.grad_buffer(P + "ln_pre.weight", e.ln_pre[0]),
+                                         self.grad_buffer(P + "ln_pre.bias", e.ln_pre[1]), rows, D)
+            ops.layernorm_bwd(S.dx, S.xpre, S.pre_stats[0], S.pre_stats[1], e.ln_pre[0], rows, D, dx=dxpre)
         if self.train_cls:
             ops.batch_rowsum(dxpre, self.grad_buffer(P + "class_embedding", e.cls).view(1, D), B, 1, D, L, 0)
         self.dxpre = dxpre
@@ -417,7 +425,8 @@ class _TextAsTower:
     def __init__(self, te):
         from types import SimpleNamespace
         c = te.cfg
-        self.cfg = SimpleNamespace(width=c.width, heads=c.heads, mlp_ratio=4.0, layers=c.layers, quick_gelu=c.quick_gelu)
+        self.cfg = SimpleNamespace(width=c.width, heads=c.heads, mlp_ratio=4.0, layers=c.layers, quick_gelu=c.quick_gelu,
+                                   ln_eps=c.ln_eps, pre_norm=False)
         self.device, self.res_dtype, self.gemm_cfg, self.math = te.device, torch.float32, te.gemm_cfg, te.math
         self.blocks, self.projT, self.ln_post = te.blocks, te.projT, te.ln_final
         self.tok, self.pos = te.tok, te.pos
@@ -449,7 +458,7 @@ class TextTowerTrainer(TowerTrainer):
             mm = self._block_forward(S, l, B, L, mm=mm)
         eot = text.argmax(dim=-1).contiguous()            # index-exact EOT position (model.py:539)
         ops.layernorm(S.X[2 * self.layers], e.ln_post[0], e.ln_post[1], S.pooled, B, D, x_row_stride=D, row_index=eot, row_mul=L,
-                      mean=S.post_stats[0], rstd=S.post_stats[1])
+                      mean=S.post_stats[0], rstd=S.post_stats[1], eps=e.cfg.ln_eps)
         feat = ops.gemm(S.pooled, e.projT, None, epi=ops.EPI_F32, cfg=e.gemm_cfg)
         self.ctx = (B, L, text, eot)
         return feat
@@ -896,6 +905,7 @@ def refresh_trainer(tr, sd, names):
     """After the engine under trainer `tr` was updated in place for the parameters `names` (relative to the tower prefix):
     refresh what the trainer derived from them - transposed weights, the point tokenizer's masters - keeping the trainer
     and its activation buffers (a rebuild re-allocates tens of GB at ViT-L size)."""
+    names = _engine.eva_param_names(names)      # (a no-op on the CLIP tower's names)
     tower = getattr(tr, "tower", None)
     if tower is not None:
         tower.refresh_derived({int(n.split(".")[2]) for n in names if n.startswith("transformer.resblocks.")}, "proj" in names)
