@@ -795,7 +795,23 @@ typedef struct vl_adamw_slot {
  * grad_scale * sqrt(sumsq).  max_norm > 0. */
 int vl_adamw_multi_step(const vl_adamw_slot* slots, int nslots, float lr, float beta1, float beta2, float eps, int step,
                         float grad_scale, float max_norm, const float* sumsq, float* norm_out, hipStream_t stream);
+/* What vl_adamw_multi_step_groups adds to slot s of the table, in an array of its own beside it (8 bytes per tensor). */
+typedef struct vl_adamw_group {
+  float lr_scale;                               /* the tensor steps with lr * lr_scale (parameter groups with their own lr) */
+  int no_clip;                                  /* 1: outside clip_grad_norm_'s parameter list - the tensor sees coef = 1 */
+} vl_adamw_group;
+/* vl_adamw_multi_step with parameter groups: slot s steps with lr * groups[s].lr_scale (an fp32 product), and a slot with
+ * no_clip set is updated with coef = 1.  sumsq is then the squared norm of the gradients of the CLIPPED tensors only (lay them
+ * out contiguously and it is one vl_sumsq_f32 call); norm_out receives grad_scale * sqrt(sumsq), the unclipped norm of that set.
+ * groups: DEVICE array of nslots entries, read per slot like weight_decay; groups_host: the HOST array the caller uploaded it
+ * from, which this entry checks (lr_scale finite and >= 0, no_clip 0 or 1) before anything is launched - the device is never
+ * read back.  With every lr_scale == 1.0f and no exempt tensor the results are the bits of vl_adamw_multi_step. */
+int vl_adamw_multi_step_groups(const vl_adamw_slot* slots, const vl_adamw_group* groups, const vl_adamw_group* groups_host,
+                               int nslots, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                               float max_norm, const float* sumsq, float* norm_out, hipStream_t stream);
 int vl_clamp_scalar(float* p, float lo, float hi, hipStream_t stream);
+/* p[i] = value for i < n (fp32; the accumulators of a step start from zero without a framework fill). */
+int vl_fill_f32(float* p, float value, long n, hipStream_t stream);
 int vl_axpy_f32(float* y, const float* x, float alpha, long n, hipStream_t stream);
 /* out[i] = x[i] * exp(log_scale[0]) * mul (in place allowed): `logit_scale.exp()` (open_clip/model.py:619, loss.py:125-127)
  * applied on the device, so that a training step never reads the temperature on the host (hipGraph-capturable). */

@@ -5,6 +5,7 @@
 //   vl_adamw_step         torch.optim.AdamW update (decoupled weight decay), one launch per tensor
 //   vl_sumsq_f32          squared 2-norm of the flat gradient buffer: two stages, fp64 partials, bit-reproducible
 //   vl_adamw_multi_step   the same update on a device table of tensors in ONE launch, with clip_grad_norm_'s coefficient
+//   vl_adamw_multi_step_groups   the same launch with a learning-rate scale per tensor and tensors exempt from clipping
 //                         derived on the device from that squared norm (training/train.py: --grad-clip-norm)
 //   vl_clamp_scalar       logit_scale.clamp_(0, ln 100)   (training/train.py:248-249)
 // Autograd counterparts of open_clip/transformer.py:17-34 (LayerNorm), :226-234 (MLP) and of
@@ -233,8 +234,13 @@ __device__ __forceinline__ float clip_coef(const float norm, const float max_nor
   return c > 1.0f ? 1.0f : c;
 }
 
-__global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* slots, int nslots, AdamwC c, float gscale,
-                                                          float max_norm, const float* sumsq, float* norm_out) {
+// GROUPS (vl_adamw_multi_step_groups): slot s steps with lr * groups[s].lr_scale, and a slot with groups[s].no_clip set sees
+// coef = 1 - read per slot beside weight_decay.  lr * 1.0f is lr, so a table of ones with no exempt slot gives the bits of the
+// instantiation without groups, which compiles from the same source as before.
+template <bool GROUPS>
+__global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* slots, const vl_adamw_group* groups, int nslots,
+                                                          AdamwC c, float gscale, float max_norm, const float* sumsq,
+                                                          float* norm_out) {
   // first[s] = index of slot s's first tile; wave 0 scans the tile counts (16 consecutive slots per lane)
   __shared__ int first[VL_ADAMW_MAX_SLOTS + 1];
   if (threadIdx.x < 64) {
@@ -277,6 +283,13 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* s
     const int cntE = (int)min((long)kAdamTile, S.n - base);
     float* p = S.p + base; const float* g = S.g + base; float* m = S.m + base; float* v = S.v + base;
     const float wd = S.weight_decay;
+    AdamwC cs = c;
+    float gm = gmul;
+    if (GROUPS) {
+      const vl_adamw_group G = groups[lo];
+      cs.lr = c.lr * G.lr_scale;
+      if (G.no_clip) gm = 1.0f;
+    }
     const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
     const int nvec = vec ? (cntE >> 2) : 0;
     for (int i = threadIdx.x; i < nvec; i += 256) {
@@ -285,14 +298,14 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* s
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pp[e], me = mm[e], ve = vv[e];
-        adamw_update(pe, gg[e] * gscale * gmul, me, ve, c, wd);
+        adamw_update(pe, gg[e] * gscale * gm, me, ve, cs, wd);
         pp[e] = pe; mm[e] = me; vv[e] = ve;
       }
       ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)p)[i] = pp;
     }
     for (int i = nvec * 4 + threadIdx.x; i < cntE; i += 256) {
       float pe = p[i], me = m[i], ve = v[i];
-      adamw_update(pe, g[i] * gscale * gmul, me, ve, c, wd);
+      adamw_update(pe, g[i] * gscale * gm, me, ve, cs, wd);
       m[i] = me; v[i] = ve; p[i] = pe;
     }
   }
@@ -300,6 +313,11 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const vl_adamw_slot* s
 
 // (fminf / fmaxf return the other operand for a NaN: a diverged logit_scale would come out as lo.  torch.clamp_ keeps the NaN)
 __global__ void clamp_scalar_kernel(float* p, float lo, float hi) { const float v = *p; *p = v != v ? v : fminf(fmaxf(v, lo), hi); }
+
+// p[i] = value: the accumulators of a step (loss terms, hit counters - the bits of 0.0f are those of int 0) start from zero
+__global__ void __launch_bounds__(256) fill_kernel(float* p, float value, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = value;
+}
 
 // out[i] = a[i] + b[i] (f32), used to merge gradient contributions of shared tensors
 __global__ void __launch_bounds__(256) axpy_kernel(float* y, const float* x, float alpha, long n) {
@@ -450,13 +468,45 @@ extern "C" int vl_adamw_multi_step(const vl_adamw_slot* slots, int nslots, float
   if (nslots == 0) return 0;
   const AdamwC c{lr, beta1, beta2, eps, 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step))};
   // the table lives on the device: the grid cannot follow the element count, the tiles are dealt round-robin to 2048 workgroups
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(2048), dim3(256), 0, stream, slots, nslots, c, grad_scale, max_norm, sumsq, norm_out);
+  hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3(2048), dim3(256), 0, stream, slots, (const vl_adamw_group*)nullptr, nslots, c,
+                     grad_scale, max_norm, sumsq, norm_out);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int vl_adamw_multi_step_groups(const vl_adamw_slot* slots, const vl_adamw_group* groups,
+                                          const vl_adamw_group* groups_host, int nslots, float lr, float beta1, float beta2,
+                                          float eps, int step, float grad_scale, float max_norm, const float* sumsq,
+                                          float* norm_out, hipStream_t stream) {
+  if (nslots < 0 || nslots > VL_ADAMW_MAX_SLOTS) return vl_set_error("vl_adamw_multi_step_groups: 0 <= nslots <= VL_ADAMW_MAX_SLOTS");
+  if (step < 1) return vl_set_error("vl_adamw_multi_step_groups: step counts from 1");
+  if (!(max_norm > 0.0f)) return vl_set_error("vl_adamw_multi_step_groups: max_norm must be positive");
+  if (!sumsq || (nslots > 0 && (!slots || !groups || !groups_host))) return vl_set_error("vl_adamw_multi_step_groups: null argument");
+  // the table is checked on the host's copy of it: nothing on the device is read back
+  for (int s = 0; s < nslots; ++s) {
+    const float ls = groups_host[s].lr_scale;
+    if (!(ls >= 0.0f) || std::isinf(ls)) return vl_set_error("vl_adamw_multi_step_groups: lr_scale must be finite and >= 0");
+    if (groups_host[s].no_clip != 0 && groups_host[s].no_clip != 1)
+      return vl_set_error("vl_adamw_multi_step_groups: no_clip is 0 or 1");
+  }
+  if (nslots == 0) return 0;
+  const AdamwC c{lr, beta1, beta2, eps, 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step))};
+  hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3(2048), dim3(256), 0, stream, slots, groups, nslots, c, grad_scale, max_norm,
+                     sumsq, norm_out);
   VL_HIP_OK(hipGetLastError());
   return 0;
 }
 
 extern "C" int vl_clamp_scalar(float* p, float lo, float hi, hipStream_t stream) {
   hipLaunchKernelGGL(clamp_scalar_kernel, dim3(1), dim3(1), 0, stream, p, lo, hi);
+  VL_HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int vl_fill_f32(float* p, float value, long n, hipStream_t stream) {
+  if (n < 0 || (n > 0 && !p)) return vl_set_error("vl_fill_f32: n >= 0 and a buffer");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(256), 0, stream, p, value, n);
   VL_HIP_OK(hipGetLastError());
   return 0;
 }

@@ -113,7 +113,9 @@ SIGNATURES = {
     "vl_sumsq_ws_floats": [],
     "vl_sumsq_f32": [P, L, P, P, P],
     "vl_adamw_multi_step": [P, I, F, F, F, F, I, F, F, P, P, P],
+    "vl_adamw_multi_step_groups": [P, P, P, I, F, F, F, F, I, F, F, P, P, P],
     "vl_clamp_scalar": [P, F, F, P],
+    "vl_fill_f32": [P, F, L, P],
     "vl_axpy_f32": [P, P, F, L, P],
     "vl_scale_exp_f32": [P, P, L, P, F, P],
     "vl_batch_rowsum": [P, P, I, I, I, L, L, P],

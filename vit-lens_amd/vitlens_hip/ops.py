@@ -987,8 +987,46 @@ def adamw_multi(slots, nslots, lr, beta1, beta2, eps, step, grad_scale, max_norm
                                    float(grad_scale), float(max_norm), _p(sumsq), _p(norm_out), _stream()))
 
 
+def adamw_multi_step_groups(slots, groups, groups_host, nslots, lr, beta1, beta2, eps, step, grad_scale, max_norm, sumsq,
+                            norm_out=None):
+    """`adamw_multi` with parameter groups (vl_adamw_multi_step_groups): slot s steps with lr * lr_scale[s], and a slot whose
+    no_clip is set is outside the clipped set - it sees coef = 1, and `sumsq` is the squared norm of the OTHER slots' gradients
+    (`grad_sumsq` over their contiguous range).  groups: int32 [nslots, 2] on the device, rows (lr_scale's f32 bits, no_clip) =
+    struct vl_adamw_group (`train.pack_adamw_groups`); groups_host: the host tensor it was uploaded from, which the library
+    checks before the launch (lr_scale finite and >= 0).  norm_out: the unclipped norm of the clipped set."""
+    if slots.dtype != torch.int64 or slots.dim() != 2 or slots.shape[1] != 6 or not slots.is_contiguous():
+        raise ValueError("adamw_multi_step_groups: slots must be a contiguous int64 [nslots, 6] table")
+    if not 0 <= int(nslots) <= min(slots.shape[0], ADAMW_MAX_SLOTS):
+        raise ValueError(f"adamw_multi_step_groups: nslots {nslots} outside the table of {slots.shape[0]} rows (at most {ADAMW_MAX_SLOTS} per launch)")
+    for t, name in ((groups, "groups"), (groups_host, "groups_host")):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < int(nslots) or not t.is_contiguous():
+            raise ValueError(f"adamw_multi_step_groups: {name} must be a contiguous int32 [nslots, 2] table")
+    if groups_host.device.type != "cpu" or groups.device != slots.device:
+        raise ValueError("adamw_multi_step_groups: groups on the slots' device, groups_host on the host")
+    if sumsq.dtype != torch.float32 or sumsq.numel() != 1:
+        raise ValueError("adamw_multi_step_groups: sumsq must be one f32 element")
+    if norm_out is not None and (norm_out.dtype != torch.float32 or norm_out.numel() != 1):
+        raise ValueError("adamw_multi_step_groups: norm_out must be one f32 element")
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"adamw_multi_step_groups: max_norm must be positive, got {max_norm}")
+    if int(step) < 1:
+        raise ValueError("adamw_multi_step_groups: step counts from 1")
+    check(_lib.vl_adamw_multi_step_groups(_p(slots), _p(groups), groups_host.data_ptr(), int(nslots), float(lr), float(beta1),
+                                          float(beta2), float(eps), int(step), float(grad_scale), float(max_norm), _p(sumsq),
+                                          _p(norm_out), _stream()))
+
+
 def clamp_scalar(p, lo, hi):
     check(_lib.vl_clamp_scalar(_p(p), float(lo), float(hi), _stream()))
+
+
+def fill(p, value=0.0):
+    """p[:] = value on a contiguous 4-byte-element tensor (f32, or int32 with value 0.0: the same bits) - a step's accumulators
+    start from zero through the library, not through a framework fill."""
+    if p.element_size() != 4 or not p.is_contiguous() or (p.dtype != torch.float32 and float(value) != 0.0):
+        raise ValueError("fill: a contiguous f32 tensor (or an int32 one with value 0)")
+    check(_lib.vl_fill_f32(_p(p), float(value), p.numel(), _stream()))
+    return p
 
 
 def axpy(y, x, alpha=1.0):

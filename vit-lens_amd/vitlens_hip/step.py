@@ -306,8 +306,22 @@ class _StepState:
         self.finish_reduce()
         if self._sumsq is None:
             self._sumsq = torch.zeros(1, device=self.dev, dtype=torch.float32)
-        ops.grad_sumsq(self.flat_grad, out=self._sumsq)
+        ops.grad_sumsq(self._clipped_grads(), out=self._sumsq)
         self.opt.step(self.grads, grad_scale=1.0 / self.world, max_norm=self.grad_clip_norm, sumsq=self._sumsq)
+
+    def _clipped_grads(self):
+        """The contiguous range of the flat gradient buffer whose norm is clipped: all of it, unless a step class keeps
+        tensors out of the clipped set (`_optimizer_groups`) - those lie outside the range it returns here."""
+        return self.flat_grad
+
+    def _optimizer_groups(self):
+        """Keyword arguments of `AdamW` beyond (lr, betas, eps, weight_decay): per-tensor lr_scale / no_clip / decay of a step
+        class whose recipe has parameter groups.  Called after `_build`, when the masters exist."""
+        return {}
+
+    def _clamp_logit_scale(self):
+        """`logit_scale.clamp_(0, ln 100)` after the optimizer step (tri_train_one_epoch, training/train.py)."""
+        ops.clamp_scalar(self.logit_scale, 0.0, math.log(100.0))
 
     @property
     def dist(self) -> bool:
@@ -377,7 +391,7 @@ class _StepState:
         """The tail of every step's `__init__`: the host state, the engines and masters of the trainable set, AdamW on them."""
         self._init_host(*host)
         self._build(*build, **build_kw)
-        self.opt = AdamW(self.masters, *adamw)
+        self.opt = AdamW(self.masters, *adamw, **self._optimizer_groups())
 
     def _trainer(self, i):
         while len(self.trainers) <= i:
@@ -479,7 +493,7 @@ class _StepState:
         else:
             self.opt.step(self.grads)
         self._refresh_operands()
-        ops.clamp_scalar(self.logit_scale, 0.0, math.log(100.0))
+        self._clamp_logit_scale()
 
     def _prepare(self, B):
         """-> (micro-batch size, number of micro-batches); trainers and gradient buffers on the first call, `flat_grad` zero."""
@@ -701,7 +715,7 @@ def _label_columns_only(col_lse, label_off: int, R: int):
 
 
 def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: float = 0.5,
-                 chunk_rows: Optional[int] = None, mask=None):
+                 chunk_rows: Optional[int] = None, mask=None, loss_acc=None):
     """loss contribution w_row*CE(scale*x y^T) + w_col*CE(columns); returns (loss[1] tensor, ctx).
 
     scale: a Python float (the temperature itself), or - round 4 - the LEARNABLE LOG-temperature as a 1-element f32 tensor
@@ -721,7 +735,10 @@ def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: flo
     the un-scaled teacher features, ~2^-17 relative), and an element off the label diagonal with sim >= thres enters both
     softmaxes as logit 0.0 - the reference multiplies the logits by the mask - and carries no gradient.  Row-blocked mode
     never holds sim whole either: each row block's sim block is computed next to its logits block, and recomputed next to
-    the recomputed logits in the backward."""
+    the recomputed logits in the backward.
+
+    loss_acc: a 1-element f32 device tensor the loss is ADDED to and that is returned (the caller zeroed it, `ops.fill`), instead
+    of a new zeroed tensor - a step that keeps its accumulators runs the loss section without a framework fill."""
     R, Cn = x.shape[0], y.shape[0]
     rb = _chunk_rows(R, Cn, chunk_rows)
     dev_scale = _is_dev_scale(scale)
@@ -740,7 +757,7 @@ def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: flo
             sim = ops.logits_gemm(tr, tc, 1.0)
             row_lse, col_lse, diag = ops.ce_stats(logits, label_off, want_cols=(w_col != 0.0), sim=sim, thres=thres)
         col_lse = _label_columns_only(col_lse, label_off, R)
-        loss = torch.zeros(1, device=x.device, dtype=torch.float32)
+        loss = torch.zeros(1, device=x.device, dtype=torch.float32) if loss_acc is None else loss_acc
         ops.ce_loss_accum(loss, row_lse if w_row != 0.0 else None, col_lse, diag, R, Cn, label_off, w_row, w_col)
         return loss, (x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, 0, None, None, sim, None, thres)
     row_lse = torch.empty(R, device=x.device); diag = torch.empty(R, device=x.device)
@@ -759,18 +776,19 @@ def pair_forward(x, y, scale, label_off: int = 0, w_row: float = 0.5, w_col: flo
             col_parts.append(cl)
         del lg
     col_lse = _label_columns_only(torch.logsumexp(torch.stack(col_parts), dim=0), label_off, R) if col_parts else None
-    loss = torch.zeros(1, device=x.device, dtype=torch.float32)
+    loss = torch.zeros(1, device=x.device, dtype=torch.float32) if loss_acc is None else loss_acc
     ops.ce_loss_accum(loss, row_lse if w_row != 0.0 else None, col_lse, diag, R, Cn, label_off, w_row, w_col)
     return loss, (x, y, None, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb, tr, tc, thres)
 
 
-def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True):
+def pair_backward(ctx, g: float = 1.0, need_dx=True, need_dy=True, dscale_acc=None):
     """-> (dx, dy, dscale).  dscale = dL/d(scale) for a float scale, dL/d(logit_scale) (log domain) for a device scale.
     With a mask (pair_forward) the masked elements of dL/dlogits are zero, so they reach neither dx, dy nor dscale; the
-    teacher features inside the mask receive nothing (the reference's mask is a comparison: no gradient)."""
+    teacher features inside the mask receive nothing (the reference's mask is a comparison: no gradient).
+    dscale_acc: as `pair_forward`'s loss_acc, for dscale."""
     x, y, logits, row_lse, col_lse, label_off, w_row, w_col, scale, rb, xb, yb, sim, tc, thres = ctx
     mk = (lambda sm: {}) if thres is None else (lambda sm: dict(sim=sm, thres=thres))
-    dscale = torch.zeros(1, device=x.device, dtype=torch.float32)
+    dscale = torch.zeros(1, device=x.device, dtype=torch.float32) if dscale_acc is None else dscale_acc
     dev_scale = _is_dev_scale(scale)
     # vl_ce_grad accumulates sum(G * logits) / logit_scale: with 1.0 that IS d/d(log-scale)
     alpha, cscale = (1.0, 1.0) if dev_scale else (scale, scale)
@@ -1152,3 +1170,262 @@ class TriModalPCStep(_PerceiverLensStep):
 
     def forward_backward(self, images, texts, points, fps_start=None) -> torch.Tensor:
         return self._forward_backward(texts, images, points, fps_start)
+
+
+# ------------------------------------------------------------------------------------------------ OpenShape
+def openshape_param_group(name: str, ndim: int, weight_decay: float = 0.2, trans_lr_scale: float = 0.1):
+    """The OpenShape optimizer's group of parameter `name` (a name of `CLIPBindWrap.named_parameters()` or of the
+    `LogitScaleNetwork`) with `ndim` dimensions -> (lr_scale, weight_decay), restated from the behaviour of
+    VitLens-OpenShape/src/main.py:197-258: a name that contains "backbone.transformer" steps at 0.1 x lr, everything else at lr;
+    within either, a parameter with fewer than two dimensions or with "bn", "ln", "bias" or "logit_scale" in its name does
+    not decay."""
+    no_decay = ndim < 2 or any(w in name for w in ("bn", "ln", "bias", "logit_scale"))
+    return (float(trans_lr_scale) if "backbone.transformer" in name else 1.0), (0.0 if no_decay else float(weight_decay))
+
+
+def _openshape_reference_key(master: str) -> str:
+    """The state_dict key (`visual.` names) of the reference parameter a master holds: the interleaved GEGLU masters and the
+    stacked self-attention projection are other layouts of `net.0.weight` / `net.0.bias` and of `to_q` + `to_kv`."""
+    if master.endswith("_il"):
+        master = master[:-3]
+    return master.replace("fn.to_qkv.weight", "fn.to_q.weight")
+
+
+class OpenShapeStep(_PerceiverLensStep):
+    """The OpenShape recipe (VitLens-OpenShape/src/main.py + train.py `train_one_epoch_openclip` with
+    training.use_openclip_loss / use_openclip_optimizer_scheduler; TRAIN_INFERENCE.md:108-133) as a fused step: the point-cloud
+    tower of `CLIPBindWrap` - pnsa tokenizer with its three BatchNorms, Perceiver, class token and the first
+    `unlock_trans_first_n_layers` blocks of the KEPT trunk trainable, the rest of the trunk and the tower's `proj` frozen -
+    against PRECOMPUTED image and text features, which take the places of the frozen towers' outputs in the tri-modal loss.
+
+    sd: the tower under `visual.` names as `CLIPBindWrap.backbone.state_dict()` holds it (the skipped blocks already gone, the
+    kept ones numbered from 0: `tower.layers` is the kept count) and `logit_scale`, the `LogitScaleNetwork` parameter.
+
+    Optimizer (main.py:197-258, train.py:970-975): `openshape_param_group` per tensor - the trunk at 0.1 x lr, the no-decay
+    rule on the reference's names - in ONE launch (vl_adamw_multi_step_groups).  `grad_clip_norm` clips the tower's
+    parameters only: the logit scale is in the optimizer (no decay, full lr) but outside the clipped norm, and it is not
+    clamped after the step - this loop has no clamp.  Its master lies LAST in the flat gradient buffer, so the clipped set is
+    one contiguous range in front of it and the unlocked blocks' buckets lie at the start; what is left - Lens, class token,
+    logit scale - is one all-reduce.
+
+    Micro-batches are the base class's feature-cache scheme, which is the accumulation of train.py:848-942: every micro-batch
+    sees the whole batch of negatives.  The tower's gradient is that loop's sum over j; the logit scale's is the gradient of
+    the loss, once (the reference's loop adds it accum_freq times: INTEGRATION.md).  BatchNorm in train mode uses the
+    statistics of each micro-batch and updates the running statistics once per micro-batch.
+
+    `last_metrics`: the loss terms and the four retrieval accuracies of openshape.TriClipLoss as device tensors, counted by
+    vl_eval_hits on the step's similarity matrices; nothing is read on the host."""
+
+    pack_text = False
+
+    def __init__(self, sd, tower: TowerCfg, lens: LensCfg, device, micro_batch: int = 16, unlock_trans_first_n_layers: int = 2,
+                 lr: float = 5e-4, betas=(0.9, 0.98), eps: float = 1e-8, weight_decay: float = 0.2, trans_lr_scale: float = 0.1,
+                 rank: int = 0, world_size: int = 1, gemm_cfg: int = -1, bn_training: bool = True, bn_sync: bool = False, comm=None,
+                 local_loss: bool = False, gather_with_grad: bool = False, train_res_dtype=torch.float32,
+                 force_comm: bool = False, overlap_backward: bool = True, grad_clip_norm: Optional[float] = None,
+                 patch_dropout: float = 0.0, drop_seed: int = 0, perceiver_attn_dropout: float = 0.0,
+                 perceiver_ff_dropout: float = 0.0, out_channel: Optional[int] = None, use_text_proj: bool = False,
+                 use_image_proj: bool = False, use_mask: bool = False):
+        if out_channel is not None and tower is not None and int(out_channel) != tower.embed_dim:
+            raise NotImplementedError(f"OpenShapeStep: out_channel {out_channel} != the tower's embed_dim {tower.embed_dim} makes "
+                                      "CLIPBindWrap drop the tower's projection for a TRAINABLE proj_layer, which this step does not "
+                                      "train (the module path, openshape.openclip_step, does)")
+        if use_text_proj or use_image_proj:
+            raise NotImplementedError("OpenShapeStep: training.use_text_proj / use_image_proj put trainable projections on the "
+                                      "precomputed features; this step takes them as they are (the module path trains them)")
+        if use_mask:
+            raise NotImplementedError("OpenShapeStep: use_mask belongs to the reference's original OpenShape loop, not to the "
+                                      "open_clip loss this step computes")
+        self.unlock_n, self.trans_lr_scale = int(unlock_trans_first_n_layers or 0), float(trans_lr_scale)
+        self._target_cache, self._last = {}, None
+        # no frozen tower runs in this step: there is nothing for `overlap_frozen` to overlap
+        self._construct((sd, device, micro_batch, rank, world_size, comm, local_loss, gather_with_grad, force_comm, False,
+                         overlap_backward, grad_clip_norm, patch_dropout, drop_seed, perceiver_attn_dropout, perceiver_ff_dropout),
+                        (lr, betas, eps, weight_decay),
+                        sd, tower, lens, gemm_cfg=gemm_cfg, train_res_dtype=train_res_dtype, bn_training=bn_training, bn_sync=bn_sync)
+
+    def _build(self, sd, tower, lens, gemm_cfg=-1, train_res_dtype=torch.float32, bn_training=True, bn_sync=False):
+        from .points import PNSATokenizerTrainer
+        device, n = self.dev, self.unlock_n
+        if lens.pc_tokenizer != "pnsa":
+            raise NotImplementedError(f"OpenShapeStep: the recipe's tokenizer is pnsa, got {lens.pc_tokenizer!r} (TriModalPCStep runs PointBERT)")
+        if not 0 <= n <= tower.layers:
+            raise ValueError(f"OpenShapeStep: cannot unlock {n} of the {tower.layers} kept blocks")
+        lens = self._lens_cfg(lens)
+        self.embed_dim = tower.embed_dim
+        self.lens = LensEngine(sd, "visual.", tower, lens, device, gemm_cfg=gemm_cfg, res_dtype=train_res_dtype)
+        eng = self.lens.vit
+        for l in range(n):                                      # (as TriModalDepthStep: a trained block carries no LayerNorm-folded operands)
+            p = f"visual.transformer.resblocks.{l}."
+            w = eng.blocks[l]
+            w.pop("in_f", None); w.pop("fc_f", None)
+            for nm, key in (("attn.in_proj_weight", "in_w"), ("attn.out_proj.weight", "out_w"), ("mlp.c_fc.weight", "fc_w"),
+                            ("mlp.c_proj.weight", "proj_w")):
+                self.masters[p + nm] = sd[p + nm].detach().float().to(device).contiguous().clone()
+                self.bf16_targets[p + nm] = (l, key)
+            for nm, key in (("ln_1.weight", "ln1_w"), ("ln_1.bias", "ln1_b"), ("ln_2.weight", "ln2_w"), ("ln_2.bias", "ln2_b"),
+                            ("attn.in_proj_bias", "in_b"), ("attn.out_proj.bias", "out_b"), ("mlp.c_fc.bias", "fc_b"),
+                            ("mlp.c_proj.bias", "proj_b")):
+                self.masters[p + nm] = w[key]
+        self.tok = PNSATokenizerTrainer(sd, "visual.visual_adapter.", lens, device, gemm_cfg=gemm_cfg, bn_training=bn_training,
+                                        bn_sync=self.comm if bn_sync and self.dist else None, world_size=self.world)
+        self._one_stream_backward = bool(bn_sync and self.dist)
+        # CLIPBindWrap.lock unlocks the class token whenever layers are skipped (clip_bind.py:69-80): it is always trained here
+        self.masters["visual.class_embedding"] = eng.cls
+        self.masters.update(self.tok.masters)
+        self._collect_perceiver(sd)
+
+    def _mk(self):
+        from .train import PCLensTrainer
+        return PCLensTrainer(self.lens, self.tok, tower_kw=dict(train_blocks=range(self.unlock_n), train_cls=True))
+
+    def _bucket_blocks(self):
+        return range(self.unlock_n)
+
+    def _bind_grads(self, t, grads=None):
+        super()._bind_grads(t, grads)
+        t.tok.grads = t.tower.grads
+        self.tok.grads = self.grads
+
+    def _refresh_operands(self):
+        if not self.trainers:
+            self._trainer(0)
+        eng = self.lens.vit
+        for name, (l, key) in self.bf16_targets.items():
+            m = self.masters[name]
+            ops.cast_bf16(m, out=eng.blocks[l][key])
+            ops.transpose_to_bf16(m, ldo=m.shape[0], out=self.trainers[0].tower.wT[l][key])
+        self._refresh_perceiver()
+        self.tok.refresh_operands()
+        for t in self.trainers:
+            t.tok.op = self.tok.op
+
+    # ---- the optimizer's groups ----
+    def param_groups(self) -> Dict[str, tuple]:
+        """master name -> (lr_scale, weight_decay): `openshape_param_group` of the reference parameter the master holds, under
+        the name `CLIPBindWrap` gives it (`visual.` -> `backbone.`) and with the dimensions it has there."""
+        wd = self._adamw_wd
+        out = {}
+        for k, m in self.masters.items():
+            key = _openshape_reference_key(k)
+            ref = self._base_sd.get(key)
+            name = key if key == "logit_scale" else "backbone." + key[len("visual."):]
+            out[k] = openshape_param_group(name, m.ndim if ref is None else ref.ndim, wd, self.trans_lr_scale)
+        return out
+
+    def _optimizer_groups(self):
+        groups = self.param_groups()
+        return dict(lr_scale={k: g[0] for k, g in groups.items() if g[0] != 1.0}, no_clip=("logit_scale",),
+                    decay={k: g[1] != 0.0 for k, g in groups.items()})
+
+    def _construct(self, host, adamw, *build, **build_kw):
+        self._adamw_wd = float(adamw[3])
+        self._init_host(*host)
+        ls = self.masters.pop("logit_scale")                    # re-inserted LAST: behind the clipped range of the flat buffer
+        self._build(*build, **build_kw)
+        self.masters["logit_scale"] = ls
+        self.opt = AdamW(self.masters, *adamw, **self._optimizer_groups())
+
+    def _alloc_flat_grads(self):
+        super()._alloc_flat_grads()
+        # the layout the optimizer relies on: the logit scale behind everything that is clipped
+        last = self.grads["logit_scale"]
+        self._clip_end = (last.data_ptr() - self.flat_grad.data_ptr()) // 4
+        assert self._clip_end + 4 >= self.flat_grad.numel() and list(self.masters)[-1] == "logit_scale", "logit_scale must lie last"
+
+    def _clipped_grads(self):
+        return self.flat_grad[:self._clip_end]
+
+    def _clamp_logit_scale(self):
+        pass                                                    # (train.py:944-1000: the OpenShape loop does not clamp)
+
+    def set_lr(self, lr: float):
+        """The base learning rate (what `training.scheduler.cosine_lr(step.opt, ...)` assigns too); the trunk's group follows at
+        `trans_lr_scale` x lr inside the kernel."""
+        self.opt.lr = lr
+
+    # ---- the step ----
+    def forward_backward(self, features: torch.Tensor, xyz: torch.Tensor, img_feat: torch.Tensor, text_feat: torch.Tensor,
+                         fps_start=None) -> torch.Tensor:
+        """features [B,N,in_dim], xyz [B,N,3] (`CLIPBindWrap.forward(features, xyz=xyz)`); img_feat / text_feat: the precomputed
+        [B,E] features, normalised here.  Returns the loss; `last_metrics` has its parts."""
+        B, E, dev = features.shape[0], self.embed_dim, self.dev
+        mb, nmb = self._prepare(B)
+        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        fi, ft = ops.l2_normalize(f32(img_feat)), ops.l2_normalize(f32(text_feat))
+        if tuple(fi.shape) != (B, E) or tuple(ft.shape) != (B, E):
+            raise ValueError(f"OpenShapeStep: img_feat / text_feat must be [{B}, {E}], got {tuple(fi.shape)} / {tuple(ft.shape)}")
+        vraw, fv, vnorm = torch.empty(B, E, device=dev), torch.empty(B, E, device=dev), torch.empty(B, device=dev)
+        drop = self.patch_dropout > 0.0
+        for i in range(nmb):
+            s = slice(i * mb, (i + 1) * mb)
+            kw = dict(zip(("keep", "inv"), self.drop_indices(DROP_TOWER_VISUAL, self.lens.vit, i * mb, mb))) if drop else {}
+            if self._lens_drop:
+                kw["drop"] = self.lens_draw(i * mb)
+            vraw[s] = self._trainer(i).forward(features[s], None if fps_start is None else fps_start[s], xyz=xyz[s], **kw)
+        ops.l2_normalize(vraw, out=fv, norms=vnorm)
+        loss, dv, ds = self._loss(fi, ft, fv)
+        self._backward_all(ops.l2_normalize_bwd(fv, dv, vnorm), nmb, mb)
+        ops.axpy(self.grads["logit_scale"], ds)
+        return loss
+
+    def _targets(self, n: int, off: int):
+        key = (n, off)
+        if key not in self._target_cache:
+            self._target_cache[key] = torch.arange(off, off + n, device=self.dev, dtype=torch.int64)
+        return self._target_cache[key]
+
+    def _count_hits(self, hits, x, y_all, off: int, logits=None):
+        """hits[0] += the rows of x whose best column of x @ y_all^T is their own (column row + off): vl_eval_hits with
+        k0 = k1 = 1.  `logits`: the similarity matrix where the loss has it already (any positive scale)."""
+        R = x.shape[0]
+        if logits is not None:
+            ops.eval_hits(logits, self._targets(R, off), ks=(1, 1), hits=hits)
+            return
+        xb, yb = ops.split_bf16x3(x, 0), ops.split_bf16x3(y_all, 1)
+        rb = _chunk_rows(R, y_all.shape[0], None) or R
+        for r0 in range(0, R, rb):
+            r1 = min(R, r0 + rb)
+            ops.eval_hits(ops.logits_gemm(xb[r0:r1], yb, 1.0), self._targets(r1 - r0, off + r0), ks=(1, 1), hits=hits)
+
+    def _loss(self, fi, ft, fv):
+        """The base class's tri-modal loss on the given image / text features, its two terms kept apart, and the retrieval hits
+        of openshape.TriClipLoss (loss.py:80-185).  The accumulators are zeroed and added to by library launches: on one rank
+        the section holds no framework kernel."""
+        acc = ops.fill(torch.empty(4, device=self.dev, dtype=torch.float32))
+        hits = ops.fill(torch.empty(3, 2, device=self.dev, dtype=torch.int32))
+        li, lt, ds, total = acc[0:1], acc[1:2], acc[2:3], acc[3:4]
+        b = fv.shape[0]
+        if self.dist:
+            ai, at, av = self._gather(fi, ft, fv)
+            kw = dict(local_loss=self.local_loss, gather_with_grad=self.gather_with_grad, need_x=False, dist=True)
+            l1, _, dv, ds1 = pair_loss_and_grads(self.comm, self.rank, self.world, fi, fv, ai, av, self.logit_scale, **kw)
+            l2, _, dv2, ds2 = pair_loss_and_grads(self.comm, self.rank, self.world, ft, fv, at, av, self.logit_scale, **kw)
+            for dst, src in ((li, l1), (lt, l2), (ds, ds1), (ds, ds2)):
+                ops.axpy(dst, src)
+            lg_i = lg_t = None
+            off = self.rank * b if self.local_loss else 0
+            qi, qt, qv = (fi, ft, fv) if self.local_loss else (ai, at, av)
+        else:
+            _, c1 = pair_forward(fi, fv, self.logit_scale, loss_acc=li)
+            _, c2 = pair_forward(ft, fv, self.logit_scale, loss_acc=lt)
+            _, dv, _ = pair_backward(c1, need_dx=False, dscale_acc=ds)
+            _, dv2, _ = pair_backward(c2, need_dx=False, dscale_acc=ds)
+            lg_i, lg_t = c1[2], c2[2]                           # (None where the pair loss ran row-blocked)
+            ai, av, off = fi, fv, 0
+            qi, qt, qv = fi, ft, fv
+        ops.axpy(dv, dv2)
+        ops.axpy(total, li); ops.axpy(total, lt)
+        self._count_hits(hits[0], qi, av, off, lg_i)            # i2v
+        self._count_hits(hits[1], qv, ai, off)                  # v2i
+        self._count_hits(hits[2], qt, av, off, lg_t)            # t2v (= v2t: loss.py:161 counts the text rows for both)
+        self._last = (acc, hits, qi.shape[0])
+        return total, dv, ds
+
+    @property
+    def last_metrics(self) -> Dict[str, torch.Tensor]:
+        """The loss dictionary of openshape.TriClipLoss for the last forward_backward, device tensors (built when asked for)."""
+        acc, hits, n = self._last
+        a = hits[:, 0].float() / n
+        return {"contrastive_loss": acc[3], "i_contra_loss": acc[0], "t_contra_loss": acc[1], "i2v_acc": a[0], "v2i_acc": a[1],
+                "t2v_acc": a[2], "v2t_acc": a[2]}

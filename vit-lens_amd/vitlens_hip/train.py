@@ -9,6 +9,7 @@ the blocks in reverse with hand-written kernels (GEMM dX with fused dGELU, atten
 LayerNorm backward); weight gradients are NT GEMMs over transposed activation copies accumulated in
 fp32 (`EPI_RES_F32` into the gradient buffer).
 """
+import math
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -529,14 +530,45 @@ def pack_adamw_slots(rows) -> torch.Tensor:
     return t
 
 
+def pack_adamw_groups(rows) -> torch.Tensor:
+    """rows of (lr_scale, no_clip) -> the int32 [len, 2] image of `struct vl_adamw_group[]` (host tensor): the f32 bits of the
+    scale, then the flag."""
+    import struct
+    return torch.tensor([[struct.unpack("<i", struct.pack("<f", ls))[0], int(bool(nc))] for ls, nc in rows],
+                        dtype=torch.int32).reshape(len(rows), 2)
+
+
+def _f32_mul(a: float, b: float) -> float:
+    """a * b as the kernels form it: both operands and the product rounded to fp32."""
+    import struct
+    r = lambda x: struct.unpack("<f", struct.pack("<f", x))[0]
+    return r(r(a) * r(b))
+
+
 class AdamW:
     """torch.optim.AdamW semantics on f32 master tensors, one fused kernel launch per tensor
     (reference: depth_tri_main.py:394-419 -- two groups: no weight decay for ndim<2 / bn / ln / bias / logit_scale).
     `step(..., max_norm=c)` clips the global gradient norm first (torch.nn.utils.clip_grad_norm_(params, c), the reference's
     --grad-clip-norm / training.grad_clip_norm) and updates every tensor in ONE launch; the norm and the coefficient stay
-    on the device, `last_grad_norm` holds the unclipped norm."""
+    on the device, `last_grad_norm` holds the unclipped norm.
 
-    def __init__(self, params: Dict[str, torch.Tensor], lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2):
+    Parameter groups, per tensor by name: `lr_scale` {name: s} - the tensor steps with lr * s (torch's groups with an lr of
+    their own; `lr` stays what a scheduler assigns); `no_clip` names - tensors outside clip_grad_norm_'s parameter list: they
+    are updated unclipped and their gradients are not in the norm; `decay` {name: bool} - overrides `decays` (a master whose
+    name is not the reference parameter's).  Defaults: 1.0, clipped, `decays`.  With any of the first two given the clipped
+    step is vl_adamw_multi_step_groups, and `sumsq` (where the caller passes it) is the squared norm of the clipped set."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2,
+                 lr_scale: Optional[Dict[str, float]] = None, no_clip: Iterable[str] = (), decay: Optional[Dict[str, bool]] = None):
+        self.lr_scale, self.no_clip, self.decay = dict(lr_scale or {}), frozenset(no_clip), dict(decay or {})
+        for k in (*self.lr_scale, *self.no_clip, *self.decay):
+            if k not in params:
+                raise ValueError(f"AdamW: {k!r} is not a parameter of this optimizer")
+        for k, v in self.lr_scale.items():
+            if not (math.isfinite(float(v)) and float(v) >= 0.0):
+                raise ValueError(f"AdamW: lr_scale of {k} must be finite and >= 0, got {v}")
+        self._grouped = bool(self.no_clip) or any(float(v) != 1.0 for v in self.lr_scale.values())
+        self._groups = self._groups_host = None
         self._slots, self._slot_key = None, None      # the device table of the clipped step, kept while no tensor moves
         self.last_grad_norm = None                    # 0-d f32 device tensor after a clipped step
         # `param_groups[i]["lr"]` is what the reference's schedulers assign (training/scheduler.py:4-6); one group here,
@@ -571,9 +603,15 @@ class AdamW:
                     raise ValueError(f"AdamW: contiguous f32 tensors required ({k})")
             if g.numel() != p.numel():
                 raise ValueError(f"AdamW: gradient of {k} has {g.numel()} elements, the parameter {p.numel()}")
-            rows.append((p.data_ptr(), g.data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), p.numel(),
-                         self.wd if self.decays(k, p) else 0.0))
+            rows.append((p.data_ptr(), g.data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), p.numel(), self._wd(k, p)))
         return rows
+
+    def _wd(self, k, p) -> float:
+        return self.wd if self.decay.get(k, self.decays(k, p)) else 0.0
+
+    def group_rows(self, grads: Dict[str, torch.Tensor]):
+        """One (lr_scale, no_clip) row per row of `slot_rows`."""
+        return [(float(self.lr_scale.get(k, 1.0)), k in self.no_clip) for k in self.params if grads.get(k) is not None]
 
     def _clipped_step(self, grads, grad_scale, max_norm, sumsq):
         if not float(max_norm) > 0.0:
@@ -585,14 +623,22 @@ class AdamW:
         key = tuple(rows)
         if key != self._slot_key:          # first step, or a tensor was re-allocated: one small host-to-device copy
             self._slots, self._slot_key = pack_adamw_slots(rows).to(dev), key
+            if self._grouped:
+                self._groups_host = pack_adamw_groups(self.group_rows(grads))
+                self._groups = self._groups_host.to(dev)
         if sumsq is None:                  # gradients in separate allocations: one reduction each, added on the device
-            parts = [ops.grad_sumsq(g) for k, g in grads.items() if k in self.params and g is not None]
+            parts = [ops.grad_sumsq(g) for k, g in grads.items() if k in self.params and g is not None and k not in self.no_clip]
             sumsq = torch.cat(parts).sum(dtype=torch.float64).float().reshape(1)
         if self.last_grad_norm is None:
             self.last_grad_norm = torch.zeros((), device=dev, dtype=torch.float32)
         self.t += 1
         for a in range(0, len(rows), ops.ADAMW_MAX_SLOTS):
             n = min(ops.ADAMW_MAX_SLOTS, len(rows) - a)
+            if self._grouped:
+                ops.adamw_multi_step_groups(self._slots[a:a + n], self._groups[a:a + n], self._groups_host[a:a + n], n, self.lr,
+                                            self.betas[0], self.betas[1], self.eps, self.t, grad_scale, max_norm, sumsq,
+                                            self.last_grad_norm)
+                continue
             ops.adamw_multi(self._slots[a:a + n], n, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale,
                             max_norm, sumsq, self.last_grad_norm)
 
@@ -608,8 +654,9 @@ class AdamW:
             g = grads.get(k)
             if g is None:
                 continue
-            wd = self.wd if self.decays(k, p) else 0.0
-            ops.adamw_step(p.view(-1), g.view(-1), self.m[k].view(-1), self.v[k].view(-1), self.lr, self.betas[0],
+            wd = self._wd(k, p)
+            lr = _f32_mul(self.lr, self.lr_scale[k]) if k in self.lr_scale else self.lr
+            ops.adamw_step(p.view(-1), g.view(-1), self.m[k].view(-1), self.v[k].view(-1), lr, self.betas[0],
                            self.betas[1], self.eps, wd, self.t, grad_scale)
 
 
@@ -897,8 +944,9 @@ class PCLensTrainer:
         ctx = self.tok.forward(pts, fps_start=fps_start, **kw)    # tokens (+ pos), bf16 [B*G, C]
         return self.tower.forward(self.perc.forward(ctx, B, drop), B, keep=keep, inv=inv)
 
-    def backward(self, dfeat: torch.Tensor):
-        self.tok.backward(self.perc.backward(self.tower.backward(dfeat)))
+    def backward(self, dfeat: torch.Tensor, on_block_done=None):
+        """on_block_done: `TowerTrainer.backward`'s, for a recipe with unlocked blocks (tower_kw train_blocks)."""
+        self.tok.backward(self.perc.backward(self.tower.backward(dfeat, on_block_done)))
 
 
 def refresh_trainer(tr, sd, names):
