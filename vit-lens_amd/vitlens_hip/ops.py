@@ -619,6 +619,15 @@ def l2_normalize(x, out=None, out_bf16=None, norms=None, eps=1e-12):
 
 
 def l2_normalize_bwd(f, df, norms, eps=1e-12):
+    """f, df: contiguous f32 [rows, D] (the kernel reads both with row stride D); norms: contiguous f32 [rows]."""
+    _chk2d(f, "l2_normalize_bwd: f", torch.float32); _chk2d(df, "l2_normalize_bwd: df", torch.float32)
+    if not f.is_contiguous() or not df.is_contiguous() or df.shape != f.shape:
+        raise ValueError(f"l2_normalize_bwd: f and df must be contiguous and of one shape, got {tuple(f.shape)} strides {f.stride()} "
+                         f"and {tuple(df.shape)} strides {df.stride()}")
+    if norms.dtype != torch.float32 or norms.dim() != 1 or norms.shape[0] != f.shape[0] or not norms.is_contiguous():
+        raise ValueError(f"l2_normalize_bwd: norms must be a contiguous f32 [{f.shape[0]}] tensor")
+    if df.device != f.device or norms.device != f.device:
+        raise ValueError("l2_normalize_bwd: f, df and norms must live on one device")
     dx = torch.empty_like(f)
     check(_lib.vl_l2_normalize_bwd(_p(f), _p(df), _p(norms), _p(dx), f.shape[0], f.shape[1], float(eps),
                                    _stream()))
@@ -727,7 +736,26 @@ def ce_stats(logits, label_off=0, want_cols=True, sim=None, thres=None):
     return row_lse, col_lse, diag
 
 
+def _chk_vec(t, n, name):
+    """A statistic of the CE entries: contiguous f32 [n] on a GPU."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n or t.stride(0) != 1:
+        raise ValueError(f"{name} must be a contiguous f32 [{n}] tensor")
+
+
 def ce_loss_accum(loss, row_lse, col_lse, diag, R, Cc, label_off, w_row, w_col):
+    """loss[0] += w_row mean_r(row_lse[r] - diag[r]) + w_col mean_r(col_lse[r + label_off] - diag[r]); row_lse / col_lse None: that
+    term is absent.  R rows are read of row_lse and diag, Cc columns may be read of col_lse."""
+    if R <= 0 or Cc <= 0:
+        raise ValueError(f"ce_loss_accum: empty problem ({R} x {Cc})")
+    _chk_vec(diag, R, "ce_loss_accum: diag")
+    if row_lse is not None:
+        _chk_vec(row_lse, R, "ce_loss_accum: row_lse")
+    if col_lse is not None:
+        _chk_vec(col_lse, Cc, "ce_loss_accum: col_lse")
+    if not torch.is_tensor(loss) or loss.dtype != torch.float32 or loss.numel() != 1:
+        raise ValueError("ce_loss_accum: loss must be a 1-element f32 tensor")
+    if any(t is not None and t.device != loss.device for t in (row_lse, col_lse, diag)):
+        raise ValueError("ce_loss_accum: every operand must live on the device of loss")
     check(_lib.vl_ce_loss_accum(_p(row_lse), _p(col_lse), _p(diag), R, Cc, label_off, float(w_row), float(w_col),
                                 _p(loss), _stream()))
 
@@ -738,10 +766,18 @@ def ce_grad(logits, row_lse, col_lse, label_off, w_row, w_col, logit_scale, dsca
     and G, GT and the d/dscale term are 0 (no gradient flows through the mask)."""
     if sim is None and thres is not None:
         raise ValueError("ce_grad: thres needs sim")
+    _chk2d(logits, "ce_grad: logits", torch.float32)
     if sim is not None:
-        _chk2d(logits, "logits", torch.float32)
         _chk_sim(logits, sim, thres, "ce_grad")
     R, Cc = logits.shape
+    if row_lse is not None:
+        _chk_vec(row_lse, R, "ce_grad: row_lse")
+    if col_lse is not None:
+        _chk_vec(col_lse, Cc, "ce_grad: col_lse")
+    if dscale is not None and (not torch.is_tensor(dscale) or dscale.dtype != torch.float32 or dscale.numel() != 1):
+        raise ValueError("ce_grad: dscale must be a 1-element f32 tensor")
+    if any(t is not None and t.device != logits.device for t in (row_lse, col_lse, dscale)):
+        raise ValueError("ce_grad: every operand must live on the logits' device")
     dev = logits.device
     ldg = (Cc + 63) // 64 * 64
     ldgt = (R + 63) // 64 * 64
