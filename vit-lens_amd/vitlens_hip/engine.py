@@ -131,6 +131,15 @@ class Bf16Arith:
     def linear_f32(self, a, w, b, out=None):
         return ops.gemm(a, w, b, out=out, epi=ops.EPI_F32, cfg=self.cfg)
 
+    # the front of a Lens (LensEngine.cols, points.pointbert_forward): the tokenizer convolution's rows; the point patches with
+    # their K padding, the group maximum and the padded centres; and the projection that adds row m // res_div of `res` in
+    # front of the activation (the group's row of the split convolution)
+    point_kp = 64
+    im2col, knn_group, group_max, pad3 = (staticmethod(f) for f in (ops.im2col, ops.knn_group, ops.group_max, ops.pad3))
+
+    def linear_rowres(self, a, w, out, res, res_div, act=ops.ACT_NONE):
+        ops.gemm(a, w, None, out=out, res=res, res_div=res_div, epi=ops.EPI_RES_BF16, act=act, cfg=self.cfg)
+
 
 class Bf16x2Arith(Bf16Arith):
     """Weights as the sum of TWO bf16 terms (prep_block_wsplit) on an fp32 stream.  A projection that writes an activation takes
@@ -454,7 +463,10 @@ class VitEngine:
     def patch_tokens(self, image: torch.Tensor) -> torch.Tensor:
         """conv1 as im2col + GEMM (transformer.py:464-470,674-676): [N,C,H,W] f32 -> [N*T, D] bf16."""
         p = self.cfg.patch
-        cols, gh, gw = ops.im2col(image.contiguous().float(), p, p, p, p, self.conv_w.shape[1])
+        return self.conv_tokens(ops.im2col(image.contiguous().float(), p, p, p, p, self.conv_w.shape[1])[0])
+
+    def conv_tokens(self, cols: torch.Tensor) -> torch.Tensor:
+        """conv1 on its im2col rows (a trainer keeps them for the weight gradient)."""
         return ops.gemm(cols, self.conv_w, None, epi=ops.EPI_BF16, cfg=self.gemm_cfg)
 
     def trunk(self, tokens: torch.Tensor, B: int, pos2: Optional[torch.Tensor] = None, use_orig_pos=True,
@@ -1119,73 +1131,84 @@ def lens_cols(im2col, x: torch.Tensor, lens: LensCfg, patch: int, Kp: int) -> to
 
 class LensEngine:
     """`visual.` tower of TriCLIP for a non-image modality: visual_adapter -> (+pos) -> Perceiver -> ViT trunk
-    (VisionTransformer.forward, open_clip/transformer.py:723-792)."""
+    (VisionTransformer.forward, open_clip/transformer.py:723-792), in the arithmetic `arith` (default: Bf16Arith(gemm_cfg);
+    f32.LensEngineF32 passes F32Arith): tower, Perceiver and tokenizer are built in its dtype."""
 
-    def __init__(self, sd, prefix: str, tower: TowerCfg, lens: LensCfg, device, res_dtype=torch.float32, gemm_cfg=-1):
+    def __init__(self, sd, prefix: str, tower: TowerCfg, lens: LensCfg, device, res_dtype=torch.float32, gemm_cfg=-1, arith=None):
         self.tower, self.lens, self.device, self.gemm_cfg = tower, lens, torch.device(device), gemm_cfg
+        self.arith = Bf16Arith(gemm_cfg) if arith is None else arith
         # a tower without ln_pre is the EVA ViT of a Perceiver_Blip_EVA_ViT (its state_dict names, eva_tower_state)
         eva = {} if tower.pre_norm else {"n_tokens": lens.num_latents + 1}
-        self.vit = (EvaVitEngine if eva else VitEngine)(sd, prefix, tower, device, res_dtype=res_dtype, gemm_cfg=gemm_cfg, **eva)
-        a = prefix + "visual_adapter."
-        self.prefix_adapter = a
-        self.adapter_pos = None
-        if lens.modality in ("depth", "audio"):
-            self.conv_w, self.conv_b = conv_weight_as_gemm(sd[a + "conv1.weight"], device), None
-            pos = sd[a + "pos_emb"].detach().float()
-            self.adapter_pos = _dev(pos * (0.0 if lens.disable_adapter_pos else 1.0), device)      # (the product is a new tensor)
-        elif lens.modality == "eeg":
-            # PatchEmbed1D: Conv1d(chans -> width, kernel = window, stride, bias) over time = a conv over [N, C, 1, T]
-            self.conv_w = conv_weight_as_gemm(sd[a + "proj.weight"].unsqueeze(2), device)
-            self.conv_b = _dev(sd[a + "proj.bias"], device)
-            self.adapter_pos = _dev(sd[a + "pos_emb"].detach().float() * (0.0 if lens.disable_adapter_pos else 1.0), device)
+        self.vit = (EvaVitEngine if eva else VitEngine)(sd, prefix, tower, device, res_dtype=res_dtype, gemm_cfg=gemm_cfg,
+                                                        arith=self.arith, **eva)
+        a = self.prefix_adapter = prefix + "visual_adapter."
+        self.conv_w = self.conv_b = self.adapter_pos = self.points = None
+        self._points_pending = None             # the parameters a PointBERT tokenizer is rebuilt from at its next use (update_params)
+        if lens.modality in ("depth", "audio", "eeg"):
+            self.conv_w, self.conv_b, self.adapter_pos = self._adapter_operands(sd, a)
         elif lens.modality == "pc":
-            if lens.pc_tokenizer == "pnsa":       # inference = the trainer class with the running BatchNorm statistics
-                from .points import PNSATokenizerTrainer
-                self.points = PNSATokenizerTrainer(sd, a, lens, device, gemm_cfg=gemm_cfg, bn_training=False)
-            else:
-                from .points import PointTokenizerEngine
-                self.points = PointTokenizerEngine(sd, a, lens, device, gemm_cfg=gemm_cfg)
+            self.points = self._point_tokenizer(sd)
         else:
             raise NotImplementedError(lens.modality)
-        self.perceiver = None if lens.perceiver_identity else PerceiverEngine(sd, prefix + "perceiver.", lens, device, gemm_cfg)
+        self.perceiver = None if lens.perceiver_identity else PerceiverEngine(sd, prefix + "perceiver.", lens, device, gemm_cfg, self.arith)
+
+    def _adapter_operands(self, sd, a: str):
+        """-> (conv weight as a GEMM operand, bias f32 or None, pos_emb f32 scaled by disable_adapter_pos) of the depth / audio
+        (conv1, no bias) or EEG tokenizer (PatchEmbed1D: Conv1d(chans -> width, kernel = window, stride, bias) over time = a conv
+        over [N, C, 1, T]), as new device tensors."""
+        eeg = self.lens.modality == "eeg"
+        w = sd[a + "proj.weight"].unsqueeze(2) if eeg else sd[a + "conv1.weight"]
+        pos = sd[a + "pos_emb"].detach().float() * (0.0 if self.lens.disable_adapter_pos else 1.0)
+        return (conv_weight_as_gemm(w, self.device, self.arith.dtype), _dev(sd[a + "proj.bias"], self.device) if eeg else None,
+                _dev(pos, self.device))
+
+    def _point_tokenizer(self, sd):
+        from .points import PNSATokenizerTrainer, PointTokenizerEngine
+        if self.lens.pc_tokenizer == "pnsa":       # inference = the trainer class with the running BatchNorm statistics
+            return PNSATokenizerTrainer(sd, self.prefix_adapter, self.lens, self.device, gemm_cfg=self.gemm_cfg, bn_training=False)
+        return PointTokenizerEngine(sd, self.prefix_adapter, self.lens, self.device, gemm_cfg=self.gemm_cfg)
 
     def update_params(self, sd, prefix: str, names):
         """In-place refresh after the parameters `names` (relative to `prefix`) changed, e.g. by an optimizer step."""
-        L, a = self.lens, prefix + "visual_adapter."
+        a = prefix + "visual_adapter."
         self.vit.update_params(sd, [n for n in names if not n.startswith(("visual_adapter.", "perceiver."))])    # (EVA names: EvaVitEngine maps them)
         if any(n.startswith("visual_adapter.") for n in names):
-            scale = 0.0 if L.disable_adapter_pos else 1.0
-            if L.modality in ("depth", "audio"):
-                self.conv_w.copy_(conv_weight_as_gemm(sd[a + "conv1.weight"], self.device))
-                self.adapter_pos.copy_(sd[a + "pos_emb"].detach().float() * scale)
-            elif L.modality == "eeg":
-                self.conv_w.copy_(conv_weight_as_gemm(sd[a + "proj.weight"].unsqueeze(2), self.device))
-                self.conv_b.copy_(sd[a + "proj.bias"])
-                self.adapter_pos.copy_(sd[a + "pos_emb"].detach().float() * scale)
-            elif L.modality == "pc":
-                if L.pc_tokenizer == "pnsa":
-                    self.points.load_params(sd)
-                else:
-                    # the inference tokenizer (BatchNorm folded into the convolutions, a host round trip) is rebuilt at its next
-                    # USE: while training every optimizer step lands here and the trainer runs its own tokenizer copy
-                    self._points_pending = {k: v for k, v in sd.items() if k.startswith(a)}
+            if self.points is None:
+                for dst, src in zip((self.conv_w, self.conv_b, self.adapter_pos), self._adapter_operands(sd, a)):
+                    if dst is not None:
+                        dst.copy_(src)
+            elif self.lens.pc_tokenizer == "pnsa":
+                self.points.load_params(sd)
+            else:
+                # the inference tokenizer (BatchNorm folded into the convolutions, a host round trip) is rebuilt at its next
+                # USE: while training every optimizer step lands here and the trainer runs its own tokenizer copy
+                self._points_pending = {k: v for k, v in sd.items() if k.startswith(a)}
         if self.perceiver is not None and any(n.startswith("perceiver.") for n in names):
             self.perceiver.update_params(sd, prefix + "perceiver.")
 
     def cols(self, x: torch.Tensor) -> torch.Tensor:
-        if not hasattr(self, "conv_w"):         # (no convolution tokenizer: the point cloud's is self.points)
+        if self.lens.modality == "pc":          # (no convolution tokenizer: the point cloud's is self.points)
             raise NotImplementedError(self.lens.modality)
-        return lens_cols(ops.im2col, x, self.lens, self.tower.patch, self.conv_w.shape[1])
+        return lens_cols(self.arith.im2col, x.to(self.device), self.lens, self.tower.patch, self.conv_w.shape[1])
+
+    def conv_tokens(self, cols: torch.Tensor) -> torch.Tensor:
+        """The tokenizer convolution on its im2col rows (a trainer keeps them for the weight gradient) -> tokens [B*T, C]."""
+        tok = torch.empty(cols.shape[0], self.conv_w.shape[0], device=cols.device, dtype=self.arith.dtype)
+        self.arith.linear(cols, self.conv_w, self.conv_b, tok)
+        return tok
 
     def tokens(self, x: torch.Tensor):
-        """-> (tokens [B*T, C] bf16, pos table [T, C] f32)."""
-        return ops.gemm(self.cols(x), self.conv_w, self.conv_b, epi=ops.EPI_BF16, cfg=self.gemm_cfg), self.adapter_pos
+        """-> (tokens [B*T, C] in the arithmetic's dtype, pos table [T, C] f32)."""
+        return self.conv_tokens(self.cols(x)), self.adapter_pos
 
     def encode(self, x: torch.Tensor, normalize: bool = False, keep: Optional[torch.Tensor] = None,
                drop: Optional[LensDrop] = None, tokens_out: bool = False, **kw) -> torch.Tensor:
         """keep int32 [B,K] (ops.patch_keep): patch dropout on the tokens that enter the ViT trunk (VitEngine.trunk).
         drop (PerceiverEngine.draw): the Perceiver's dropout of a train-mode forward without autograd.
         tokens_out: the trunk's [B, L, D] token stream instead of the pooled feature (VitEngine.trunk)."""
+        return self._encode(x, normalize, keep, drop, tokens_out, **kw)
+
+    def _encode(self, x, normalize=False, keep=None, drop=None, tokens_out=False, **kw):
         B = x.shape[0]
         if tokens_out:
             if normalize:
@@ -1193,23 +1216,16 @@ class LensEngine:
             trunk = lambda *a, **k: self.vit.trunk(*a, tokens_out=True, **k)
         else:
             trunk = self.vit.trunk
-        if self.lens.modality == "pc":
-            pend = getattr(self, "_points_pending", None)
-            if pend is not None:
-                from .points import PointTokenizerEngine
-                self.points = PointTokenizerEngine(pend, self.prefix_adapter, self.lens, self.device, gemm_cfg=self.gemm_cfg)
-                self._points_pending = None
-            tok = self.points.forward(x, **kw)                 # already x + pos, [B*G, C] bf16
-            lat = self.perceiver.forward(tok, B, drop)
-            f = trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
+        pos2 = None
+        if self.points is not None:
+            if self._points_pending is not None:
+                self.points, self._points_pending = self._point_tokenizer(self._points_pending), None
+            tok = self.points.forward(x, **kw)                 # already x + pos, [B*G, C]
         else:
-            tok, pos = self.tokens(x)
-            if self.perceiver is None:
-                f = trunk(tok, B, pos2=pos, use_orig_pos=self.lens.use_orig_pos, keep=keep)
-            else:
-                T = tok.shape[0] // B
-                xin = torch.empty_like(tok)
-                ops.add_rows(tok, pos, xin, tok.shape[0], T, tok.shape[1])
-                lat = self.perceiver.forward(xin, B, drop)
-                f = trunk(lat, B, use_orig_pos=self.lens.use_orig_pos, keep=keep)
+            tok, pos2 = self.tokens(x)
+            if self.perceiver is not None:
+                tok, pos2 = ops.add_rows(tok, pos2, torch.empty_like(tok), tok.shape[0], tok.shape[0] // B, tok.shape[1]), None
+        if self.perceiver is not None:
+            tok = self.perceiver.forward(tok, B, drop)
+        f = trunk(tok, B, pos2=pos2, use_orig_pos=self.lens.use_orig_pos, keep=keep)
         return ops.l2_normalize(f) if normalize else f

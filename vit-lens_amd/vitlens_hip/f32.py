@@ -18,8 +18,9 @@ from typing import Optional
 import torch
 
 from . import ops
-from .engine import (LensCfg, PerceiverEngine, TextCfg, TowerCfg, VitEngine, _dev, _Workspace, block_operands, conv_weight_as_gemm,
-                     deinterleave_geglu, interleave_geglu, lens_cols, text_features)  # noqa: F401  (the two GEGLU helpers: re-exported)
+from .engine import (LensCfg, LensEngine, PerceiverEngine, TextCfg, TowerCfg, VitEngine, _dev, _Workspace, block_operands,
+                     conv_weight_as_gemm, deinterleave_geglu, interleave_geglu, text_features)  # noqa: F401  (the two GEGLU helpers: re-exported)
+from .points import PointTokenizerEngine, fold_bn as fold_bn_f32, point_tokenizer_operands  # noqa: F401  (fold_bn_f32: its name here)
 
 
 def f32_head_dim_ok(dh: int) -> bool:
@@ -49,27 +50,17 @@ class F32Arith:
     def linear_f32(self, a, w, b, out=None):
         return ops.gemm_f32(a, w, b, out=out)
 
+    point_kp = 4                # (the fp32 GEMM reads 16-byte rows)
+    im2col, knn_group, group_max, pad3 = (staticmethod(f) for f in (ops.im2col_f32, ops.knn_group_f32, ops.group_max_f32, ops.pad3_f32))
+
+    def linear_rowres(self, a, w, out, res, res_div, act=ops.ACT_NONE):
+        ops.gemm_f32_ex(a, w, None, out=out, res=res, act=act, res_div=res_div, res_pre=True)
+
 
 def conv_as_gemm_f32(w: torch.Tensor, device="cpu") -> torch.Tensor:
     """Conv weight [O, C, *kernel] -> f32 [O, Kp] (K = C * prod(kernel) zero-padded to a multiple of 64, as the 16-bit stem
     lays it out; column order (c, i, j) = im2col's)."""
     return conv_weight_as_gemm(w, device, torch.float32)
-
-
-def fold_bn_f32(w, b, gamma, beta, running_mean, running_var, eps=1e-5):
-    """Eval-mode BatchNorm after a 1x1 conv, folded into it IN FP32: bn(x W^T + b) = x (s W)^T + (b - mean) s + beta with
-    s = gamma / sqrt(var + eps) (dvae.py:183-194 in eval mode).  -> (W' [O, K], b' [O]) f32."""
-    f = lambda t: t.detach().float()
-    s = f(gamma) / torch.sqrt(f(running_var) + eps)
-    return f(w) * s[:, None], (f(b) - f(running_mean)) * s + f(beta)
-
-
-def pad_k4(w: torch.Tensor) -> torch.Tensor:
-    """[O, K] -> f32 [O, K rounded up to a multiple of 4], zero columns (the fp32 GEMM reads 16-byte rows)."""
-    K = w.shape[1]
-    out = torch.zeros(w.shape[0], (K + 3) // 4 * 4, dtype=torch.float32, device=w.device)
-    out[:, :K] = w.float()
-    return out
 
 
 def f32_lens_supported(tower: TowerCfg, lens: Optional[LensCfg]) -> bool:
@@ -159,93 +150,38 @@ class PerceiverEngineF32(PerceiverEngine):
 
 
 def point_tokenizer_operands_f32(sd, a: str, eps: float = 1e-5):
-    """fp32 operands of PointTokenizerEngineF32 from the reference's parameters (prefix `a` = "...visual_adapter."), on the
-    device the parameters live on: the two eval-mode BatchNorms folded in fp32 into the convs before them, the 3-channel
-    inputs zero-padded to K = 4, second_conv.0 split into its global (first half of the input channels: the broadcast group
-    maximum, dvae.py:207-209) and local halves."""
-    f = lambda k: sd[a + k].detach().float()
-    bn = lambda k: [f(k + n) for n in (".weight", ".bias", ".running_mean", ".running_var")]
-    w1, b1 = fold_bn_f32(f("encoder.first_conv.0.weight")[:, :, 0], f("encoder.first_conv.0.bias"), *bn("encoder.first_conv.1"), eps=eps)
-    w3, b3 = fold_bn_f32(f("encoder.second_conv.0.weight")[:, :, 0], f("encoder.second_conv.0.bias"), *bn("encoder.second_conv.1"), eps=eps)
-    half = w3.shape[1] // 2
-    return {"w1": pad_k4(w1), "b1": b1, "w2": f("encoder.first_conv.3.weight")[:, :, 0], "b2": f("encoder.first_conv.3.bias"),
-            "w3g": w3[:, :half], "w3l": w3[:, half:], "b3": b3,
-            "w4": f("encoder.second_conv.3.weight")[:, :, 0], "b4": f("encoder.second_conv.3.bias"),
-            "wr": f("reduce_dim.weight"), "br": f("reduce_dim.bias"),
-            "wp0": pad_k4(f("pos_embed.0.weight")), "bp0": f("pos_embed.0.bias"), "wp2": f("pos_embed.2.weight"), "bp2": f("pos_embed.2.bias")}
+    """fp32 operands of PointTokenizerEngineF32: points.point_tokenizer_operands in fp32 with the 3-channel inputs zero-padded
+    to K = 4, on the device the parameters live on."""
+    return point_tokenizer_operands(sd, a, torch.float32, F32Arith.point_kp, eps)
 
 
-class PointTokenizerEngineF32:
-    """PointTokenizer.forward (point_encoder.py:350-362) in fp32, BatchNorm in eval mode: FPS (vl_fps, bit-exact fp32), kNN
-    grouping into fp32 centred patches (vl_knn_group_f32: the 16-bit engine's neighbour sets), the mini-PointNet (dvae.py:
-    196-212) with the BatchNorms folded in fp32, the two group maxima in fp32, reduce_dim, and the centre MLP with exact GELU.
-    forward -> tokens + pos, f32 [B*G, trans_dim]."""
+class PointTokenizerEngineF32(PointTokenizerEngine):
+    """PointTokenizer.forward (point_encoder.py:350-362) in fp32, BatchNorm in eval mode - points.pointbert_forward in F32Arith:
+    FPS (vl_fps, bit-exact fp32), kNN grouping into fp32 centred patches (vl_knn_group_f32: the 16-bit engine's neighbour sets),
+    the mini-PointNet (dvae.py:196-212) with the BatchNorms folded in fp32 where the parameters live, the two group maxima in
+    fp32, reduce_dim, and the centre MLP with exact GELU.  forward -> tokens + pos, f32 [B*G, trans_dim]."""
+    fold_on_host = False
 
     def __init__(self, sd, a: str, lens: LensCfg, device):
-        self.lens, self.device = lens, torch.device(device)
-        self.op = {k: _dev(v, device) for k, v in point_tokenizer_operands_f32(sd, a).items()}
-
-    def group(self, pts: torch.Tensor, fps_start=None, want_idx=False):
-        L = self.lens
-        pts = pts.to(self.device).contiguous().float()
-        if fps_start is None:   # misc.py:60 draws the first centre at random
-            fps_start = torch.randint(0, pts.shape[1], (pts.shape[0],), device=self.device, dtype=torch.long)
-        cidx, centers = ops.fps(pts, fps_start.to(self.device), L.pc_num_group)
-        patches, nidx = ops.knn_group_f32(pts, cidx, L.pc_group_size, Kp=self.op["w1"].shape[1], want_idx=want_idx)
-        return cidx, centers, patches, nidx
-
-    def forward(self, pts: torch.Tensor, fps_start=None) -> torch.Tensor:
-        M, o = self.lens.pc_group_size, self.op
-        _, centers, patches, _ = self.group(pts, fps_start)
-        h1 = ops.gemm_f32(patches, o["w1"], o["b1"], act=ops.ACT_RELU)                       # conv 3->128 + BN + ReLU
-        f = ops.gemm_f32(h1, o["w2"], o["b2"])                                               # conv 128->256
-        t = ops.gemm_f32(ops.group_max_f32(f, M), o["w3g"], o["b3"])                         # global half of conv 512->512 (+ BN)
-        h2 = ops.gemm_f32_ex(f, o["w3l"], None, res=t, res_div=M, res_pre=True, act=ops.ACT_RELU)   # + local half, ReLU
-        tok = ops.gemm_f32(ops.group_max_f32(ops.gemm_f32(h2, o["w4"], o["b4"]), M), o["wr"], o["br"])
-        p1 = ops.gemm_f32(ops.pad3_f32(centers, o["wp0"].shape[1]), o["wp0"], o["bp0"], act=ops.ACT_GELU)
-        return ops.gemm_f32(p1, o["wp2"], o["bp2"], res=tok)                                 # tokens + pos
+        super().__init__(sd, a, lens, device, arith=F32Arith())
 
 
-class LensEngineF32:
-    """The `visual.` tower of a Lens under precision="fp32", eval mode (VisionTransformer.forward, transformer.py:723-792):
-    audio (AST conv over [N,1,F,T] with f / t strides), EEG (PatchEmbed1D: Conv1d with bias), point cloud (pointbert) or depth
-    tokens -> + adapter pos -> PerceiverEngineF32 -> VitEngineF32.trunk.  Every matrix product on the fp32-input MFMA."""
+class LensEngineF32(LensEngine):
+    """The `visual.` tower of a Lens under precision="fp32", eval mode (VisionTransformer.forward, transformer.py:723-792) -
+    engine.LensEngine on fp32 operands in F32Arith: audio (AST conv over [N,1,F,T] with f / t strides), EEG (PatchEmbed1D: Conv1d
+    with bias), point cloud (pointbert) or depth tokens -> + adapter pos -> Perceiver -> trunk.  Every matrix product on the
+    fp32-input MFMA."""
 
     def __init__(self, sd, prefix: str, tower: TowerCfg, lens: LensCfg, device):
         if not f32_lens_supported(tower, lens):
             raise NotImplementedError("fp32 inference: this Lens is not covered (f32_lens_supported)")
-        self.tower, self.lens, self.device = tower, lens, torch.device(device)
-        self.vit = VitEngineF32(sd, prefix, tower, device)
-        a = prefix + "visual_adapter."
-        scale = 0.0 if lens.disable_adapter_pos else 1.0
-        self.adapter_pos = self.points = None
-        if lens.modality in ("depth", "audio"):
-            self.conv_w, self.conv_b = conv_as_gemm_f32(sd[a + "conv1.weight"], device), None
-        elif lens.modality == "eeg":
-            self.conv_w = conv_as_gemm_f32(sd[a + "proj.weight"].unsqueeze(2), device)
-            self.conv_b = _dev(sd[a + "proj.bias"], device)
-        else:
-            self.points = PointTokenizerEngineF32(sd, a, lens, device)
-        if self.points is None:
-            self.adapter_pos = _dev(sd[a + "pos_emb"].detach().float() * scale, device)
-        self.perceiver = None if lens.perceiver_identity else PerceiverEngineF32(sd, prefix + "perceiver.", lens, device)
+        super().__init__(sd, prefix, tower, lens, device, arith=F32Arith())
 
-    def tokens(self, x: torch.Tensor) -> torch.Tensor:
-        """-> tokens f32 [B*T, width] of the depth / audio / EEG tokenizer (without the adapter pos)."""
-        cols = lens_cols(ops.im2col_f32, x.to(self.device), self.lens, self.tower.patch, self.conv_w.shape[1])
-        return ops.gemm_f32(cols, self.conv_w, self.conv_b)
+    def _point_tokenizer(self, sd):
+        return PointTokenizerEngineF32(sd, self.prefix_adapter, self.lens, self.device)
 
     def encode(self, x: torch.Tensor, normalize: bool = False, fps_start=None, **kw) -> torch.Tensor:
-        B = x.shape[0]
-        if self.points is not None:
-            tok = self.points.forward(x, fps_start)                   # tokens + pos, f32 [B*G, trans_dim]
-        else:
-            t = self.tokens(x)
-            if self.perceiver is None:
-                f = self.vit.trunk(t, B, pos2=self.adapter_pos, use_orig_pos=self.lens.use_orig_pos)
-                return ops.l2_normalize(f) if normalize else f
-            tok = torch.empty_like(t)
-            ops.add_rows(t, self.adapter_pos, tok, t.shape[0], t.shape[0] // B, t.shape[1])
-        lat = self.perceiver.forward(tok, B)
-        f = self.vit.trunk(lat, B, use_orig_pos=self.lens.use_orig_pos)
-        return ops.l2_normalize(f) if normalize else f
+        """The one body of LensEngine.encode, for an eval-mode forward.  Every other keyword is accepted and IGNORED, as it always
+        was here: keep (patch dropout), drop (the Perceiver's dropout) and tokens_out belong to train-mode or token-stream
+        forwards, which the fp32 engines do not run."""
+        return self._encode(x, normalize, **({} if self.points is None else {"fps_start": fps_start}))

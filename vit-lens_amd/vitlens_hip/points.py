@@ -1,70 +1,119 @@
-"""PointBERT tokenizer of the 3D Lens on the HIP kernels (PointTokenizer.forward,
-open_clip/modal_3d/models/pointbert/point_encoder.py:350-362): FPS -> kNN grouping -> mini-PointNet
-(Encoder, dvae.py:179-212) -> reduce_dim, plus the centre MLP positional embedding; returns x + pos.
+"""The point-cloud tokenizers of the 3D Lens on the HIP kernels.
 
-BatchNorm runs in EVAL mode (running statistics folded into the 1x1-conv weights at load time).  Train-mode
-batch statistics (and SyncBN) for the PC recipe are not implemented yet and raise.
+PointBERT (PointTokenizer.forward, open_clip/modal_3d/models/pointbert/point_encoder.py:350-362): FPS -> kNN grouping ->
+mini-PointNet (Encoder, dvae.py:179-212) -> reduce_dim, plus the centre MLP positional embedding; returns x + pos.  The dataflow
+is written once, `pointbert_forward`, and run by three executors: PointTokenizerEngine (bf16 operands, the eval-mode BatchNorms
+folded into the 1x1 convolutions at load time), f32.PointTokenizerEngineF32 (the same in fp32) and PointTokenizerTrainer (the
+BatchNorm layers as launches of their own - batch statistics per rank or, with a communicator, SyncBatchNorm over the ranks, with
+the running-statistics update; or the running statistics in eval mode - activations kept, and the backward pass).
+`pnsa` (PointNSATokenizer, pointnet_util.py:345-368): PNSATokenizerTrainer, forward and backward, which also serves inference.
 """
 import torch
 
 from . import ops
+from .engine import Bf16Arith, _dev
 
 BF = torch.bfloat16
 
 
-def _fold_bn(w, b, sd, p, eps=1e-5):
-    s = sd[p + "weight"].float() / torch.sqrt(sd[p + "running_var"].float() + eps)
-    return w * s[:, None], (b - sd[p + "running_mean"].float()) * s + sd[p + "bias"].float()
+def fold_bn(w, b, gamma, beta, running_mean, running_var, eps=1e-5):
+    """Eval-mode BatchNorm after a 1x1 conv, folded into it IN FP32: bn(x W^T + b) = x (s W)^T + (b - mean) s + beta with
+    s = gamma / sqrt(var + eps) (dvae.py:183-194 in eval mode).  -> (W' [O, K], b' [O]) f32."""
+    f = lambda t: t.detach().float()
+    s = f(gamma) / torch.sqrt(f(running_var) + eps)
+    return f(w) * s[:, None], (f(b) - f(running_mean)) * s + f(beta)
 
 
-def _padk(w, K=64):
-    out = torch.zeros(w.shape[0], K)
-    out[:, :w.shape[1]] = w
-    return out
+def point_tokenizer_operands(sd, a: str, dtype, Kp: int, eps: float = 1e-5):
+    """The folded operand table of the PointBERT tokenizer from the reference's parameters (prefix `a` = "...visual_adapter."),
+    computed in fp32 on the device the parameters live on: the two eval-mode BatchNorms folded into the convs before them, the
+    3-channel inputs zero-padded to a multiple of `Kp` columns, second_conv.0 split into its global (first half of the input
+    channels: the broadcast group maximum, dvae.py:207-209) and local halves.  Weights w* in `dtype`, biases b* f32."""
+    f = lambda k: sd[a + k].detach().float()
+    conv = lambda k: f(k + ".weight")[:, :, 0]
+    bn = lambda k: [f(k + n) for n in (".weight", ".bias", ".running_mean", ".running_var")]
+
+    def padk(w):
+        out = torch.zeros(w.shape[0], (w.shape[1] + Kp - 1) // Kp * Kp, dtype=torch.float32, device=w.device)
+        out[:, :w.shape[1]] = w
+        return out
+    w1, b1 = fold_bn(conv("encoder.first_conv.0"), f("encoder.first_conv.0.bias"), *bn("encoder.first_conv.1"), eps=eps)
+    w3, b3 = fold_bn(conv("encoder.second_conv.0"), f("encoder.second_conv.0.bias"), *bn("encoder.second_conv.1"), eps=eps)
+    half = w3.shape[1] // 2
+    w = {"w1": padk(w1), "w2": conv("encoder.first_conv.3"), "w3g": w3[:, :half], "w3l": w3[:, half:], "w4": conv("encoder.second_conv.3"),
+         "wr": f("reduce_dim.weight"), "wp0": padk(f("pos_embed.0.weight")), "wp2": f("pos_embed.2.weight")}
+    b = {"b1": b1, "b2": f("encoder.first_conv.3.bias"), "b3": b3, "b4": f("encoder.second_conv.3.bias"), "br": f("reduce_dim.bias"),
+         "bp0": f("pos_embed.0.bias"), "bp2": f("pos_embed.2.bias")}
+    return {**{k: v.to(dtype) for k, v in w.items()}, **b}
+
+
+def point_groups(lens, pts: torch.Tensor, fps_start, ar, Kp: int, device, want_idx=False):
+    """FPS centres and their kNN patches: -> (centre indices, centres f32 [B,G,3], centred patches [B*G*M, Kp] in the
+    arithmetic's dtype, neighbour indices or None)."""
+    pts = pts.to(device).contiguous().float()
+    if fps_start is None:   # misc.py:60 draws the first centre at random
+        fps_start = torch.randint(0, pts.shape[1], (pts.shape[0],), device=device, dtype=torch.long)
+    cidx, centers = ops.fps(pts, fps_start.to(device), lens.pc_num_group)
+    patches, nidx = ar.knn_group(pts, cidx, lens.pc_group_size, Kp=Kp, want_idx=want_idx)
+    return cidx, centers, patches, nidx
+
+
+def pointbert_forward(op, lens, pts: torch.Tensor, fps_start, ar, device, train=None) -> torch.Tensor:
+    """pts [B,N,3] -> tokens + pos [B*G, trans_dim] in the arithmetic `ar` (engine.Bf16Arith, f32.F32Arith) on the operand table
+    `op` (w1 .. wp2, b1 .. bp2).
+    train None: an engine - the table is point_tokenizer_operands' (BatchNorms folded), ReLU rides in the GEMM epilogues, nothing
+    is kept.  train = a PointTokenizerTrainer: the convs run without activation and its `_bn` follows each, the centre MLP saves
+    the GELU derivative, and the tensors the backward reads are left in `train.ctx`."""
+    M = lens.pc_group_size
+    relu = ops.ACT_RELU if train is None else ops.ACT_NONE
+    bn = (lambda z, k: (z, None)) if train is None else train._bn
+
+    def lin(x, w, b, act=ops.ACT_NONE, res=None, out2=None):
+        out = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=ar.dtype)
+        ar.linear(x, w, b, out, res=res, act=act, out2=out2)
+        return out
+    _, centers, patches, _ = point_groups(lens, pts, fps_start, ar, op["w1"].shape[1], device)
+    z1 = lin(patches, op["w1"], op["b1"], relu)                           # conv 3->128 (+ folded BN + ReLU)
+    h1, s1 = bn(z1, "encoder.first_conv.1")
+    f = lin(h1, op["w2"], op["b2"])                                       # conv 128->256
+    g = ar.group_max(f, M)
+    t = lin(g, op["w3g"], op["b3"])                                       # global half of conv 512->512: one row per group
+    z3 = torch.empty(f.shape[0], op["w3l"].shape[0], device=f.device, dtype=ar.dtype)
+    ar.linear_rowres(f, op["w3l"], z3, t, M, relu)                        # + local half, the group's row added before the ReLU
+    h2, s3 = bn(z3, "encoder.second_conv.1")
+    f2 = lin(h2, op["w4"], op["b4"])
+    g2 = ar.group_max(f2, M)
+    tok = lin(g2, op["wr"], op["br"])                                     # [B*G, trans]
+    c3 = ar.pad3(centers, op["wp0"].shape[1])
+    if train is None:
+        p1 = lin(c3, op["wp0"], op["bp0"], ops.ACT_GELU)
+    else:
+        u = torch.empty(c3.shape[0], op["wp0"].shape[0], device=c3.device, dtype=ar.dtype)
+        p1 = lin(c3, op["wp0"], op["bp0"], ops.ACT_GELU_DSAVE, out2=u)
+        train.ctx = (patches, z1, s1[0], s1[1], h1, f, g, z3, s3[0], s3[1], h2, f2, g2, c3, u, p1, s1[2], s3[2])
+    return lin(p1, op["wp2"], op["bp2"], res=tok)                         # pos + tokens
 
 
 class PointTokenizerEngine:
-    def __init__(self, sd, a: str, lens, device, gemm_cfg=-1, bn_training=False):
+    """PointTokenizer.forward in eval mode on folded operands: bf16 by default (the fold runs on the host), in the arithmetic
+    `arith` otherwise (f32.PointTokenizerEngineF32).  forward -> tokens + pos [B*G, trans_dim]."""
+    fold_on_host = True
+
+    def __init__(self, sd, a: str, lens, device, gemm_cfg=-1, bn_training=False, arith=None):
         if bn_training:
             raise NotImplementedError("the inference engine folds the running statistics; train-mode BatchNorm = PointTokenizerTrainer")
-        self.lens, self.device, self.cfg = lens, torch.device(device), gemm_cfg
-        f = lambda k: sd[a + k].detach().float().cpu()
-        bn_sd = {k: v.detach().cpu() for k, v in sd.items() if k.startswith((a + "encoder.first_conv.1.", a + "encoder.second_conv.1."))}
-        w1, b1 = _fold_bn(f("encoder.first_conv.0.weight")[:, :, 0], f("encoder.first_conv.0.bias"), bn_sd, a + "encoder.first_conv.1.")
-        w3, b3 = _fold_bn(f("encoder.second_conv.0.weight")[:, :, 0], f("encoder.second_conv.0.bias"), bn_sd, a + "encoder.second_conv.1.")
-        half = w3.shape[1] // 2
-        d = lambda t, dt=BF: t.to(device=device, dtype=dt).contiguous()
-        self.w1, self.b1 = d(_padk(w1)), d(b1, torch.float32)
-        self.w2, self.b2 = d(f("encoder.first_conv.3.weight")[:, :, 0]), d(f("encoder.first_conv.3.bias"), torch.float32)
-        self.w3g, self.w3l, self.b3 = d(w3[:, :half]), d(w3[:, half:]), d(b3, torch.float32)
-        self.w4, self.b4 = d(f("encoder.second_conv.3.weight")[:, :, 0]), d(f("encoder.second_conv.3.bias"), torch.float32)
-        self.wr, self.br = d(f("reduce_dim.weight")), d(f("reduce_dim.bias"), torch.float32)
-        self.wp0, self.bp0 = d(_padk(f("pos_embed.0.weight"))), d(f("pos_embed.0.bias"), torch.float32)
-        self.wp2, self.bp2 = d(f("pos_embed.2.weight")), d(f("pos_embed.2.bias"), torch.float32)
+        self.lens, self.device = lens, torch.device(device)
+        self.ar = Bf16Arith(gemm_cfg) if arith is None else arith
+        if self.fold_on_host:
+            sd = {k: v.detach().cpu() for k, v in sd.items() if k.startswith(a)}
+        self.op = {k: _dev(v, device, v.dtype) for k, v in point_tokenizer_operands(sd, a, self.ar.dtype, self.ar.point_kp).items()}
 
     def group(self, pts: torch.Tensor, fps_start=None, want_idx=False):
-        L = self.lens
-        pts = pts.to(self.device).contiguous().float()
-        if fps_start is None:   # misc.py:60 draws the first centre at random
-            fps_start = torch.randint(0, pts.shape[1], (pts.shape[0],), device=self.device, dtype=torch.long)
-        cidx, centers = ops.fps(pts, fps_start.to(self.device), L.pc_num_group)
-        patches, nidx = ops.knn_group(pts, cidx, L.pc_group_size, Kp=64, want_idx=want_idx)
-        return cidx, centers, patches, nidx
+        return point_groups(self.lens, pts, fps_start, self.ar, self.op["w1"].shape[1], self.device, want_idx)
 
     def forward(self, pts: torch.Tensor, fps_start=None) -> torch.Tensor:
-        """pts [B,N,3] -> tokens + pos, bf16 [B*G, trans_dim]."""
-        M, c = self.lens.pc_group_size, self.cfg
-        cidx, centers, patches, _ = self.group(pts, fps_start)
-        h1 = ops.gemm(patches, self.w1, self.b1, act=ops.ACT_RELU, cfg=c)                    # conv 3->128 + BN + ReLU
-        f = ops.gemm(h1, self.w2, self.b2, cfg=c)                                            # conv 128->256
-        t = ops.gemm(ops.group_max(f, M), self.w3g, self.b3, cfg=c)                          # global half of conv 512->512
-        h2 = torch.empty(f.shape[0], self.w3l.shape[0], device=self.device, dtype=BF)
-        ops.gemm(f, self.w3l, None, out=h2, res=t, res_div=M, epi=ops.EPI_RES_BF16, act=ops.ACT_RELU, cfg=c)
-        tok = ops.gemm(ops.group_max(ops.gemm(h2, self.w4, self.b4, cfg=c), M), self.wr, self.br, cfg=c)   # [B*G, trans]
-        p1 = ops.gemm(ops.pad3(centers), self.wp0, self.bp0, act=ops.ACT_GELU, cfg=c)
-        out = torch.empty_like(tok)
-        ops.gemm(p1, self.wp2, self.bp2, out=out, res=tok, epi=ops.EPI_RES_BF16, cfg=c)      # pos + tokens
-        return out
+        """pts [B,N,3] -> tokens + pos [B*G, trans_dim]."""
+        return pointbert_forward(self.op, self.lens, pts, fps_start, self.ar, self.device)
 
 
 class PointTokenizerTrainer:
@@ -77,27 +126,28 @@ class PointTokenizerTrainer:
     FPS / kNN produce indices only (misc.fps, knn_point run under no_grad-equivalent integer ops), so the
     backward stops at the gathered, centre-subtracted patches."""
 
-    KP = 64
     BN_EPS, BN_MOMENTUM = 1e-5, 0.1           # nn.BatchNorm1d defaults (dvae.py:186,191)
 
     def __init__(self, sd, a: str, lens, device, grads=None, gemm_cfg=-1, bn_training=True, bn_sync=None, world_size=1):
         """bn_sync: a communicator (all_gather / all_reduce_sum, e.g. step.TorchComm) turns the two BatchNorm layers into
         SyncBatchNorm over `world_size` ranks (--use-bn-sync); None = per-rank statistics, the reference's default."""
+        f32 = self._init_common(sd, a, lens, device, grads, gemm_cfg, bn_training, bn_sync, world_size)
+        m = self.masters
+        for k in ("encoder.first_conv.0", "encoder.first_conv.3", "encoder.second_conv.0", "encoder.second_conv.3"):
+            m[a + k + ".weight"] = f32(k + ".weight")[:, :, 0].contiguous(); m[a + k + ".bias"] = f32(k + ".bias")
+        for k in ("encoder.first_conv.1", "encoder.second_conv.1", "reduce_dim", "pos_embed.0", "pos_embed.2"):
+            m[a + k + ".weight"] = f32(k + ".weight"); m[a + k + ".bias"] = f32(k + ".bias")
+        self.running = {k: (f32(k + ".running_mean"), f32(k + ".running_var")) for k in ("encoder.first_conv.1", "encoder.second_conv.1")}
+        self.refresh_operands()
+
+    def _init_common(self, sd, a, lens, device, grads, gemm_cfg, bn_training, bn_sync, world_size):
+        """The fields both tokenizer trainers have; -> the reader of an fp32 master (never an alias of the caller's tensor)."""
         self.a, self.lens, self.device, self.cfg, self.bn_training = a, lens, torch.device(device), gemm_cfg, bn_training
         self.bn_sync, self.world = bn_sync, world_size
         self.grads = {} if grads is None else grads
-        f32 = lambda k: sd[a + k].detach().float().to(device).contiguous().clone()      # masters never alias the caller's tensors
-        m = self.masters = {}
-        for k in ("encoder.first_conv.0", "encoder.first_conv.3", "encoder.second_conv.0", "encoder.second_conv.3"):
-            m[a + k + ".weight"] = f32(k + ".weight")[:, :, 0].contiguous(); m[a + k + ".bias"] = f32(k + ".bias")
-        for k in ("encoder.first_conv.1", "encoder.second_conv.1"):
-            m[a + k + ".weight"] = f32(k + ".weight"); m[a + k + ".bias"] = f32(k + ".bias")
-        for k in ("reduce_dim", "pos_embed.0", "pos_embed.2"):
-            m[a + k + ".weight"] = f32(k + ".weight"); m[a + k + ".bias"] = f32(k + ".bias")
-        self.running = {k: (f32(k + ".running_mean"), f32(k + ".running_var")) for k in ("encoder.first_conv.1", "encoder.second_conv.1")}
-        self.op = {}
-        self.refresh_operands()
-        self.ctx = None
+        self.ar = Bf16Arith(gemm_cfg)
+        self.masters, self.op, self.ctx = {}, {}, None
+        return lambda k: sd[a + k].detach().float().to(device).contiguous().clone()
 
     def load_params(self, sd):
         """Masters and running statistics re-read from `sd` (reference names and shapes), in place; operands re-derived."""
@@ -107,13 +157,14 @@ class PointTokenizerTrainer:
             rm.copy_(sd[self.a + k + ".running_mean"]); rv.copy_(sd[self.a + k + ".running_var"])
         self.refresh_operands()
 
-    # bf16 GEMM operands (forward: W, backward: W^T) derived from the f32 masters
+    # bf16 GEMM operands (forward: W, backward: W^T) derived from the f32 masters, under pointbert_forward's names; the biases
+    # are the masters themselves
     def refresh_operands(self):
         a, m, o = self.a, self.masters, self.op
         bf = lambda t: t.to(BF).contiguous()
 
         def padk(w):
-            out = torch.zeros(w.shape[0], self.KP, device=w.device, dtype=BF)
+            out = torch.zeros(w.shape[0], self.ar.point_kp, device=w.device, dtype=BF)
             out[:, :w.shape[1]] = w.to(BF)
             return out
         w3 = m[a + "encoder.second_conv.0.weight"]
@@ -126,6 +177,9 @@ class PointTokenizerTrainer:
         o["wr"] = bf(m[a + "reduce_dim.weight"]); o["wrT"] = bf(m[a + "reduce_dim.weight"].t())
         o["wp0"] = padk(m[a + "pos_embed.0.weight"])
         o["wp2"] = bf(m[a + "pos_embed.2.weight"]); o["wp2T"] = bf(m[a + "pos_embed.2.weight"].t())
+        for b, k in (("b1", "encoder.first_conv.0"), ("b2", "encoder.first_conv.3"), ("b3", "encoder.second_conv.0"),
+                     ("b4", "encoder.second_conv.3"), ("br", "reduce_dim"), ("bp0", "pos_embed.0"), ("bp2", "pos_embed.2")):
+            o[b] = m[a + k + ".bias"]
 
     def grad_buffer(self, name):
         g = self.grads.get(name)
@@ -162,32 +216,8 @@ class PointTokenizerTrainer:
         return ops.bn_bwd_apply(*args, sums, total, self.BN_EPS, relu=True)
 
     def forward(self, pts: torch.Tensor, fps_start=None) -> torch.Tensor:
-        """pts [B,N,3] -> tokens + pos, bf16 [B*G, trans_dim]."""
-        L, a, m, o, c = self.lens, self.a, self.masters, self.op, self.cfg
-        M = L.pc_group_size
-        pts = pts.to(self.device).contiguous().float()
-        if fps_start is None:
-            fps_start = torch.randint(0, pts.shape[1], (pts.shape[0],), device=self.device, dtype=torch.long)
-        cidx, centers = ops.fps(pts, fps_start.to(self.device), L.pc_num_group)
-        patches, _ = ops.knn_group(pts, cidx, L.pc_group_size, Kp=self.KP)
-        z1 = ops.gemm(patches, o["w1"], m[a + "encoder.first_conv.0.bias"], cfg=c)
-        h1, s1 = self._bn(z1, "encoder.first_conv.1")
-        f = ops.gemm(h1, o["w2"], m[a + "encoder.first_conv.3.bias"], cfg=c)
-        g = ops.group_max(f, M)
-        t = ops.gemm(g, o["w3g"], m[a + "encoder.second_conv.0.bias"], cfg=c)
-        z3 = torch.empty(f.shape[0], o["w3l"].shape[0], device=self.device, dtype=BF)
-        ops.gemm(f, o["w3l"], None, out=z3, res=t, res_div=M, epi=ops.EPI_RES_BF16, cfg=c)
-        h2, s3 = self._bn(z3, "encoder.second_conv.1")
-        f2 = ops.gemm(h2, o["w4"], m[a + "encoder.second_conv.3.bias"], cfg=c)
-        g2 = ops.group_max(f2, M)
-        tok = ops.gemm(g2, o["wr"], m[a + "reduce_dim.bias"], cfg=c)
-        c3 = ops.pad3(centers, self.KP)
-        u = torch.empty(c3.shape[0], o["wp0"].shape[0], device=self.device, dtype=BF)
-        p1 = ops.gemm(c3, o["wp0"], m[a + "pos_embed.0.bias"], act=ops.ACT_GELU_DSAVE, cfg=c, out2=u)
-        out = torch.empty_like(tok)
-        ops.gemm(p1, o["wp2"], m[a + "pos_embed.2.bias"], out=out, res=tok, epi=ops.EPI_RES_BF16, cfg=c)
-        self.ctx = (patches, z1, s1[0], s1[1], h1, f, g, z3, s3[0], s3[1], h2, f2, g2, c3, u, p1, s1[2], s3[2])
-        return out
+        """pts [B,N,3] -> tokens + pos, bf16 [B*G, trans_dim]; the activations the backward reads are kept in self.ctx."""
+        return pointbert_forward(self.op, self.lens, pts, fps_start, self.ar, self.device, train=self)
 
     def _dw_into(self, dy, x, g):
         """g += dy^T x (bf16 [rows, *] operands): token-major operands for the dW kernel (narrow channel counts zero-padded to
@@ -252,11 +282,8 @@ class PNSATokenizerTrainer(PointTokenizerTrainer):
     FPS / ball query produce indices only, so the backward stops at the gathered rows."""
 
     def __init__(self, sd, a: str, lens, device, grads=None, gemm_cfg=-1, bn_training=True, bn_sync=None, world_size=1):
-        self.a, self.lens, self.device, self.cfg, self.bn_training = a, lens, torch.device(device), gemm_cfg, bn_training
-        self.bn_sync, self.world = bn_sync, world_size
-        self.grads = {} if grads is None else grads
-        f32 = lambda k: sd[a + k].detach().float().to(device).contiguous().clone()
-        m = self.masters = {}
+        f32 = self._init_common(sd, a, lens, device, grads, gemm_cfg, bn_training, bn_sync, world_size)
+        m = self.masters
         for i in range(3):
             w = f32(f"sa.mlp_convs.{i}.weight")
             m[a + f"sa.mlp_convs.{i}.weight"] = w.reshape(w.shape[0], -1).contiguous(); m[a + f"sa.mlp_convs.{i}.bias"] = f32(f"sa.mlp_convs.{i}.bias")
@@ -266,9 +293,7 @@ class PNSATokenizerTrainer(PointTokenizerTrainer):
         m[a + "lift.2.weight"] = f32("lift.2.weight"); m[a + "lift.2.bias"] = f32("lift.2.bias")
         self.running = {f"sa.mlp_bns.{i}": (f32(f"sa.mlp_bns.{i}.running_mean"), f32(f"sa.mlp_bns.{i}.running_var")) for i in range(3)}
         self.in_ch = m[a + "sa.mlp_convs.0.weight"].shape[1]               # 3 + in_dim
-        self.op = {}
         self.refresh_operands()
-        self.ctx = None
 
     @staticmethod
     def _pad64(n):

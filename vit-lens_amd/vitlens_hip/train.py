@@ -372,7 +372,7 @@ class DepthLensTrainer:
         """keep / inv: patch dropout in front of the ViT trunk (TowerTrainer.forward); the tokenizer stays dense."""
         le = self.le
         cols = le.cols(x)
-        tok = ops.gemm(cols, le.conv_w, None, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
+        tok = le.conv_tokens(cols)
         self.ctx = (cols, x.shape[0])
         return self.tower.forward(tok, x.shape[0], pos2=le.adapter_pos, keep=keep, inv=inv)
 
@@ -408,7 +408,7 @@ class ImageTowerTrainer:
         e = self.eng
         p = e.cfg.patch
         cols, gh, gw = ops.im2col(x.contiguous().float(), p, p, p, p, e.conv_w.shape[1])
-        tok = ops.gemm(cols, e.conv_w, None, epi=ops.EPI_BF16, cfg=e.gemm_cfg)
+        tok = e.conv_tokens(cols)
         self.ctx = cols
         return self.tower.forward(tok, x.shape[0], keep=keep, inv=inv)
 
@@ -873,12 +873,6 @@ class AudioLensTrainer:
     def grads(self):
         return self.tower.grads
 
-    def _tokens(self, x):
-        """-> (the im2col rows bf16 [B*T, Kp], which the backward keeps, and the tokenizer convolution's output [B*T, D])."""
-        le = self.le
-        cols = le.cols(x)
-        return cols, ops.gemm(cols, le.conv_w, le.conv_b, epi=ops.EPI_BF16, cfg=le.gemm_cfg)
-
     def _conv_bias_grad(self, ddata):
         pass                                          # (the AST convolution's bias is not in the trainable set)
 
@@ -887,7 +881,8 @@ class AudioLensTrainer:
         stay dense.  drop (PerceiverEngine.draw): the Perceiver's own attention / FeedForward dropout."""
         le = self.le
         B = x.shape[0]
-        cols, tok = self._tokens(x)
+        cols = le.cols(x)                             # (the im2col rows bf16 [B*T, Kp], which the backward keeps)
+        tok = le.conv_tokens(cols)
         T = tok.shape[0] // B
         xin = torch.empty_like(tok)
         ops.add_rows(tok, le.adapter_pos, xin, tok.shape[0], T, tok.shape[1])
